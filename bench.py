@@ -20,6 +20,9 @@ CUPS accounting is the reference's (similarities/bench.rs:413-414): cells = sum 
 algorithm skips. Fields of the line:
 
   value              rate of the K timed synchronous steps (barrier + synchronize on both sides, max over ranks)
+  ms_per_step        milliseconds of one of those steps (their wall time over K)
+  full               whether this run was `--full`: a plain run measures `value` and nothing else; the fields below are in
+                     the line of a `--full` run only (and at N > 1 so are `gather_ok`, `gather`, C5 and `single_process`)
   value_steady       the same calls over at least `--steady-seconds` (default 1 s) of wall time
   value_pipelined    K steps enqueued asynchronously on two internal lanes (not the reference's metric; what a caller
                      that does not need each result before the next call gets)
@@ -33,10 +36,15 @@ algorithm skips. Fields of the line:
   details            where the full entries were written
 
 Order of a run: data, tapes, `--prewarm-seconds` of untimed steps (an idle MI355X needs a few hundred milliseconds of work
-to reach its clocks), W warm-up steps, the K timed steps, a profiled repeat, the steady-state loop, the pipelined steps,
-the checks, the other configs, the CPU rows.
+to reach its clocks), W warm-up steps, the K timed steps, `--dump-outputs` -- and that is all of a plain run. `--full` goes on
+with a profiled repeat, the steady-state loop, the pipelined steps, the checks, the other configs, the CPU rows.
 
-    python bench.py                       # 1 GPU, defaults
+`--dump-outputs DIR` writes the distances the last timed step delivered (rank 0's gathered vector at N > 1) to DIR/distances.npy
+as float64; beyond 2 M pairs a fixed sample of them, with their positions in DIR/distances_index.npy. The inputs are seeded
+(`--seed`), so two builds run with the same arguments can be compared output for output.
+
+    python bench.py                       # 1 GPU, defaults: the headline only
+    python bench.py --full                # ... and everything else the line can carry
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N              # the same N ranks: without WORLD_SIZE in the environment the script starts
@@ -183,6 +191,11 @@ def parse_args():
     p.add_argument("--c5-pairs", type=int, default=0, help="at N > 1: total pairs of the C5 strong-scaling entry (default 100 M; testing)")
     p.add_argument("--details-out", default=os.path.join(ROOT, "bench_configs.json"),
                    help="where rank 0 writes the FULL per-config entries, CPU rows and rank list (the stdout line carries their summary only)")
+    p.add_argument("--full", action="store_true",
+                   help="beyond the headline: the profiled repeat (roofline), steady-state and pipelined steps, the oracle check, the other configs, "
+                        "the CPU rows and --details-out; at N > 1 also the gather's checksums and cost, C5 strong scaling and the single-process leg")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the distances of the last timed step to DIR/distances.npy (float64; a fixed sample beyond 2 M pairs)")
     return p.parse_args()
 
 
@@ -596,6 +609,24 @@ def write_details(path, details):
         return f"not written ({error})"
 
 
+DUMP_MAX_VALUES = 1 << 21      # 16 MB of float64 distances (+ 16 MB of positions when sampled): the dump stays under 64 MB
+
+
+def dump_outputs(directory, distances):
+    """--dump-outputs: the distances as float64 (exact for every u32) in DIR/distances.npy. Above DUMP_MAX_VALUES a sample whose
+    positions depend on the count alone (a fixed seed, sorted) is written instead, with those positions in DIR/distances_index.npy."""
+    os.makedirs(directory, exist_ok=True)
+    values = np.asarray(distances)
+    index_path = os.path.join(directory, "distances_index.npy")
+    if values.size > DUMP_MAX_VALUES:
+        index = np.sort(np.random.default_rng(0).choice(values.size, DUMP_MAX_VALUES, replace=False))
+        np.save(index_path, index.astype(np.float64))
+        values = values[index]
+    elif os.path.exists(index_path):
+        os.remove(index_path)      # an earlier run's sample positions do not describe this file
+    np.save(os.path.join(directory, "distances.npy"), values.astype(np.float64))
+
+
 def fit_line(line, world):
     """Serialises the headline line and holds it to its byte budget: what does not fit is dropped from the least important end
     (the per-config map loses its kernel names and times first), never the contract's keys."""
@@ -742,6 +773,8 @@ def run_single_process(args):
     elapsed = time.perf_counter() - start
     shard = scope.shard_timing()
     got = out[:total_pairs].cpu().numpy().astype(np.uint32)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, got)
     parity = None
     if not args.no_cpu_baseline:
         import oracle  # the checker; never on the timed path
@@ -770,9 +803,11 @@ def run_single_process(args):
     print(json.dumps(line), flush=True)
 
 
-def measure(cfg_name, args, env, steps, warmup, prewarm_seconds, steady_seconds, with_pipelined, pairs_arg=None, gather_cost=False, gather_transport=None):
+def measure(cfg_name, args, env, steps, warmup, prewarm_seconds, steady_seconds, with_pipelined, pairs_arg=None, gather_cost=False, gather_transport=None,
+            full=True, keep_result=True):
     """The measurement of one bench config on this rank's GPU (+ the collective at N > 1): returns what the line needs.
-    Every rank makes the same calls in the same order (a step contains the collective)."""
+    Every rank makes the same calls in the same order (a step contains the collective). `full`: the gather's checksums and the
+    profiled repeat too; `keep_result`: the distances of the last timed step are read back (`sync_result`, `delivered`)."""
     torch, dist, sw, sharding = env["torch"], env["dist"], env["sw"], env["sharding"]
     world, rank, device, comm_device, scope = env["world"], env["rank"], env["device"], env["comm_device"], env["scope"]
     cfg = CONFIGS[cfg_name]
@@ -945,21 +980,24 @@ def measure(cfg_name, args, env, steps, warmup, prewarm_seconds, steady_seconds,
     else:
         total_cells = cells
     last_slot = (counter[0] - 1) & 1
-    sync_result = outs[last_slot][:pairs].cpu().numpy().astype(np.uint32)   # produced by the timed steps
+    sync_result = outs[last_slot][:pairs].cpu().numpy().astype(np.uint32) if keep_result else None   # produced by the timed steps
+    # what a caller holds after the last timed step: the distances, at N > 1 on rank 0 the vector gathered there
+    delivered = sync_result
+    if keep_result and world > 1:
+        delivered = None
+        if rank == 0:
+            delivered = (gathers[last_slot].full.cpu().numpy() if strong
+                         else np.concatenate([g.cpu().numpy() for g in gathered[last_slot]])).astype(np.uint32)
 
     # ---- every rank's slice of the gathered vector, against a checksum the rank computed locally ---------------------
     gather_ok = None
-    if world > 1:
+    if world > 1 and full:
         mine = torch.tensor([int(sync_result.astype(np.int64).sum()), int(np.bitwise_xor.reduce(sync_result)) if pairs else 0],
                             dtype=torch.int64, device=comm_device)
         sums = [torch.zeros(2, dtype=torch.int64, device=comm_device) for _ in range(world)]
         dist.all_gather(sums, mine)
         if rank == 0:
-            if strong:
-                full = gathers[last_slot].full.cpu().numpy().astype(np.uint32)
-                slices = [full[l:h] for l, h in ranges]
-            else:
-                slices = [g.cpu().numpy().astype(np.uint32) for g in gathered[last_slot]]
+            slices = [delivered[l:h] for l, h in ranges]
             gather_ok = all(int(s.astype(np.int64).sum()) == int(sums[r][0]) and
                             (int(np.bitwise_xor.reduce(s)) if s.size else 0) == int(sums[r][1]) for r, s in enumerate(slices))
             gather_ok = bool(gather_ok and (slices[0] == sync_result).all())
@@ -995,12 +1033,14 @@ def measure(cfg_name, args, env, steps, warmup, prewarm_seconds, steady_seconds,
 
     # ---- the same steps with the library's hipEvent pairs on (kernel durations on the kernels' own streams) ----------
     # They cost a few microseconds per call, so `value` above comes from the run without them; same calls, same conditions
-    # -- what `rocprofv3 --kernel-trace --stats` of `bench.py --no-pipelined --no-configs --no-cpu-baseline` averages over.
-    scope.set_profiling(True)
-    profiled_elapsed = max_over_ranks(timed_region(steps))
-    totals = scope.timing_totals()
-    sync_timing = scope.last_timing()
-    scope.set_profiling(False)
+    # -- what `rocprofv3 --kernel-trace --stats` of `bench.py --full --no-pipelined --no-configs --no-cpu-baseline` averages over.
+    totals, sync_timing, profiled_elapsed = None, None, None
+    if full:
+        scope.set_profiling(True)
+        profiled_elapsed = max_over_ranks(timed_region(steps))
+        totals = scope.timing_totals()
+        sync_timing = scope.last_timing()
+        scope.set_profiling(False)
 
     # ---- steady state: the same synchronous steps for at least --steady-seconds ---------------------------------------
     steady = None
@@ -1030,7 +1070,7 @@ def measure(cfg_name, args, env, steps, warmup, prewarm_seconds, steady_seconds,
         scope.set_async(False)
     fence()
     return dict(cfg=cfg, workload=workload, strong=strong, a=a, b=b, pairs=pairs, total_pairs=total_pairs, cells=cells, total_cells=total_cells,
-                offsets_dtype=offsets_dtype, n_pieces=len(pieces), elapsed=elapsed, steps=steps, sync_result=sync_result, gather_ok=gather_ok,
+                offsets_dtype=offsets_dtype, n_pieces=len(pieces), elapsed=elapsed, steps=steps, sync_result=sync_result, delivered=delivered, gather_ok=gather_ok,
                 gather=gather, totals=totals, sync_timing=sync_timing, profiled_elapsed=profiled_elapsed, steady=steady, pipelined_rate=pipelined_rate,
                 pipelined_result=pipelined_result, pipelined_ms=pipelined_ms, ranges=ranges)
 
@@ -1137,12 +1177,15 @@ def run(args):
 
     if args.die_rank == rank and args.die_at == "measure":
         os._exit(3)                            # test hook: a rank that dies while the others are in their first collective
-    head = measure(args.config, args, env, args.steps, args.warmup, args.prewarm_seconds, args.steady_seconds, not args.no_pipelined,
-                   pairs_arg=args.pairs, gather_cost=world > 1)
+    head = measure(args.config, args, env, args.steps, args.warmup, args.prewarm_seconds, args.steady_seconds if args.full else 0.0,
+                   args.full and not args.no_pipelined, pairs_arg=args.pairs, gather_cost=args.full and world > 1, full=args.full,
+                   keep_result=args.full or bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head["delivered"])
 
     # ---- N > 1: BASELINE configs[4] beside the headline -- the 100 M short-word pairs, strong scaling -------------------
     c5 = None
-    if world > 1 and args.config == "c2" and not args.no_configs:
+    if world > 1 and args.full and args.config == "c2" and not args.no_configs:
         c5_pairs = args.c5_pairs or CONFIGS["c5"]["pairs"]
         # the entry is what the north star names -- the u32 distances gathered as they are --; the same steps with bytes on the wire
         # (no distance of word-sized pairs exceeds 255; widened on the root) ride beside it as `gather_u8`
@@ -1162,8 +1205,21 @@ def run(args):
 
     line = None
     if rank == 0:
+        cfg, strong, pairs = head["cfg"], head["strong"], head["pairs"]
+        # the headline: all that a plain run measures; --full adds the rest below
+        line = {
+            "metric": "GCUPS (DP cell updates/s) batched Levenshtein", "value": round(head["total_cells"] * args.steps / head["elapsed"] / 1e9, 2),
+            "unit": "GCUPS", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(head["elapsed"] / args.steps * 1e3, 4), "higher_is_better": True, "scaling": cfg["scaling"], "vs_baseline": None,
+            "dtype": "u32", "data": "synthetic", "full": args.full,
+            "config": {"workload": cfg["text"].format(pairs=head["total_pairs"] if strong else pairs) + ", tapes prepared and resident in HBM",
+                       "step": "one synchronous call (results visible on return)" + (" + gather of the u32 distances to rank 0" if world > 1 else ""),
+                       "pairs_per_gpu": pairs, "pairs_total": head["total_pairs"], "cells_per_gpu": head["cells"], "algorithm": args.algorithm,
+                       "offsets": str(head["offsets_dtype"]), "pieces_per_step": head["n_pieces"], "collective": collective_text(strong, world), "seed": args.seed},
+        }
+    if rank == 0 and args.full:
         constants = load_pmc_constants()
-        cfg, strong, pairs, cells = head["cfg"], head["strong"], head["pairs"], head["cells"]
+        cells = head["cells"]
         n_pieces = head["n_pieces"]
         totals, sync_timing = head["totals"], head["sync_timing"]
         calls_timed = max(totals["calls"], 1)
@@ -1235,8 +1291,7 @@ def run(args):
         if not args.no_cpu_baseline and world == 1:   # the CPU baseline is timed at N = 1 only
             cpu_baselines = cpu_rows(head["a"], head["b"], budget_s=args.cpu_seconds)
             cpu_baseline = {k: v for k, v in cpu_baselines[0].items() if k != "name"}
-        elapsed, steady = head["elapsed"], head["steady"]
-        ms_per_step = elapsed / args.steps * 1e3
+        steady = head["steady"]
         # the full entries (--details-out, stderr) ...
         details = {
             "headline": {"config": args.config, "workload": cfg["text"].format(pairs=head["total_pairs"] if strong else pairs) + ", tapes prepared and resident in HBM",
@@ -1250,17 +1305,9 @@ def run(args):
                          "device_prewarm_s": args.prewarm_seconds, "roofline": roofline, "gather": head["gather"]},
             "configs": leg_entries or [], "cpu_baselines": cpu_baselines or [], "ranks_seen": ranks_seen,
         }
-        # ... and the headline line: the contract's keys, every number of the roofline object, one summary per config
-        line = {
-            "metric": "GCUPS (DP cell updates/s) batched Levenshtein", "value": round(head["total_cells"] * args.steps / elapsed / 1e9, 2),
-            "unit": "GCUPS", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": cfg["scaling"], "vs_baseline": None,
-            "dtype": "u32", "data": "synthetic",
+        # ... and in the headline line: every number of the roofline object, one summary per config
+        line.update({
             "value_steady": steady["value"] if steady else None, "value_pipelined": head["pipelined_rate"],
-            "config": {"workload": cfg["text"].format(pairs=head["total_pairs"] if strong else pairs) + ", tapes prepared and resident in HBM",
-                       "step": "one synchronous call (results visible on return)" + (" + gather of the u32 distances to rank 0" if world > 1 else ""),
-                       "pairs_per_gpu": pairs, "pairs_total": head["total_pairs"], "cells_per_gpu": cells, "algorithm": args.algorithm,
-                       "offsets": str(head["offsets_dtype"]), "pieces_per_step": n_pieces, "collective": collective_text(strong, world), "seed": args.seed},
             "roofline": compact_roofline(roofline),
             "cpu_baseline": {k: (v[:200] if isinstance(v, str) else v) for k, v in cpu_baseline.items()} if cpu_baseline else None,
             "cpu_baselines": {row["name"]: {"value": row["value"], "cores": row["cores"]} for row in cpu_baselines} if cpu_baselines else None,
@@ -1268,11 +1315,11 @@ def run(args):
             "parity_vs_oracle": parity, "gather_ok": head["gather_ok"],
             "gather": {k: head["gather"][k] for k in ("exposed_ms_per_step", "alone_ms", "transport", "bytes_to_root_per_step", "compute_only_ms_per_step")} if head["gather"] else None,
             "ranks_seen": {k: ranks_seen[k] for k in ("world_size", "backend", "rccl_version", "distinct_devices")} if ranks_seen else None,
-        }
+        })
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if line is not None and world > 1 and not args.no_single_process:
+    if line is not None and world > 1 and args.full and not args.no_single_process:
         # The in-library multi-device path (one scope over all N devices, ncclSend / ncclRecv inside csrc/sharded.hip) on the same
         # devices, once the ranks are done with them: a CHILD process of rank 0 (never an exec), bounded by a timeout so that a
         # hang there cannot cost the line. The other ranks have nothing left to do and exit.
@@ -1297,9 +1344,10 @@ def run(args):
         details["single_process"] = child
         line["single_process"] = compact_single_process(child)
     if line is not None:
-        for entry in details["configs"]:                     # one short line per config, before the headline line
-            print(json.dumps({"leg": entry["config"], **compact_leg(entry)}), flush=True)
-        line["details"] = write_details(args.details_out, details)
+        if args.full:
+            for entry in details["configs"]:                     # one short line per config, before the headline line
+                print(json.dumps({"leg": entry["config"], **compact_leg(entry)}), flush=True)
+            line["details"] = write_details(args.details_out, details)
         print(fit_line(line, world), flush=True)
 
 

@@ -8,6 +8,8 @@ import subprocess
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -111,6 +113,27 @@ def test_pmc_constants_folds_counter_passes(tmp_path):
                     "--calls", "1", "--variant", "k8", "--out", str(out)], check=True, capture_output=True)
     book = json.load(open(out))["kernels"]
     assert set(book) == {"bitparallel_tiled|tokens64", "bitparallel_tiled|tokens64|k8"} and abs(book["bitparallel_tiled|tokens64|k8"]["valu_insts"] - 246e6) < 1
+
+
+def test_bench_dump_outputs_are_float64_and_a_fixed_sample_when_large(tmp_path, monkeypatch):
+    """--dump-outputs: the distances as float64 (exact for u32). Above DUMP_MAX_VALUES a sample whose positions depend on the count
+    alone is written with those positions, under 64 MB in all; a later dump that needs no sample leaves no stale positions behind.
+    A plain run is the default: `--full` is off unless given."""
+    bench = load(os.path.join(ROOT, "bench.py"), "bench_module_dump")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench.parse_args()
+    assert args.full is False and args.dump_outputs is None and args.steps == 3
+    big = np.arange(3 * bench.DUMP_MAX_VALUES, dtype=np.uint32)[::-1].copy()
+    bench.dump_outputs(str(tmp_path), big)
+    values, index = np.load(tmp_path / "distances.npy"), np.load(tmp_path / "distances_index.npy")
+    assert values.dtype == index.dtype == np.float64 and values.shape == index.shape == (bench.DUMP_MAX_VALUES,)
+    assert (np.diff(index) > 0).all() and (values == big[index.astype(np.int64)]).all()
+    assert sum(os.path.getsize(tmp_path / name) for name in os.listdir(tmp_path)) <= 64 << 20
+    bench.dump_outputs(str(tmp_path / "again"), np.zeros(big.size, dtype=np.uint32))
+    assert (np.load(tmp_path / "again" / "distances_index.npy") == index).all()
+    small = np.array([0, 7, 2 ** 32 - 1], dtype=np.uint32)
+    bench.dump_outputs(str(tmp_path), small)
+    assert (np.load(tmp_path / "distances.npy") == small.astype(np.float64)).all() and not (tmp_path / "distances_index.npy").exists()
 
 
 def test_bench_refuses_a_world_size_other_than_gpus():

@@ -2211,8 +2211,35 @@ def bench_stdout(done):
     return [r for r in rows[:-1] if "leg" in r], rows[-1], len(done.stdout.splitlines()[-1])
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_what_it_computed(tmp_path, sw, orc):
+    """A plain `bench.py --steps K --warmup W` (scaled down): ONE stdout line with the contract's keys, `steps` = K and `value` / `ms_per_step`
+    from the same K steps, nothing of what `--full` adds (no roofline, configs, CPU rows or details file). `--dump-outputs` writes the
+    distances of the last timed step as float64, equal to the oracle's on the same seeded pairs."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    details_path = tmp_path / "bench_configs.json"
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--pairs", "50000", "--steps", "7", "--warmup", "2", "--prewarm-seconds", "0.05",
+           "--seed", "42", "--details-out", str(details_path), "--dump-outputs", str(out)]
+    done = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert done.returncode == 0, (done.stdout[-1000:], done.stderr[-3000:])
+    rows = [json.loads(l) for l in done.stdout.splitlines() if l.startswith("{")]
+    assert len(rows) == 1, done.stdout[-2000:]
+    line = rows[0]
+    assert line["unit"] == "GCUPS" and line["higher_is_better"] is True and line["dtype"] == "u32" and line["metric"].startswith("GCUPS")
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["full"] is False and line["value"] > 0 and line["ms_per_step"] > 0
+    assert abs(line["value"] - line["config"]["cells_per_gpu"] * 7 / (line["ms_per_step"] * 7e-3) / 1e9) < 0.02 * line["value"]
+    assert not {"roofline", "configs", "cpu_baseline", "cpu_baselines", "value_steady", "value_pipelined", "details"} & set(line), sorted(line)
+    assert not details_path.exists()
+    got = np.load(out / "distances.npy")
+    a, b = sw.generate_pairs("tokens64", 50000, seed=42)
+    assert got.dtype == np.float64 and got.shape == (50000,) and not (out / "distances_index.npy").exists()
+    assert (got == orc.levenshtein_pairs(a, b, algo="hyyro")).all()
+
+
 def test_bench_line_is_short_and_the_details_carry_every_config(tmp_path):
-    """`bench.py` as the driver runs it at N = 1 (scaled down). The LAST stdout line is the headline only -- the contract's keys, the
+    """`bench.py --full` at N = 1 (scaled down). The LAST stdout line is the headline only -- the contract's keys, the
     full roofline numbers, `cpu_baseline`, one {value, frac, parity} summary per config -- and fits 6 KB (the driver could not parse
     round 5's 24 KB line); one short `{"leg": ...}` line per config precedes it; the full entries (C1, C3 prepared and raw, C4 linear /
     affine / full byte alphabet, C5, Smith-Waterman, the cross-product call: rate, kernel time, roofline object, parity sample) and the
@@ -2221,7 +2248,7 @@ def test_bench_line_is_short_and_the_details_carry_every_config(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     details_path = str(tmp_path / "bench_configs.json")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--pairs", "50000", "--steps", "5", "--warmup", "1", "--prewarm-seconds", "0.05",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--pairs", "50000", "--steps", "5", "--warmup", "1", "--prewarm-seconds", "0.05",
            "--steady-seconds", "0.05", "--cpu-seconds", "0.2", "--leg-pairs", "600", "--details-out", details_path]
     done = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert done.returncode == 0, (done.stdout[-1000:], done.stderr[-3000:])
@@ -2253,24 +2280,33 @@ def test_bench_line_is_short_and_the_details_carry_every_config(tmp_path):
 
 
 @pytest.mark.parametrize("config,pairs", [("c2", 60_000), ("c5", 600_000)])
-def test_bench_two_ranks_share_the_gpu(config, pairs):
-    """`bench.py` as the driver launches it for N > 1 -- one process per rank under torch.distributed -- with both ranks on
+def test_bench_two_ranks_share_the_gpu(config, pairs, tmp_path, sw, orc):
+    """`bench.py --full` as the driver launches it for N > 1 -- one process per rank under torch.distributed -- with both ranks on
     cuda:0 and gloo in RCCL's place (one-GPU boxes): the sharding, the pipelined steps, the gather (weak: `dist.gather`;
     strong: the chunked send/recv of cells-balanced shards) and its checksums run for real; rank 0's shard is compared with
-    the oracle."""
+    the oracle, and so is the whole gathered vector that `--dump-outputs` writes."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     port = 29600 + (os.getpid() % 300) + (0 if config == "c2" else 1)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--config", config, "--pairs", str(pairs),
-           "--steps", "3", "--warmup", "1", "--backend", "gloo", "--share-gpu", "--details-out", ""]
+           "--steps", "3", "--warmup", "1", "--backend", "gloo", "--share-gpu", "--full", "--details-out", "", "--seed", "42",
+           "--dump-outputs", str(tmp_path)]
     done = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert done.returncode == 0, (done.stdout[-1000:], done.stderr[-3000:])
     _, line, line_bytes = bench_stdout(done)
     assert line_bytes <= 8192, line_bytes
     assert line["n_gpus"] == 2 and line["gather_ok"] is True and line["parity_vs_oracle"] is True
     assert line["scaling"] == ("weak" if config == "c2" else "strong") and line["value"] > 0
+    from stringwars_amd import sharding
+    if config == "c2":     # weak: rank r scored pairs [r * P, (r + 1) * P) of the seeded stream
+        want = np.concatenate([orc.levenshtein_pairs(*sw.generate_pairs("tokens64", pairs, seed=42, first=sharding.weak_shard_first(r, pairs)), algo="hyyro")
+                               for r in range(2)])
+    else:                  # strong: the ranks split the stream of `pairs` pairs
+        want = orc.levenshtein_pairs(*sw.generate_pairs("short_words", pairs, seed=42), algo="hyyro")
+    got = np.load(tmp_path / "distances.npy")
+    assert got.dtype == np.float64 and (got == want).all()
 
 
 def test_bench_starts_two_ranks_by_itself(tmp_path):
@@ -2285,7 +2321,7 @@ def test_bench_starts_two_ranks_by_itself(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     details_path = str(tmp_path / "bench_configs.json")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--pairs", "60000", "--c5-pairs", "700000", "--steps", "3", "--warmup", "1",
-           "--prewarm-seconds", "0.05", "--steady-seconds", "0.05", "--backend", "gloo", "--share-gpu", "--details-out", details_path]
+           "--prewarm-seconds", "0.05", "--steady-seconds", "0.05", "--backend", "gloo", "--share-gpu", "--full", "--details-out", details_path]
     done = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert done.returncode == 0, (done.stdout[-1000:], done.stderr[-3000:])
     legs, line, line_bytes = bench_stdout(done)
@@ -2325,7 +2361,7 @@ def test_bench_failures_at_two_ranks_end_with_a_line():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--pairs", "30000", "--steps", "2", "--warmup", "1", "--prewarm-seconds", "0.05",
-            "--steady-seconds", "0.05", "--backend", "gloo", "--share-gpu", "--no-configs", "--no-cpu-baseline", "--details-out", ""]
+            "--steady-seconds", "0.05", "--backend", "gloo", "--share-gpu", "--full", "--no-configs", "--no-cpu-baseline", "--details-out", ""]
     for at in ("after-init", "measure"):
         started = time.time()
         done = subprocess.run(base + ["--die-rank", "1", "--die-at", at, "--collective-timeout", "40", "--launch-timeout", "200"],
@@ -2339,19 +2375,22 @@ def test_bench_failures_at_two_ranks_end_with_a_line():
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["gather_ok"] is True and "error" in line["single_process"], line.get("single_process")
 
 
-def test_bench_single_process_mode():
+def test_bench_single_process_mode(tmp_path, sw, orc):
     """`bench.py --gpus 3 --single-process --config c5`: one process, one scope over three member devices (all of them device 0 on
-    this box), `swh_sharded_prepare_*` + `swh_levenshtein_pairs_sharded` per step with the self-check on every call."""
+    this box), `swh_sharded_prepare_*` + `swh_levenshtein_pairs_sharded` per step with the self-check on every call; `--dump-outputs`
+    writes the distances the last step left on the first device."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "3", "--single-process", "--share-gpu", "--config", "c5", "--pairs", "900000",
-           "--steps", "3", "--warmup", "1", "--prewarm-seconds", "0.05"]
+           "--steps", "3", "--warmup", "1", "--prewarm-seconds", "0.05", "--seed", "42", "--dump-outputs", str(tmp_path)]
     done = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert done.returncode == 0, (done.stdout[-1000:], done.stderr[-3000:])
     line = json.loads([l for l in done.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 3 and line["mode"] == "single-process" and line["scaling"] == "strong" and line["parity_vs_oracle"] is True
     assert line["config"]["shard_cuts"][0] == 0 and line["config"]["shard_cuts"][-1] == 900000 and line["value"] > 0
+    got = np.load(tmp_path / "distances.npy")
+    assert got.dtype == np.float64 and (got == orc.levenshtein_pairs(*sw.generate_pairs("short_words", 900000, seed=42), algo="hyyro")).all()
 
 
 @pytest.mark.parametrize("local", [False, True])

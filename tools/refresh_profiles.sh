@@ -48,14 +48,14 @@ done
 if [ "${REFRESH_PMC_ONLY:-0}" = 1 ]; then rm -rf "$OUT"/pmc_*/; ls "$OUT"; exit 0; fi
 # 2. rocprofv3 --kernel-trace --stats of the bench command (synchronous steps only: what `roofline.kernel_ms` averages over) and of every leg
 stats() { name=$1; shift; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rp_$name" -o "$name" -- python3 "$@" > "$OUT/rp_$name.log" 2>&1; cp "$OUT/rp_$name/${name}_kernel_stats.csv" "$OUT/${name}_kernel_stats.csv" 2>/dev/null; rm -rf "$OUT/rp_$name"; }
-stats bench_c2_sync "$REPO/bench.py" --no-cpu-baseline --no-configs --no-pipelined
-stats bench_c2_full "$REPO/bench.py" --no-cpu-baseline --no-configs
+stats bench_c2_sync "$REPO/bench.py" --full --no-cpu-baseline --no-configs --no-pipelined
+stats bench_c2_full "$REPO/bench.py" --full --no-cpu-baseline --no-configs
 for leg in $LEGS; do stats leg_$leg "$REPO/bench.py" --only-config $leg --no-cpu-baseline; done
 # 3. the bench lines themselves, with the fresh constants in place
 cd "$REPO"
 mkdir -p profiles/r6 && cp "$OUT/pmc_constants.json" profiles/r6/pmc_constants.json
-timeout -k 10 900 python3 bench.py --details-out "$OUT/bench_configs.json" > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
-timeout -k 10 400 python3 bench.py --config c5 --steps 20 --warmup 2 --no-cpu-baseline --no-configs > "$OUT/bench_c5_100m.json" 2> "$OUT/bench_c5_100m.err"
+timeout -k 10 900 python3 bench.py --full --details-out "$OUT/bench_configs.json" > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
+timeout -k 10 400 python3 bench.py --full --config c5 --steps 20 --warmup 2 --no-cpu-baseline --no-configs > "$OUT/bench_c5_100m.json" 2> "$OUT/bench_c5_100m.err"
 timeout -k 10 300 python3 tools/bench_cross.py > "$OUT/crossproduct_table.jsonl" 2> "$OUT/cross.err"
 timeout -k 10 300 python3 tools/bench_bounds.py > "$OUT/bounds_table.jsonl" 2> "$OUT/bounds.err"
 timeout -k 10 300 python3 tools/bench_bounds.py --bytes >> "$OUT/bounds_table.jsonl" 2>> "$OUT/bounds.err"
