@@ -206,6 +206,34 @@ swh_status_t swh_levenshtein_cross_prepared(swh_levenshtein_t engine, swh_scope_
                                             const swh_prepared_view_t *b, size_t *out, size_t row_stride_bytes,
                                             const char **error);
 
+/* ---- Top-k search: the k nearest candidates of every query (rapidfuzz `process.extract(query, choices, limit=k,
+ *      score_cutoff=bound)` with the Levenshtein distance as the scorer, for every query at once). --------------------------
+ * For every query i, the k candidates j with the smallest key (d(i, j), j) among those with d(i, j) <= bound:
+ *  - ascending by distance; ties break by the SMALLER candidate index, so every row is unique and exactly checkable;
+ *  - d is the engine's own cost model (unit costs or match / mismatch / open / extend); symbols are bytes, or code points in
+ *    the UTF-8 variant (invalid UTF-8 -> swh_invalid_utf8_k); the prepared variant takes what the tapes were prepared as;
+ *  - bound == SWH_UNBOUNDED means no cutoff;
+ *  - a row with fewer than k admissible candidates is padded with index 0xFFFFFFFF and distance 0xFFFFFFFF;
+ *  - 1 <= k <= SWH_TOPK_MAX; any other k returns swh_invalid_argument_k;
+ *  - candidates == NULL means queries x queries, diagonal included (a string's distance to itself is 0);
+ *  - candidates->count must be below 0xFFFFFFFF; queries->count x candidates->count has NO 2^32 limit (the matrix is never built);
+ *  - `indices` and `distances` are uint32_t arrays of queries->count x k, row-major and contiguous, in host or device memory;
+ *  - queries->count == 0 succeeds and does nothing; candidates->count == 0 makes every row padding.
+ * The call is synchronous on every scope: on an asynchronous or pipelined scope it first joins the outstanding work (as
+ * swh_scope_synchronize) and returns with the results visible. With profiling on, swh_scope_last_timing describes the whole
+ * search: `cells` = sum len(q) len(c) over all pairs; `dominant_name` is "cross_topk" for the fused word-sized kernel, or
+ * "topk_select/<kernel>" for the general path (the candidates scored in slices, <kernel> the longest scoring kernel). */
+#define SWH_TOPK_MAX 64
+swh_status_t swh_levenshtein_topk_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *queries,
+                                          const swh_tape_u64_t *candidates, size_t k, uint32_t bound,
+                                          uint32_t *indices, uint32_t *distances, const char **error);
+swh_status_t swh_levenshtein_utf8_topk_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *queries,
+                                               const swh_tape_u64_t *candidates, size_t k, uint32_t bound,
+                                               uint32_t *indices, uint32_t *distances, const char **error);
+swh_status_t swh_levenshtein_topk_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *queries,
+                                           const swh_prepared_view_t *candidates, size_t k, uint32_t bound,
+                                           uint32_t *indices, uint32_t *distances, const char **error);
+
 /* ---- One batch over the GPUs of a multi-device scope (BASELINE config 5). --------------------------------
  * `swh_sharded_prepare_*`: HOST tapes of equal count are cut into contiguous shards balanced on the prefix sum of
  * len(a_i)*len(b_i) (DP cells, not pair counts); shard r is uploaded to and prepared on device r. The handle is the steady
@@ -309,7 +337,8 @@ swh_status_t swh_sw_pairs_sharded(swh_sw_t engine, swh_scope_t scope, swh_sharde
 
 /* ---- Introspection: `log_stringzilla_metadata` (utils.rs:78-92). --------------------------- */
 const char *swh_version(void);
-/* Comma-separated capability string, e.g. "gfx950,hip,wavefront,bitparallel,banded,utf8,...". */
+/* Comma-separated capability string, e.g. "gfx950,hip,wavefront,bitparallel,banded,utf8,...";
+ * "topk" when the swh_levenshtein_topk_* calls are present. */
 const char *swh_capabilities(void);
 
 #ifdef __cplusplus

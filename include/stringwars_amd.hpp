@@ -208,6 +208,23 @@ public:
         swh_status_t status__ = swh_levenshtein_cross_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, matrix, row_stride_bytes, &err);
         check(status__, err);
     }
+    /// Top-k search (swh_levenshtein_topk_*): the k nearest candidates of every query, `indices` / `distances` of
+    /// queries.count x k (host or device memory); rows ascending by (distance, index), only d <= bound, padded with 0xFFFFFFFF.
+    void topk(const DeviceScope &scope, const BytesTapeView &queries, const BytesTapeView *candidates, size_t k, uint32_t *indices,
+              uint32_t *distances, uint32_t bound = SWH_UNBOUNDED) const {
+        const char *err = nullptr;
+        swh_tape_u64_t q = queries.c(), c = candidates ? candidates->c() : q;
+        auto fn = utf8_ ? swh_levenshtein_utf8_topk_u64tape : swh_levenshtein_topk_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &q, candidates ? &c : nullptr, k, bound, indices, distances, &err);
+        check(status__, err);
+    }
+    void topk(const DeviceScope &scope, const PreparedTape &queries, const PreparedTape *candidates, size_t k, uint32_t *indices,
+              uint32_t *distances, uint32_t bound = SWH_UNBOUNDED) const {
+        const char *err = nullptr;
+        swh_prepared_view_t q = queries.c(), c = candidates ? candidates->c() : q;
+        swh_status_t status__ = swh_levenshtein_topk_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, k, bound, indices, distances, &err);
+        check(status__, err);
+    }
     /// `compute_into` over every GPU of a multi-device scope: each device fills its rows of the matrix.
     void compute_into(const DeviceScope &scope, const ShardedCross &product, size_t *matrix, size_t row_stride_bytes = 0) const {
         const char *err = nullptr;

@@ -50,6 +50,7 @@ STATUS_NAMES = {
     5: "no_device", 6: "device_error", 7: "not_implemented", 8: "rccl_error",
 }
 UNBOUNDED = 0xFFFFFFFF
+TOPK_MAX = 64   # SWH_TOPK_MAX: the largest k of a top-k search
 ALGORITHM_AUTO, ALGORITHM_WAVEFRONT, ALGORITHM_BITPARALLEL, ALGORITHM_TILED = 0, 1, 2, 3
 
 
@@ -170,6 +171,9 @@ SIGNATURES = {
     "swh_nw_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, C.c_size_t, _ERR]),
     "swh_sw_pairs_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, C.c_size_t, _ERR]),
     "swh_sw_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_topk_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_size_t, C.c_uint32, _P, _P, _ERR]),
+    "swh_levenshtein_utf8_topk_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_size_t, C.c_uint32, _P, _P, _ERR]),
+    "swh_levenshtein_topk_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_size_t, C.c_uint32, _P, _P, _ERR]),
     "swh_version": (C.c_char_p, []),
     "swh_capabilities": (C.c_char_p, []),
     # harness header

@@ -1100,7 +1100,7 @@ using namespace swh;
 extern "C" {
 
 const char *swh_version(void) { return "0.1.0"; }
-const char *swh_capabilities(void) { return "gfx950,hip,wavefront,bitparallel,tiled,banded,utf8,bounded,nw-linear,nw-affine,sw-linear,sw-affine,cross,prepared,multi-gpu-rccl"; }
+const char *swh_capabilities(void) { return "gfx950,hip,wavefront,bitparallel,tiled,banded,utf8,bounded,nw-linear,nw-affine,sw-linear,sw-affine,cross,prepared,topk,multi-gpu-rccl"; }
 
 static swh_status_t scope_init(int device, void *stream, bool borrow, swh_scope_t *out, const char **error) {
     if (!out) return fail(error, swh_invalid_argument_k, "null scope pointer");
@@ -1181,6 +1181,7 @@ swh_status_t swh_scope_free(swh_scope_t handle) {
     if (scope->utf8_status) (void)hipFree(scope->utf8_status);
     if (scope->stage) (void)hipFree(scope->stage);
     if (scope->boundary) (void)hipFree(scope->boundary);
+    if (scope->topk_scratch) (void)hipFree(scope->topk_scratch);
     if (scope->plan_host) (void)hipHostFree(scope->plan_host);
     if (scope->summary_host) (void)hipHostFree(scope->summary_host);
     if (scope->plan_area) (void)hipFree(scope->plan_area);
@@ -1785,6 +1786,246 @@ swh_status_t swh_sw_pairs_prepared(swh_sw_t e, swh_scope_t s, const swh_prepared
 swh_status_t swh_sw_cross_prepared(swh_sw_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b, ptrdiff_t *out,
                                    size_t row_stride, const char **error) {
     return prepared_call(e, 2, s, a, b, true, SWH_UNBOUNDED, out, row_stride, error);
+}
+
+// ---- top-k search (topk.hip) ----------------------------------------------------------------------------------------------------------
+// Word-sized byte strings on unit costs run the fused kernel (k_cross_topk): the search a dense cross-product of the same views would run
+// on k_cross_short (run_call_on's route choice for prepared tapes). Everything else takes the general path: the candidates in slices,
+// each slice scored by the ordinary cross-product routes into a u32 matrix in scratch (with the caller's bound, so long strings may take
+// the banded kernel), then folded into the running lists by k_topk_select.
+static bool topk_fused_route(const Engine *engine, const Prepared *pq, const Prepared *pc, bool utf8, uint32_t bound) {
+    if (engine->kind != 0 || !engine->unit_costs || engine->algorithm != swh_algorithm_auto_k || utf8) return false;
+    if (pq->off64 != pc->off64 || short_route_choice() == 2) return false;
+    const uint32_t longest = std::max(pq->longest_bytes, pc->longest_bytes);
+    const bool band_pays = bound <= 63 ? longest > 32 : bound <= band_max_bound() && band_cost(bound) < 28u * ((longest + 31) >> 5);
+    return !band_pays && longest <= tiled_longest_limit() && longest <= 32;
+}
+// STRINGWARS_AMD_TOPK_PRUNE=0 (test library): the fused kernel walks every chunk, also those the length bound rules out (the comparison knob)
+static uint32_t topk_prune() {
+    static const uint32_t on = [] { const char *e = test_hook("STRINGWARS_AMD_TOPK_PRUNE"); return !e || atoi(e) != 0 ? 1u : 0u; }();
+    return on;
+}
+// STRINGWARS_AMD_TOPK_ROUTE=select (test library): every search on the general path
+static bool topk_force_select() {
+    static const bool on = [] { const char *e = test_hook("STRINGWARS_AMD_TOPK_ROUTE"); return e && !strcmp(e, "select"); }();
+    return on;
+}
+
+struct TopkRequest {
+    const Prepared *pq, *pc;
+    size_t q_first, q_count, c_first, c_count;
+    uint32_t k, bound;
+    uint32_t *indices, *distances;
+};
+
+static swh_status_t topk_run(Scope *scope, const Engine *engine, const TopkRequest &r, const char **error) {
+    harvest_timing(scope, false);
+    scope->stamps_used = 0;
+    scope->last_timing = swh_timing_t{};
+    const uint64_t nq = r.q_count, nc = r.c_count, k = r.k;
+    if (nq == 0) return swh_success_k;
+    const bool utf8 = r.pq->utf8 && !(r.pq->ascii && r.pc->ascii && r.pq->off64 == r.pc->off64);
+    const uint64_t cap = r.bound == SWH_UNBOUNDED ? ~0ull : ((uint64_t)r.bound + 1) << 32;
+    const size_t out_bytes = nq * k * sizeof(uint32_t);
+    try {
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        const bool dev_i = is_device_pointer(r.indices), dev_d = is_device_pointer(r.distances);
+        if (nc == 0) {   // every row is padding
+            if (dev_i) SWH_HIP_CHECK(hipMemsetAsync(r.indices, 0xFF, out_bytes, stream)); else memset(r.indices, 0xFF, out_bytes);
+            if (dev_d) SWH_HIP_CHECK(hipMemsetAsync(r.distances, 0xFF, out_bytes, stream)); else memset(r.distances, 0xFF, out_bytes);
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            return swh_success_k;
+        }
+        auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
+        const size_t ow = r.pq->off64 ? 8 : 4;
+        auto view = [&](const Prepared *p, size_t first, size_t count) {
+            TapeRef t;
+            t.data = p->bytes.data; t.offsets = (const char *)p->bytes.offsets + first * ow; t.count = count;
+            return t;
+        };
+        auto finish_outputs = [&](uint32_t *ind, uint32_t *dist) {
+            if (!dev_i) SWH_HIP_CHECK(hipMemcpyAsync(r.indices, ind, out_bytes, hipMemcpyDeviceToHost, stream));
+            if (!dev_d) SWH_HIP_CHECK(hipMemcpyAsync(r.distances, dist, out_bytes, hipMemcpyDeviceToHost, stream));
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        };
+
+        if (!topk_force_select() && topk_fused_route(engine, r.pq, r.pc, utf8, r.bound)) {
+            // ---- fused: slices enough for ~32 items per compute unit (a few rounds of its 12 wave slots: 65 536 x 1 M words ran at 4.6
+            // TCUPS with 16, 5.9 with 32); the partial lists stay under 256 MB ------------------------------------------------------------
+            const uint64_t qblocks = (nq + 15) / 16, chunks = (nc + 63) / 64;
+            const uint64_t target = (uint64_t)scope->compute_units * 32;
+            uint64_t slices = std::min<uint64_t>(std::max<uint64_t>((target + qblocks - 1) / qblocks, 1), chunks);
+            slices = std::max<uint64_t>(1, std::min<uint64_t>(slices, ((uint64_t)256 << 20) / (nq * k * 8)));
+            const uint64_t slice_chunks = (chunks + slices - 1) / slices;
+            slices = (chunks + slice_chunks - 1) / slice_chunks;
+            const size_t need = (slices > 1 ? pad(nq * slices * k * 8) : 0) + (dev_i ? 0 : pad(out_bytes)) + (dev_d ? 0 : pad(out_bytes));
+            ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
+            Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
+            TopkLaunch t{};
+            t.a = view(r.pq, r.q_first, nq); t.b = view(r.pc, r.c_first, nc);
+            t.off64 = r.pq->off64; t.k = (uint32_t)k; t.slices = (uint32_t)slices; t.prune = topk_prune();
+            t.slice_chunks = slice_chunks; t.cap = cap;
+            t.partial = slices > 1 ? sc.take<uint64_t>(nq * slices * k) : nullptr;
+            t.indices = dev_i ? r.indices : sc.take<uint32_t>(nq * k);
+            t.distances = dev_d ? r.distances : sc.take<uint32_t>(nq * k);
+            scope->summary_slot = 0;
+            launch_cross_topk(scope, t);
+            finish_outputs(t.indices, t.distances);
+            const CallSummary sm = scope->summary_host[0];
+            if (!sm.violation) {
+                if (scope->profiling && scope->stamps_used) {
+                    collect_timing(scope);
+                    scope->totals.total_ms += scope->last_timing.total_ms;
+                    scope->totals.dominant_ms += scope->last_timing.dominant_ms;
+                    scope->totals.compute_ms += scope->last_timing.compute_ms;
+                    scope->totals.calls += 1;
+                }
+                scope->last_timing.cells = sm.cells;
+                scope->last_timing.bytes = r.pq->total_bytes + r.pc->total_bytes + (nq + nc) * ow + 2 * out_bytes;
+                return swh_success_k;
+            }
+            // a string longer than the kernel takes (the memory of a prepared tape changed since it was measured): the general path
+            scope->stamps_used = 0;
+            scope->last_timing = swh_timing_t{};
+        }
+
+        // ---- general path: query blocks of at most 2^18 rows x candidate slices of at most 2^26 pairs (a 256 MB u32 matrix) ----------------
+        const uint64_t q_step = std::min<uint64_t>(nq, (uint64_t)1 << 18);
+        const uint64_t c_step = std::max<uint64_t>(1, std::min<uint64_t>(nc, ((uint64_t)1 << 26) / q_step));
+        const size_t need = pad(q_step * c_step * 4) + pad(q_step * k * 8) + (dev_i ? 0 : pad(out_bytes)) + (dev_d ? 0 : pad(out_bytes));
+        ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
+        Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
+        uint32_t *matrix = sc.take<uint32_t>(q_step * c_step);
+        uint64_t *lists = sc.take<uint64_t>(q_step * k);
+        uint32_t *ind = dev_i ? r.indices : sc.take<uint32_t>(nq * k);
+        uint32_t *dist = dev_d ? r.distances : sc.take<uint32_t>(nq * k);
+        const swh_timing_totals_t totals_before = scope->totals;
+        swh_timing_t sum{};
+        char scoring_name[64] = "";
+        for (uint64_t q0 = 0; q0 < nq; q0 += q_step) {
+            const uint64_t rows = std::min<uint64_t>(q_step, nq - q0);
+            SWH_HIP_CHECK(hipMemsetAsync(lists, 0xFF, rows * k * 8, stream));
+            for (uint64_t c0 = 0; c0 < nc; c0 += c_step) {
+                const uint64_t columns = std::min<uint64_t>(c_step, nc - c0);
+                CallSpec spec{};
+                spec.a = HostTape{nullptr, nullptr, (size_t)rows, 0};
+                spec.b = HostTape{nullptr, nullptr, (size_t)columns, 0};
+                spec.cross = true; spec.utf8 = r.pq->utf8; spec.bound = r.bound;
+                spec.out = matrix; spec.out_stride = 4; spec.row_stride = columns * 4; spec.out64 = false;
+                spec.pa = r.pq; spec.pb = r.pc; spec.a_first = r.q_first + q0; spec.b_first = r.c_first + c0;
+                const swh_status_t status = run_call_on(scope, engine, spec, error);
+                if (status != swh_success_k) return status;
+                const swh_timing_t &dp = scope->last_timing;
+                sum.cells += dp.cells; sum.bytes += dp.bytes;
+                sum.total_ms += dp.total_ms; sum.compute_ms += dp.compute_ms; sum.kernels += dp.kernels;
+                if (dp.dominant_ms > sum.dominant_ms) { sum.dominant_ms = dp.dominant_ms; snprintf(scoring_name, sizeof scoring_name, "%s", dp.dominant_name); }
+                scope->stamps_used = 0;
+                scope->stamps_pending = false;
+                launch_topk_select(scope, matrix, rows, columns, q0, c0, (uint32_t)k, cap, lists, c0 + columns == nc, ind, dist);
+                if (scope->profiling) {
+                    SWH_HIP_CHECK(hipStreamSynchronize(stream));
+                    collect_timing(scope);
+                    sum.total_ms += scope->last_timing.total_ms; sum.compute_ms += scope->last_timing.compute_ms; sum.kernels += 1;
+                    scope->stamps_used = 0;
+                }
+            }
+        }
+        finish_outputs(ind, dist);
+        scope->summary_pending = false;
+        scope->stamps_pending = false;
+        // the search as one call: its name says which path ran and which kernel scored the pairs
+        snprintf(sum.dominant_name, sizeof sum.dominant_name, "topk_select/%s", scoring_name);
+        scope->last_timing = sum;
+        if (scope->profiling) {
+            scope->totals = totals_before;
+            scope->totals.total_ms += sum.total_ms; scope->totals.dominant_ms += sum.dominant_ms; scope->totals.compute_ms += sum.compute_ms;
+            scope->totals.calls += 1;
+        }
+        return swh_success_k;
+    } catch (const HipFailure &f) {
+        return fail_hip(error, f);
+    } catch (const std::bad_alloc &) {
+        return fail(error, swh_bad_alloc_k, "host allocation failed");
+    }
+}
+
+// The call is synchronous on every scope: outstanding asynchronous / pipelined work is joined first, and the search runs on the scope
+// itself (not on a pipeline lane) with the asynchronous mode held off until it returns.
+struct TopkModeGuard {
+    Scope *scope; bool async, pipelined;
+    explicit TopkModeGuard(Scope *s) : scope(s), async(s->async), pipelined(s->pipelined) { s->async = false; s->pipelined = false; }
+    ~TopkModeGuard() { scope->async = async; scope->pipelined = pipelined; }
+};
+struct PreparedOwner {
+    Prepared *p = nullptr;
+    ~PreparedOwner() { free_prepared(p); }
+};
+
+static swh_status_t topk_checks(swh_levenshtein_t e, swh_scope_t s, size_t k, size_t queries, size_t candidates, const uint32_t *indices,
+                                const uint32_t *distances, const char **error) {
+    if (!s || !e) return fail(error, swh_invalid_argument_k, "null scope or engine");
+    if (((Engine *)e)->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (k < 1 || k > SWH_TOPK_MAX) return fail(error, swh_invalid_argument_k, "k must lie in [1, SWH_TOPK_MAX]");
+    if (candidates >= 0xFFFFFFFFull) return fail(error, swh_unsupported_length_k, "2^32 - 1 candidates or more");
+    if (queries && (!indices || !distances)) return fail(error, swh_invalid_argument_k, "null output pointer");
+    return swh_success_k;
+}
+static swh_status_t topk_join(Scope *scope, const char **error) {
+    if (!scope->async && !scope->pipelined) return swh_success_k;
+    return swh_scope_synchronize((swh_scope_t)scope, error);
+}
+
+static swh_status_t topk_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *q, const swh_tape_u64_t *c, bool utf8, size_t k,
+                               uint32_t bound, uint32_t *indices, uint32_t *distances, const char **error) {
+    if (!q) return fail(error, swh_invalid_argument_k, "null tape");
+    const swh_tape_u64_t *cc = c ? c : q;
+    swh_status_t status = topk_checks(e, s, k, q->count, cc->count, indices, distances, error);
+    if (status != swh_success_k) return status;
+    Scope *scope = (Scope *)s;
+    if ((status = topk_join(scope, error)) != swh_success_k) return status;
+    if (q->count == 0) return swh_success_k;
+    TopkModeGuard mode(scope);
+    // raw tapes are made resident and measured for the call (prepare_tape: device tapes in place, host tapes uploaded; UTF-8 validated and
+    // decoded): the route is then chosen on lengths that are known, not believed
+    PreparedOwner pq, pc;
+    status = prepare_tape(scope, SWH_TAPE(q, 1), utf8, (swh_prepared_t *)&pq.p, error);
+    if (status != swh_success_k) return status;
+    if (c) {
+        status = prepare_tape(scope, SWH_TAPE(c, 1), utf8, (swh_prepared_t *)&pc.p, error);
+        if (status != swh_success_k) return status;
+    }
+    TopkRequest r{pq.p, c ? pc.p : pq.p, 0, q->count, 0, cc->count, (uint32_t)k, bound, indices, distances};
+    return topk_run(scope, (Engine *)e, r, error);
+}
+swh_status_t swh_levenshtein_topk_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries, const swh_tape_u64_t *candidates,
+                                          size_t k, uint32_t bound, uint32_t *indices, uint32_t *distances, const char **error) {
+    return topk_tapes(e, s, queries, candidates, false, k, bound, indices, distances, error);
+}
+swh_status_t swh_levenshtein_utf8_topk_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries,
+                                               const swh_tape_u64_t *candidates, size_t k, uint32_t bound, uint32_t *indices,
+                                               uint32_t *distances, const char **error) {
+    return topk_tapes(e, s, queries, candidates, true, k, bound, indices, distances, error);
+}
+swh_status_t swh_levenshtein_topk_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *queries,
+                                           const swh_prepared_view_t *candidates, size_t k, uint32_t bound, uint32_t *indices,
+                                           uint32_t *distances, const char **error) {
+    if (!queries || !queries->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
+    const swh_prepared_view_t *cc = (candidates && candidates->tape) ? candidates : queries;
+    const Prepared *pq = (const Prepared *)queries->tape, *pc = (const Prepared *)cc->tape;
+    if (queries->first > pq->bytes.count || queries->count > pq->bytes.count - queries->first || cc->first > pc->bytes.count ||
+        cc->count > pc->bytes.count - cc->first)
+        return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
+    swh_status_t status = topk_checks(e, s, k, queries->count, cc->count, indices, distances, error);
+    if (status != swh_success_k) return status;
+    if (pq->utf8 != pc->utf8) return fail(error, swh_invalid_argument_k, "one tape was prepared as UTF-8, the other as bytes");
+    Scope *scope = (Scope *)s;
+    if (pq->device != scope->device || pc->device != scope->device)
+        return fail(error, swh_invalid_argument_k, "a prepared tape lives on another device than the scope");
+    if ((status = topk_join(scope, error)) != swh_success_k) return status;
+    TopkModeGuard mode(scope);
+    TopkRequest r{pq, pc, queries->first, queries->count, cc->first, cc->count, (uint32_t)k, bound, indices, distances};
+    return topk_run(scope, (Engine *)e, r, error);
 }
 
 }  // extern "C"

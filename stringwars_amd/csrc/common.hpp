@@ -390,6 +390,10 @@ struct Scope {
     // right-edge columns of multi-pass wavefront groups
     char *boundary = nullptr;
     size_t boundary_bytes = 0;
+    // top-k searches (topk.hip): running lists, slice matrices and partial lists -- apart from `scratch`, which the
+    // cross-product calls of a search's general path carve for themselves
+    char *topk_scratch = nullptr;
+    size_t topk_scratch_bytes = 0;
     Plan *plan_host = nullptr;  // pinned
     char *plan_area = nullptr;  // device: hist | cursor | partials | plan, zeroed once (the scan kernel re-zeroes hist)
     uint32_t *plan_hist = nullptr, *plan_cursor = nullptr, *plan_leftover = nullptr;   // carved from plan_area at scope creation
@@ -544,6 +548,18 @@ TilePlan plan_tiles(uint64_t pairs, uint32_t slots, uint32_t longest_text, uint3
 void launch_bitparallel_tiled(Scope *scope, const KernelArgs &args, uint64_t pairs, uint32_t longest_text);
 // cross.hip: dense queries x candidates for word-sized strings, the query's match table shared by a wave
 void launch_cross_short(Scope *scope, const Job &job, uint32_t off64, uint32_t sym_bytes);   // sym_bytes 4: code points (decoded tapes)
+// topk.hip: the fused word-sized search (k_cross_topk, then k_topk_merge when slices > 1) and the general path's fold (k_topk_select)
+struct TopkLaunch {
+    TapeRef a, b;                     // queries, candidates: device byte tapes with `off64`-wide offsets
+    uint32_t off64, k, slices, prune;
+    uint64_t slice_chunks, cap;       // chunks of 64 candidates per slice; keys must be below cap
+    uint64_t *partial;                // slices > 1: [query][slice][k] keys
+    uint32_t *indices, *distances;    // [query][k]
+};
+size_t topk_fused_lds(uint32_t k);
+void launch_cross_topk(Scope *scope, const TopkLaunch &t);
+void launch_topk_select(Scope *scope, const uint32_t *scores, uint64_t rows, uint64_t columns, uint64_t row_first, uint64_t col_first, uint32_t k,
+                        uint64_t cap, uint64_t *lists, bool emit, uint32_t *indices, uint32_t *distances);
 // short.hip: pairwise batches of strings <= 16 bytes: chunks staged in LDS, affixes cut, sorted by what remains
 // `mean_bytes`: mean string length of the longer tape, x16 (0: unknown); sizes the chunks so that their segments fit the LDS arrays
 void launch_short_tiled(Scope *scope, const Job &job, uint32_t off64, uint32_t mean_bytes_x16);

@@ -24,11 +24,12 @@ from . import _native as N
 
 __all__ = [
     "DeviceScope", "Strs", "DeviceTape", "PreparedTape", "ShardedPairs", "shard_cuts", "LevenshteinDistances", "LevenshteinDistancesUTF8",
-    "NeedlemanWunschScores", "SmithWatermanScores", "edit_distance", "StringWarsError", "UNBOUNDED",
+    "NeedlemanWunschScores", "SmithWatermanScores", "edit_distance", "StringWarsError", "UNBOUNDED", "TOPK_MAX",
 ]
 
 StringWarsError = N.StringWarsError
 UNBOUNDED = N.UNBOUNDED
+TOPK_MAX = N.TOPK_MAX
 
 
 def _pointer(obj) -> int:
@@ -550,6 +551,46 @@ class LevenshteinDistances(_Engine):
         else:
             fns = (N.lib.swh_levenshtein_pairs_u32tape, N.lib.swh_levenshtein_pairs_u64tape)
         return self._pairs(fns[0], fns[1], a, b, scope, out, np.uint32, extra=(C.c_uint32(bound_value),))
+
+    def topk(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None, *, k: int,
+             bound: Optional[int] = None, out=None):
+        """The ``k`` nearest candidates of every query: ``(indices, distances)``, each ``(len(queries), k)`` of uint32, rows ordered
+        by distance and then by candidate index, only candidates with ``d <= bound``, short rows padded with ``0xFFFFFFFF``.
+        ``candidates=None`` searches the queries themselves (diagonal included). ``out=(indices, distances)`` fills given arrays
+        or device tensors (contiguous, ``len(queries) * k`` uint32 / int32 each) instead of returning new numpy arrays.
+        rapidfuzz: ``process.extract(q, candidates, scorer=Levenshtein.distance, limit=k, score_cutoff=bound)`` per query."""
+        if scope is None:
+            raise ValueError("a DeviceScope is required")
+        queries = _as_tape(queries)
+        if candidates is not None:
+            candidates = _as_tape(candidates)
+        count = len(queries)
+        if out is None:
+            indices, distances = np.empty((count, int(k)), dtype=np.uint32), np.empty((count, int(k)), dtype=np.uint32)
+        else:
+            indices, distances = out
+            for array in (indices, distances):
+                if isinstance(array, np.ndarray) and (array.dtype.itemsize != 4 or array.size != count * int(k) or not array.flags.c_contiguous):
+                    raise ValueError("out arrays must be contiguous (len(queries), k) arrays of 32-bit integers")
+        bound_value = C.c_uint32(N.UNBOUNDED if bound is None else int(bound))
+        err = C.c_char_p()
+        if isinstance(queries, PreparedTape) or isinstance(candidates, PreparedTape):
+            if not isinstance(queries, PreparedTape) or not (candidates is None or isinstance(candidates, PreparedTape)):
+                raise TypeError("both tapes of a call must be prepared, or neither")
+            if self._utf8 != queries.utf8:
+                raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
+            vq, vc = queries.view(), (candidates.view() if candidates is not None else None)
+            status = N.lib.swh_levenshtein_topk_prepared(self._handle, scope.handle, C.byref(vq), C.byref(vc) if vc is not None else None,
+                                                         int(k), bound_value, C.c_void_p(_pointer(indices)), C.c_void_p(_pointer(distances)), C.byref(err))
+        else:
+            tq, _, keep_q = _c_tape(queries, want64=True)
+            tc, _, keep_c = _c_tape(candidates, want64=True) if candidates is not None else (None, None, None)
+            fn = N.lib.swh_levenshtein_utf8_topk_u64tape if self._utf8 else N.lib.swh_levenshtein_topk_u64tape
+            status = fn(self._handle, scope.handle, C.byref(tq), C.byref(tc) if tc is not None else None, int(k), bound_value,
+                        C.c_void_p(_pointer(indices)), C.c_void_p(_pointer(distances)), C.byref(err))
+            del keep_q, keep_c
+        N.check(status, err)
+        return indices, distances
 
     def pairs_sharded(self, batch: "ShardedPairs", scope: DeviceScope, bound: Optional[int] = None, out=None):
         """One batch over every GPU of a multi-device scope; the distances come back gathered, in pair order."""

@@ -99,6 +99,9 @@ extern "C" {
     fn swh_levenshtein_utf8_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, out: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_pairs_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, bound: u32, out: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_cross_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, out: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_topk_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, k: usize, bound: u32, indices: *mut u32, distances: *mut u32, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_topk_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, k: usize, bound: u32, indices: *mut u32, distances: *mut u32, error: Err) -> c_int;
+    fn swh_levenshtein_topk_prepared(engine: Handle, scope: Handle, queries: *const PreparedView, candidates: *const PreparedView, k: usize, bound: u32, indices: *mut u32, distances: *mut u32, error: Err) -> c_int;
     fn swh_sharded_prepare_u32tape(scope: Handle, a: *const TapeU32, b: *const TapeU32, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_prepare_u64tape(scope: Handle, a: *const TapeU64, b: *const TapeU64, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_free(sharded: Handle) -> c_int;
@@ -401,6 +404,26 @@ impl LevenshteinDistances {
         check(unsafe { swh_levenshtein_cross_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64),
                                                      matrix.as_mut_ptr(), columns * 8, &mut message) }, message)
     }
+    /// Top-k search: the `k` nearest candidates of every query (`process.extract(limit = k, score_cutoff = bound)` per query),
+    /// `indices` / `distances` of `queries.len() * k`, rows ascending by (distance, index), padded with `u32::MAX`; `None` = q x q.
+    pub fn topk_into(&self, scope: &DeviceScope, queries: &BytesTapeView<u64>, candidates: Option<&BytesTapeView<u64>>, k: usize, bound: Option<u32>,
+                     indices: &mut [u32], distances: &mut [u32]) -> Result<(), Error> {
+        assert!(indices.len() >= queries.len() * k && distances.len() >= queries.len() * k);
+        let tq = bytes_tape(queries);
+        let tc = candidates.map(bytes_tape);
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_topk_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64), k,
+                                                    bound.unwrap_or(UNBOUNDED), indices.as_mut_ptr(), distances.as_mut_ptr(), &mut message) }, message)
+    }
+    pub fn topk_into_prepared(&self, scope: &DeviceScope, queries: &PreparedTape, candidates: Option<&PreparedTape>, k: usize, bound: Option<u32>,
+                              indices: &mut [u32], distances: &mut [u32]) -> Result<(), Error> {
+        assert!(indices.len() >= queries.len() * k && distances.len() >= queries.len() * k);
+        let vq = queries.view();
+        let vc = candidates.map(|c| c.view());
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_topk_prepared(self.handle, scope.handle, &vq, vc.as_ref().map_or(ptr::null(), |v| v as *const PreparedView), k,
+                                                     bound.unwrap_or(UNBOUNDED), indices.as_mut_ptr(), distances.as_mut_ptr(), &mut message) }, message)
+    }
     pub fn compute_into_prepared(&self, scope: &DeviceScope, queries: &PreparedTape, candidates: Option<&PreparedTape>, matrix: &mut [usize]) -> Result<(), Error> {
         let columns = candidates.map_or(queries.len(), |c| c.len());
         let vq = queries.view();
@@ -436,6 +459,16 @@ impl LevenshteinDistancesUtf8 {
         let (va, vb) = (a.view(), b.view());
         let mut message = ptr::null();
         check(unsafe { swh_levenshtein_pairs_prepared(self.handle, scope.handle, &va, &vb, bound.unwrap_or(UNBOUNDED), out.as_mut_ptr(), 4, &mut message) }, message)
+    }
+    /// Top-k search over code points (see `LevenshteinDistances::topk_into`).
+    pub fn topk_into(&self, scope: &DeviceScope, queries: &CharsTapeView<u64>, candidates: Option<&CharsTapeView<u64>>, k: usize, bound: Option<u32>,
+                     indices: &mut [u32], distances: &mut [u32]) -> Result<(), Error> {
+        assert!(indices.len() >= queries.len() * k && distances.len() >= queries.len() * k);
+        let tq = chars_tape(queries);
+        let tc = candidates.map(chars_tape);
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_utf8_topk_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64), k,
+                                                         bound.unwrap_or(UNBOUNDED), indices.as_mut_ptr(), distances.as_mut_ptr(), &mut message) }, message)
     }
     /// `compute_into(&scope, AnyCharsTape::View64(q), Some(AnyCharsTape::View64(c)), &mut matrix)` (bench.rs:538-546, :625-629).
     pub fn compute_into(&self, scope: &DeviceScope, queries: &CharsTapeView<u64>, candidates: Option<&CharsTapeView<u64>>, matrix: &mut [usize]) -> Result<(), Error> {
