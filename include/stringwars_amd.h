@@ -234,6 +234,45 @@ swh_status_t swh_levenshtein_topk_prepared(swh_levenshtein_t engine, swh_scope_t
                                            const swh_prepared_view_t *candidates, size_t k, uint32_t bound,
                                            uint32_t *indices, uint32_t *distances, const char **error);
 
+/* ---- Alignments: the edit operations of every pair (rapidfuzz `Levenshtein.editops`, edlib `task="path"`, bio
+ *      `Aligner::global(a, b).operations`), unit costs only. -------------------------------------------------------------
+ * For every pair i of a pairwise batch (a->count == b->count, else swh_invalid_argument_k):
+ *  - distances[i] = min(d(a_i, b_i), bound + 1), bit-identical to swh_levenshtein_pairs_* on the same pairs and bound;
+ *    bound == SWH_UNBOUNDED means no cutoff;
+ *  - the operations of pair i are ops[ops_offsets[i] .. ops_offsets[i + 1]), one SWH_OP_* byte each, in forward order;
+ *    ops_offsets has count + 1 entries, ops_offsets[0] = 0, and the layout is compact; a pair over the bound gets an empty range;
+ *  - for an in-bound pair: #'=' + #'X' + #'D' = len(a_i), #'=' + #'X' + #'I' = len(b_i), and the non-'=' ops number d;
+ *  - the script is the CANONICAL one among the optimal ones: walking back over the Wagner-Fischer matrix D from (m, n) to
+ *    (0, 0), each cell takes '=' if i, j > 0 and a_i = b_j; else 'X' if i, j > 0 and D[i-1][j-1] + 1 = D[i][j]; else 'D'
+ *    if i > 0 and D[i-1][j] + 1 = D[i][j]; else 'I'. kitten -> sitting: "X===X=I"; aa -> a: "D=";
+ *  - symbols, and the lengths above, are bytes, or code points in the UTF-8 variant (invalid UTF-8 -> swh_invalid_utf8_k); the
+ *    prepared variant takes what the tapes were prepared as;
+ *  - ops_capacity must be at least sum len(a_i) + len(b_i) in symbols (the byte totals of the two tapes always are), else
+ *    swh_invalid_argument_k and nothing is written;
+ *  - a pair with len(a_i) * len(b_i) > SWH_ALIGN_MAX_CELLS makes the call return swh_unsupported_length_k before any output is
+ *    written; the message names the first such pair;
+ *  - an engine whose costs are not (match 0, mismatch 1, open 1, extend 1) returns swh_not_implemented_k;
+ *  - `distances` (uint32_t), `ops_offsets` (size_t, 64-bit) and `ops` (one char per op) may each be in host or device memory;
+ *  - count == 0 succeeds and writes only ops_offsets[0] = 0.
+ * The call is synchronous on every scope: on an asynchronous or pipelined scope it first joins the outstanding work (as
+ * swh_scope_synchronize) and returns with the results visible. With profiling on, swh_scope_last_timing describes the whole call:
+ * `cells` = sum len(a_i) len(b_i); `dominant_name` is its longest kernel ("align" for bytes, "align_u32" for code points, when
+ * the forward pass and the walk dominate). */
+#define SWH_ALIGN_MAX_CELLS (1ull << 30)   /* len(a_i) * len(b_i) accepted per pair */
+#define SWH_OP_MATCH '='  /* consumes a symbol of a and of b; they are equal */
+#define SWH_OP_SUBST 'X'  /* consumes a symbol of a and of b; they differ */
+#define SWH_OP_DEL 'D'    /* consumes a symbol of a only */
+#define SWH_OP_INS 'I'    /* consumes a symbol of b only */
+swh_status_t swh_levenshtein_align_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                           const swh_tape_u64_t *b, uint32_t bound, uint32_t *distances,
+                                           size_t *ops_offsets, char *ops, size_t ops_capacity, const char **error);
+swh_status_t swh_levenshtein_utf8_align_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                const swh_tape_u64_t *b, uint32_t bound, uint32_t *distances,
+                                                size_t *ops_offsets, char *ops, size_t ops_capacity, const char **error);
+swh_status_t swh_levenshtein_align_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *a,
+                                            const swh_prepared_view_t *b, uint32_t bound, uint32_t *distances,
+                                            size_t *ops_offsets, char *ops, size_t ops_capacity, const char **error);
+
 /* ---- One batch over the GPUs of a multi-device scope (BASELINE config 5). --------------------------------
  * `swh_sharded_prepare_*`: HOST tapes of equal count are cut into contiguous shards balanced on the prefix sum of
  * len(a_i)*len(b_i) (DP cells, not pair counts); shard r is uploaded to and prepared on device r. The handle is the steady
@@ -338,7 +377,7 @@ swh_status_t swh_sw_pairs_sharded(swh_sw_t engine, swh_scope_t scope, swh_sharde
 /* ---- Introspection: `log_stringzilla_metadata` (utils.rs:78-92). --------------------------- */
 const char *swh_version(void);
 /* Comma-separated capability string, e.g. "gfx950,hip,wavefront,bitparallel,banded,utf8,...";
- * "topk" when the swh_levenshtein_topk_* calls are present. */
+ * "topk" when the swh_levenshtein_topk_* calls are present, "align" when the swh_levenshtein_align_* calls are. */
 const char *swh_capabilities(void);
 
 #ifdef __cplusplus

@@ -208,6 +208,23 @@ public:
         swh_status_t status__ = swh_levenshtein_cross_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, matrix, row_stride_bytes, &err);
         check(status__, err);
     }
+    /// Alignments (swh_levenshtein_align_*): pair i's canonical edit script is ops[ops_offsets[i] .. ops_offsets[i + 1]) (SWH_OP_* chars),
+    /// distances[i] = min(d, bound + 1); ops_offsets holds a.count + 1 entries; all three in host or device memory.
+    void align(const DeviceScope &scope, const BytesTapeView &a, const BytesTapeView &b, uint32_t *distances, size_t *ops_offsets, char *ops,
+               size_t ops_capacity, uint32_t bound = SWH_UNBOUNDED) const {
+        const char *err = nullptr;
+        swh_tape_u64_t ta = a.c(), tb = b.c();
+        auto fn = utf8_ ? swh_levenshtein_utf8_align_u64tape : swh_levenshtein_align_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &ta, &tb, bound, distances, ops_offsets, ops, ops_capacity, &err);
+        check(status__, err);
+    }
+    void align(const DeviceScope &scope, const PreparedTape &a, const PreparedTape &b, uint32_t *distances, size_t *ops_offsets, char *ops,
+               size_t ops_capacity, uint32_t bound = SWH_UNBOUNDED) const {
+        const char *err = nullptr;
+        swh_prepared_view_t va = a.c(), vb = b.c();
+        swh_status_t status__ = swh_levenshtein_align_prepared(handle_, scope.handle(), &va, &vb, bound, distances, ops_offsets, ops, ops_capacity, &err);
+        check(status__, err);
+    }
     /// Top-k search (swh_levenshtein_topk_*): the k nearest candidates of every query, `indices` / `distances` of
     /// queries.count x k (host or device memory); rows ascending by (distance, index), only d <= bound, padded with 0xFFFFFFFF.
     void topk(const DeviceScope &scope, const BytesTapeView &queries, const BytesTapeView *candidates, size_t k, uint32_t *indices,

@@ -12,7 +12,9 @@
 #include <new>
 
 #include "common.hpp"
+#include "align.hpp"
 #include <algorithm>
+#include <mutex>
 #include <utility>
 
 namespace swh {
@@ -1094,13 +1096,26 @@ static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSp
 
 using namespace swh;
 
+// Alignment scratch (align.hip) of every scope that ran an alignment: stored delta vectors, op slots, scans. Kept here rather than in
+// Scope so that common.hpp -- which every kernel family's profile stamp hashes -- stays as it is; freed with the scope.
+struct AlignScratch { char *buf = nullptr; size_t bytes = 0; };
+static std::mutex g_align_scratch_lock;
+static std::unordered_map<const Scope *, AlignScratch> g_align_scratch;
+static void free_align_scratch(const Scope *scope) {
+    std::lock_guard<std::mutex> hold(g_align_scratch_lock);
+    auto it = g_align_scratch.find(scope);
+    if (it == g_align_scratch.end()) return;
+    if (it->second.buf) (void)hipFree(it->second.buf);
+    g_align_scratch.erase(it);
+}
+
 // =====================================================================================================
 // extern "C"
 // =====================================================================================================
 extern "C" {
 
 const char *swh_version(void) { return "0.1.0"; }
-const char *swh_capabilities(void) { return "gfx950,hip,wavefront,bitparallel,tiled,banded,utf8,bounded,nw-linear,nw-affine,sw-linear,sw-affine,cross,prepared,topk,multi-gpu-rccl"; }
+const char *swh_capabilities(void) { return "gfx950,hip,wavefront,bitparallel,tiled,banded,utf8,bounded,nw-linear,nw-affine,sw-linear,sw-affine,cross,prepared,topk,align,multi-gpu-rccl"; }
 
 static swh_status_t scope_init(int device, void *stream, bool borrow, swh_scope_t *out, const char **error) {
     if (!out) return fail(error, swh_invalid_argument_k, "null scope pointer");
@@ -1182,6 +1197,7 @@ swh_status_t swh_scope_free(swh_scope_t handle) {
     if (scope->stage) (void)hipFree(scope->stage);
     if (scope->boundary) (void)hipFree(scope->boundary);
     if (scope->topk_scratch) (void)hipFree(scope->topk_scratch);
+    free_align_scratch(scope);
     if (scope->plan_host) (void)hipHostFree(scope->plan_host);
     if (scope->summary_host) (void)hipHostFree(scope->summary_host);
     if (scope->plan_area) (void)hipFree(scope->plan_area);
@@ -2026,6 +2042,255 @@ swh_status_t swh_levenshtein_topk_prepared(swh_levenshtein_t e, swh_scope_t s, c
     TopkModeGuard mode(scope);
     TopkRequest r{pq, pc, queries->first, queries->count, cc->first, cc->count, (uint32_t)k, bound, indices, distances};
     return topk_run(scope, (Engine *)e, r, error);
+}
+
+// ---- alignments (align.hip) ----------------------------------------------------------------------------------------------------------
+// k_align_sizes measures the batch (stored bytes, symbols, cells, the first pair over SWH_ALIGN_MAX_CELLS) and the stored bytes and slot
+// sizes are scanned on the device; one read-back of the measurements decides the errors and the chunks, before any output is written.
+// Then per chunk of consecutive pairs the forward pass + walk (k_align), the counts scanned into the offsets, and k_align_emit places
+// the ops -- no host round trip between the forward pass and the outputs.
+// A chunk holds enough pairs to fill the device -- kAlignFillWaves waves per compute unit, a lane per pair -- and, beyond that, as many
+// as keep its stored delta vectors near 128 MiB, where the walk still reads the forward pass's stores from the Infinity Cache. Long
+// pairs therefore give up the residency rather than the parallelism (1 K protein pairs of 4 K symbols store 6 GB: one chunk).
+// STRINGWARS_AMD_ALIGN_CHUNK_KB=n (test library) sets the byte target and drops the fill minimum, to put many chunks in a small test.
+constexpr uint64_t kAlignFillWaves = 8;
+static const char *align_chunk_hook() {
+    static const char *e = test_hook("STRINGWARS_AMD_ALIGN_CHUNK_KB");
+    return e;
+}
+static uint64_t align_chunk_pairs(const Scope *scope, uint64_t count, uint64_t store_total) {
+    const char *hook = align_chunk_hook();
+    const uint64_t target = hook ? (uint64_t)atol(hook) << 10 : (uint64_t)128 << 20;
+    const uint64_t fill = hook ? 1 : (uint64_t)scope->compute_units * kAlignFillWaves * 64;
+    const uint64_t mean = std::max<uint64_t>(1, store_total / std::max<uint64_t>(count, 1));
+    uint64_t pairs = std::max<uint64_t>(fill, target / mean);
+    // no chunk asks for more than half the device memory that is free
+    size_t free_bytes = 0, total_bytes = 0;
+    if (hipMemGetInfo(&free_bytes, &total_bytes) == hipSuccess && free_bytes)
+        pairs = std::min<uint64_t>(pairs, std::max<uint64_t>(1, (uint64_t)(free_bytes / 2) / mean));
+    return std::max<uint64_t>(1, std::min<uint64_t>(pairs, count));
+}
+
+struct AlignRequest {
+    const Prepared *pa, *pb;
+    size_t a_first, b_first, count;
+    uint32_t bound;
+    uint32_t *distances;
+    uint64_t *offsets;
+    uint8_t *ops;
+    size_t capacity;
+};
+
+static swh_status_t align_run(Scope *scope, const AlignRequest &r, const char **error) {
+    harvest_timing(scope, false);
+    scope->stamps_used = 0;
+    scope->last_timing = swh_timing_t{};
+    const uint64_t count = r.count;
+    try {
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        const bool dev_d = is_device_pointer(r.distances), dev_o = is_device_pointer(r.offsets), dev_ops = is_device_pointer(r.ops);
+        if (count == 0) {
+            const uint64_t zero = 0;
+            if (dev_o) SWH_HIP_CHECK(hipMemcpyAsync(r.offsets, &zero, sizeof zero, hipMemcpyHostToDevice, stream)); else r.offsets[0] = 0;
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            return swh_success_k;
+        }
+        const bool cp = r.pa->utf8;
+        AlignTapes t{};
+        auto view = [&](const Prepared *p, size_t first, uint32_t &off64) {
+            const TapeRef &src = cp ? p->symbols : p->bytes;
+            off64 = cp ? 1 : p->off64;
+            TapeRef v = src;
+            v.offsets = (const char *)src.offsets + first * (off64 ? 8 : 4);
+            v.count = count;
+            return v;
+        };
+        t.a = view(r.pa, r.a_first, t.a_off64);
+        t.b = view(r.pb, r.b_first, t.b_off64);
+        t.cp = cp ? 1 : 0;
+        t.count = count;
+
+        auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
+        AlignScratch *sc_entry;
+        {
+            std::lock_guard<std::mutex> hold(g_align_scratch_lock);
+            sc_entry = &g_align_scratch[scope];
+        }
+        // fixed part: sizes | store_base | slot_base | counts | offsets | distances | scan partials
+        const size_t partial_words = align_scan_partials(count);
+        const size_t fixed = pad(sizeof(AlignSizes)) + 2 * pad((count + 1) * 8) + pad(count * 4) + (dev_o ? 0 : pad((count + 1) * 8)) +
+                             (dev_d ? 0 : pad(count * 4)) + pad(partial_words * 8);
+        ensure(sc_entry->buf, sc_entry->bytes, fixed);
+        Carver sc{sc_entry->buf, 0, sc_entry->bytes};
+        AlignSizes *sizes = sc.take<AlignSizes>(1);
+        uint64_t *store_base = sc.take<uint64_t>(count + 1), *slot_base = sc.take<uint64_t>(count + 1);
+        uint32_t *counts = sc.take<uint32_t>(count);
+        uint64_t *offsets = dev_o ? r.offsets : sc.take<uint64_t>(count + 1);
+        uint32_t *distances = dev_d ? r.distances : sc.take<uint32_t>(count);
+        uint64_t *partials = sc.take<uint64_t>(partial_words);
+
+        AlignSizes init{};
+        init.first_oversize = ~0ull;
+        SWH_HIP_CHECK(hipMemcpyAsync(sizes, &init, sizeof init, hipMemcpyHostToDevice, stream));
+        launch_align_sizes(scope, t, store_base, slot_base, sizes);
+        launch_align_scan(scope, store_base, count, partials);
+        launch_align_scan(scope, slot_base, count, partials);
+        AlignSizes got{};
+        SWH_HIP_CHECK(hipMemcpyAsync(&got, sizes, sizeof got, hipMemcpyDeviceToHost, stream));
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        if (got.first_oversize != ~0ull) {
+            const size_t i = (size_t)got.first_oversize;
+            const uint64_t la = read_offset(t.a.offsets, t.a_off64, i + 1, true, stream) - read_offset(t.a.offsets, t.a_off64, i, true, stream);
+            const uint64_t lb = read_offset(t.b.offsets, t.b_off64, i + 1, true, stream) - read_offset(t.b.offsets, t.b_off64, i, true, stream);
+            snprintf(g_error_text, sizeof g_error_text, "pair %zu: %llu x %llu symbols exceeds SWH_ALIGN_MAX_CELLS (2^30 cells per pair)", i,
+                     (unsigned long long)la, (unsigned long long)lb);
+            scope->stamps_used = 0;
+            if (error) *error = g_error_text;
+            return swh_unsupported_length_k;
+        }
+        if (r.capacity < got.symbols) {
+            snprintf(g_error_text, sizeof g_error_text, "ops_capacity %zu is below the %llu symbols of the two tapes", r.capacity,
+                     (unsigned long long)got.symbols);
+            scope->stamps_used = 0;
+            if (error) *error = g_error_text;
+            return swh_invalid_argument_k;
+        }
+
+        // chunks of consecutive pairs; where they start in the storage space is read back (one strided copy) to size the largest
+        const uint64_t per_chunk = align_chunk_pairs(scope, count, got.store_total);
+        const uint64_t chunks = (count + per_chunk - 1) / per_chunk;
+        std::vector<uint64_t> starts(chunks + 1, 0);
+        if (chunks > 1) {
+            SWH_HIP_CHECK(hipMemcpy2DAsync(starts.data(), 8, store_base, per_chunk * 8, 8, chunks, hipMemcpyDeviceToHost, stream));
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        }
+        starts[chunks] = got.store_total;
+        uint64_t widest = 0;
+        for (uint64_t q = 0; q < chunks; ++q) widest = std::max<uint64_t>(widest, starts[q + 1] - starts[q]);
+        // variable part: the op slots (whole batch) | staged ops for host outputs | the widest chunk of stored delta vectors
+        const size_t store_bytes = (size_t)widest;
+        const size_t need = fixed + pad(got.symbols + 16) + (dev_ops ? 0 : pad(got.symbols + 16)) + pad(store_bytes + 16);
+        if (need > sc_entry->bytes) {
+            // keep what the fixed part already holds: the measurements and scans live there
+            char *grown = nullptr;
+            const size_t want = need + need / 4 + (1 << 20);
+            SWH_HIP_CHECK(hipMalloc((void **)&grown, want));
+            SWH_HIP_CHECK(hipMemcpyAsync(grown, sc_entry->buf, fixed, hipMemcpyDeviceToDevice, stream));
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            SWH_HIP_CHECK(hipFree(sc_entry->buf));
+            sc_entry->buf = grown;
+            sc_entry->bytes = want;
+            sc = Carver{grown, 0, want};
+            sizes = sc.take<AlignSizes>(1);
+            store_base = sc.take<uint64_t>(count + 1); slot_base = sc.take<uint64_t>(count + 1);
+            counts = sc.take<uint32_t>(count);
+            offsets = dev_o ? r.offsets : sc.take<uint64_t>(count + 1);
+            distances = dev_d ? r.distances : sc.take<uint32_t>(count);
+            partials = sc.take<uint64_t>(partial_words);
+        }
+        uint8_t *slots = sc.take<uint8_t>(got.symbols + 16);
+        uint8_t *ops = dev_ops ? r.ops : sc.take<uint8_t>(got.symbols + 16);
+        char *store = sc.take<char>(store_bytes + 16);
+
+        AlignChunk c{};
+        c.store_base = store_base; c.slot_base = slot_base; c.store = store; c.slots = slots;
+        c.counts = counts; c.distances = distances; c.bound = r.bound;
+        for (uint64_t q = 0; q < chunks; ++q) {
+            c.pair_first = q * per_chunk;
+            c.pair_end = std::min<uint64_t>(count, (q + 1) * per_chunk);
+            c.store_first = starts[q];
+            launch_align_chunk(scope, t, c);
+        }
+        launch_align_scan_counts(scope, counts, offsets, count, partials);
+        launch_align_emit(scope, count, slot_base, counts, offsets, slots, ops);
+        if (!dev_d) SWH_HIP_CHECK(hipMemcpyAsync(r.distances, distances, count * 4, hipMemcpyDeviceToHost, stream));
+        if (!dev_o) SWH_HIP_CHECK(hipMemcpyAsync(r.offsets, offsets, (count + 1) * 8, hipMemcpyDeviceToHost, stream));
+        if (!dev_ops) {
+            uint64_t total_ops = 0;
+            SWH_HIP_CHECK(hipMemcpyAsync(&total_ops, offsets + count, 8, hipMemcpyDeviceToHost, stream));
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            if (total_ops) SWH_HIP_CHECK(hipMemcpyAsync(r.ops, ops, total_ops, hipMemcpyDeviceToHost, stream));
+        }
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        if (scope->profiling && scope->stamps_used) {
+            collect_timing(scope);
+            scope->totals.total_ms += scope->last_timing.total_ms;
+            scope->totals.dominant_ms += scope->last_timing.dominant_ms;
+            scope->totals.compute_ms += scope->last_timing.compute_ms;
+            scope->totals.calls += 1;
+        }
+        scope->stamps_used = 0;
+        scope->last_timing.cells = got.cells;
+        scope->last_timing.bytes = (cp ? 4 : 1) * got.symbols + 2 * (count + 1) * 8 + count * 4 + got.symbols;
+        return swh_success_k;
+    } catch (const HipFailure &f) {
+        return fail_hip(error, f);
+    } catch (const std::bad_alloc &) {
+        return fail(error, swh_bad_alloc_k, "host allocation failed");
+    }
+}
+
+static swh_status_t align_checks(swh_levenshtein_t e, swh_scope_t s, size_t a_count, size_t b_count, const uint32_t *distances,
+                                 const uint64_t *offsets, const uint8_t *ops, const char **error) {
+    if (!s || !e) return fail(error, swh_invalid_argument_k, "null scope or engine");
+    const Engine *engine = (const Engine *)e;
+    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (!engine->unit_costs) return fail(error, swh_not_implemented_k, "alignments need unit costs (match 0, mismatch 1, open 1, extend 1)");
+    if (a_count != b_count) return fail(error, swh_invalid_argument_k, "a and b must hold the same number of strings");
+    if (!offsets || (a_count && (!distances || !ops))) return fail(error, swh_invalid_argument_k, "null output pointer");
+    return swh_success_k;
+}
+
+static swh_status_t align_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, bool utf8, uint32_t bound,
+                                uint32_t *distances, uint64_t *offsets, uint8_t *ops, size_t capacity, const char **error) {
+    if (!a || !b) return fail(error, swh_invalid_argument_k, "null tape");
+    swh_status_t status = align_checks(e, s, a->count, b->count, distances, offsets, ops, error);
+    if (status != swh_success_k) return status;
+    Scope *scope = (Scope *)s;
+    if ((status = topk_join(scope, error)) != swh_success_k) return status;
+    TopkModeGuard mode(scope);
+    AlignRequest r{nullptr, nullptr, 0, 0, a->count, bound, distances, offsets, ops, capacity};
+    if (a->count == 0) {
+        Prepared none;
+        r.pa = r.pb = &none;
+        return align_run(scope, r, error);
+    }
+    // raw tapes are made resident, measured and (UTF-8) validated and decoded for the call, as for top-k
+    PreparedOwner pa, pb;
+    status = prepare_tape(scope, SWH_TAPE(a, 1), utf8, (swh_prepared_t *)&pa.p, error);
+    if (status != swh_success_k) return status;
+    status = prepare_tape(scope, SWH_TAPE(b, 1), utf8, (swh_prepared_t *)&pb.p, error);
+    if (status != swh_success_k) return status;
+    r.pa = pa.p; r.pb = pb.p;
+    return align_run(scope, r, error);
+}
+swh_status_t swh_levenshtein_align_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,
+                                           uint32_t *distances, size_t *ops_offsets, char *ops, size_t ops_capacity, const char **error) {
+    return align_tapes(e, s, a, b, false, bound, distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity, error);
+}
+swh_status_t swh_levenshtein_utf8_align_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                uint32_t bound, uint32_t *distances, size_t *ops_offsets, char *ops, size_t ops_capacity,
+                                                const char **error) {
+    return align_tapes(e, s, a, b, true, bound, distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity, error);
+}
+swh_status_t swh_levenshtein_align_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                            uint32_t bound, uint32_t *distances, size_t *ops_offsets, char *ops, size_t ops_capacity,
+                                            const char **error) {
+    if (!a || !a->tape || !b || !b->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
+    const Prepared *pa = (const Prepared *)a->tape, *pb = (const Prepared *)b->tape;
+    if (a->first > pa->bytes.count || a->count > pa->bytes.count - a->first || b->first > pb->bytes.count || b->count > pb->bytes.count - b->first)
+        return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
+    swh_status_t status = align_checks(e, s, a->count, b->count, distances, (const uint64_t *)ops_offsets, (const uint8_t *)ops, error);
+    if (status != swh_success_k) return status;
+    if (pa->utf8 != pb->utf8) return fail(error, swh_invalid_argument_k, "one tape was prepared as UTF-8, the other as bytes");
+    Scope *scope = (Scope *)s;
+    if (pa->device != scope->device || pb->device != scope->device)
+        return fail(error, swh_invalid_argument_k, "a prepared tape lives on another device than the scope");
+    if ((status = topk_join(scope, error)) != swh_success_k) return status;
+    TopkModeGuard mode(scope);
+    AlignRequest r{pa, pb, a->first, b->first, a->count, bound, distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity};
+    return align_run(scope, r, error);
 }
 
 }  // extern "C"

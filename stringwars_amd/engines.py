@@ -25,11 +25,13 @@ from . import _native as N
 __all__ = [
     "DeviceScope", "Strs", "DeviceTape", "PreparedTape", "ShardedPairs", "shard_cuts", "LevenshteinDistances", "LevenshteinDistancesUTF8",
     "NeedlemanWunschScores", "SmithWatermanScores", "edit_distance", "StringWarsError", "UNBOUNDED", "TOPK_MAX",
+    "ALIGN_MAX_CELLS", "Alignments",
 ]
 
 StringWarsError = N.StringWarsError
 UNBOUNDED = N.UNBOUNDED
 TOPK_MAX = N.TOPK_MAX
+ALIGN_MAX_CELLS = N.ALIGN_MAX_CELLS
 
 
 def _pointer(obj) -> int:
@@ -389,6 +391,69 @@ class ShardedCross:
 TapeLike = Union[Strs, DeviceTape, PreparedTape, Sequence[Union[bytes, str]]]
 
 
+class Alignments:
+    """The result of ``LevenshteinDistances.align``: a tape of edit operations, one string of op bytes per pair.
+
+    ``distances[i]`` is ``min(d, bound + 1)``; pair ``i``'s ops are ``ops[offsets[i]:offsets[i + 1]]``, in forward order, each one of
+    ``=`` (match), ``X`` (substitution), ``D`` (a symbol of ``a`` only) and ``I`` (a symbol of ``b`` only); a pair over the bound has none.
+    The script is the library's CANONICAL one among the optimal ones (walking back from the end: ``=`` on equal symbols, else ``X`` if the
+    diagonal is optimal, else ``D`` if the cell above is, else ``I``) -- not necessarily the one rapidfuzz or edlib picks when several are
+    optimal, though it has the same length and cost. Positions count symbols: bytes, or code points for the UTF-8 engine."""
+
+    _TAGS = {N.OP_SUBST: "replace", N.OP_DEL: "delete", N.OP_INS: "insert"}
+
+    def __init__(self, distances, offsets, ops):
+        self.distances = np.asarray(distances, dtype=np.uint32)
+        self.offsets = np.asarray(offsets, dtype=np.uint64)
+        self.ops = np.asarray(ops, dtype=np.uint8)
+        if len(self.offsets) != len(self.distances) + 1:
+            raise ValueError("offsets must have one entry more than distances")
+
+    def __len__(self) -> int:
+        return len(self.distances)
+
+    def __getitem__(self, i: int) -> bytes:
+        """The op bytes of pair ``i``, e.g. ``b"X===X=I"``."""
+        if not -len(self) <= i < len(self):
+            raise IndexError("pair index out of range")
+        i %= len(self)
+        return self.ops[int(self.offsets[i]):int(self.offsets[i + 1])].tobytes()
+
+    def cigar(self, i: int) -> str:
+        """SAM extended CIGAR of pair ``i`` (``=`` / ``X`` / ``D`` / ``I`` runs, ``a`` as the read, ``b`` as the reference): kitten -> sitting
+        gives ``"1X3=1X1=1I"``. Empty for a pair over the bound and for two empty strings."""
+        ops = self[i]
+        out, run, last = [], 0, None
+        for op in ops:
+            if op == last:
+                run += 1
+                continue
+            if last is not None:
+                out.append("%d%c" % (run, last))
+            last, run = op, 1
+        if last is not None:
+            out.append("%d%c" % (run, last))
+        return "".join(out)
+
+    def editops(self, i: int):
+        """rapidfuzz-shaped ``Levenshtein.editops``: ``(tag, src_pos, dest_pos)`` tuples with the tags ``replace`` / ``delete`` /
+        ``insert``, positions in symbols of ``a`` (source) and ``b`` (destination). The canonical script of this library, which is one of
+        the optimal ones but need not be the one rapidfuzz returns."""
+        result, src, dst = [], 0, 0
+        for op in self[i]:
+            if op == N.OP_MATCH:
+                src += 1; dst += 1
+                continue
+            result.append((self._TAGS[op], src, dst))
+            if op == N.OP_SUBST:
+                src += 1; dst += 1
+            elif op == N.OP_DEL:
+                src += 1
+            else:
+                dst += 1
+        return result
+
+
 def _as_tape(obj: TapeLike):
     if isinstance(obj, (Strs, DeviceTape, PreparedTape)):
         return obj
@@ -591,6 +656,50 @@ class LevenshteinDistances(_Engine):
             del keep_q, keep_c
         N.check(status, err)
         return indices, distances
+
+    def align(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None, bound: Optional[int] = None) -> "Alignments":
+        """The edit operations of every pair ``(a[i], b[i])`` on unit costs (``swh_levenshtein_align_*``): an :class:`Alignments` with
+        ``distances`` (``min(d, bound + 1)``, equal to ``pairs``), ``offsets`` and ``ops``. ``a`` and ``b`` are tapes, or both
+        ``PreparedTape``s. The script of each pair is the library's canonical one among the optimal ones (see ``Alignments``);
+        rapidfuzz: ``Levenshtein.editops(a[i], b[i])`` up to the choice among optimal scripts."""
+        if scope is None:
+            raise ValueError("a DeviceScope is required")
+        a, b = _as_tape(a), _as_tape(b)
+        if isinstance(a, DeviceTape) or isinstance(b, DeviceTape):   # measured on the device, like the raw calls do internally
+            a = a if isinstance(a, PreparedTape) else PreparedTape(scope, a, utf8=self._utf8)
+            b = b if isinstance(b, PreparedTape) else PreparedTape(scope, b, utf8=self._utf8)
+        if len(a) != len(b):
+            raise ValueError("a and b must hold the same number of strings")
+        count = len(a)
+        bound_value = C.c_uint32(N.UNBOUNDED if bound is None else int(bound))
+        distances = np.empty(count, dtype=np.uint32)
+        offsets = np.zeros(count + 1, dtype=np.uint64)
+        err = C.c_char_p()
+        if isinstance(a, PreparedTape) or isinstance(b, PreparedTape):
+            if not (isinstance(a, PreparedTape) and isinstance(b, PreparedTape)):
+                raise TypeError("both tapes of a call must be prepared, or neither")
+            if self._utf8 != a.utf8 or self._utf8 != b.utf8:
+                raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
+            # the symbols of a sub-view are not known on the host: the whole tapes' bound the view's, and np.empty only reserves the
+            # pages -- the call writes (and touches) the view's ops alone; a result much smaller than the buffer is copied out below
+            capacity = a._root.info["symbols"] + b._root.info["symbols"]
+            ops = np.empty(max(capacity, 1), dtype=np.uint8)
+            va, vb = a.view(), b.view()
+            status = N.lib.swh_levenshtein_align_prepared(self._handle, scope.handle, C.byref(va), C.byref(vb), bound_value,
+                                                          C.c_void_p(distances.ctypes.data), C.c_void_p(offsets.ctypes.data),
+                                                          C.c_void_p(ops.ctypes.data), capacity, C.byref(err))
+        else:
+            ta, _, keep_a = _c_tape(a, want64=True)
+            tb, _, keep_b = _c_tape(b, want64=True)
+            capacity = int(keep_a.offsets[-1]) - int(keep_a.offsets[0]) + int(keep_b.offsets[-1]) - int(keep_b.offsets[0]) if count else 0
+            ops = np.empty(max(capacity, 1), dtype=np.uint8)
+            fn = N.lib.swh_levenshtein_utf8_align_u64tape if self._utf8 else N.lib.swh_levenshtein_align_u64tape
+            status = fn(self._handle, scope.handle, C.byref(ta), C.byref(tb), bound_value, C.c_void_p(distances.ctypes.data),
+                        C.c_void_p(offsets.ctypes.data), C.c_void_p(ops.ctypes.data), capacity, C.byref(err))
+            del keep_a, keep_b
+        N.check(status, err)
+        used = int(offsets[-1])
+        return Alignments(distances, offsets, ops[:used].copy() if 2 * used < len(ops) else ops[:used])
 
     def pairs_sharded(self, batch: "ShardedPairs", scope: DeviceScope, bound: Optional[int] = None, out=None):
         """One batch over every GPU of a multi-device scope; the distances come back gathered, in pair order."""

@@ -46,6 +46,13 @@ pub struct TimingTotals { pub total_ms: f64, pub dominant_ms: f64, pub compute_m
 pub struct ShardTiming { pub compute_ms: f64, pub gather_ms: f64, pub cells: u64, pub pairs: u64 }
 
 pub const UNBOUNDED: u32 = u32::MAX;
+/// `SWH_ALIGN_MAX_CELLS`: len(a_i) * len(b_i) an alignment accepts per pair.
+pub const ALIGN_MAX_CELLS: u64 = 1 << 30;
+/// `SWH_OP_*`: the op bytes of an alignment.
+pub const OP_MATCH: u8 = b'=';
+pub const OP_SUBST: u8 = b'X';
+pub const OP_DEL: u8 = b'D';
+pub const OP_INS: u8 = b'I';
 pub const ALGORITHM_AUTO: c_int = 0;
 pub const ALGORITHM_WAVEFRONT: c_int = 1;
 pub const ALGORITHM_BITPARALLEL: c_int = 2;
@@ -102,6 +109,9 @@ extern "C" {
     fn swh_levenshtein_topk_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, k: usize, bound: u32, indices: *mut u32, distances: *mut u32, error: Err) -> c_int;
     fn swh_levenshtein_utf8_topk_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, k: usize, bound: u32, indices: *mut u32, distances: *mut u32, error: Err) -> c_int;
     fn swh_levenshtein_topk_prepared(engine: Handle, scope: Handle, queries: *const PreparedView, candidates: *const PreparedView, k: usize, bound: u32, indices: *mut u32, distances: *mut u32, error: Err) -> c_int;
+    fn swh_levenshtein_align_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, bound: u32, distances: *mut u32, ops_offsets: *mut usize, ops: *mut c_char, ops_capacity: usize, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_align_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, bound: u32, distances: *mut u32, ops_offsets: *mut usize, ops: *mut c_char, ops_capacity: usize, error: Err) -> c_int;
+    fn swh_levenshtein_align_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, bound: u32, distances: *mut u32, ops_offsets: *mut usize, ops: *mut c_char, ops_capacity: usize, error: Err) -> c_int;
     fn swh_sharded_prepare_u32tape(scope: Handle, a: *const TapeU32, b: *const TapeU32, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_prepare_u64tape(scope: Handle, a: *const TapeU64, b: *const TapeU64, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_free(sharded: Handle) -> c_int;
@@ -415,6 +425,25 @@ impl LevenshteinDistances {
         check(unsafe { swh_levenshtein_topk_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64), k,
                                                     bound.unwrap_or(UNBOUNDED), indices.as_mut_ptr(), distances.as_mut_ptr(), &mut message) }, message)
     }
+    /// Alignments (`swh_levenshtein_align_*`): pair i's canonical edit script is `ops[offsets[i] .. offsets[i + 1])`, one `OP_*` byte per
+    /// op, `distances[i] = min(d, bound + 1)`; `offsets` holds `a.len() + 1` entries and `ops` at least the two tapes' symbols.
+    /// The batched form of `rapidfuzz::distance::levenshtein::editops` (up to the choice among optimal scripts).
+    pub fn align_into(&self, scope: &DeviceScope, a: &BytesTapeView<u64>, b: &BytesTapeView<u64>, bound: Option<u32>, distances: &mut [u32],
+                      offsets: &mut [usize], ops: &mut [u8]) -> Result<(), Error> {
+        assert!(distances.len() >= a.len() && offsets.len() > a.len());
+        let (ta, tb) = (bytes_tape(a), bytes_tape(b));
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_align_u64tape(self.handle, scope.handle, &ta, &tb, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
+                                                     offsets.as_mut_ptr(), ops.as_mut_ptr() as *mut c_char, ops.len(), &mut message) }, message)
+    }
+    pub fn align_into_prepared(&self, scope: &DeviceScope, a: &PreparedTape, b: &PreparedTape, bound: Option<u32>, distances: &mut [u32],
+                               offsets: &mut [usize], ops: &mut [u8]) -> Result<(), Error> {
+        assert!(distances.len() >= a.len() && offsets.len() > a.len());
+        let (va, vb) = (a.view(), b.view());
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_align_prepared(self.handle, scope.handle, &va, &vb, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
+                                                      offsets.as_mut_ptr(), ops.as_mut_ptr() as *mut c_char, ops.len(), &mut message) }, message)
+    }
     pub fn topk_into_prepared(&self, scope: &DeviceScope, queries: &PreparedTape, candidates: Option<&PreparedTape>, k: usize, bound: Option<u32>,
                               indices: &mut [u32], distances: &mut [u32]) -> Result<(), Error> {
         assert!(indices.len() >= queries.len() * k && distances.len() >= queries.len() * k);
@@ -459,6 +488,23 @@ impl LevenshteinDistancesUtf8 {
         let (va, vb) = (a.view(), b.view());
         let mut message = ptr::null();
         check(unsafe { swh_levenshtein_pairs_prepared(self.handle, scope.handle, &va, &vb, bound.unwrap_or(UNBOUNDED), out.as_mut_ptr(), 4, &mut message) }, message)
+    }
+    /// Alignments over code points (see `LevenshteinDistances::align_into`).
+    pub fn align_into(&self, scope: &DeviceScope, a: &CharsTapeView<u64>, b: &CharsTapeView<u64>, bound: Option<u32>, distances: &mut [u32],
+                      offsets: &mut [usize], ops: &mut [u8]) -> Result<(), Error> {
+        assert!(distances.len() >= a.len() && offsets.len() > a.len());
+        let (ta, tb) = (chars_tape(a), chars_tape(b));
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_utf8_align_u64tape(self.handle, scope.handle, &ta, &tb, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
+                                                          offsets.as_mut_ptr(), ops.as_mut_ptr() as *mut c_char, ops.len(), &mut message) }, message)
+    }
+    pub fn align_into_prepared(&self, scope: &DeviceScope, a: &PreparedTape, b: &PreparedTape, bound: Option<u32>, distances: &mut [u32],
+                               offsets: &mut [usize], ops: &mut [u8]) -> Result<(), Error> {
+        assert!(distances.len() >= a.len() && offsets.len() > a.len());
+        let (va, vb) = (a.view(), b.view());
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_align_prepared(self.handle, scope.handle, &va, &vb, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
+                                                      offsets.as_mut_ptr(), ops.as_mut_ptr() as *mut c_char, ops.len(), &mut message) }, message)
     }
     /// Top-k search over code points (see `LevenshteinDistances::topk_into`).
     pub fn topk_into(&self, scope: &DeviceScope, queries: &CharsTapeView<u64>, candidates: Option<&CharsTapeView<u64>>, k: usize, bound: Option<u32>,
