@@ -6,6 +6,7 @@
 // swh_no_device_k.
 #include <atomic>
 #include <chrono>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,17 +22,17 @@ namespace swh {
 
 // ---- error text (static storage, one slot per thread) ----------------------------------------
 static thread_local char g_error_text[512];
-static swh_status_t fail(const char **error, swh_status_t status, const char *fmt, const char *a = "",
-                         const char *b = "") {
-    snprintf(g_error_text, sizeof g_error_text, fmt, a, b);
+__attribute__((format(printf, 3, 4))) static swh_status_t fail(const char **error, swh_status_t status, const char *fmt, ...) {
+    va_list args;
+    va_start(args, fmt);
+    vsnprintf(g_error_text, sizeof g_error_text, fmt, args);
+    va_end(args);
     if (error) *error = g_error_text;
     return status;
 }
 static swh_status_t fail_hip(const char **error, const HipFailure &f) {
-    snprintf(g_error_text, sizeof g_error_text, "HIP error '%s' in %s", hipGetErrorString(f.code), f.what);
-    if (error) *error = g_error_text;
     (void)hipGetLastError();
-    return f.code == hipErrorOutOfMemory ? swh_bad_alloc_k : swh_device_error_k;
+    return fail(error, f.code == hipErrorOutOfMemory ? swh_bad_alloc_k : swh_device_error_k, "HIP error '%s' in %s", hipGetErrorString(f.code), f.what);
 }
 
 // ---- kernel stamps -------------------------------------------------------------------------------
@@ -107,6 +108,13 @@ static void collect_timing(Scope *scope) {
     t.compute_ms = covered;
 }
 
+static void add_to_totals(swh_timing_totals_t &totals, const swh_timing_t &call) {
+    totals.total_ms += call.total_ms;
+    totals.dominant_ms += call.dominant_ms;
+    totals.compute_ms += call.compute_ms;
+    totals.calls += 1;
+}
+
 // Reads the events of the scope's last call once they are complete and adds the call to the running totals.
 // `complete`: the caller has synchronised with the scope's last call. Otherwise (the start of the next call in
 // asynchronous mode) completion is only known when profiling is on, through the call's stop events.
@@ -141,22 +149,17 @@ static void harvest_timing(Scope *scope, bool complete) {
         }
     }
     scope->summary_pending = false;
-    if (timed) {
-        scope->totals.total_ms += scope->last_timing.total_ms;
-        scope->totals.dominant_ms += scope->last_timing.dominant_ms;
-        scope->totals.compute_ms += scope->last_timing.compute_ms;
-        scope->totals.calls += 1;
-    }
+    if (timed) add_to_totals(scope->totals, scope->last_timing);
     scope->stamps_pending = false;
 }
 
 // ---- scratch -------------------------------------------------------------------------------------
+static size_t pad(size_t n) { return (n + 255) & ~(size_t)255; }
 struct Carver {
     char *base; size_t used, cap;
     template <typename T> T *take(size_t n) {
-        size_t bytes = (n * sizeof(T) + 255) & ~(size_t)255;
         char *p = base ? base + used : nullptr;
-        used += bytes;
+        used += pad(n * sizeof(T));
         return (T *)p;
     }
 };
@@ -237,6 +240,26 @@ struct CallSpec {
     uint32_t skip_upto = 0;                        // ... where that kernel HAS scored every pair of two strings of at most this many symbols
     bool flat_staging = false;                     // redo of a raw UTF-8 call whose string-by-string staging met a string too long for it
 };
+
+// ---- prepared tapes in a call -------------------------------------------------------------------------------------------------
+static bool view_fits(const swh_prepared_view_t *view) {
+    const Prepared *p = (const Prepared *)view->tape;
+    return view->first <= p->bytes.count && view->count <= p->bytes.count - view->first;
+}
+static swh_status_t check_prepared_pair(const Scope *scope, const Prepared *pa, const Prepared *pb, const char **error) {
+    if (pa->utf8 != pb->utf8) return fail(error, swh_invalid_argument_k, "one tape was prepared as UTF-8, the other as bytes");
+    if (pa->device != scope->device || pb->device != scope->device)
+        return fail(error, swh_invalid_argument_k, "a prepared tape lives on another device than the scope");
+    return swh_success_k;
+}
+// strings [first, first + count) of a prepared tape: its code points (`code_points` on a UTF-8 tape: u64 offsets) or its bytes
+static TapeRef prepared_view(const Prepared *p, bool code_points, size_t first, size_t count) {
+    const bool decoded = code_points && p->utf8;
+    TapeRef t = decoded ? p->symbols : p->bytes;
+    t.offsets = (const char *)t.offsets + first * (decoded || p->off64 ? 8 : 4);
+    t.count = count;
+    return t;
+}
 
 static uint64_t read_offset(const void *offs, int off64, size_t i, bool device, hipStream_t stream) {
     uint64_t v = 0;
@@ -391,139 +414,290 @@ static int short_route_choice() {
     return choice;
 }
 
-static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSpec &spec, const char **error) {
+static bool bitparallel_ok(const Engine *engine) {
+    return engine->kind == 0 && engine->unit_costs && engine->algorithm != swh_algorithm_wavefront_k;
+}
+static uint64_t call_pairs(const CallSpec &spec) { return spec.cross ? (uint64_t)spec.a.count * spec.b.count : spec.a.count; }
+
+// What a call knows about its strings' lengths before it launches anything: a guarantee for prepared tapes, a belief from the scope's
+// previous call (the kernels verify it), or -- a Levenshtein engine forced onto the tiled kernel -- that kernel's 2048 symbols.
+struct Lengths {
+    bool known = false, guaranteed = false;
+    uint32_t la_max = 0, lb_max = 0;
+    uint64_t prepared_mean_x16 = 0;   // prepared tapes: the longer mean string of the two whole tapes, bytes x 16
+};
+static Lengths call_lengths(const Scope *scope, const Engine *engine, const CallSpec &spec, bool utf8) {
+    Lengths l;
+    if (spec.pa) {
+        l.known = l.guaranteed = true;
+        l.la_max = utf8 ? spec.pa->longest_symbols : spec.pa->longest_bytes;
+        l.lb_max = utf8 ? spec.pb->longest_symbols : spec.pb->longest_bytes;
+        const uint64_t ma = spec.pa->bytes.count ? spec.pa->total_bytes * 16 / spec.pa->bytes.count : 0;
+        const uint64_t mb = spec.pb->bytes.count ? spec.pb->total_bytes * 16 / spec.pb->bytes.count : 0;
+        l.prepared_mean_x16 = std::max(ma, mb);
+    } else if (scope->hint_lengths) {
+        l.known = true;
+        l.la_max = scope->hint_max_la; l.lb_max = scope->hint_max_lb;
+    } else if (engine->kind == 0 && engine->algorithm == swh_algorithm_tiled_k) {
+        l.known = true;
+        l.la_max = l.lb_max = 2048;
+    }
+    return l;
+}
+
+struct RouteChoice {
+    Route route = kRoutePlanned;
+    uint32_t longest = 0;      // what the plan-free kernel is launched for
+    bool align_wide = false;   // kRouteAlignShort on k_align_cross_wide (its alphabet condition is checked by the kernel)
+};
+// Which kernels a call runs on (DESIGN.md §4's route table). Calls no HIP API and changes nothing on the scope. `dev_out`: the output is
+// in device memory, where an asynchronous call cannot look at the outcome -- it only acts on lengths that are guaranteed.
+static RouteChoice pick_route(const Scope *scope, const Engine *engine, const CallSpec &spec, bool utf8, bool dev_out, const Lengths &len) {
+    RouteChoice r;
+    const bool can_verify = !scope->async || !dev_out;
+    const bool usable = len.known && (len.guaranteed || can_verify);
+    const uint32_t both = std::max(len.la_max, len.lb_max);
+    if (engine->kind == 0) {
+        // Unit-cost Levenshtein whose string lengths are known skips the planning pre-pass altogether.
+        if (!bitparallel_ok(engine) || spec.force_planned || engine->algorithm == swh_algorithm_bitparallel_k || !usable) return r;
+        r.longest = both;
+        // plan_key(): the banded kernel wins from ~6 blocks at k = 32 (bounds of 64 .. 255: where band_cost() says so)
+        const bool band_pays = spec.bound <= 63 ? both > 32
+                                                : spec.bound <= band_max_bound() && band_cost(spec.bound) < (utf8 ? 40u : 28u) * ((both + 31) >> 5);
+        const int choice = short_route_choice();
+        if (engine->algorithm == swh_algorithm_tiled_k)
+            r.route = (!len.guaranteed || std::min(len.la_max, len.lb_max) <= 2048) ? kRouteTiled : kRoutePlanned;
+        else if (!band_pays && both <= tiled_longest_limit()) {
+            if (both <= 32 && choice != 2 && spec.cross) r.route = kRouteCrossShort;   // k_cross_short, or k_cross_short_cp for code points
+            else if (both <= 32 && choice != 2 && !utf8)
+                r.route = both <= 16 && call_pairs(spec) >= short_tiled_min_pairs() && choice == 0 ? kRouteShortTiled : kRouteDirectShort;
+            else r.route = kRouteTiled;
+        }
+        return r;
+    }
+    // Alignment scores on a class table when both tapes hold word-sized strings only (the reference's default `words` token mode,
+    // bench.rs:271): one pair per lane, no pre-pass (alignshort.hip). STRINGWARS_AMD_ALIGN_SHORT=0 keeps them on the planned path.
+    static const bool align_short_on = [] { const char *e = test_hook("STRINGWARS_AMD_ALIGN_SHORT"); return !e || atoi(e) != 0; }();
+    if (!engine->scoring.class_table || utf8 || spec.force_planned || !align_short_on) return r;
+    // up to 128 symbols for cross-products with linear gaps, as long as the candidates of a work item use at most eight symbol
+    // classes (DNA; the kernel checks per item, a scope that met richer text stops trying -- `align_wide_off`)
+    static const bool wide_on = [] { const char *e = test_hook("STRINGWARS_AMD_ALIGN_WIDE"); return !e || atoi(e) != 0; }();   // comparison knob: 0 = the multi-pass kernel instead
+    // (what the latch is keyed by: prepared handles, else the tapes' data pointers -- sub-views of one tape share them)
+    const void *key_a = spec.pa ? (const void *)spec.pa : (const void *)spec.a.data, *key_b = spec.pb ? (const void *)spec.pb : (const void *)spec.b.data;
+    const bool wide_off = scope->align_wide_off.engine == engine->uid && scope->align_wide_off.a == key_a && scope->align_wide_off.b == key_b;
+    const bool affine = engine->scoring.open != engine->scoring.extend;
+    const bool wide = wide_on && spec.cross && both <= 128 && !affine && !wide_off && can_verify;
+    const uint32_t per_item = align_long_queries(scope, spec.a.count, spec.b.count);
+    const uint64_t long_items = ((uint64_t)(spec.b.count + 63) / 64) * ((uint64_t)(spec.a.count + per_item - 1) / per_item);
+    if (usable && (both <= 32 || wide)) {
+        r.route = kRouteAlignShort;
+        r.longest = both;
+        r.align_wide = both > 32;
+    } else if (len.known && can_verify && spec.cross && !wide_off && both <= std::min(align_long_limit(), align_long_pays(engine->kind == 2, affine)) &&
+               align_long_fits(scope, long_items, len.la_max, affine)) {
+        // longer ones on the same small-alphabet condition: columns in passes of 128 (local or Gotoh: 64, both: 32), the boundary
+        // column between passes through global memory (alignshort.hip: k_align_cross_long), up to where it beats the
+        // column-profile kernel (align_long_pays)
+        r.route = kRouteAlignLong;
+        r.longest = len.la_max;
+    } else if (usable && both <= 64) {
+        // tokens of up to 64 bytes over any alphabet (multilingual words: ~5 code points are ~11 bytes, their tail reaches past 32):
+        // the lane-per-pair kernel with a register row of 64 cells
+        r.route = kRouteAlignShort;
+        r.longest = both;
+    } else if (len.known && can_verify && !scope->async) {
+        // word tokens with a FEW long ones among them (a URL, a sentence of a script that writes no spaces): the lane kernel scores
+        // every pair of two strings that fit its 64 cells, reports that some did not, and the redo plans only the pairs with a
+        // longer string (`skip_upto`) -- instead of 4 M word pairs on kernels built for long strings (2048 x 2048 multilingual
+        // words with one token of 70 bytes: 2.2 ms per call, NW linear). Taken when the mean string is word-sized.
+        const uint64_t mean_x16 = spec.pa ? len.prepared_mean_x16 : scope->hint_mean_string_x16;
+        if (mean_x16 && mean_x16 <= 24 * 16) {
+            r.route = kRouteAlignShort;
+            r.longest = 64;
+        }
+    }
+    return r;
+}
+
+// ---- one engine call, in phases ----------------------------------------------------------------------------------------------
+// run_call_on checks the call, then runs attempts until one is done. An attempt that finds out that what it launched cannot stand
+// (the tapes' totals changed, a string too long for the string-by-string staging, a length or alphabet belief that did not hold,
+// a fused planner that could not gather its grid) updates the scope where it found out and hands back the spec of the next attempt.
+static swh_status_t check_call(Scope *scope, const Engine *engine, const CallSpec &spec, const char **error) {
     if (!scope || !engine) return fail(error, swh_invalid_argument_k, "null scope or engine");
     if (!spec.out && spec.a.count) return fail(error, swh_invalid_argument_k, "null output pointer");
     if (!spec.cross && spec.a.count != spec.b.count)
         return fail(error, swh_invalid_argument_k, "pairwise call needs tapes of equal count");
-    const uint64_t pairs = spec.cross ? (uint64_t)spec.a.count * spec.b.count : spec.a.count;
-    if (pairs >= 0xFFFFFFF0ull) return fail(error, swh_unsupported_length_k, "more than 2^32 pairs in one call");
-    const bool prepared = spec.pa != nullptr;
-    if (prepared) {
-        if (!spec.pb) return fail(error, swh_invalid_argument_k, "both tapes must be prepared, or neither");
-        if (spec.pa->utf8 != spec.pb->utf8) return fail(error, swh_invalid_argument_k, "one tape was prepared as UTF-8, the other as bytes");
-        if (spec.pa->device != scope->device || spec.pb->device != scope->device)
-            return fail(error, swh_invalid_argument_k, "a prepared tape lives on another device than the scope");
-    }
-    harvest_timing(scope, false);   // an earlier asynchronous call on this scope / lane
-    scope->stamps_used = 0;
-    scope->last_timing = swh_timing_t{};
-    if (pairs == 0) return swh_success_k;
+    if (call_pairs(spec) >= 0xFFFFFFF0ull) return fail(error, swh_unsupported_length_k, "more than 2^32 pairs in one call");
+    if (!spec.pa) return swh_success_k;
+    if (!spec.pb) return fail(error, swh_invalid_argument_k, "both tapes must be prepared, or neither");
+    return check_prepared_pair(scope, spec.pa, spec.pb, error);
+}
+
+static bool believe_sizes() {
+    static const bool believe = [] { const char *e = test_hook("STRINGWARS_AMD_SIZE_BELIEF"); return !e || atoi(e) != 0; }();
+    return believe;
+}
+static bool same_as_believed(const HostTape &t, const Scope::SizeBelief &slot) {
+    return slot.valid && slot.data == t.data && slot.offsets == t.offsets && slot.count == t.count && slot.off64 == t.off64;
+}
+static void remember_total(Scope::SizeBelief &slot, const HostTape &t, uint64_t bytes, bool valid) {
+    slot = Scope::SizeBelief{t.data, t.offsets, t.count, t.off64, bytes, valid, false};
+}
+// Does the allocation that holds `p` reach `bytes` beyond it? A belief about a raw device tape is only acted on where it does.
+static bool allocation_covers(const void *p, uint64_t bytes) {
+    void *base = nullptr; size_t size = 0;
+    return hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)p) == hipSuccess && (const char *)p + bytes <= (const char *)base + size;
+}
+
+constexpr uint32_t kDoublingBound = 63;
+struct Doubling { bool on = false; double need = 0; };
+
+// One attempt at a call: its state, filled phase by phase, and the phases. What follows from the spec alone comes first.
+struct Call {
+    Scope *scope; const Engine *engine; const CallSpec &spec; const char **error;
+    hipStream_t stream = scope->stream;
+    uint64_t pairs = call_pairs(spec);
+    bool prepared = spec.pa != nullptr, bitpar_ok = bitparallel_ok(engine);
     // code points of pure-ASCII tapes are their bytes: such a pair of prepared tapes runs on the byte kernels
     // (only when both byte tapes have the same offset width: whether a UTF-8 call is accepted must not depend on what the
     // tapes contain -- a u32 / u64 mix falls back to the decoded tapes, whose offsets are always u64)
-    const bool utf8 = prepared ? (spec.pa->utf8 && !(spec.pa->ascii && spec.pb->ascii && spec.pa->off64 == spec.pb->off64)) : spec.utf8;
-    if (prepared && !utf8 && spec.pa->off64 != spec.pb->off64)
-        return fail(error, swh_invalid_argument_k, "prepared byte tapes must share one offset width");
-    if (utf8 && engine->scoring.matrix)
-        return fail(error, swh_not_implemented_k, "substitution-matrix scoring over UTF-8 code points (the matrix is indexed by bytes)");
-    try {
-        SWH_HIP_CHECK(hipSetDevice(scope->device));
-        hipStream_t stream = scope->stream;
-        const size_t ow = prepared ? (utf8 ? 8 : (spec.pa->off64 ? 8 : 4)) : (spec.a.off64 ? 8 : 4);
-        const size_t elem = spec.out64 ? 8 : 4;
+    bool utf8 = prepared ? (spec.pa->utf8 && !(spec.pa->ascii && spec.pb->ascii && spec.pa->off64 == spec.pb->off64)) : spec.utf8;
+    size_t ow = prepared ? (utf8 ? 8 : (spec.pa->off64 ? 8 : 4)) : (spec.a.off64 ? 8 : 4), elem = spec.out64 ? 8 : 4;
+    // residency of raw tapes (prepared ones are resident) and of the output; the tapes' byte totals where the call needs them
+    bool dev_a_data = true, dev_a_off = true, dev_b_data = true, dev_b_off = true, same_tape = false, dev_out = false;
+    bool need_sizes = false, believed_sizes = false;
+    uint64_t a_bytes = 0, b_bytes = 0;
+    // the tapes and the output as the kernels see them
+    TapeRef ta{}, tb{};
+    uint32_t sym_bytes = 1, off64 = 0;
+    char *out_dev = nullptr;
+    size_t dev_out_stride = 0, dev_row_stride = 0, out_bytes = 0;
+    Lengths lengths;
+    RouteChoice rc;
+    uint32_t *invalid_dev = nullptr, *invalid_host = nullptr;   // UTF-8 staging flags: device words, their pinned copy
+    bool staged_by_string = false;
+    PrepassArgs pre{};
+    KernelArgs k{};
+    bool redo = false;   // the attempt is to be followed by another one, of `next`
+    CallSpec next{};
+    swh_status_t redo_with(const CallSpec &spec_of_next) { redo = true; next = spec_of_next; return swh_success_k; }
 
-        // -- residency --------------------------------------------------------------------------
-        bool dev_a_data = true, dev_a_off = true, dev_b_data = true, dev_b_off = true;
-        bool same_tape = false;
-        if (!prepared) {
-            dev_a_data = is_device_pointer(spec.a.data); dev_a_off = is_device_pointer(spec.a.offsets);
-            dev_b_data = is_device_pointer(spec.b.data); dev_b_off = is_device_pointer(spec.b.offsets);
-            same_tape = spec.b.data == spec.a.data && spec.b.offsets == spec.a.offsets && spec.b.count == spec.a.count;
+    // The attempt (its arguments passed check_call).
+    swh_status_t attempt() {
+        if (pairs == 0) return swh_success_k;
+        if (prepared && !utf8 && spec.pa->off64 != spec.pb->off64)
+            return fail(error, swh_invalid_argument_k, "prepared byte tapes must share one offset width");
+        if (utf8 && engine->scoring.matrix)
+            return fail(error, swh_not_implemented_k, "substitution-matrix scoring over UTF-8 code points (the matrix is indexed by bytes)");
+        try {
+            SWH_HIP_CHECK(hipSetDevice(scope->device));
+            if (!prepared) {
+                dev_a_data = is_device_pointer(spec.a.data); dev_a_off = is_device_pointer(spec.a.offsets);
+                dev_b_data = is_device_pointer(spec.b.data); dev_b_off = is_device_pointer(spec.b.offsets);
+                same_tape = spec.b.data == spec.a.data && spec.b.offsets == spec.a.offsets && spec.b.count == spec.a.count;
+            }
+            dev_out = is_device_pointer(spec.out);
+            swh_status_t status = swh_success_k;
+            if (ascii_shortcut(status)) return status;
+            read_totals();
+            place_buffers();
+            lengths = call_lengths(scope, engine, spec, utf8);
+            rc = pick_route(scope, engine, spec, utf8, dev_out, lengths);
+            carve_scratch();
+            if (spec.cross && spec.b.count >= 0xFFFFFFFFull) return fail(error, swh_unsupported_length_k, "more than 2^32 candidates");
+            set_up_kernels();
+            invalid_host = (uint32_t *)(scope->plan_host + 1);
+            *invalid_host = 0;
+            return rc.route == kRoutePlanned ? run_planned() : run_plan_free();
+        } catch (const HipFailure &f) {
+            return fail_hip(error, f);
+        } catch (const std::bad_alloc &) {
+            return fail(error, swh_bad_alloc_k, "host allocation failed");
         }
-        const bool dev_out = is_device_pointer(spec.out);
-        static const bool believe = [] { const char *e = test_hook("STRINGWARS_AMD_SIZE_BELIEF"); return !e || atoi(e) != 0; }();
-        auto same_as_believed = [](const HostTape &t, const Scope::SizeBelief &slot) {
-            return slot.valid && slot.data == t.data && slot.offsets == t.offsets && slot.count == t.count && slot.off64 == t.off64;
-        };
-        // -- raw UTF-8 tapes that were pure ASCII the last time this scope staged them: code points of ASCII text are its bytes, so the
-        // call runs on the byte kernels -- no staging, the word-sized and cross-product kernels instead of the code-point ones -- behind
-        // a kernel that checks every byte of both tapes; if one is above 0x7F after all, the call is done again the long way.
-        // (Synchronous scopes only: an asynchronous call cannot be redone behind the caller's back.)
-        if (believe && utf8 && !prepared && !scope->async && !spec.force_planned && dev_a_data && dev_a_off && dev_b_data && dev_b_off &&
-            same_as_believed(spec.a, scope->size_belief[0]) && scope->size_belief[0].ascii &&
-            (same_tape || (same_as_believed(spec.b, scope->size_belief[1]) && scope->size_belief[1].ascii))) {
-            const Scope::SizeBelief &ba = scope->size_belief[0], &bb = same_tape ? scope->size_belief[0] : scope->size_belief[1];
-            void *base = nullptr; size_t size = 0;
-            const bool covered = hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)spec.a.data) == hipSuccess &&
-                                 (const char *)spec.a.data + ba.bytes <= (const char *)base + size &&
-                                 hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)spec.b.data) == hipSuccess &&
-                                 (const char *)spec.b.data + bb.bytes <= (const char *)base + size;
-            if (covered) {
-                uint32_t *seen_host = (uint32_t *)((char *)scope->summary_host + 128), *seen_dev = (uint32_t *)((char *)scope->summary_dev + 128);
-                *seen_host = 0;
-                const uint64_t most = std::max<uint64_t>(ba.bytes, bb.bytes);
-                const uint32_t blocks = (uint32_t)std::min<uint64_t>((most + 4095) / 4096 + 1, (uint64_t)scope->compute_units * 8);
-                hipLaunchKernelGGL(k_ascii_check, dim3(blocks), dim3(256), 0, stream, (const uint8_t *)spec.a.data, spec.a.offsets, (uint64_t)spec.a.count,
-                                   (const uint8_t *)spec.b.data, same_tape ? nullptr : spec.b.offsets, (uint64_t)spec.b.count, (uint32_t)spec.a.off64, seen_dev);
-                SWH_HIP_CHECK(hipGetLastError());
-                CallSpec as_bytes = spec;
-                as_bytes.utf8 = false;
-                const swh_status_t status = run_call_on(scope, engine, as_bytes, error);
-                if (status != swh_success_k) return status;
-                // (the check ran in front of the byte kernels on the same stream: it is complete when their results are)
-                if (__atomic_load_n(seen_host, __ATOMIC_ACQUIRE) == 0) return swh_success_k;
-                scope->size_belief[0].ascii = scope->size_belief[1].ascii = false;
-                scope->summary_pending = false;
-                scope->stamps_pending = false;
-            } else {
+    }
+
+    // Raw UTF-8 tapes that were pure ASCII the last time this scope staged them: code points of ASCII text are its bytes, so the call runs on
+    // the byte kernels -- no staging, the word-sized and cross-product kernels instead of the code-point ones -- behind a kernel that checks
+    // every byte of both tapes. True when that settled the call (`status`). False when it was not tried, or when a byte above 0x7F turned
+    // up after all: the call then goes on the long way in the same attempt, after the byte kernels' stamps.
+    // (Synchronous scopes only: an asynchronous call cannot be redone behind the caller's back.)
+    bool ascii_shortcut(swh_status_t &status) {
+        if (!(believe_sizes() && utf8 && !prepared && !scope->async && !spec.force_planned && dev_a_data && dev_a_off && dev_b_data &&
+              dev_b_off && same_as_believed(spec.a, scope->size_belief[0]) && scope->size_belief[0].ascii &&
+              (same_tape || (same_as_believed(spec.b, scope->size_belief[1]) && scope->size_belief[1].ascii))))
+            return false;
+        const Scope::SizeBelief &ba = scope->size_belief[0], &bb = same_tape ? scope->size_belief[0] : scope->size_belief[1];
+        if (!allocation_covers(spec.a.data, ba.bytes) || !allocation_covers(spec.b.data, bb.bytes)) {
+            (void)hipGetLastError();
+            return false;
+        }
+        uint32_t *seen_host = (uint32_t *)((char *)scope->summary_host + 128), *seen_dev = (uint32_t *)((char *)scope->summary_dev + 128);
+        *seen_host = 0;
+        const uint64_t most = std::max<uint64_t>(ba.bytes, bb.bytes);
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>((most + 4095) / 4096 + 1, (uint64_t)scope->compute_units * 8);
+        hipLaunchKernelGGL(k_ascii_check, dim3(blocks), dim3(256), 0, stream, (const uint8_t *)spec.a.data, spec.a.offsets, (uint64_t)spec.a.count,
+                           (const uint8_t *)spec.b.data, same_tape ? nullptr : spec.b.offsets, (uint64_t)spec.b.count, (uint32_t)spec.a.off64, seen_dev);
+        SWH_HIP_CHECK(hipGetLastError());
+        CallSpec as_bytes = spec;
+        as_bytes.utf8 = false;
+        status = run_call_on(scope, engine, as_bytes, error);
+        // (the check ran in front of the byte kernels on the same stream: it is complete when their results are)
+        if (status != swh_success_k || __atomic_load_n(seen_host, __ATOMIC_ACQUIRE) == 0) return true;
+        scope->size_belief[0].ascii = scope->size_belief[1].ascii = false;
+        scope->summary_pending = false;
+        scope->stamps_pending = false;
+        return false;
+    }
+
+    // The tapes' byte totals, where the call needs them before its first launch (scratch, grids): host tapes and raw UTF-8 tapes. A UTF-8
+    // call on raw device tapes would pay two synchronous 4-byte copies for them, ~25 us of a 0.7 ms call: the same tapes as last time
+    // (pointers, count) are believed to hold the same totals if the allocations still cover them; k_utf8_finish compares with
+    // offsets[count] and the call is redone if not.
+    void read_totals() {
+        need_sizes = !prepared && (!dev_a_data || !dev_b_data || utf8);
+        if (!need_sizes) return;
+        const bool may_believe = believe_sizes() && utf8 && !spec.force_planned;
+        auto total_of = [&](const HostTape &t, bool dev_data, bool dev_off, Scope::SizeBelief &slot) -> uint64_t {
+            if (may_believe && dev_data && dev_off && same_as_believed(t, slot)) {
+                if (allocation_covers(t.data, slot.bytes) && allocation_covers(t.offsets, (t.count + 1) * (t.off64 ? 8 : 4))) {
+                    believed_sizes = true;
+                    return slot.bytes;
+                }
                 (void)hipGetLastError();
             }
+            const uint64_t bytes = read_offset(t.offsets, t.off64, t.count, dev_off, stream);
+            remember_total(slot, t, bytes, dev_data && dev_off);
+            return bytes;
+        };
+        // (two device tapes the scope has no belief about: both totals in ONE round trip -- two copies, one wait -- instead of two)
+        const bool both_fresh = !same_tape && dev_a_off && dev_b_off && dev_a_data && dev_b_data &&
+                                !(may_believe && (same_as_believed(spec.a, scope->size_belief[0]) || same_as_believed(spec.b, scope->size_belief[1])));
+        if (both_fresh) {
+            uint64_t *words = (uint64_t *)(scope->plan_host + 1) + 3;   // (pinned: bytes 24 .. 39 behind the plan; the UTF-8 flag words land in its first 20)
+            words[0] = words[1] = 0;
+            const size_t wa = spec.a.off64 ? 8 : 4, wb = spec.b.off64 ? 8 : 4;
+            SWH_HIP_CHECK(hipMemcpyAsync(&words[0], (const char *)spec.a.offsets + spec.a.count * wa, wa, hipMemcpyDeviceToHost, stream));
+            SWH_HIP_CHECK(hipMemcpyAsync(&words[1], (const char *)spec.b.offsets + spec.b.count * wb, wb, hipMemcpyDeviceToHost, stream));
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            a_bytes = words[0]; b_bytes = words[1];
+            remember_total(scope->size_belief[0], spec.a, a_bytes, true);
+            remember_total(scope->size_belief[1], spec.b, b_bytes, true);
+        } else {
+            a_bytes = total_of(spec.a, dev_a_data, dev_a_off, scope->size_belief[0]);
+            b_bytes = same_tape ? a_bytes : total_of(spec.b, dev_b_data, dev_b_off, scope->size_belief[1]);
         }
-        uint64_t a_bytes = 0, b_bytes = 0;
-        const bool need_sizes = !prepared && (!dev_a_data || !dev_b_data || utf8);
-        bool believed_sizes = false;
-        if (need_sizes) {
-            // A UTF-8 call on raw device tapes needs the tapes' byte totals before its first launch (scratch, grids): two synchronous
-            // 4-byte copies, ~25 us of a 0.7 ms call. The same tapes as last time (pointers, count) are believed to hold the same
-            // totals if the allocations still cover them; k_utf8_finish compares with offsets[count] and the call is redone if not.
-            auto total_of = [&](const HostTape &t, bool dev_data, bool dev_off, Scope::SizeBelief &slot) -> uint64_t {
-                if (believe && utf8 && dev_data && dev_off && !spec.force_planned && same_as_believed(t, slot)) {
-                    void *base = nullptr; size_t size = 0;
-                    const size_t ow_t = t.off64 ? 8 : 4;
-                    bool covered = hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)t.data) == hipSuccess &&
-                                   (const char *)t.data + slot.bytes <= (const char *)base + size;
-                    covered = covered && hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)t.offsets) == hipSuccess &&
-                              (const char *)t.offsets + (t.count + 1) * ow_t <= (const char *)base + size;
-                    if (covered) { believed_sizes = true; return slot.bytes; }
-                    (void)hipGetLastError();
-                }
-                const uint64_t bytes = read_offset(t.offsets, t.off64, t.count, dev_off, stream);
-                slot.data = t.data; slot.offsets = t.offsets; slot.count = t.count; slot.off64 = t.off64; slot.bytes = bytes; slot.valid = dev_data && dev_off;
-                slot.ascii = false;
-                return bytes;
-            };
-            // (two device tapes the scope has no belief about: both totals in ONE round trip -- two copies, one wait -- instead of two)
-            const bool both_fresh = !same_tape && dev_a_off && dev_b_off && dev_a_data && dev_b_data &&
-                                    !(believe && utf8 && !spec.force_planned && (same_as_believed(spec.a, scope->size_belief[0]) || same_as_believed(spec.b, scope->size_belief[1])));
-            if (both_fresh) {
-                uint64_t *words = (uint64_t *)(scope->plan_host + 1) + 3;   // (pinned: bytes 24 .. 39 behind the plan; the UTF-8 flag words land in its first 20)
-                words[0] = words[1] = 0;
-                const size_t wa = spec.a.off64 ? 8 : 4, wb = spec.b.off64 ? 8 : 4;
-                SWH_HIP_CHECK(hipMemcpyAsync(&words[0], (const char *)spec.a.offsets + spec.a.count * wa, wa, hipMemcpyDeviceToHost, stream));
-                SWH_HIP_CHECK(hipMemcpyAsync(&words[1], (const char *)spec.b.offsets + spec.b.count * wb, wb, hipMemcpyDeviceToHost, stream));
-                SWH_HIP_CHECK(hipStreamSynchronize(stream));
-                a_bytes = words[0]; b_bytes = words[1];
-                auto remember = [](Scope::SizeBelief &slot, const HostTape &t, uint64_t bytes) {
-                    slot.data = t.data; slot.offsets = t.offsets; slot.count = t.count; slot.off64 = t.off64; slot.bytes = bytes; slot.valid = true; slot.ascii = false;
-                };
-                remember(scope->size_belief[0], spec.a, a_bytes);
-                remember(scope->size_belief[1], spec.b, b_bytes);
-            } else {
-                a_bytes = total_of(spec.a, dev_a_data, dev_a_off, scope->size_belief[0]);
-                b_bytes = same_tape ? a_bytes : total_of(spec.b, dev_b_data, dev_b_off, scope->size_belief[1]);
-            }
-        }
-        // device-resident outputs are written in place with the caller's strides; host outputs are produced
-        // compactly in device staging and scattered into the caller's strides by a 2-D copy
-        const size_t dev_out_stride = dev_out ? spec.out_stride : elem;
-        const size_t dev_row_stride = dev_out ? spec.row_stride : spec.b.count * elem;
-        size_t out_bytes = spec.cross ? (spec.a.count ? (spec.a.count - 1) * dev_row_stride + spec.b.count * elem : 0)
-                                      : (size_t)(pairs - 1) * dev_out_stride + elem;
+    }
 
-        // -- staging of host-resident buffers -----------------------------------------------------
+    // Where the kernels find the tapes and put the results: views of prepared tapes, device buffers in place, host buffers copied into the
+    // scope's staging area. Device-resident outputs are written in place with the caller's strides; host outputs are produced compactly
+    // in the staging area and scattered into the caller's strides by a 2-D copy (copy_results_back).
+    void place_buffers() {
+        dev_out_stride = dev_out ? spec.out_stride : elem;
+        dev_row_stride = dev_out ? spec.row_stride : spec.b.count * elem;
+        out_bytes = spec.cross ? (spec.a.count ? (spec.a.count - 1) * dev_row_stride + spec.b.count * elem : 0)
+                           : (size_t)(pairs - 1) * dev_out_stride + elem;
         size_t stage_need = 0;
-        auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
         if (!dev_a_data) stage_need += pad(a_bytes + 8);
         if (!dev_a_off) stage_need += pad((spec.a.count + 1) * ow + 8);
         if (!same_tape) {
@@ -539,19 +713,10 @@ static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSp
             if (bytes) SWH_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
             return dst;
         };
-        TapeRef ta, tb;
-        uint32_t sym_bytes = 1, off64 = (uint32_t)spec.a.off64;
+        off64 = (uint32_t)spec.a.off64;
         if (prepared) {
-            auto view = [&](const Prepared *pt, size_t first, size_t count) {
-                const TapeRef &whole = utf8 ? pt->symbols : pt->bytes;
-                TapeRef t;
-                t.data = whole.data;
-                t.offsets = (const char *)whole.offsets + first * ow;
-                t.count = count;
-                return t;
-            };
-            ta = view(spec.pa, spec.a_first, spec.a.count);
-            tb = view(spec.pb, spec.b_first, spec.b.count);
+            ta = prepared_view(spec.pa, utf8, spec.a_first, spec.a.count);
+            tb = prepared_view(spec.pb, utf8, spec.b_first, spec.b.count);
             sym_bytes = utf8 ? 4 : 1;
             off64 = utf8 ? 1 : spec.pa->off64;
         } else {
@@ -565,236 +730,128 @@ static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSp
                 tb.count = spec.b.count;
             }
         }
-        char *out_dev = dev_out ? (char *)spec.out : st.take<char>(out_bytes);
+        out_dev = dev_out ? (char *)spec.out : st.take<char>(out_bytes);
+    }
 
-        // -- which kernels? ------------------------------------------------------------------------------
-        // Unit-cost Levenshtein whose string lengths are known -- from prepared tapes (a guarantee) or from the previous
-        // call on this scope (a belief the kernels verify) -- skips the planning pre-pass altogether.
-        const bool bitpar_ok = engine->kind == 0 && engine->unit_costs && engine->algorithm != swh_algorithm_wavefront_k;
-        Route route = kRoutePlanned;
-        uint32_t longest = 0;
-        bool guaranteed = false;
-        if (bitpar_ok && !spec.force_planned && engine->algorithm != swh_algorithm_bitparallel_k) {
-            const bool forced = engine->algorithm == swh_algorithm_tiled_k;
-            bool known = false;
-            uint32_t la_max = 0, lb_max = 0;
-            if (prepared) {
-                known = guaranteed = true;
-                la_max = utf8 ? spec.pa->longest_symbols : spec.pa->longest_bytes;
-                lb_max = utf8 ? spec.pb->longest_symbols : spec.pb->longest_bytes;
-            } else if (scope->hint_lengths) {
-                known = true;
-                la_max = scope->hint_max_la; lb_max = scope->hint_max_lb;
-            } else if (forced) {
-                known = true;
-                la_max = lb_max = 2048;
-            }
-            // an unverified belief needs the host to look at the outcome: synchronous calls with a device or host output
-            const bool can_verify = !scope->async || !dev_out;
-            if (known && (guaranteed || can_verify)) {
-                longest = la_max > lb_max ? la_max : lb_max;
-                const uint32_t shorter_side = la_max < lb_max ? la_max : lb_max;
-                // plan_key(): the banded kernel wins from ~6 blocks at k = 32 (bounds of 64 .. 255: where band_cost() says so)
-                const bool band_pays = spec.bound <= 63 ? longest > 32
-                                                        : spec.bound <= band_max_bound() && band_cost(spec.bound) < (utf8 ? 40u : 28u) * ((longest + 31) >> 5);
-                if (forced) route = (!guaranteed || shorter_side <= 2048) ? kRouteTiled : kRoutePlanned;
-                else if (!band_pays && longest <= tiled_longest_limit())
-                    route = (longest <= 32 && !utf8 && short_route_choice() != 2)
-                                ? (spec.cross ? kRouteCrossShort : (longest <= 16 && pairs >= short_tiled_min_pairs() && short_route_choice() == 0 ? kRouteShortTiled : kRouteDirectShort))
-                                : ((longest <= 32 && utf8 && spec.cross && short_route_choice() != 2) ? kRouteCrossShort   // word-sized code points: k_cross_short_cp
-                                                                                                          : kRouteTiled);
-            }
+    // The call's scratch: the planned path's permutation and keys, then what the UTF-8 staging of raw tapes carves (stage_utf8).
+    void carve_scratch() {
+        const bool planned = rc.route == kRoutePlanned, staged = utf8 && !prepared;
+        Carver probe{nullptr, 0, 0};
+        if (planned) { probe.take<uint32_t>(pairs); probe.take<uint16_t>(pairs); }
+        if (staged) {
+            probe.take<uint32_t>(a_bytes + 4); probe.take<uint64_t>(spec.a.count + 1);
+            probe.take<uint32_t>(utf8_scratch_words(a_bytes));
+            probe.take<uint32_t>(b_bytes + 4); probe.take<uint64_t>(spec.b.count + 1);
+            probe.take<uint32_t>(utf8_scratch_words(b_bytes));
+            probe.take<uint32_t>(kUtf8FlagWords);
+            probe.take<uint64_t>(2 * spec.a.count + 2); probe.take<uint64_t>(2 * spec.b.count + 2);   // (first, end) pairs of the string-by-string staging
         }
-
-        // Alignment scores on a class table when both tapes hold word-sized strings only (the reference's default `words` token mode,
-        // bench.rs:271): one pair per lane, no pre-pass (alignshort.hip). STRINGWARS_AMD_ALIGN_SHORT=0 keeps them on the planned path.
-        static const bool align_short_on = [] { const char *e = test_hook("STRINGWARS_AMD_ALIGN_SHORT"); return !e || atoi(e) != 0; }();
-        bool align_wide = false;   // kRouteAlignShort on k_align_cross_wide (its alphabet condition is checked by the kernel)
-        if (engine->kind != 0 && engine->scoring.class_table && !utf8 && !spec.force_planned && align_short_on) {
-            bool known = false;
-            uint32_t la_max = 0, lb_max = 0;
-            if (prepared) { known = guaranteed = true; la_max = spec.pa->longest_bytes; lb_max = spec.pb->longest_bytes; }
-            else if (scope->hint_lengths) { known = true; la_max = scope->hint_max_la; lb_max = scope->hint_max_lb; }
-            const bool can_verify = !scope->async || !dev_out;
-            const uint32_t both = la_max > lb_max ? la_max : lb_max;
-            // up to 128 symbols for cross-products with linear gaps, as long as the candidates of a work item use at most eight symbol
-            // classes (DNA; the kernel checks per item, a scope that met richer text stops trying -- `align_wide_off`)
-            static const bool wide_on = [] { const char *e = test_hook("STRINGWARS_AMD_ALIGN_WIDE"); return !e || atoi(e) != 0; }();   // comparison knob: 0 = the multi-pass kernel instead
-            // (what the latch is keyed by: prepared handles, else the tapes' data pointers -- sub-views of one tape share them)
-            const void *key_a = spec.pa ? (const void *)spec.pa : (const void *)spec.a.data, *key_b = spec.pb ? (const void *)spec.pb : (const void *)spec.b.data;
-            const bool wide_off = scope->align_wide_off.engine == engine->uid && scope->align_wide_off.a == key_a && scope->align_wide_off.b == key_b;
-            const bool wide = wide_on && spec.cross && both <= 128 && engine->scoring.open == engine->scoring.extend && !wide_off && can_verify;
-            if (known && (guaranteed || can_verify) && (both <= 32 || wide)) {
-                route = kRouteAlignShort;
-                longest = both;
-                align_wide = both > 32;
-            } else if (known && can_verify && spec.cross && !wide_off &&
-                       both <= std::min(align_long_limit(), align_long_pays(engine->kind == 2, engine->scoring.open != engine->scoring.extend)) &&
-                       align_long_fits(scope, ((uint64_t)(spec.b.count + 63) / 64) * ((uint64_t)(spec.a.count + align_long_queries(scope, spec.a.count, spec.b.count) - 1) /
-                                                                                      align_long_queries(scope, spec.a.count, spec.b.count)),
-                                       la_max, engine->scoring.open != engine->scoring.extend)) {
-                // longer ones on the same small-alphabet condition: columns in passes of 128 (local or Gotoh: 64, both: 32), the boundary
-                // column between passes through global memory (alignshort.hip: k_align_cross_long), up to where it beats the
-                // column-profile kernel (align_long_pays)
-                route = kRouteAlignLong;
-                longest = la_max;
-            } else if (known && (guaranteed || can_verify) && both <= 64) {
-                // tokens of up to 64 bytes over any alphabet (multilingual words: ~5 code points are ~11 bytes, their tail reaches past 32):
-                // the lane-per-pair kernel with a register row of 64 cells
-                route = kRouteAlignShort;
-                longest = both;
-            } else if (known && can_verify && !scope->async) {
-                // word tokens with a FEW long ones among them (a URL, a sentence of a script that writes no spaces): the lane kernel scores
-                // every pair of two strings that fit its 64 cells, reports that some did not, and the redo plans only the pairs with a
-                // longer string (`skip_upto`) -- instead of 4 M word pairs on kernels built for long strings (2048 x 2048 multilingual
-                // words with one token of 70 bytes: 2.2 ms per call, NW linear). Taken when the mean string is word-sized.
-                uint64_t mean_x16 = scope->hint_mean_string_x16;
-                if (prepared) {
-                    const uint64_t ma = spec.pa->bytes.count ? spec.pa->total_bytes * 16 / spec.pa->bytes.count : 0;
-                    const uint64_t mb = spec.pb->bytes.count ? spec.pb->total_bytes * 16 / spec.pb->bytes.count : 0;
-                    mean_x16 = std::max(ma, mb);
-                }
-                if (mean_x16 && mean_x16 <= 24 * 16) {
-                    route = kRouteAlignShort;
-                    longest = 64;
-                }
-            }
-        }
-
-        // -- scratch carving ------------------------------------------------------------------------
-        size_t need = 0;
-        {
-            Carver probe{nullptr, 0, 0};
-            if (route == kRoutePlanned) {
-                probe.take<uint32_t>(pairs);            // perm
-                probe.take<uint16_t>(pairs);            // plan keys
-            }
-            if (utf8 && !prepared) {
-                probe.take<uint32_t>(a_bytes + 4); probe.take<uint64_t>(spec.a.count + 1);
-                probe.take<uint32_t>(utf8_scratch_words(a_bytes));
-                probe.take<uint32_t>(b_bytes + 4); probe.take<uint64_t>(spec.b.count + 1);
-                probe.take<uint32_t>(utf8_scratch_words(b_bytes));
-                probe.take<uint32_t>(kUtf8FlagWords);
-                probe.take<uint64_t>(2 * spec.a.count + 2); probe.take<uint64_t>(2 * spec.b.count + 2);   // (first, end) pairs of the string-by-string staging
-            }
-            need = probe.used;
-        }
-        ensure(scope->scratch, scope->scratch_bytes, need);
+        ensure(scope->scratch, scope->scratch_bytes, probe.used);
         Carver sc{scope->scratch, 0, scope->scratch_bytes};
-        uint32_t *perm = nullptr;
-        uint16_t *plan_keys = nullptr;
-        if (route == kRoutePlanned) {
-            perm = sc.take<uint32_t>(pairs);
-            plan_keys = sc.take<uint16_t>(pairs);
+        if (planned) {
+            pre.perm = sc.take<uint32_t>(pairs);
+            k.perm = pre.perm;
+            pre.keys = sc.take<uint16_t>(pairs);
         }
-        Plan *plan_dev = scope->plan_dev;
+        if (staged) stage_utf8(sc);
+    }
 
-        // -- UTF-8 staging ----------------------------------------------------------------------------
-        uint32_t *invalid_dev = nullptr;
-        bool staged_by_string = false;
-        if (utf8 && !prepared) {
-            uint32_t decode_slot = 0;
-            auto decode = [&](const TapeRef &in, uint64_t bytes, TapeRef &out_tape, uint64_t first_word, bool opened) {
-                Utf8Args u{};
-                u.slot = decode_slot++;
-                u.in = in; u.off64 = off64; u.total_bytes = bytes;
-                u.symbols = sc.take<uint32_t>(bytes + 4);
-                u.offsets = sc.take<uint64_t>(in.count + 1);
-                u.counts = sc.take<uint32_t>(utf8_scratch_words(bytes));
-                u.invalid = invalid_dev;
-                if (utf8_one_pass()) launch_utf8_decode_pair(scope, u, nullptr, first_word, opened);
-                else launch_utf8_decode(scope, u);
-                out_tape.data = u.symbols; out_tape.offsets = u.offsets; out_tape.count = in.count;
+    // Raw UTF-8 tapes are decoded into code-point tapes in scratch before the DP launches.
+    void stage_utf8(Carver &sc) {
+        uint32_t decode_slot = 0;
+        auto args_for = [&](const TapeRef &in, uint64_t bytes) {
+            Utf8Args u{};
+            u.slot = decode_slot++;
+            u.in = in; u.off64 = off64; u.total_bytes = bytes;
+            u.symbols = sc.take<uint32_t>(bytes + 4);
+            u.offsets = sc.take<uint64_t>(in.count + 1);
+            u.counts = sc.take<uint32_t>(utf8_scratch_words(bytes));
+            u.invalid = invalid_dev;
+            return u;
+        };
+        auto decoded = [](const Utf8Args &u) { return TapeRef{u.symbols, u.offsets, u.in.count}; };
+        auto decode = [&](const TapeRef &in, uint64_t bytes, uint64_t first_word, bool opened) {
+            const Utf8Args u = args_for(in, bytes);
+            if (utf8_one_pass()) launch_utf8_decode_pair(scope, u, nullptr, first_word, opened);
+            else launch_utf8_decode(scope, u);
+            return decoded(u);
+        };
+        TapeRef da, db;
+        invalid_dev = sc.take<uint32_t>(kUtf8FlagWords);   // one flag + two balance words + the tile tickets, shared by both decodes
+        SWH_HIP_CHECK(hipMemsetAsync(invalid_dev, 0, kUtf8FlagWords * sizeof(uint32_t), stream));
+        // Lines and longer strings are staged string by string (prepass.hip: k_utf8_strings -- one launch, no look-back; the code-point
+        // tapes it leaves have gaps, TapeRef::gap): the routes whose kernels take their extents through pair_extent.
+        const uint64_t all_strings = (uint64_t)spec.a.count + (same_tape ? 0 : spec.b.count), all_bytes = a_bytes + (same_tape ? 0 : b_bytes);
+        if (scope->utf8_strings_rest) --scope->utf8_strings_rest;
+        // (a too-long string sends the call back to the flat staging: the plan-free route can only do that where the host looks at the outcome)
+        const Route route = rc.route;
+        staged_by_string = (route == kRoutePlanned || (route == kRouteTiled && (!scope->async || !dev_out))) && utf8_strings_mode() != 2 && !spec.flat_staging &&
+                             (utf8_strings_mode() == 1 || (scope->utf8_strings_rest == 0 && all_bytes >= (uint64_t)kUtf8StringsMeanBytes * all_strings));
+        if (staged_by_string) {
+            auto job_of = [&](const TapeRef &in, uint64_t bytes) {
+                Utf8StringsJob j{};
+                j.data = (const uint8_t *)in.data; j.offsets = in.offsets; j.count = in.count; j.total = bytes;
+                j.symbols = sc.take<uint32_t>(bytes + 4);
+                j.extents = sc.take<uint64_t>(2 * in.count + 2);
+                return j;
             };
-            TapeRef da, db;
-            invalid_dev = sc.take<uint32_t>(kUtf8FlagWords);   // one flag + two balance words + the tile tickets, shared by both decodes
-            SWH_HIP_CHECK(hipMemsetAsync(invalid_dev, 0, kUtf8FlagWords * sizeof(uint32_t), stream));
-            // Lines and longer strings are staged string by string (prepass.hip: k_utf8_strings -- one launch, no look-back; the code-point
-            // tapes it leaves have gaps, TapeRef::gap): the routes whose kernels take their extents through pair_extent.
-            const uint64_t all_strings = (uint64_t)spec.a.count + (same_tape ? 0 : spec.b.count), all_bytes = a_bytes + (same_tape ? 0 : b_bytes);
-            if (scope->utf8_strings_rest) --scope->utf8_strings_rest;
-            // (a too-long string sends the call back to the flat staging: the plan-free route can only do that where the host looks at the outcome)
-            staged_by_string = (route == kRoutePlanned || (route == kRouteTiled && (!scope->async || !dev_out))) && utf8_strings_mode() != 2 && !spec.flat_staging &&
-                               (utf8_strings_mode() == 1 || (scope->utf8_strings_rest == 0 && all_bytes >= (uint64_t)kUtf8StringsMeanBytes * all_strings));
-            if (staged_by_string) {
-                auto job_of = [&](const TapeRef &in, uint64_t bytes) {
-                    Utf8StringsJob j{};
-                    j.data = (const uint8_t *)in.data; j.offsets = in.offsets; j.count = in.count; j.total = bytes;
-                    j.symbols = sc.take<uint32_t>(bytes + 4);
-                    j.extents = sc.take<uint64_t>(2 * in.count + 2);
-                    return j;
-                };
-                const Utf8StringsJob sa = job_of(ta, a_bytes);
-                da.data = sa.symbols; da.offsets = sa.extents; da.count = ta.count; da.gap = 1;
-                if (same_tape) {
-                    launch_utf8_strings(scope, sa, nullptr, off64, invalid_dev);
-                    db = da;
-                } else {
-                    const Utf8StringsJob sb = job_of(tb, b_bytes);
-                    launch_utf8_strings(scope, sa, &sb, off64, invalid_dev);
-                    db.data = sb.symbols; db.offsets = sb.extents; db.count = tb.count; db.gap = 1;
-                }
-            } else if (same_tape) {
-                decode(ta, a_bytes, da, 0, false);
+            const Utf8StringsJob sa = job_of(ta, a_bytes);
+            da = TapeRef{sa.symbols, sa.extents, ta.count, 1};
+            if (same_tape) {
+                launch_utf8_strings(scope, sa, nullptr, off64, invalid_dev);
                 db = da;
-            } else if (utf8_one_pass() && a_bytes + b_bytes <= utf8_merged_bytes()) {
-                // both tapes in the same two launches (tile decode, then string offsets + balance): what a small call costs is
-                // its launches (10 K word pairs: 135 -> 107 us per call). Since the tile kernel draws from one ticket PER TAPE
-                // (round 4) this is the path for every size (tools/mid_utf8.py, us per call, one launch pair : a launch pair and
-                // a stream per tape -- 4 MB of tapes 186 : 205, 16 MB 216 : 240, 31 MB 256 : 283, 63 MB 330 : 352, 200 MB
-                // 684 : 685); with one ticket for both tapes 2 x 100 MB took 0.33 ms in one launch against 0.27 in two.
-                // STRINGWARS_AMD_UTF8_MERGED_MB=n sends tapes beyond n MB to the two-stream path below.
-                auto prepare = [&](const TapeRef &in, uint64_t bytes, Utf8Args &u) {
-                    u.slot = decode_slot++;
-                    u.in = in; u.off64 = off64; u.total_bytes = bytes;
-                    u.symbols = sc.take<uint32_t>(bytes + 4);
-                    u.offsets = sc.take<uint64_t>(in.count + 1);
-                    u.counts = sc.take<uint32_t>(utf8_scratch_words(bytes));
-                    u.invalid = invalid_dev;
-                };
-                Utf8Args ua{}, ub{};
-                prepare(ta, a_bytes, ua);
-                prepare(tb, b_bytes, ub);
-                launch_utf8_decode_pair(scope, ua, &ub, 0, false);
-                da.data = ua.symbols; da.offsets = ua.offsets; da.count = ta.count;
-                db.data = ub.symbols; db.offsets = ub.offsets; db.count = tb.count;
             } else {
-                // The two tapes decode side by side: the staging kernels are barrier- and latency-bound (half the issue
-                // slots idle), so the second tape's run on the side stream, forked after the inputs are in place.
-                struct StreamSwap {   // launch_utf8_decode and its event stamps follow scope->stream
-                    Scope *s; hipStream_t keep;
-                    StreamSwap(Scope *sc_, hipStream_t to) : s(sc_), keep(sc_->stream) { s->stream = to; }
-                    ~StreamSwap() { s->stream = keep; }
-                };
-                const uint64_t a_tiles = (a_bytes + kUtf8Tile - 1) / kUtf8Tile, b_tiles = (b_bytes + kUtf8Tile - 1) / kUtf8Tile;
-                if (utf8_one_pass()) utf8_status_open(scope, a_tiles + b_tiles);   // before the fork: it may clear the words
-                SWH_HIP_CHECK(hipEventRecord(scope->fork_ev, stream));
-                SWH_HIP_CHECK(hipStreamWaitEvent(scope->side_stream, scope->fork_ev, 0));
-                decode(ta, a_bytes, da, 0, true);
-                {
-                    StreamSwap swap(scope, scope->side_stream);
-                    decode(tb, b_bytes, db, a_tiles, true);
-                }
-                SWH_HIP_CHECK(hipEventRecord(scope->join_ev, scope->side_stream));
-                SWH_HIP_CHECK(hipStreamWaitEvent(stream, scope->join_ev, 0));
+                const Utf8StringsJob sb = job_of(tb, b_bytes);
+                launch_utf8_strings(scope, sa, &sb, off64, invalid_dev);
+                db = TapeRef{sb.symbols, sb.extents, tb.count, 1};
             }
-            ta = da; tb = db;
-            sym_bytes = 4; off64 = 1;
+        } else if (same_tape) {
+            da = db = decode(ta, a_bytes, 0, false);
+        } else if (utf8_one_pass() && a_bytes + b_bytes <= utf8_merged_bytes()) {
+            // both tapes in the same two launches (tile decode, then string offsets + balance): what a small call costs is
+            // its launches (10 K word pairs: 135 -> 107 us per call). Since the tile kernel draws from one ticket PER TAPE
+            // (round 4) this is the path for every size (tools/mid_utf8.py, us per call, one launch pair : a launch pair and
+            // a stream per tape -- 4 MB of tapes 186 : 205, 16 MB 216 : 240, 31 MB 256 : 283, 63 MB 330 : 352, 200 MB
+            // 684 : 685); with one ticket for both tapes 2 x 100 MB took 0.33 ms in one launch against 0.27 in two.
+            // STRINGWARS_AMD_UTF8_MERGED_MB=n sends tapes beyond n MB to the two-stream path below.
+            const Utf8Args ua = args_for(ta, a_bytes), ub = args_for(tb, b_bytes);
+            launch_utf8_decode_pair(scope, ua, &ub, 0, false);
+            da = decoded(ua);
+            db = decoded(ub);
+        } else {
+            // The two tapes decode side by side: the staging kernels are barrier- and latency-bound (half the issue
+            // slots idle), so the second tape's run on the side stream, forked after the inputs are in place.
+            struct StreamSwap {   // launch_utf8_decode and its event stamps follow scope->stream
+                Scope *s; hipStream_t keep;
+                StreamSwap(Scope *sc_, hipStream_t to) : s(sc_), keep(sc_->stream) { s->stream = to; }
+                ~StreamSwap() { s->stream = keep; }
+            };
+            const uint64_t a_tiles = (a_bytes + kUtf8Tile - 1) / kUtf8Tile, b_tiles = (b_bytes + kUtf8Tile - 1) / kUtf8Tile;
+            if (utf8_one_pass()) utf8_status_open(scope, a_tiles + b_tiles);   // before the fork: it may clear the words
+            SWH_HIP_CHECK(hipEventRecord(scope->fork_ev, stream));
+            SWH_HIP_CHECK(hipStreamWaitEvent(scope->side_stream, scope->fork_ev, 0));
+            da = decode(ta, a_bytes, 0, true);
+            {
+                StreamSwap swap(scope, scope->side_stream);
+                db = decode(tb, b_bytes, a_tiles, true);
+            }
+            SWH_HIP_CHECK(hipEventRecord(scope->join_ev, scope->side_stream));
+            SWH_HIP_CHECK(hipStreamWaitEvent(stream, scope->join_ev, 0));
         }
+        ta = da; tb = db;
+        sym_bytes = 4; off64 = 1;
+    }
 
-        // -- job ----------------------------------------------------------------------------------------------
+    // The arguments of the planning pre-pass and of the DP kernels.
+    void set_up_kernels() {
         Job job{};
         job.a = ta; job.b = tb; job.pairs = pairs; job.b_count = spec.b.count; job.cross = spec.cross ? 1 : 0;
         job.bound = engine->kind == 0 ? spec.bound : SWH_UNBOUNDED;
         job.out = out_dev; job.out_stride = dev_out_stride; job.row_stride = dev_row_stride;
         job.out_elem64 = spec.out64 ? 1 : 0;
         job.negate = engine->kind == 0 ? 1 : 0;
-        if (spec.cross) {
-            if (spec.b.count >= 0xFFFFFFFFull) return fail(error, swh_unsupported_length_k, "more than 2^32 candidates");
-            cross_divider((uint32_t)spec.b.count, job.div_magic, job.div_shift);
-        }
+        if (spec.cross) cross_divider((uint32_t)spec.b.count, job.div_magic, job.div_shift);
 
-        PrepassArgs pre{};
         pre.job = job;
         pre.mode = bitpar_ok ? kPlanBitParallel : kPlanWavefront;
         pre.off64 = off64; pre.sym_bytes = sym_bytes;
@@ -805,152 +862,140 @@ static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSp
         pre.direct_short = bitpar_ok && sym_bytes == 1 && engine->algorithm == swh_algorithm_auto_k && scope->hint_short ? 1 : 0;
         pre.skip_upto = spec.skip_upto;
         pre.banded = pre.unit_costs && spec.bound <= band_max_bound() && engine->algorithm == swh_algorithm_auto_k ? 1 : 0;
-        pre.perm = perm; pre.keys = plan_keys; pre.hist = scope->plan_hist; pre.cursor = scope->plan_cursor;
-        pre.partials = scope->plan_partials; pre.leftover = scope->plan_leftover; pre.plan = plan_dev;
+        pre.hist = scope->plan_hist; pre.cursor = scope->plan_cursor;
+        pre.partials = scope->plan_partials; pre.leftover = scope->plan_leftover; pre.plan = scope->plan_dev;
 
-        KernelArgs k{};
-        k.job = job; k.perm = perm; k.plan = plan_dev; k.scoring = engine->scoring;
+        k.job = job; k.plan = scope->plan_dev; k.scoring = engine->scoring;
         k.off64 = off64; k.sym_bytes = sym_bytes; k.symmetric = pre.symmetric;
         k.affine = engine->scoring.open != engine->scoring.extend ? 1 : 0;
         k.local = engine->kind == 2 ? 1 : 0;
+    }
 
-        uint32_t *invalid_host = (uint32_t *)(scope->plan_host + 1);
-        *invalid_host = 0;
-        auto copy_results_back = [&]() {
-            if (dev_out) return;
-            if (spec.cross) {
-                SWH_HIP_CHECK(hipMemcpy2DAsync(spec.out, spec.row_stride, out_dev, dev_row_stride, spec.b.count * elem,
-                                               spec.a.count, hipMemcpyDeviceToHost, stream));
-            } else if (spec.out_stride == elem) {
-                SWH_HIP_CHECK(hipMemcpyAsync(spec.out, out_dev, out_bytes, hipMemcpyDeviceToHost, stream));
-            } else {
-                SWH_HIP_CHECK(hipMemcpy2DAsync(spec.out, spec.out_stride, out_dev, elem, elem, pairs,
-                                               hipMemcpyDeviceToHost, stream));
-            }
-        };
-        // what the staging saw of the tapes' bytes (one-pass kernel only): the next call on the same tapes may believe it
-        auto learn_ascii = [&]() {
-            if (!invalid_dev || !utf8_one_pass()) return;
-            if (same_as_believed(spec.a, scope->size_belief[0])) scope->size_belief[0].ascii = invalid_host[kUtf8AsciiWord] == 0;
-            if (!same_tape && same_as_believed(spec.b, scope->size_belief[1])) scope->size_belief[1].ascii = invalid_host[kUtf8AsciiWord + 1] == 0;
-        };
-        auto invalid_utf8 = [&]() -> swh_status_t {
-            SWH_HIP_CHECK(hipStreamSynchronize(stream));
-            if (*invalid_host == kUtf8SizesChanged && believed_sizes) {
-                // the tapes changed behind the belief: read their totals afresh and do the call again
-                scope->size_belief[0].valid = scope->size_belief[1].valid = false;
-                scope->summary_pending = false;
-                scope->stamps_pending = false;
-                return run_call_on(scope, engine, spec, error);
-            }
-            if (*invalid_host == kUtf8StringTooLong && staged_by_string) {
-                // a string too long for a wave of its own (k_utf8_strings): this call and the scope's next few stage the flat way
-                scope->utf8_strings_rest = 16;
-                scope->summary_pending = false;
-                scope->stamps_pending = false;
-                CallSpec flat = spec;
-                flat.flat_staging = true;
-                return run_call_on(scope, engine, flat, error);
-            }
-            snprintf(g_error_text, sizeof g_error_text, "invalid UTF-8 in an input tape (marker %u: the string's index when staged string by string, else a 4-byte word inside the 1 KiB tile that failed)", *invalid_host - 1);
-            if (error) *error = g_error_text;
-            return swh_invalid_utf8_k;
-        };
-
-        if (route != kRoutePlanned) {
-            // ---- no pre-pass: one DP launch; its summary (work units, longest strings, "a pair did not fit") arrives in
-            // host-mapped memory with the kernel's completion ------------------------------------------------------------
-            // (an asynchronous call reports into slot 1, whose `sticky` word outlives the summary: see CallSummary)
-            scope->summary_slot = (scope->async && dev_out) ? 1u : 0u;
-            const bool early = !scope->async && dev_out && !scope->profiling && !invalid_dev && early_return_on() && is_plain_device_memory(spec.out, scope->device);
-            if (early) scope->summary_host[0].landed = 0;
-            if (route == kRouteDirectShort) launch_direct_short_alone(scope, pre);
-            else if (route == kRouteShortTiled) {
-                // mean string length, for the chunk size: exact for prepared tapes (their totals), else what the last call saw
-                uint32_t mean_x16 = scope->hint_mean_x16;
-                if (prepared) {
-                    const uint64_t ma = spec.pa->bytes.count ? spec.pa->total_bytes * 16 / spec.pa->bytes.count : 0;
-                    const uint64_t mb = spec.pb->bytes.count ? spec.pb->total_bytes * 16 / spec.pb->bytes.count : 0;
-                    mean_x16 = (uint32_t)std::min<uint64_t>(std::max(ma, mb), 0xFFFFFFu);
-                }
-                launch_short_tiled(scope, job, off64, mean_x16);
-            }
-            else if (route == kRouteCrossShort) launch_cross_short(scope, job, off64, (uint32_t)sym_bytes);
-            else if (route == kRouteAlignShort) launch_align_short(scope, k, longest, align_wide);
-            else if (route == kRouteAlignLong) {
-                const uint32_t per_item = align_long_queries(scope, spec.a.count, spec.b.count);
-                const uint64_t items = ((uint64_t)(spec.b.count + 63) / 64) * ((uint64_t)(spec.a.count + per_item - 1) / per_item);
-                const uint64_t ints = (uint64_t)align_long_waves(scope, items, longest, k.affine != 0) * (longest + 8) * 64 * (k.affine ? 2 : 1);
-                ensure(scope->boundary, scope->boundary_bytes, ints * sizeof(int32_t));
-                k.boundary = (int32_t *)scope->boundary;
-                launch_align_long(scope, k, longest);
-            }
-            else launch_bitparallel_tiled(scope, k, pairs, longest);
-            if (invalid_dev) SWH_HIP_CHECK(hipMemcpyAsync(invalid_host, invalid_dev, 4 * (kUtf8AsciiWord + 2), hipMemcpyDeviceToHost, stream));
-            copy_results_back();
-            scope->summary_sym_bytes = need_sizes ? 0 : sym_bytes;
-            scope->summary_pairs = pairs; scope->summary_ow = ow; scope->summary_elem = elem;
-            scope->summary_strings = spec.cross ? (uint64_t)spec.a.count + spec.b.count : 2 * (uint64_t)pairs;
-            scope->summary_extra_bytes = need_sizes ? a_bytes + b_bytes : 0;
-            scope->summary_pending = true;
-            scope->stamps_pending = scope->profiling;
-            if (!scope->async || !dev_out) {
-                if (early) wait_for_summary(scope, stream);
-                else SWH_HIP_CHECK(hipStreamSynchronize(stream));
-                if (*invalid_host) return invalid_utf8();
-                learn_ascii();
-                if (scope->summary_host[0].violation) {
-                    // the belief about the lengths was wrong (it came from an earlier batch): redo on the planned path
-                    scope->hint_lengths = false;
-                    // the compacting kernels stay off this scope only when the ALPHABET was the reason (violation bit 1); a string longer
-                    // than the believed lengths just drops the belief, and the next batch of the same shape is routed afresh
-                    const bool compact_route = (route == kRouteAlignShort && align_wide) || route == kRouteAlignLong;
-                    const bool compact_failed = compact_route && (scope->summary_host[0].violation & 2u) != 0;
-                    if (compact_failed) {
-                        scope->align_wide_off.engine = engine->uid;
-                        scope->align_wide_off.a = spec.pa ? (const void *)spec.pa : (const void *)spec.a.data;
-                        scope->align_wide_off.b = spec.pb ? (const void *)spec.pb : (const void *)spec.b.data;
-                    }
-                    scope->summary_pending = false;
-                    scope->stamps_pending = false;
-                    CallSpec again = spec;
-                    // (prepared tapes know their lengths: when only the small-alphabet kernels' condition failed, the redo may still take
-                    // the lane-per-pair kernel -- `align_wide_off` keeps it off the compacting ones)
-                    again.force_planned = !(compact_failed && prepared);
-                    // the lane-per-pair kernel has scored every pair whose two strings fit its register row: the redo plans the others
-                    if (route == kRouteAlignShort && !align_wide) again.skip_upto = longest <= 16 ? 16u : (longest <= 32 ? 32u : 64u);
-                    return run_call_on(scope, engine, again, error);
-                }
-                harvest_timing(scope, true);
-            }
-            return swh_success_k;
+    void copy_results_back() const {
+        if (dev_out) return;
+        if (spec.cross) {
+            SWH_HIP_CHECK(hipMemcpy2DAsync(spec.out, spec.row_stride, out_dev, dev_row_stride, spec.b.count * elem,
+                                           spec.a.count, hipMemcpyDeviceToHost, stream));
+        } else if (spec.out_stride == elem) {
+            SWH_HIP_CHECK(hipMemcpyAsync(spec.out, out_dev, out_bytes, hipMemcpyDeviceToHost, stream));
+        } else {
+            SWH_HIP_CHECK(hipMemcpy2DAsync(spec.out, spec.out_stride, out_dev, elem, elem, pairs, hipMemcpyDeviceToHost, stream));
         }
+    }
+    // what the staging saw of the tapes' bytes (one-pass kernel only): the next call on the same tapes may believe it
+    void learn_ascii() const {
+        if (!invalid_dev || !utf8_one_pass()) return;
+        if (same_as_believed(spec.a, scope->size_belief[0])) scope->size_belief[0].ascii = invalid_host[kUtf8AsciiWord] == 0;
+        if (!same_tape && same_as_believed(spec.b, scope->size_belief[1])) scope->size_belief[1].ascii = invalid_host[kUtf8AsciiWord + 1] == 0;
+    }
+    // The UTF-8 staging raised its flag: the call is redone where what it believed did not hold, else the input is invalid.
+    swh_status_t utf8_flagged() {
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        const uint32_t marker = *invalid_host;
+        if (marker == kUtf8SizesChanged && believed_sizes) {
+            // the tapes changed behind the belief: read their totals afresh and do the call again
+            scope->size_belief[0].valid = scope->size_belief[1].valid = false;
+            return redo_with(spec);
+        }
+        if (marker == kUtf8StringTooLong && staged_by_string) {
+            // a string too long for a wave of its own (k_utf8_strings): this call and the scope's next few stage the flat way
+            scope->utf8_strings_rest = 16;
+            CallSpec flat = spec;
+            flat.flat_staging = true;
+            return redo_with(flat);
+        }
+        return fail(error, swh_invalid_utf8_k, "invalid UTF-8 in an input tape (marker %u: the string's index when staged string by string, else a 4-byte word inside the 1 KiB tile that failed)", marker - 1);
+    }
 
-        // ---- planned path: classify + counting sort on the device, then the DP kernels the plan's classes call for ----
-        // Doubling. A unit-cost call whose bound lies beyond one band word (or that has none) first runs the ONE-WORD band at k1 = 63 over
-        // the pairs long enough for it: whatever comes back <= 63 is the distance, under any larger bound, and only the pairs that
-        // came back 64 are planned again with the call's own bound (two-word band, bit-parallel blocks). The reference's CPU row does
-        // the same inside every call -- rapidfuzz doubles a score hint of 31 until the result fits under it -- and text that is compared
-        // for similarity mostly is similar: config C3's lines, unbounded, 26 -> ~50 TCUPS. The first stage costs band_cost(63) per
-        // column where the second costs `later`; the share of pairs it has to settle for that to pay (plus a quarter: a second plan, a
-        // second tail) is held against what the scope's previous doubling call saw, and a scope that saw less sits eight calls out.
-        bool doubling = false;
-        double doubling_need = 0;
-        constexpr uint32_t kDoublingBound = 63;
+    // No pre-pass: one DP launch; its summary (work units, longest strings, "a pair did not fit") arrives in host-mapped memory with the
+    // kernel's completion. A synchronous call whose belief about the lengths did not hold is redone on the planned path.
+    swh_status_t run_plan_free() {
+        const Route route = rc.route;
+        const uint32_t longest = rc.longest;
+        // (an asynchronous call reports into slot 1, whose `sticky` word outlives the summary: see CallSummary)
+        scope->summary_slot = (scope->async && dev_out) ? 1u : 0u;
+        const bool early = !scope->async && dev_out && !scope->profiling && !invalid_dev && early_return_on() && is_plain_device_memory(spec.out, scope->device);
+        if (early) scope->summary_host[0].landed = 0;
+        if (route == kRouteDirectShort) launch_direct_short_alone(scope, pre);
+        else if (route == kRouteShortTiled) {
+            // mean string length, for the chunk size: exact for prepared tapes (their totals), else what the last call saw
+            const uint32_t mean_x16 = prepared ? (uint32_t)std::min<uint64_t>(lengths.prepared_mean_x16, 0xFFFFFFu) : scope->hint_mean_x16;
+            launch_short_tiled(scope, pre.job, off64, mean_x16);
+        }
+        else if (route == kRouteCrossShort) launch_cross_short(scope, pre.job, off64, sym_bytes);
+        else if (route == kRouteAlignShort) launch_align_short(scope, k, longest, rc.align_wide);
+        else if (route == kRouteAlignLong) {
+            const uint32_t per_item = align_long_queries(scope, spec.a.count, spec.b.count);
+            const uint64_t items = ((uint64_t)(spec.b.count + 63) / 64) * ((uint64_t)(spec.a.count + per_item - 1) / per_item);
+            const uint64_t ints = (uint64_t)align_long_waves(scope, items, longest, k.affine != 0) * (longest + 8) * 64 * (k.affine ? 2 : 1);
+            ensure(scope->boundary, scope->boundary_bytes, ints * sizeof(int32_t));
+            k.boundary = (int32_t *)scope->boundary;
+            launch_align_long(scope, k, longest);
+        }
+        else launch_bitparallel_tiled(scope, k, pairs, longest);
+        if (invalid_dev) SWH_HIP_CHECK(hipMemcpyAsync(invalid_host, invalid_dev, 4 * (kUtf8AsciiWord + 2), hipMemcpyDeviceToHost, stream));
+        copy_results_back();
+        scope->summary_sym_bytes = need_sizes ? 0 : sym_bytes;
+        scope->summary_pairs = pairs; scope->summary_ow = ow; scope->summary_elem = elem;
+        scope->summary_strings = spec.cross ? (uint64_t)spec.a.count + spec.b.count : 2 * (uint64_t)pairs;
+        scope->summary_extra_bytes = need_sizes ? a_bytes + b_bytes : 0;
+        scope->summary_pending = true;
+        scope->stamps_pending = scope->profiling;
+        if (scope->async && dev_out) return swh_success_k;
+        if (early) wait_for_summary(scope, stream);
+        else SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        if (*invalid_host) return utf8_flagged();
+        learn_ascii();
+        if (scope->summary_host[0].violation) {
+            // the belief about the lengths was wrong (it came from an earlier batch): redo on the planned path
+            scope->hint_lengths = false;
+            // the compacting kernels stay off this scope only when the ALPHABET was the reason (violation bit 1); a string longer
+            // than the believed lengths just drops the belief, and the next batch of the same shape is routed afresh
+            const bool compact_route = (route == kRouteAlignShort && rc.align_wide) || route == kRouteAlignLong;
+            const bool compact_failed = compact_route && (scope->summary_host[0].violation & 2u) != 0;
+            if (compact_failed) {
+                scope->align_wide_off.engine = engine->uid;
+                scope->align_wide_off.a = spec.pa ? (const void *)spec.pa : (const void *)spec.a.data;
+                scope->align_wide_off.b = spec.pb ? (const void *)spec.pb : (const void *)spec.b.data;
+            }
+            CallSpec again = spec;
+            // (prepared tapes know their lengths: when only the small-alphabet kernels' condition failed, the redo may still take
+            // the lane-per-pair kernel -- `align_wide_off` keeps it off the compacting ones)
+            again.force_planned = !(compact_failed && prepared);
+            // the lane-per-pair kernel has scored every pair whose two strings fit its register row: the redo plans the others
+            if (route == kRouteAlignShort && !rc.align_wide) again.skip_upto = longest <= 16 ? 16u : (longest <= 32 ? 32u : 64u);
+            return redo_with(again);
+        }
+        harvest_timing(scope, true);
+        return swh_success_k;
+    }
+
+    // Doubling. A unit-cost call whose bound lies beyond one band word (or that has none) first runs the ONE-WORD band at k1 = 63 over
+    // the pairs long enough for it: whatever comes back <= 63 is the distance, under any larger bound, and only the pairs that
+    // came back 64 are planned again with the call's own bound (two-word band, bit-parallel blocks). The reference's CPU row does
+    // the same inside every call -- rapidfuzz doubles a score hint of 31 until the result fits under it -- and text that is compared
+    // for similarity mostly is similar: config C3's lines, unbounded, 26 -> ~50 TCUPS. The first stage costs band_cost(63) per
+    // column where the second costs `later`; the share of pairs it has to settle for that to pay (plus a quarter: a second plan, a
+    // second tail) is held against what the scope's previous doubling call saw, and a scope that saw less sits eight calls out.
+    Doubling decide_doubling() const {
         static const bool doubling_on = [] { const char *e = test_hook("STRINGWARS_AMD_DOUBLING"); return !e || atoi(e) != 0; }();
         static const uint64_t doubling_min = [] { const char *e = test_hook("STRINGWARS_AMD_DOUBLING_MIN"); return e ? (uint64_t)atoll(e) : (uint64_t)200000; }();   // tuning knob: pairs x blocks
-        if (doubling_on && bitpar_ok && pre.unit_costs && engine->algorithm == swh_algorithm_auto_k && spec.bound > kDoublingBound &&
-            (prepared || scope->hint_lengths)) {
-            const uint32_t la_max = prepared ? (utf8 ? spec.pa->longest_symbols : spec.pa->longest_bytes) : scope->hint_max_la;
-            const uint32_t lb_max = prepared ? (utf8 ? spec.pb->longest_symbols : spec.pb->longest_bytes) : scope->hint_max_lb;
-            const uint32_t blocks = (std::min(la_max, lb_max) + 31) >> 5;
-            const uint32_t unbounded_cost = (sym_bytes == 4 ? 40u : 28u) * blocks;
-            const uint32_t later = spec.bound <= band_max_bound() ? std::min(band_cost(spec.bound), unbounded_cost) : unbounded_cost;
-            doubling_need = 1.25 * band_cost(kDoublingBound) / std::max(later, 1u);
-            if (scope->doubling_rest) --scope->doubling_rest;
-            else doubling = doubling_need <= 0.95 && (uint64_t)pairs * blocks >= doubling_min;   // (a second plan and a second tail: not for small batches)
-        }
-        if (doubling) {
+        Doubling d;
+        if (!(doubling_on && bitpar_ok && pre.unit_costs && engine->algorithm == swh_algorithm_auto_k && spec.bound > kDoublingBound && lengths.known))
+            return d;
+        const uint32_t blocks = (std::min(lengths.la_max, lengths.lb_max) + 31) >> 5;
+        const uint32_t unbounded_cost = (sym_bytes == 4 ? 40u : 28u) * blocks;
+        const uint32_t later = spec.bound <= band_max_bound() ? std::min(band_cost(spec.bound), unbounded_cost) : unbounded_cost;
+        d.need = 1.25 * band_cost(kDoublingBound) / std::max(later, 1u);
+        if (scope->doubling_rest) --scope->doubling_rest;
+        else d.on = d.need <= 0.95 && (uint64_t)pairs * blocks >= doubling_min;   // (a second plan and a second tail: not for small batches)
+        return d;
+    }
+
+    // The planned path: classify + counting sort on the device, then the DP kernels the plan's classes call for.
+    swh_status_t run_planned() {
+        const Doubling doubling = decide_doubling();
+        if (doubling.on) {
             PrepassArgs first = pre;
             first.job.bound = kDoublingBound; first.banded = 1; first.stage1 = 1; first.direct_short = 0; first.skip_upto = 0;
             launch_prepass(scope, first);
@@ -976,7 +1021,7 @@ static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSp
         if (bitpar_ok && !bitpar_deferred) launch_bitparallel(scope, k, pairs);
         Plan &plan = *scope->plan_host;
         SWH_HIP_CHECK(hipStreamWaitEvent(scope->side_stream, scope->plan_ready, 0));
-        SWH_HIP_CHECK(hipMemcpyAsync(&plan, plan_dev, sizeof(Plan), hipMemcpyDeviceToHost, scope->side_stream));
+        SWH_HIP_CHECK(hipMemcpyAsync(&plan, scope->plan_dev, sizeof(Plan), hipMemcpyDeviceToHost, scope->side_stream));
         if (invalid_dev)
             SWH_HIP_CHECK(hipMemcpyAsync(invalid_host, invalid_dev, 4 * (kUtf8AsciiWord + 2), hipMemcpyDeviceToHost, scope->side_stream));
         SWH_HIP_CHECK(hipStreamSynchronize(scope->side_stream));
@@ -985,8 +1030,7 @@ static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSp
             // kernels found an empty plan; plan again with the three passes, now and from here on
             SWH_HIP_CHECK(hipStreamSynchronize(stream));
             scope->fused_disabled = true;
-            scope->stamps_pending = false;
-            return run_call_on(scope, engine, spec, error);
+            return redo_with(spec);
         }
         // enqueue k_direct_short next time only if short pairs are a real share of the batch (it sweeps all offsets)
         scope->hint_short = (uint64_t)plan.short_pairs * 4 >= pairs;
@@ -996,19 +1040,19 @@ static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSp
             const uint64_t strings = 2 * (uint64_t)pairs;   // (the planner sums la + lb over PAIRS, also for a cross-product)
             scope->hint_mean_string_x16 = strings ? (uint32_t)std::min<uint64_t>(plan.symbols * 16 / strings, 0xFFFFFFu) : 0u;
         }
-        if (*invalid_host) return invalid_utf8();
+        if (*invalid_host) return utf8_flagged();
         learn_ascii();
-        if (doubling) {
+        if (doubling.on) {
             // what the first stage left over: the pairs the second plan filed under a kernel class
-            const uint64_t redo = plan.class_start[kMaxClasses] - plan.class_count[kClassTrivial];
-            const double settled = 1.0 - (double)redo / (double)pairs;
+            const uint64_t left = plan.class_start[kMaxClasses] - plan.class_count[kClassTrivial];
+            const double settled = 1.0 - (double)left / (double)pairs;
             scope->doubling_settled = (float)settled;
-            if (settled < doubling_need) scope->doubling_rest = 8;
+            if (settled < doubling.need) scope->doubling_rest = 8;
         }
 
         if (bitpar_deferred) {
             bool any_bp = false;
-            for (int c = kClassBp0; c < kClassBp0 + 64; ++c) any_bp |= plan.class_count[c] != 0;
+            for (int cls = kClassBp0; cls < kClassBp0 + 64; ++cls) any_bp |= plan.class_count[cls] != 0;
             if (any_bp) launch_bitparallel(scope, k, pairs);
         }
         // patterns of more than 64 blocks: multi-pass bit-parallel kernel, carries between passes in scratch
@@ -1031,15 +1075,15 @@ static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSp
         Plan wf_plan = plan;
         if ((engine->kind == 1 || engine->kind == 2) && (engine->scoring.class_table || engine->scoring.wide_table) && sym_bytes == 1 && !nw_classic) {
             profile_first = plan.class_start[kClassWf64 + kNwProfileFirstWide];
-            for (int c = kClassWf64 + kNwProfileFirstWide; c <= kClassWfMulti; ++c) { profile_count += plan.class_count[c]; wf_plan.class_count[c] = 0; }
+            for (int cls = kClassWf64 + kNwProfileFirstWide; cls <= kClassWfMulti; ++cls) { profile_count += plan.class_count[cls]; wf_plan.class_count[cls] = 0; }
         }
         // wavefront classes (all of them when the plan is wavefront-only)
         bool any_wf = false, multi = false;
-        for (int c = kClassWf16; c <= kClassWfMulti; ++c) {
-            if (!wf_plan.class_count[c]) continue;
+        for (int cls = kClassWf16; cls <= kClassWfMulti; ++cls) {
+            if (!wf_plan.class_count[cls]) continue;
             any_wf = true;
-            if (c == kClassWfMulti || (k.affine && c >= kClassWf64 + 8)) multi = true;  // (affine strips are capped: the widest classes take several passes)
-            if (wavefront_strip_cap() && c >= kClassWf64 && wide_w(c - kClassWf64 < kNumWideW ? c - kClassWf64 : kNumWideW - 1) > wavefront_strip_cap()) multi = true;
+            if (cls == kClassWfMulti || (k.affine && cls >= kClassWf64 + 8)) multi = true;  // (affine strips are capped: the widest classes take several passes)
+            if (wavefront_strip_cap() && cls >= kClassWf64 && wide_w(cls - kClassWf64 < kNumWideW ? cls - kClassWf64 : kNumWideW - 1) > wavefront_strip_cap()) multi = true;
         }
         if (any_wf || profile_count) {
             // int32 scores with a -2^29 "minus infinity": keep every reachable score well inside it
@@ -1085,10 +1129,23 @@ static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSp
             harvest_timing(scope, true);
         }
         return swh_success_k;
-    } catch (const HipFailure &f) {
-        return fail_hip(error, f);
-    } catch (const std::bad_alloc &) {
-        return fail(error, swh_bad_alloc_k, "host allocation failed");
+    }
+};
+
+static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSpec &first, const char **error) {
+    const swh_status_t checked = check_call(scope, engine, first, error);
+    if (checked != swh_success_k) return checked;
+    CallSpec spec = first;
+    for (;;) {
+        harvest_timing(scope, false);   // an earlier asynchronous call on this scope / lane
+        scope->stamps_used = 0;
+        scope->last_timing = swh_timing_t{};
+        Call call{scope, engine, spec, error};
+        const swh_status_t status = call.attempt();
+        if (!call.redo) return status;
+        scope->summary_pending = false;
+        scope->stamps_pending = false;
+        spec = call.next;
     }
 }
 
@@ -1445,9 +1502,7 @@ static swh_status_t prepare_tape(Scope *scope, const HostTape &tape, bool utf8, 
             if (decode_error != hipSuccess) throw HipFailure{decode_error, "UTF-8 decode"};
             if (host_words[4]) {
                 free_prepared(p);
-                snprintf(g_error_text, sizeof g_error_text, "invalid UTF-8 in the tape (marker %u: a 4-byte word inside the 1 KiB tile that failed)", host_words[4] - 1);
-                if (error) *error = g_error_text;
-                return swh_invalid_utf8_k;
+                return fail(error, swh_invalid_utf8_k, "invalid UTF-8 in the tape (marker %u: a 4-byte word inside the 1 KiB tile that failed)", host_words[4] - 1);
             }
             p->longest_bytes = host_words[0];
             p->longest_symbols = host_words[1];
@@ -1760,10 +1815,8 @@ static swh_status_t prepared_call(void *e, int kind, swh_scope_t s, const swh_pr
     if (e && ((Engine *)e)->kind != kind) return fail(error, swh_invalid_argument_k, "engine kind mismatch");
     const swh_prepared_view_t *bb = (b && b->tape) ? b : (cross ? a : nullptr);
     if (!bb) return fail(error, swh_invalid_argument_k, "null prepared view");
+    if (!view_fits(a) || !view_fits(bb)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
     const Prepared *pa = (const Prepared *)a->tape, *pb = (const Prepared *)bb->tape;
-    if (a->first > pa->bytes.count || a->count > pa->bytes.count - a->first || bb->first > pb->bytes.count ||
-        bb->count > pb->bytes.count - bb->first)
-        return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
     CallSpec spec{};
     spec.a = HostTape{nullptr, nullptr, a->count, 0};
     spec.b = HostTape{nullptr, nullptr, bb->count, 0};
@@ -1806,16 +1859,9 @@ swh_status_t swh_sw_cross_prepared(swh_sw_t e, swh_scope_t s, const swh_prepared
 
 // ---- top-k search (topk.hip) ----------------------------------------------------------------------------------------------------------
 // Word-sized byte strings on unit costs run the fused kernel (k_cross_topk): the search a dense cross-product of the same views would run
-// on k_cross_short (run_call_on's route choice for prepared tapes). Everything else takes the general path: the candidates in slices,
-// each slice scored by the ordinary cross-product routes into a u32 matrix in scratch (with the caller's bound, so long strings may take
-// the banded kernel), then folded into the running lists by k_topk_select.
-static bool topk_fused_route(const Engine *engine, const Prepared *pq, const Prepared *pc, bool utf8, uint32_t bound) {
-    if (engine->kind != 0 || !engine->unit_costs || engine->algorithm != swh_algorithm_auto_k || utf8) return false;
-    if (pq->off64 != pc->off64 || short_route_choice() == 2) return false;
-    const uint32_t longest = std::max(pq->longest_bytes, pc->longest_bytes);
-    const bool band_pays = bound <= 63 ? longest > 32 : bound <= band_max_bound() && band_cost(bound) < 28u * ((longest + 31) >> 5);
-    return !band_pays && longest <= tiled_longest_limit() && longest <= 32;
-}
+// on k_cross_short (pick_route for prepared tapes). Everything else takes the general path: the candidates in slices, each slice scored
+// by the ordinary cross-product routes into a u32 matrix in scratch (with the caller's bound, so long strings may take the banded
+// kernel), then folded into the running lists by k_topk_select.
 // STRINGWARS_AMD_TOPK_PRUNE=0 (test library): the fused kernel walks every chunk, also those the length bound rules out (the comparison knob)
 static uint32_t topk_prune() {
     static const uint32_t on = [] { const char *e = test_hook("STRINGWARS_AMD_TOPK_PRUNE"); return !e || atoi(e) != 0 ? 1u : 0u; }();
@@ -1853,20 +1899,18 @@ static swh_status_t topk_run(Scope *scope, const Engine *engine, const TopkReque
             SWH_HIP_CHECK(hipStreamSynchronize(stream));
             return swh_success_k;
         }
-        auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
         const size_t ow = r.pq->off64 ? 8 : 4;
-        auto view = [&](const Prepared *p, size_t first, size_t count) {
-            TapeRef t;
-            t.data = p->bytes.data; t.offsets = (const char *)p->bytes.offsets + first * ow; t.count = count;
-            return t;
-        };
         auto finish_outputs = [&](uint32_t *ind, uint32_t *dist) {
             if (!dev_i) SWH_HIP_CHECK(hipMemcpyAsync(r.indices, ind, out_bytes, hipMemcpyDeviceToHost, stream));
             if (!dev_d) SWH_HIP_CHECK(hipMemcpyAsync(r.distances, dist, out_bytes, hipMemcpyDeviceToHost, stream));
             SWH_HIP_CHECK(hipStreamSynchronize(stream));
         };
 
-        if (!topk_force_select() && topk_fused_route(engine, r.pq, r.pc, utf8, r.bound)) {
+        CallSpec whole{};   // the dense cross-product of the two views, as run_call_on would route it
+        whole.a.count = nq; whole.b.count = nc; whole.cross = true; whole.bound = r.bound; whole.pa = r.pq; whole.pb = r.pc;
+        const bool fused = !topk_force_select() && !utf8 && engine->algorithm == swh_algorithm_auto_k && r.pq->off64 == r.pc->off64 &&
+                           pick_route(scope, engine, whole, false, dev_i, call_lengths(scope, engine, whole, false)).route == kRouteCrossShort;
+        if (fused) {
             // ---- fused: slices enough for ~32 items per compute unit (a few rounds of its 12 wave slots: 65 536 x 1 M words ran at 4.6
             // TCUPS with 16, 5.9 with 32); the partial lists stay under 256 MB ------------------------------------------------------------
             const uint64_t qblocks = (nq + 15) / 16, chunks = (nc + 63) / 64;
@@ -1879,7 +1923,7 @@ static swh_status_t topk_run(Scope *scope, const Engine *engine, const TopkReque
             ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
             Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
             TopkLaunch t{};
-            t.a = view(r.pq, r.q_first, nq); t.b = view(r.pc, r.c_first, nc);
+            t.a = prepared_view(r.pq, false, r.q_first, nq); t.b = prepared_view(r.pc, false, r.c_first, nc);
             t.off64 = r.pq->off64; t.k = (uint32_t)k; t.slices = (uint32_t)slices; t.prune = topk_prune();
             t.slice_chunks = slice_chunks; t.cap = cap;
             t.partial = slices > 1 ? sc.take<uint64_t>(nq * slices * k) : nullptr;
@@ -1892,10 +1936,7 @@ static swh_status_t topk_run(Scope *scope, const Engine *engine, const TopkReque
             if (!sm.violation) {
                 if (scope->profiling && scope->stamps_used) {
                     collect_timing(scope);
-                    scope->totals.total_ms += scope->last_timing.total_ms;
-                    scope->totals.dominant_ms += scope->last_timing.dominant_ms;
-                    scope->totals.compute_ms += scope->last_timing.compute_ms;
-                    scope->totals.calls += 1;
+                    add_to_totals(scope->totals, scope->last_timing);
                 }
                 scope->last_timing.cells = sm.cells;
                 scope->last_timing.bytes = r.pq->total_bytes + r.pc->total_bytes + (nq + nc) * ow + 2 * out_bytes;
@@ -1955,8 +1996,7 @@ static swh_status_t topk_run(Scope *scope, const Engine *engine, const TopkReque
         scope->last_timing = sum;
         if (scope->profiling) {
             scope->totals = totals_before;
-            scope->totals.total_ms += sum.total_ms; scope->totals.dominant_ms += sum.dominant_ms; scope->totals.compute_ms += sum.compute_ms;
-            scope->totals.calls += 1;
+            add_to_totals(scope->totals, sum);
         }
         return swh_success_k;
     } catch (const HipFailure &f) {
@@ -1966,12 +2006,12 @@ static swh_status_t topk_run(Scope *scope, const Engine *engine, const TopkReque
     }
 }
 
-// The call is synchronous on every scope: outstanding asynchronous / pipelined work is joined first, and the search runs on the scope
-// itself (not on a pipeline lane) with the asynchronous mode held off until it returns.
-struct TopkModeGuard {
+// Top-k searches and alignments are synchronous on every scope: outstanding asynchronous / pipelined work is joined first, and the call
+// runs on the scope itself (not on a pipeline lane) with the asynchronous mode held off until it returns.
+struct HoldSynchronous {
     Scope *scope; bool async, pipelined;
-    explicit TopkModeGuard(Scope *s) : scope(s), async(s->async), pipelined(s->pipelined) { s->async = false; s->pipelined = false; }
-    ~TopkModeGuard() { scope->async = async; scope->pipelined = pipelined; }
+    explicit HoldSynchronous(Scope *s) : scope(s), async(s->async), pipelined(s->pipelined) { s->async = false; s->pipelined = false; }
+    ~HoldSynchronous() { scope->async = async; scope->pipelined = pipelined; }
 };
 struct PreparedOwner {
     Prepared *p = nullptr;
@@ -1987,7 +2027,7 @@ static swh_status_t topk_checks(swh_levenshtein_t e, swh_scope_t s, size_t k, si
     if (queries && (!indices || !distances)) return fail(error, swh_invalid_argument_k, "null output pointer");
     return swh_success_k;
 }
-static swh_status_t topk_join(Scope *scope, const char **error) {
+static swh_status_t join_outstanding(Scope *scope, const char **error) {
     if (!scope->async && !scope->pipelined) return swh_success_k;
     return swh_scope_synchronize((swh_scope_t)scope, error);
 }
@@ -1999,9 +2039,9 @@ static swh_status_t topk_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tap
     swh_status_t status = topk_checks(e, s, k, q->count, cc->count, indices, distances, error);
     if (status != swh_success_k) return status;
     Scope *scope = (Scope *)s;
-    if ((status = topk_join(scope, error)) != swh_success_k) return status;
+    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
     if (q->count == 0) return swh_success_k;
-    TopkModeGuard mode(scope);
+    HoldSynchronous mode(scope);
     // raw tapes are made resident and measured for the call (prepare_tape: device tapes in place, host tapes uploaded; UTF-8 validated and
     // decoded): the route is then chosen on lengths that are known, not believed
     PreparedOwner pq, pc;
@@ -2028,18 +2068,14 @@ swh_status_t swh_levenshtein_topk_prepared(swh_levenshtein_t e, swh_scope_t s, c
                                            uint32_t *distances, const char **error) {
     if (!queries || !queries->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
     const swh_prepared_view_t *cc = (candidates && candidates->tape) ? candidates : queries;
+    if (!view_fits(queries) || !view_fits(cc)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
     const Prepared *pq = (const Prepared *)queries->tape, *pc = (const Prepared *)cc->tape;
-    if (queries->first > pq->bytes.count || queries->count > pq->bytes.count - queries->first || cc->first > pc->bytes.count ||
-        cc->count > pc->bytes.count - cc->first)
-        return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
     swh_status_t status = topk_checks(e, s, k, queries->count, cc->count, indices, distances, error);
     if (status != swh_success_k) return status;
-    if (pq->utf8 != pc->utf8) return fail(error, swh_invalid_argument_k, "one tape was prepared as UTF-8, the other as bytes");
     Scope *scope = (Scope *)s;
-    if (pq->device != scope->device || pc->device != scope->device)
-        return fail(error, swh_invalid_argument_k, "a prepared tape lives on another device than the scope");
-    if ((status = topk_join(scope, error)) != swh_success_k) return status;
-    TopkModeGuard mode(scope);
+    if ((status = check_prepared_pair(scope, pq, pc, error)) != swh_success_k) return status;
+    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
+    HoldSynchronous mode(scope);
     TopkRequest r{pq, pc, queries->first, queries->count, cc->first, cc->count, (uint32_t)k, bound, indices, distances};
     return topk_run(scope, (Engine *)e, r, error);
 }
@@ -2098,20 +2134,13 @@ static swh_status_t align_run(Scope *scope, const AlignRequest &r, const char **
         }
         const bool cp = r.pa->utf8;
         AlignTapes t{};
-        auto view = [&](const Prepared *p, size_t first, uint32_t &off64) {
-            const TapeRef &src = cp ? p->symbols : p->bytes;
-            off64 = cp ? 1 : p->off64;
-            TapeRef v = src;
-            v.offsets = (const char *)src.offsets + first * (off64 ? 8 : 4);
-            v.count = count;
-            return v;
-        };
-        t.a = view(r.pa, r.a_first, t.a_off64);
-        t.b = view(r.pb, r.b_first, t.b_off64);
+        t.a = prepared_view(r.pa, cp, r.a_first, count);
+        t.b = prepared_view(r.pb, cp, r.b_first, count);
+        t.a_off64 = cp ? 1 : r.pa->off64;
+        t.b_off64 = cp ? 1 : r.pb->off64;
         t.cp = cp ? 1 : 0;
         t.count = count;
 
-        auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
         AlignScratch *sc_entry;
         {
             std::lock_guard<std::mutex> hold(g_align_scratch_lock);
@@ -2143,18 +2172,14 @@ static swh_status_t align_run(Scope *scope, const AlignRequest &r, const char **
             const size_t i = (size_t)got.first_oversize;
             const uint64_t la = read_offset(t.a.offsets, t.a_off64, i + 1, true, stream) - read_offset(t.a.offsets, t.a_off64, i, true, stream);
             const uint64_t lb = read_offset(t.b.offsets, t.b_off64, i + 1, true, stream) - read_offset(t.b.offsets, t.b_off64, i, true, stream);
-            snprintf(g_error_text, sizeof g_error_text, "pair %zu: %llu x %llu symbols exceeds SWH_ALIGN_MAX_CELLS (2^30 cells per pair)", i,
-                     (unsigned long long)la, (unsigned long long)lb);
             scope->stamps_used = 0;
-            if (error) *error = g_error_text;
-            return swh_unsupported_length_k;
+            return fail(error, swh_unsupported_length_k, "pair %zu: %llu x %llu symbols exceeds SWH_ALIGN_MAX_CELLS (2^30 cells per pair)", i,
+                        (unsigned long long)la, (unsigned long long)lb);
         }
         if (r.capacity < got.symbols) {
-            snprintf(g_error_text, sizeof g_error_text, "ops_capacity %zu is below the %llu symbols of the two tapes", r.capacity,
-                     (unsigned long long)got.symbols);
             scope->stamps_used = 0;
-            if (error) *error = g_error_text;
-            return swh_invalid_argument_k;
+            return fail(error, swh_invalid_argument_k, "ops_capacity %zu is below the %llu symbols of the two tapes", r.capacity,
+                        (unsigned long long)got.symbols);
         }
 
         // chunks of consecutive pairs; where they start in the storage space is read back (one strided copy) to size the largest
@@ -2215,10 +2240,7 @@ static swh_status_t align_run(Scope *scope, const AlignRequest &r, const char **
         SWH_HIP_CHECK(hipStreamSynchronize(stream));
         if (scope->profiling && scope->stamps_used) {
             collect_timing(scope);
-            scope->totals.total_ms += scope->last_timing.total_ms;
-            scope->totals.dominant_ms += scope->last_timing.dominant_ms;
-            scope->totals.compute_ms += scope->last_timing.compute_ms;
-            scope->totals.calls += 1;
+            add_to_totals(scope->totals, scope->last_timing);
         }
         scope->stamps_used = 0;
         scope->last_timing.cells = got.cells;
@@ -2248,8 +2270,8 @@ static swh_status_t align_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_ta
     swh_status_t status = align_checks(e, s, a->count, b->count, distances, offsets, ops, error);
     if (status != swh_success_k) return status;
     Scope *scope = (Scope *)s;
-    if ((status = topk_join(scope, error)) != swh_success_k) return status;
-    TopkModeGuard mode(scope);
+    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
+    HoldSynchronous mode(scope);
     AlignRequest r{nullptr, nullptr, 0, 0, a->count, bound, distances, offsets, ops, capacity};
     if (a->count == 0) {
         Prepared none;
@@ -2278,17 +2300,14 @@ swh_status_t swh_levenshtein_align_prepared(swh_levenshtein_t e, swh_scope_t s, 
                                             uint32_t bound, uint32_t *distances, size_t *ops_offsets, char *ops, size_t ops_capacity,
                                             const char **error) {
     if (!a || !a->tape || !b || !b->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
+    if (!view_fits(a) || !view_fits(b)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
     const Prepared *pa = (const Prepared *)a->tape, *pb = (const Prepared *)b->tape;
-    if (a->first > pa->bytes.count || a->count > pa->bytes.count - a->first || b->first > pb->bytes.count || b->count > pb->bytes.count - b->first)
-        return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
     swh_status_t status = align_checks(e, s, a->count, b->count, distances, (const uint64_t *)ops_offsets, (const uint8_t *)ops, error);
     if (status != swh_success_k) return status;
-    if (pa->utf8 != pb->utf8) return fail(error, swh_invalid_argument_k, "one tape was prepared as UTF-8, the other as bytes");
     Scope *scope = (Scope *)s;
-    if (pa->device != scope->device || pb->device != scope->device)
-        return fail(error, swh_invalid_argument_k, "a prepared tape lives on another device than the scope");
-    if ((status = topk_join(scope, error)) != swh_success_k) return status;
-    TopkModeGuard mode(scope);
+    if ((status = check_prepared_pair(scope, pa, pb, error)) != swh_success_k) return status;
+    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
+    HoldSynchronous mode(scope);
     AlignRequest r{pa, pb, a->first, b->first, a->count, bound, distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity};
     return align_run(scope, r, error);
 }
