@@ -623,6 +623,8 @@ class LevenshteinDistances(_Engine):
         by distance and then by candidate index, only candidates with ``d <= bound``, short rows padded with ``0xFFFFFFFF``.
         ``candidates=None`` searches the queries themselves (diagonal included). ``out=(indices, distances)`` fills given arrays
         or device tensors (contiguous, ``len(queries) * k`` uint32 / int32 each) instead of returning new numpy arrays.
+        Two prepared byte tapes must share one offset width: one prepared from uint32 and one from uint64 offsets raise
+        ``StringWarsError('invalid_argument')`` and nothing is written.
         rapidfuzz: ``process.extract(q, candidates, scorer=Levenshtein.distance, limit=k, score_cutoff=bound)`` per query."""
         if scope is None:
             raise ValueError("a DeviceScope is required")

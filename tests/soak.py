@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomized parity soak on the GPU: batches with mixed length regimes, alphabets, bounds and engines, every result
-compared with the CPU oracle bit for bit. Lives under tests/ (the oracle is test infrastructure) but is not collected
+compared with the CPU oracle bit for bit -- distances and scores, top-k rows, and alignments (validity of the whole batch, sampled
+scripts against the reference script of tests/test_align.py). Lives under tests/ (the oracle is test infrastructure) but is not collected
 by pytest: minutes, not seconds.
 
     python tests/soak.py --seconds 240 --seed 1
@@ -19,6 +20,8 @@ sys.path.insert(0, ROOT)
 os.environ.setdefault("STRINGWARS_AMD_DOUBLING_MIN", "1")
 import stringwars_amd as sw  # noqa: E402
 import oracle  # noqa: E402
+from test_align import check_exact, check_valid_batch, code_point_tape  # noqa: E402
+from test_topk import check_rows, expected_topk, oracle_matrix  # noqa: E402
 
 REGIMES = [(0, 8), (0, 40), (20, 140), (100, 700), (500, 2100), (1900, 2300), (2000, 5000), (0, 5000)]
 ALPHABETS = {"acgt": [ord(c) for c in "ACGT"], "lower": list(range(97, 123)), "byte": list(range(256)),
@@ -30,10 +33,9 @@ CODE_POINT_POOLS = [SCRIPTS, SCRIPTS + list(range(0x430, 0x450)) + list(range(0x
                     SCRIPTS + list(range(0x4E00, 0x4E00 + 900)) + list(range(0x1F300, 0x1F340))]
 
 
-def random_batch(rng, utf8):
+def random_batch(rng, utf8, budget=1.5e9):
     regime = REGIMES[int(rng.integers(0, len(REGIMES)))]
     mixed = rng.random() < 0.3
-    budget = 1.5e9
     alphabet = np.array(CODE_POINT_POOLS[int(rng.integers(0, 3))] if utf8 else ALPHABETS[str(rng.choice(list(ALPHABETS)))], np.uint32)
     items_a, items_b, cells = [], [], 0
     while cells < budget and len(items_a) < 20000:
@@ -60,6 +62,22 @@ def random_batch(rng, utf8):
     return sw.Strs(items_a), sw.Strs(items_b)
 
 
+def random_search(rng, utf8):
+    """Queries, candidates, k and bound of a top-k round: word-sized strings (the fused kernel on bytes), or mostly words with longer
+    strings among them (the general path); few symbols, so that rows have ties and bounds cut them."""
+    word_sized = rng.random() < 0.6
+    symbols = np.array(CODE_POINT_POOLS[0][:int(rng.integers(2, 9))] if utf8 else ALPHABETS[str(rng.choice(["acgt", "binary", "lower", "byte"]))], np.uint32)
+    enc = (lambda x: "".join(map(chr, x)).encode("utf-8")) if utf8 else (lambda x: bytes(x.astype(np.uint8)))
+
+    def strings(count):
+        lengths = rng.integers(0, 13, count) if word_sized else np.where(rng.random(count) < 0.9, rng.integers(0, 33, count), rng.integers(33, 200, count))
+        return sw.Strs([enc(symbols[rng.integers(0, len(symbols), int(n))]) for n in lengths])
+    queries, candidates = strings(int(rng.integers(1, 300))), strings(int(rng.integers(1, 2500)))
+    k = int(rng.integers(1, sw.TOPK_MAX + 1))
+    bound = None if rng.random() < 0.4 else int(rng.integers(0, 10))
+    return queries, candidates, k, bound
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=240)
@@ -76,8 +94,46 @@ def main():
     multi = sw.DeviceScope(gpu_devices=[0, 0, 0])
     t0, rounds, pairs_total = time.time(), 0, 0
     while time.time() - t0 < args.seconds or 0 <= rounds <= args.only:
-        kind = str(rng.choice(["lev", "lev", "lev_utf8", "nw", "sw"]))
-        if kind in ("lev", "lev_utf8"):
+        kind = str(rng.choice(["lev", "lev", "lev_utf8", "nw", "sw", "topk", "align"]))
+        selected = args.only < 0 or (args.first if args.first >= 0 else args.only) <= rounds <= args.only
+        if kind == "topk":   # every random number of the round is drawn before the device is touched: a replay draws the same ones
+            utf8 = bool(rng.random() < 0.5)
+            a, candidates, k, bound = random_search(rng, utf8)
+            lo = int(rng.integers(0, len(a)))
+            if args.verbose:
+                print(f"batch {rounds}: topk utf8 {utf8} queries {len(a)} candidates {len(candidates)} k {k} bound {bound}", flush=True)
+            if selected:
+                engine = (sw.LevenshteinDistancesUTF8 if utf8 else sw.LevenshteinDistances)(capabilities=scope)
+                d = oracle_matrix(sw, oracle, a, candidates, utf8=utf8)
+                want = expected_topk(d, k, bound)
+                check_rows(engine.topk(a, candidates, scope, k=k, bound=bound), want, f"topk raw utf8={utf8} k={k} bound={bound}")
+                pq, pc = sw.PreparedTape(scope, a, utf8=utf8), sw.PreparedTape(scope, candidates, utf8=utf8)
+                check_rows(engine.topk(pq, pc, scope, k=k, bound=bound), want, f"topk prepared utf8={utf8} k={k} bound={bound}")
+                check_rows(engine.topk(pq[lo:], pc, scope, k=k, bound=bound), (want[0][lo:], want[1][lo:]), "topk prepared sub-view")
+        elif kind == "align":
+            utf8 = bool(rng.random() < 0.3)
+            a, b = random_batch(rng, utf8, budget=3e8)
+            bound = None if rng.random() < 0.5 else int(rng.integers(0, 141))
+            sample = sorted(set(rng.integers(0, len(a), 12).tolist()))
+            if args.verbose:
+                print(f"batch {rounds}: align utf8 {utf8} pairs {len(a)} longest {int(max(a.lengths.max(), b.lengths.max()))} bound {bound}", flush=True)
+            if selected:
+                engine = (sw.LevenshteinDistancesUTF8 if utf8 else sw.LevenshteinDistances)(capabilities=scope)
+                want = oracle.levenshtein_pairs(a, b, utf8=utf8, algo="wf" if utf8 else "hyyro", bound=bound)
+                decode = (lambda t: [t[i].decode("utf-8") for i in range(len(t))]) if utf8 else (lambda t: [t[i] for i in range(len(t))])
+                items_a, items_b = decode(a), decode(b)
+                for tapes in ((a, b), (sw.PreparedTape(scope, a, utf8=utf8), sw.PreparedTape(scope, b, utf8=utf8))):
+                    got = engine.align(tapes[0], tapes[1], scope, bound=bound)
+                    assert (got.distances == want).all(), ("align distances", utf8, bound)
+                    if bound is None:   # the whole batch: op counts, costs, '=' exactly on equal symbols
+                        if utf8:
+                            check_valid_batch(code_point_tape(items_a), code_point_tape(items_b), got, utf8=True)
+                        else:
+                            check_valid_batch((a.data, a.offsets), (b.data, b.offsets), got)
+                    else:
+                        assert (np.diff(got.offsets.astype(np.int64))[want > bound] == 0).all(), ("scripts beyond the bound", bound)
+                    check_exact(sw, got, items_a, items_b, utf8=utf8, bound=bound, indices=sample)
+        elif kind in ("lev", "lev_utf8"):
             utf8 = kind == "lev_utf8"
             a, b = random_batch(rng, utf8)
             bound = None if rng.random() < 0.5 else int(rng.integers(0, 141))   # (64 .. 127: the banded kernel's two-word window)

@@ -396,3 +396,194 @@ def test_many_chunks(request, sw, orc):
     assert kernels > 50   # sizes + 2 scans + the chunks + 1 scan + emit
     assert (got.distances == lev.pairs(sw.Strs(a), sw.Strs(b), scope)).all()
     check_exact(sw, got, a, b)
+
+
+# ---- adversarial cases: offset widths, bounds across blocks, code-point groups, scan edges, the cell limit ----------------------------
+def mutated(rng, s, edits, draw):
+    """`s` (a list of symbols) after `edits` random substitutions, insertions and deletions with symbols from `draw()`."""
+    s = list(s)
+    for _ in range(edits):
+        op, at = int(rng.integers(0, 3)), int(rng.integers(0, max(len(s), 1)))
+        if op == 0 and s:
+            s[at] = draw()
+        elif op == 1:
+            s.insert(at, draw())
+        elif s:
+            del s[at]
+    return s
+
+
+def same_alignments(got, want):
+    return (got.distances == want.distances).all() and (got.offsets == want.offsets).all() and got.ops.tobytes() == want.ops.tobytes()
+
+
+@pytest.mark.gpu
+def test_offset_widths(sw, scope, lev):
+    """k_align<uint8_t, OffA, OffB>: prepared tapes with 32- and 64-bit offsets in all four combinations, byte for byte the all-64-bit
+    result (which is checked against the reference script), whole tapes and sub-views."""
+    rng = np.random.default_rng(31)
+    a = random_strs(rng, 400, 0, 300, 4)
+    b = [bytes(mutated(rng, x, int(rng.integers(0, 12)), lambda: int(rng.integers(0, 4)))) for x in a[:250]] + random_strs(rng, 150, 0, 300, 4)
+    a[0], b[0], a[-1], b[-1] = b"", b"", bytes(300), bytes(299)
+    # the two tapes differ in size and in where their strings start, so an offset read from the wrong tape or at the wrong width shows
+    assert sum(map(len, a)) != sum(map(len, b)) and max(map(len, a + b)) >= 300 and min(map(len, a + b)) == 0
+    tapes = {(w, name): sw.PreparedTape(scope, sw.Strs(items).with_offsets(w)) for w in (np.uint32, np.uint64) for name, items in (("a", a), ("b", b))}
+    want = lev.align(tapes[(np.uint64, "a")], tapes[(np.uint64, "b")], scope)
+    check_exact(sw, want, a, b)
+    assert same_alignments(lev.align(sw.Strs(a), sw.Strs(b), scope), want)
+    for wa, wb in itertools.product((np.uint32, np.uint64), repeat=2):
+        pa, pb = tapes[(wa, "a")], tapes[(wb, "b")]
+        assert same_alignments(lev.align(pa, pb, scope), want), (wa, wb)
+        sub = lev.align(pa[37:333], pb[37:333], scope, bound=25)
+        bounded = lev.align(tapes[(np.uint64, "a")][37:333], tapes[(np.uint64, "b")][37:333], scope, bound=25)
+        assert same_alignments(sub, bounded), (wa, wb)
+        assert all(sub[i] == (want[37 + i] if want.distances[37 + i] <= 25 else b"") for i in range(296)), (wa, wb)
+
+
+BLOCK_LENGTHS = (31, 32, 33, 63, 64, 65, 95, 96, 97, 129, 300, 1000)   # around the edges of the pattern's 32-row blocks, and many blocks
+
+
+@pytest.mark.gpu
+def test_bounds_across_blocks(sw, scope, lev):
+    """Every pair of lengths around the 32-row block edges, both ways round (the pattern is the longer string: one orientation runs
+    transposed), related pairs a known number of edits apart and unrelated ones, under bounds that fall below the length difference
+    (the early exit), between it and the distance (the exit after the forward pass), and above the distance (the script)."""
+    rng = np.random.default_rng(32)
+    a, b, edits_of = [], [], []
+    for la in BLOCK_LENGTHS:
+        for lb in BLOCK_LENGTHS:
+            base = rng.integers(97, 123, max(la, lb)).astype(np.uint8)
+            for edits in (0, 1, 5, 40):   # substitutions at distinct places of the common prefix, on top of the length difference
+                y = base[:lb].copy()
+                at = rng.choice(min(la, lb), min(edits, la, lb), replace=False)
+                y[at] = 97 + (y[at] - 97 + rng.integers(1, 26, len(at))) % 26
+                a.append(base[:la].tobytes()); b.append(y.tobytes()); edits_of.append(abs(la - lb) + len(at))
+            a.append(bytes(rng.integers(0, 4, la).astype(np.uint8))); b.append(bytes(rng.integers(0, 4, lb).astype(np.uint8))); edits_of.append(None)
+    reference = [reference_script(x, y) for x, y in zip(a, b)]
+    for (d, _), edits, x, y in zip(reference, edits_of, a, b):
+        assert abs(len(x) - len(y)) <= d <= (edits if edits is not None else max(len(x), len(y)))
+    # (the edit count is the distance unless the longer string's tail offers the shorter one better matches)
+    assert sum(d == e for (d, _), e in zip(reference, edits_of)) > 350
+    sa, sb = sw.Strs(a), sw.Strs(b)
+    for bound in (0, 1, 5, 40, 200):
+        got = lev.align(sa, sb, scope, bound=bound)
+        assert (got.distances == lev.pairs(sa, sb, scope, bound=bound)).all(), bound
+        by_gap = by_distance = within = 0
+        for i, (d, ops) in enumerate(reference):
+            if d > bound:
+                assert int(got.distances[i]) == bound + 1 and got[i] == b"", (bound, i, len(a[i]), len(b[i]))
+                by_gap += abs(len(a[i]) - len(b[i])) > bound
+                by_distance += abs(len(a[i]) - len(b[i])) <= bound
+            else:
+                assert int(got.distances[i]) == d and got[i] == ops, (bound, i, len(a[i]), len(b[i]), got[i][:80], ops[:80])
+                within += 1
+        assert by_gap and by_distance and within, (bound, by_gap, by_distance, within)
+
+
+# code points that differ from 0x41 in exactly one of the seven 3-bit groups GroupTables3 looks up (bits 0, 3, 7, 9, 12, 16, 20), two that
+# differ in the two top groups alone, and the edges of the UTF-8 lengths
+GROUP_SYMBOLS = [0x41, 0x40, 0x49, 0xC1, 0x241, 0x1041, 0x10041, 0x100041, 0x7F, 0x80, 0x7FF, 0x800, 0xFFFF, 0x10000, 0xFFFFF, 0x10FFFF]
+
+
+def test_group_symbols_differ_in_single_groups():
+    groups = lambda c: [(c >> (3 * g)) & 7 for g in range(7)]
+    differing = [sum(x != y for x, y in zip(groups(0x41), groups(c))) for c in GROUP_SYMBOLS[1:8]]
+    assert differing == [1] * 7 and sorted(next(g for g in range(7) if groups(c)[g] != groups(0x41)[g]) for c in GROUP_SYMBOLS[1:8]) == list(range(7))
+    assert [g for g in range(7) if groups(0xFFFFF)[g] != groups(0x10FFFF)[g]] == [5, 6]
+    assert all("".join(map(chr, GROUP_SYMBOLS)).encode("utf-8").decode("utf-8")[i] == chr(c) for i, c in enumerate(GROUP_SYMBOLS))
+
+
+@pytest.mark.gpu
+def test_code_point_groups(sw, scope, lev8):
+    """Exact scripts over symbols a wrong 3-bit group would confuse -- every pair checked -- and over patterns of >= 300 distinct ones."""
+    rng = np.random.default_rng(33)
+    draw = lambda: int(rng.choice(GROUP_SYMBOLS))
+    a, b = [], []
+    for i in range(1500):
+        x = [draw() for _ in range(int(rng.integers(0, 121)))]
+        y = mutated(rng, x, int(rng.integers(0, 10)), draw) if i % 3 else [draw() for _ in range(int(rng.integers(0, 121)))]
+        a.append("".join(map(chr, x))); b.append("".join(map(chr, y[:120])))
+    got = lev8.align(sw.Strs(a), sw.Strs(b), scope)
+    assert (got.distances == lev8.pairs(sw.Strs(a), sw.Strs(b), scope)).all()
+    check_exact(sw, got, a, b, utf8=True)
+    # many distinct symbols per pattern, among them pairs that differ in one group only (c and c ^ 0x10000, c and c ^ 8)
+    wide = np.concatenate([np.arange(0x4E00, 0x4E00 + 700), np.arange(0x4E00, 0x4E00 + 700) ^ 0x10000, np.arange(0x4E00, 0x4E00 + 700) ^ 0x1000])
+    assert len(set(wide.tolist())) == 2100
+    a, b = [], []
+    for i in range(24):
+        x = rng.choice(wide, int(rng.integers(320, 420)), replace=False).tolist()
+        y = mutated(rng, x, int(rng.integers(0, 20)), lambda: int(rng.choice(wide)))
+        if i % 4 == 3:
+            x, y = y, x
+        assert min(len(set(x)), len(set(y))) >= 300
+        a.append("".join(map(chr, x))); b.append("".join(map(chr, y)))
+    got = lev8.align(sw.Strs(a), sw.Strs(b), scope)
+    check_exact(sw, got, a, b, utf8=True)
+
+
+def check_offsets_from_ops(a, b, got):
+    """The offsets are the running sums of the pairs' op counts la + lb - (ops that consume a symbol of both strings)."""
+    offsets = got.offsets.astype(np.int64)
+    assert offsets[0] == 0 and offsets[-1] == len(got.ops) and (np.diff(offsets) >= 0).all()
+    seg = np.repeat(np.arange(len(got)), np.diff(offsets))
+    both = np.bincount(seg[(got.ops == ord("=")) | (got.ops == ord("X"))], minlength=len(got))
+    counts = a.lengths + b.lengths - both
+    within = np.diff(offsets) > 0
+    assert (np.diff(offsets)[within] == counts[within]).all()
+    return within
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("count", [2047, 2048, 2049, 4096, 256 * 2048 + 1])
+def test_scan_and_emit_edges(sw, scope, lev, count):
+    """Pair counts at the edges of the scans: one tile of 2048 values less one, exactly, plus one, two tiles, and one pair more than 256
+    tiles (the tile sums are then scanned two per thread)."""
+    a, b = sw.generate_pairs("short_words", count, seed=count)
+    assert len(a) == len(b) == count
+    got = lev.align(a, b, scope)
+    assert (got.distances == lev.pairs(a, b, scope)).all()
+    check_valid_batch((a.data, a.offsets), (b.data, b.offsets), got)
+    within = check_offsets_from_ops(a, b, got)
+    assert within.sum() >= count - (a.lengths + b.lengths == 0).sum()
+    rng = np.random.default_rng(count)
+    edges = [i for t in range(0, count + 1, 2048) for i in (t - 2, t - 1, t, t + 1) if 0 <= i < count] if count < 10_000 else \
+            [i for t in (0, 2048, 4096, 255 * 2048, 256 * 2048) for i in (t - 2, t - 1, t, t + 1) if 0 <= i < count]
+    sample = sorted(set(edges + [0, count - 1] + rng.choice(count, 500, replace=False).tolist()))
+    check_exact(sw, got, {i: a[i] for i in sample}, {i: b[i] for i in sample}, indices=sample)
+
+
+@pytest.mark.gpu
+def test_mostly_empty_scripts(sw, scope, lev):
+    """Only every 1000th pair is within the bound: nearly every count the scans add is zero."""
+    rng = np.random.default_rng(35)
+    a, other = sw.generate_pairs("short_words", 100_000, seed=35)
+    items_a = [a[i] for i in range(len(a))]
+    items_b = [bytes(reversed(x)) + b"##" for x in items_a]                      # at least two edits away
+    for i in range(0, len(a), 1000):
+        items_b[i] = items_a[i][:3] + b"#" + items_a[i][4:]                       # at most one
+    b = sw.Strs(items_b)
+    got = lev.align(a, b, scope, bound=1)
+    assert (got.distances == lev.pairs(a, b, scope, bound=1)).all()
+    within = np.nonzero(got.distances <= 1)[0]
+    assert within.tolist() == list(range(0, len(a), 1000))
+    lengths = np.diff(got.offsets.astype(np.int64))
+    assert (lengths[got.distances > 1] == 0).all() and (lengths[within] > 0).all() and got.offsets[-1] == len(got.ops)
+    check_exact(sw, got, items_a, items_b, bound=1, indices=list(within) + [1, 999, 1001, 2047, 2048, 2049, 99_999])
+
+
+@pytest.mark.gpu
+def test_cell_limit(sw, scope, lev):
+    """SWH_ALIGN_MAX_CELLS exactly: a pair of 2^20 x 1024 symbols (2^30 cells) is aligned, one of (2^20 + 1) x 1024 is refused."""
+    rng = np.random.default_rng(36)
+    long_a = bytes(rng.integers(0, 4, (1 << 20) + 1).astype(np.uint8))
+    short_b = bytes(rng.integers(0, 4, 1024).astype(np.uint8))
+    assert sw.ALIGN_MAX_CELLS == (1 << 20) * 1024
+    for a, b in (([b"ab", long_a], [b"ba", short_b]), ([b"ab", short_b], [b"ba", long_a])):
+        with pytest.raises(sw.StringWarsError, match="unsupported_length") as info:
+            lev.align(sw.Strs(a), sw.Strs(b), scope)
+        assert "pair 1" in str(info.value) and "1048577" in str(info.value)
+    a, b = sw.Strs([b"ab", long_a[:-1]]), sw.Strs([b"ba", short_b])
+    got = lev.align(a, b, scope)
+    assert (got.distances == lev.pairs(a, b, scope)).all() and got[0] == b"XX"
+    assert (1 << 20) - 1024 <= int(got.distances[1]) <= 1 << 20
+    assert script_errors(long_a[:-1], short_b, got[1], int(got.distances[1])) is None
