@@ -273,6 +273,41 @@ swh_status_t swh_levenshtein_align_prepared(swh_levenshtein_t engine, swh_scope_
                                             const swh_prepared_view_t *b, uint32_t bound, uint32_t *distances,
                                             size_t *ops_offsets, char *ops, size_t ops_capacity, const char **error);
 
+/* ---- Infix search: the best approximate occurrence of every pattern in its text (edlib `mode="HW"`, rapidfuzz
+ *      `partial_ratio_alignment`, bio `Aligner::semiglobal`), unit costs only. -----------------------------------------------
+ * For every pair i of a pairwise batch (patterns->count == texts->count, else swh_invalid_argument_k), pattern p_i of m symbols
+ * and text t_i of n symbols:
+ *  - d_i = min over 0 <= s <= e <= n of d(p_i, t_i[s..e)), the unit-cost Levenshtein distance to the best substring;
+ *    distances[i] = min(d_i, bound + 1); bound == SWH_UNBOUNDED means no cutoff, bound == 0 is exact substring search;
+ *  - the occurrence reported is the CANONICAL one: ends[i] is the smallest e for which some s reaches d_i, starts[i] the largest
+ *    s <= e with d(p_i, t_i[s..e)) = d_i -- the shortest occurrence that ends there. So an empty pattern gives (0, 0, 0), an empty
+ *    text (m, 0, 0), and a pattern that matches nowhere better than by deleting all of it (m, 0, 0).
+ *    kitten in "the sitting cat": (2, 5, 10); abc in xxabcxx: (0, 2, 5); lawn in "flaw in law": (1, 1, 4); ab in ba: (1, 0, 1);
+ *    aaa in bbb: (3, 0, 0);
+ *  - a pair with d_i > bound gets distances[i] = bound + 1 and starts[i] = ends[i] = SWH_INFIX_NONE;
+ *  - symbols and positions are bytes, or code points in the UTF-8 variant (invalid UTF-8 -> swh_invalid_utf8_k); the prepared
+ *    variant takes what the tapes were prepared as (both of the same kind, any mix of 32- and 64-bit offsets);
+ *  - a pattern of more than SWH_INFIX_MAX_PATTERN symbols makes the call return swh_unsupported_length_k before any output is
+ *    written; the message names the first such pair. Texts have no limit beyond the tapes' own;
+ *  - an engine whose costs are not (match 0, mismatch 1, open 1, extend 1) returns swh_not_implemented_k;
+ *  - `distances`, `starts` and `ends` (uint32_t, one entry per pair) may each be in host or device memory;
+ *  - count == 0 succeeds and writes nothing.
+ * The call is synchronous on every scope: on an asynchronous or pipelined scope it first joins the outstanding work (as
+ * swh_scope_synchronize) and returns with the results visible. With profiling on, swh_scope_last_timing describes the whole call:
+ * `cells` = sum m n; `dominant_name` is its longest kernel ("infix" for bytes, "infix_u32" for code points, when the forward
+ * pass dominates). The edit script of an occurrence: swh_levenshtein_align_* on p_i against t_i[starts[i]..ends[i]). */
+#define SWH_INFIX_MAX_PATTERN 2048u     /* symbols per pattern: one wave's 64 blocks of 32 rows */
+#define SWH_INFIX_NONE 0xFFFFFFFFu      /* start / end of a pair whose best occurrence is over the bound */
+swh_status_t swh_levenshtein_infix_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *patterns,
+                                           const swh_tape_u64_t *texts, uint32_t bound, uint32_t *distances, uint32_t *starts,
+                                           uint32_t *ends, const char **error);
+swh_status_t swh_levenshtein_utf8_infix_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *patterns,
+                                                const swh_tape_u64_t *texts, uint32_t bound, uint32_t *distances, uint32_t *starts,
+                                                uint32_t *ends, const char **error);
+swh_status_t swh_levenshtein_infix_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *patterns,
+                                            const swh_prepared_view_t *texts, uint32_t bound, uint32_t *distances, uint32_t *starts,
+                                            uint32_t *ends, const char **error);
+
 /* ---- One batch over the GPUs of a multi-device scope (BASELINE config 5). --------------------------------
  * `swh_sharded_prepare_*`: HOST tapes of equal count are cut into contiguous shards balanced on the prefix sum of
  * len(a_i)*len(b_i) (DP cells, not pair counts); shard r is uploaded to and prepared on device r. The handle is the steady
@@ -377,7 +412,8 @@ swh_status_t swh_sw_pairs_sharded(swh_sw_t engine, swh_scope_t scope, swh_sharde
 /* ---- Introspection: `log_stringzilla_metadata` (utils.rs:78-92). --------------------------- */
 const char *swh_version(void);
 /* Comma-separated capability string, e.g. "gfx950,hip,wavefront,bitparallel,banded,utf8,...";
- * "topk" when the swh_levenshtein_topk_* calls are present, "align" when the swh_levenshtein_align_* calls are. */
+ * "topk" when the swh_levenshtein_topk_* calls are present, "align" when the swh_levenshtein_align_* calls are,
+ * "infix" when the swh_levenshtein_infix_* calls are. */
 const char *swh_capabilities(void);
 
 #ifdef __cplusplus

@@ -225,6 +225,24 @@ public:
         swh_status_t status__ = swh_levenshtein_align_prepared(handle_, scope.handle(), &va, &vb, bound, distances, ops_offsets, ops, ops_capacity, &err);
         check(status__, err);
     }
+    /// Infix search (swh_levenshtein_infix_*): the best approximate occurrence of patterns[i] in texts[i] -- distances[i] = min(d, bound + 1),
+    /// the occurrence texts[i][starts[i] .. ends[i]) (the smallest end that reaches d, then the shortest substring), SWH_INFIX_NONE in both
+    /// for a pair over the bound; one entry per pair, each array in host or device memory.
+    void infix(const DeviceScope &scope, const BytesTapeView &patterns, const BytesTapeView &texts, uint32_t *distances, uint32_t *starts,
+               uint32_t *ends, uint32_t bound = SWH_UNBOUNDED) const {
+        const char *err = nullptr;
+        swh_tape_u64_t tp = patterns.c(), tt = texts.c();
+        auto fn = utf8_ ? swh_levenshtein_utf8_infix_u64tape : swh_levenshtein_infix_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &tp, &tt, bound, distances, starts, ends, &err);
+        check(status__, err);
+    }
+    void infix(const DeviceScope &scope, const PreparedTape &patterns, const PreparedTape &texts, uint32_t *distances, uint32_t *starts,
+               uint32_t *ends, uint32_t bound = SWH_UNBOUNDED) const {
+        const char *err = nullptr;
+        swh_prepared_view_t vp = patterns.c(), vt = texts.c();
+        swh_status_t status__ = swh_levenshtein_infix_prepared(handle_, scope.handle(), &vp, &vt, bound, distances, starts, ends, &err);
+        check(status__, err);
+    }
     /// Top-k search (swh_levenshtein_topk_*): the k nearest candidates of every query, `indices` / `distances` of
     /// queries.count x k (host or device memory); rows ascending by (distance, index), only d <= bound, padded with 0xFFFFFFFF.
     void topk(const DeviceScope &scope, const BytesTapeView &queries, const BytesTapeView *candidates, size_t k, uint32_t *indices,

@@ -14,6 +14,7 @@
 
 #include "common.hpp"
 #include "align.hpp"
+#include "infix.hpp"
 #include <algorithm>
 #include <mutex>
 #include <utility>
@@ -1172,7 +1173,7 @@ static void free_align_scratch(const Scope *scope) {
 extern "C" {
 
 const char *swh_version(void) { return "0.1.0"; }
-const char *swh_capabilities(void) { return "gfx950,hip,wavefront,bitparallel,tiled,banded,utf8,bounded,nw-linear,nw-affine,sw-linear,sw-affine,cross,prepared,topk,align,multi-gpu-rccl"; }
+const char *swh_capabilities(void) { return "gfx950,hip,wavefront,bitparallel,tiled,banded,utf8,bounded,nw-linear,nw-affine,sw-linear,sw-affine,cross,prepared,topk,align,infix,multi-gpu-rccl"; }
 
 static swh_status_t scope_init(int device, void *stream, bool borrow, swh_scope_t *out, const char **error) {
     if (!out) return fail(error, swh_invalid_argument_k, "null scope pointer");
@@ -2310,6 +2311,159 @@ swh_status_t swh_levenshtein_align_prepared(swh_levenshtein_t e, swh_scope_t s, 
     HoldSynchronous mode(scope);
     AlignRequest r{pa, pb, a->first, b->first, a->count, bound, distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity};
     return align_run(scope, r, error);
+}
+
+// ---- infix search (infix.hip) ---------------------------------------------------------------------------------------------------------
+// k_infix_sizes measures the batch (cells, the first pattern over SWH_INFIX_MAX_PATTERN) and cuts it into work items; one read-back of
+// the measurements decides the errors before any output is written. Then the forward pass (distance and end of every pair) and the
+// start pass (the starts, the bound) over the same items, and the copy-out of outputs that live on the host. The scratch -- the item
+// list and, for host outputs, the three result arrays -- is the scope's alignment scratch: both calls are synchronous.
+struct InfixRequest {
+    const Prepared *pp, *pt;
+    size_t p_first, t_first, count;
+    uint32_t bound;
+    uint32_t *distances, *starts, *ends;
+};
+
+static swh_status_t infix_run(Scope *scope, const InfixRequest &r, const char **error) {
+    harvest_timing(scope, false);
+    scope->stamps_used = 0;
+    scope->last_timing = swh_timing_t{};
+    const uint64_t count = r.count;
+    if (count == 0) return swh_success_k;
+    try {
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        const bool dev_d = is_device_pointer(r.distances), dev_s = is_device_pointer(r.starts), dev_e = is_device_pointer(r.ends);
+        const bool cp = r.pp->utf8;
+        InfixTapes t{};
+        t.patterns = prepared_view(r.pp, cp, r.p_first, count);
+        t.texts = prepared_view(r.pt, cp, r.t_first, count);
+        t.p_off64 = cp ? 1 : r.pp->off64;
+        t.t_off64 = cp ? 1 : r.pt->off64;
+        t.cp = cp ? 1 : 0;
+        t.count = count;
+
+        AlignScratch *sc_entry;
+        {
+            std::lock_guard<std::mutex> hold(g_align_scratch_lock);
+            sc_entry = &g_align_scratch[scope];
+        }
+        // sizes | items | distances | starts | ends (the last three only where the caller's array lives on the host)
+        const size_t need = pad(sizeof(InfixSizes)) + pad(count * sizeof(InfixItem)) + ((dev_d ? 0 : 1) + (dev_s ? 0 : 1) + (dev_e ? 0 : 1)) * pad(count * 4);
+        ensure(sc_entry->buf, sc_entry->bytes, need);
+        Carver sc{sc_entry->buf, 0, sc_entry->bytes};
+        InfixSizes *sizes = sc.take<InfixSizes>(1);
+        InfixItem *items = sc.take<InfixItem>(count);
+        uint32_t *distances = dev_d ? r.distances : sc.take<uint32_t>(count);
+        uint32_t *starts = dev_s ? r.starts : sc.take<uint32_t>(count);
+        uint32_t *ends = dev_e ? r.ends : sc.take<uint32_t>(count);
+
+        InfixSizes init{};
+        init.first_oversize = ~0ull;
+        SWH_HIP_CHECK(hipMemcpyAsync(sizes, &init, sizeof init, hipMemcpyHostToDevice, stream));
+        launch_infix_sizes(scope, t, sizes, items);
+        InfixSizes got{};
+        SWH_HIP_CHECK(hipMemcpyAsync(&got, sizes, sizeof got, hipMemcpyDeviceToHost, stream));
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        if (got.first_oversize != ~0ull) {
+            const size_t i = (size_t)got.first_oversize;
+            const uint64_t m = read_offset(t.patterns.offsets, t.p_off64, i + 1, true, stream) - read_offset(t.patterns.offsets, t.p_off64, i, true, stream);
+            scope->stamps_used = 0;
+            return fail(error, swh_unsupported_length_k, "pair %zu: a pattern of %llu symbols exceeds SWH_INFIX_MAX_PATTERN (2048)", i,
+                        (unsigned long long)m);
+        }
+
+        InfixRun run{};
+        run.items = items; run.item_count = got.items;
+        run.distances = distances; run.starts = starts; run.ends = ends;
+        run.bound = r.bound;
+        run.wide_text = !cp && got.text_symbols >= 16;
+        launch_infix_forward(scope, t, run);
+        launch_infix_starts(scope, t, run);
+        if (!dev_d) SWH_HIP_CHECK(hipMemcpyAsync(r.distances, distances, count * 4, hipMemcpyDeviceToHost, stream));
+        if (!dev_s) SWH_HIP_CHECK(hipMemcpyAsync(r.starts, starts, count * 4, hipMemcpyDeviceToHost, stream));
+        if (!dev_e) SWH_HIP_CHECK(hipMemcpyAsync(r.ends, ends, count * 4, hipMemcpyDeviceToHost, stream));
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        if (scope->profiling && scope->stamps_used) {
+            collect_timing(scope);
+            add_to_totals(scope->totals, scope->last_timing);
+        }
+        scope->stamps_used = 0;
+        scope->last_timing.cells = got.cells;
+        scope->last_timing.bytes = (cp ? 4 : 1) * got.symbols + 2 * (count + 1) * 8 + 3 * count * 4;
+        return swh_success_k;
+    } catch (const HipFailure &f) {
+        return fail_hip(error, f);
+    } catch (const std::bad_alloc &) {
+        return fail(error, swh_bad_alloc_k, "host allocation failed");
+    }
+}
+
+// no scope or engine can exist without a device: a call that gets none says so, as scope creation does
+static swh_status_t infix_handles(swh_levenshtein_t e, swh_scope_t s, const char **error) {
+    if (s && e) return swh_success_k;
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0) {
+        (void)hipGetLastError();
+        return fail(error, swh_no_device_k, "no HIP device visible (this backend has no CPU path)");
+    }
+    return fail(error, swh_invalid_argument_k, "null scope or engine");
+}
+static swh_status_t infix_checks(swh_levenshtein_t e, swh_scope_t s, size_t p_count, size_t t_count, const uint32_t *distances,
+                                 const uint32_t *starts, const uint32_t *ends, const char **error) {
+    const Engine *engine = (const Engine *)e;
+    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (!engine->unit_costs) return fail(error, swh_not_implemented_k, "infix search needs unit costs (match 0, mismatch 1, open 1, extend 1)");
+    if (p_count != t_count) return fail(error, swh_invalid_argument_k, "patterns and texts must hold the same number of strings");
+    if (p_count && (!distances || !starts || !ends)) return fail(error, swh_invalid_argument_k, "null output pointer");
+    return swh_success_k;
+}
+
+static swh_status_t infix_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts, bool utf8,
+                                uint32_t bound, uint32_t *distances, uint32_t *starts, uint32_t *ends, const char **error) {
+    swh_status_t status = infix_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    if (!patterns || !texts) return fail(error, swh_invalid_argument_k, "null tape");
+    status = infix_checks(e, s, patterns->count, texts->count, distances, starts, ends, error);
+    if (status != swh_success_k) return status;
+    Scope *scope = (Scope *)s;
+    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
+    HoldSynchronous mode(scope);
+    InfixRequest r{nullptr, nullptr, 0, 0, patterns->count, bound, distances, starts, ends};
+    if (patterns->count == 0) return infix_run(scope, r, error);
+    // raw tapes are made resident, measured and (UTF-8) validated and decoded for the call, as for top-k and alignments
+    PreparedOwner pp, pt;
+    status = prepare_tape(scope, SWH_TAPE(patterns, 1), utf8, (swh_prepared_t *)&pp.p, error);
+    if (status != swh_success_k) return status;
+    status = prepare_tape(scope, SWH_TAPE(texts, 1), utf8, (swh_prepared_t *)&pt.p, error);
+    if (status != swh_success_k) return status;
+    r.pp = pp.p; r.pt = pt.p;
+    return infix_run(scope, r, error);
+}
+swh_status_t swh_levenshtein_infix_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts,
+                                           uint32_t bound, uint32_t *distances, uint32_t *starts, uint32_t *ends, const char **error) {
+    return infix_tapes(e, s, patterns, texts, false, bound, distances, starts, ends, error);
+}
+swh_status_t swh_levenshtein_utf8_infix_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts,
+                                                uint32_t bound, uint32_t *distances, uint32_t *starts, uint32_t *ends, const char **error) {
+    return infix_tapes(e, s, patterns, texts, true, bound, distances, starts, ends, error);
+}
+swh_status_t swh_levenshtein_infix_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *patterns,
+                                            const swh_prepared_view_t *texts, uint32_t bound, uint32_t *distances, uint32_t *starts,
+                                            uint32_t *ends, const char **error) {
+    if (swh_status_t status = infix_handles(e, s, error)) return status;
+    if (!patterns || !patterns->tape || !texts || !texts->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
+    if (!view_fits(patterns) || !view_fits(texts)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
+    const Prepared *pp = (const Prepared *)patterns->tape, *pt = (const Prepared *)texts->tape;
+    swh_status_t status = infix_checks(e, s, patterns->count, texts->count, distances, starts, ends, error);
+    if (status != swh_success_k) return status;
+    Scope *scope = (Scope *)s;
+    if ((status = check_prepared_pair(scope, pp, pt, error)) != swh_success_k) return status;
+    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
+    HoldSynchronous mode(scope);
+    InfixRequest r{pp, pt, patterns->first, texts->first, patterns->count, bound, distances, starts, ends};
+    return infix_run(scope, r, error);
 }
 
 }  // extern "C"

@@ -1,0 +1,46 @@
+// infix.hpp -- launchers of the Levenshtein infix-search kernels (infix.hip), called by api.hip.
+// Kept apart from common.hpp, which every kernel family's profile stamp hashes (tools/kernel_sources.py).
+#pragma once
+#include "common.hpp"
+
+namespace swh {
+
+// One pairwise batch on prepared (device-resident, measured, decoded) tapes: pattern i is searched in text i. Symbols are bytes
+// (`cp` = 0, each tape's offsets u32 or u64 by its `off64`) or code points (`cp` = 1: u32 symbols, u64 offsets).
+struct InfixTapes {
+    TapeRef patterns, texts;
+    uint32_t p_off64, t_off64, cp;
+    uint64_t count;
+};
+
+// What k_infix_sizes measures over the whole batch, read back by the host before anything is written.
+struct InfixSizes {
+    unsigned long long cells;            // sum m_i * n_i
+    unsigned long long symbols;          // sum m_i + n_i
+    unsigned long long first_oversize;   // the first pair whose pattern has more than SWH_INFIX_MAX_PATTERN symbols, or ~0
+    unsigned long long items;            // work items written to the item list
+    unsigned long long text_symbols;     // symbols the text tape (the view of it the call sees) holds
+};
+
+// A work item of the two passes: `pairs` consecutive pairs from `first` on, `blocks` lanes (32-row blocks) each; pairs * blocks <= 64.
+struct InfixItem {
+    uint64_t first;
+    uint32_t pairs, blocks;
+};
+
+// Measures the batch into `sizes` (zeroed by the caller, first_oversize set to ~0) and cuts it into items (`items`: room for `count`).
+void launch_infix_sizes(Scope *scope, const InfixTapes &t, InfixSizes *sizes, InfixItem *items);
+
+// The forward pass writes every pair's distance and end (unclamped) to `distances` / `ends`; the start pass reads them, finds the
+// starts of the pairs within the bound and writes all three arrays in their final form (the bound applied).
+struct InfixRun {
+    const InfixItem *items;
+    uint64_t item_count;
+    uint32_t *distances, *starts, *ends;
+    uint32_t bound;
+    bool wide_text;   // the text tape holds at least 16 bytes: the forward pass reads it with 128-bit loads
+};
+void launch_infix_forward(Scope *scope, const InfixTapes &t, const InfixRun &r);
+void launch_infix_starts(Scope *scope, const InfixTapes &t, const InfixRun &r);
+
+}  // namespace swh

@@ -25,13 +25,15 @@ from . import _native as N
 __all__ = [
     "DeviceScope", "Strs", "DeviceTape", "PreparedTape", "ShardedPairs", "shard_cuts", "LevenshteinDistances", "LevenshteinDistancesUTF8",
     "NeedlemanWunschScores", "SmithWatermanScores", "edit_distance", "StringWarsError", "UNBOUNDED", "TOPK_MAX",
-    "ALIGN_MAX_CELLS", "Alignments",
+    "ALIGN_MAX_CELLS", "Alignments", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches",
 ]
 
 StringWarsError = N.StringWarsError
 UNBOUNDED = N.UNBOUNDED
 TOPK_MAX = N.TOPK_MAX
 ALIGN_MAX_CELLS = N.ALIGN_MAX_CELLS
+INFIX_MAX_PATTERN = N.INFIX_MAX_PATTERN
+INFIX_NONE = N.INFIX_NONE
 
 
 def _pointer(obj) -> int:
@@ -454,6 +456,38 @@ class Alignments:
         return result
 
 
+class InfixMatches:
+    """The result of ``LevenshteinDistances.infix``: the best approximate occurrence of every pattern in its text.
+
+    ``distances[i]`` is ``min(d, bound + 1)``, ``d`` the smallest distance of pattern ``i`` to any substring of text ``i``; the occurrence
+    is ``text[starts[i]:ends[i]]`` -- the CANONICAL one: the smallest end that reaches ``d`` and, for that end, the shortest substring.
+    A pair over the bound has ``starts[i] == ends[i] == INFIX_NONE``. Positions count symbols: bytes, or code points for the UTF-8 engine."""
+
+    def __init__(self, distances, starts, ends):
+        self.distances = np.asarray(distances, dtype=np.uint32)
+        self.starts = np.asarray(starts, dtype=np.uint32)
+        self.ends = np.asarray(ends, dtype=np.uint32)
+        if not len(self.distances) == len(self.starts) == len(self.ends):
+            raise ValueError("distances, starts and ends must have one entry per pair")
+
+    def __len__(self) -> int:
+        return len(self.distances)
+
+    @property
+    def found(self) -> np.ndarray:
+        """Bool mask of the pairs whose best occurrence is within the bound."""
+        return self.ends != np.uint32(N.INFIX_NONE)
+
+    def __getitem__(self, i: int):
+        """``(distance, start, end)`` of pair ``i``, or ``None`` when its best occurrence is over the bound."""
+        if not -len(self) <= i < len(self):
+            raise IndexError("pair index out of range")
+        i %= len(self)
+        if int(self.ends[i]) == N.INFIX_NONE:
+            return None
+        return int(self.distances[i]), int(self.starts[i]), int(self.ends[i])
+
+
 def _as_tape(obj: TapeLike):
     if isinstance(obj, (Strs, DeviceTape, PreparedTape)):
         return obj
@@ -702,6 +736,40 @@ class LevenshteinDistances(_Engine):
         N.check(status, err)
         used = int(offsets[-1])
         return Alignments(distances, offsets, ops[:used].copy() if 2 * used < len(ops) else ops[:used])
+
+    def infix(self, patterns: TapeLike, texts: TapeLike, scope: Optional[DeviceScope] = None, bound: Optional[int] = None) -> "InfixMatches":
+        """Where, and how well, ``patterns[i]`` approximately occurs in ``texts[i]`` on unit costs (``swh_levenshtein_infix_*``): an
+        :class:`InfixMatches` with ``distances``, ``starts`` and ``ends``. Patterns hold at most ``INFIX_MAX_PATTERN`` symbols. The two
+        sides are tapes, or both ``PreparedTape``s. edlib: ``align(p, t, mode="HW", k=bound)`` (``editDistance``, ``locations[0]`` with an
+        inclusive end); rapidfuzz: ``partial_ratio_alignment`` (``dest_start`` / ``dest_end``)."""
+        if scope is None:
+            raise ValueError("a DeviceScope is required")
+        patterns, texts = _as_tape(patterns), _as_tape(texts)
+        if isinstance(patterns, DeviceTape) or isinstance(texts, DeviceTape):   # measured on the device, like the raw calls do internally
+            patterns = patterns if isinstance(patterns, PreparedTape) else PreparedTape(scope, patterns, utf8=self._utf8)
+            texts = texts if isinstance(texts, PreparedTape) else PreparedTape(scope, texts, utf8=self._utf8)
+        if len(patterns) != len(texts):
+            raise ValueError("patterns and texts must hold the same number of strings")
+        count = len(patterns)
+        bound_value = C.c_uint32(N.UNBOUNDED if bound is None else int(bound))
+        distances, starts, ends = (np.empty(count, dtype=np.uint32) for _ in range(3))
+        outs = tuple(C.c_void_p(array.ctypes.data) for array in (distances, starts, ends))
+        err = C.c_char_p()
+        if isinstance(patterns, PreparedTape) or isinstance(texts, PreparedTape):
+            if not (isinstance(patterns, PreparedTape) and isinstance(texts, PreparedTape)):
+                raise TypeError("both tapes of a call must be prepared, or neither")
+            if self._utf8 != patterns.utf8 or self._utf8 != texts.utf8:
+                raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
+            vp, vt = patterns.view(), texts.view()
+            status = N.lib.swh_levenshtein_infix_prepared(self._handle, scope.handle, C.byref(vp), C.byref(vt), bound_value, *outs, C.byref(err))
+        else:
+            tp, _, keep_p = _c_tape(patterns, want64=True)
+            tt, _, keep_t = _c_tape(texts, want64=True)
+            fn = N.lib.swh_levenshtein_utf8_infix_u64tape if self._utf8 else N.lib.swh_levenshtein_infix_u64tape
+            status = fn(self._handle, scope.handle, C.byref(tp), C.byref(tt), bound_value, *outs, C.byref(err))
+            del keep_p, keep_t
+        N.check(status, err)
+        return InfixMatches(distances, starts, ends)
 
     def pairs_sharded(self, batch: "ShardedPairs", scope: DeviceScope, bound: Optional[int] = None, out=None):
         """One batch over every GPU of a multi-device scope; the distances come back gathered, in pair order."""

@@ -48,6 +48,10 @@ pub struct ShardTiming { pub compute_ms: f64, pub gather_ms: f64, pub cells: u64
 pub const UNBOUNDED: u32 = u32::MAX;
 /// `SWH_ALIGN_MAX_CELLS`: len(a_i) * len(b_i) an alignment accepts per pair.
 pub const ALIGN_MAX_CELLS: u64 = 1 << 30;
+/// `SWH_INFIX_MAX_PATTERN`: symbols per pattern an infix search accepts.
+pub const INFIX_MAX_PATTERN: u32 = 2048;
+/// `SWH_INFIX_NONE`: start / end of a pair whose best occurrence is over the bound.
+pub const INFIX_NONE: u32 = u32::MAX;
 /// `SWH_OP_*`: the op bytes of an alignment.
 pub const OP_MATCH: u8 = b'=';
 pub const OP_SUBST: u8 = b'X';
@@ -112,6 +116,9 @@ extern "C" {
     fn swh_levenshtein_align_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, bound: u32, distances: *mut u32, ops_offsets: *mut usize, ops: *mut c_char, ops_capacity: usize, error: Err) -> c_int;
     fn swh_levenshtein_utf8_align_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, bound: u32, distances: *mut u32, ops_offsets: *mut usize, ops: *mut c_char, ops_capacity: usize, error: Err) -> c_int;
     fn swh_levenshtein_align_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, bound: u32, distances: *mut u32, ops_offsets: *mut usize, ops: *mut c_char, ops_capacity: usize, error: Err) -> c_int;
+    fn swh_levenshtein_infix_u64tape(engine: Handle, scope: Handle, patterns: *const TapeU64, texts: *const TapeU64, bound: u32, distances: *mut u32, starts: *mut u32, ends: *mut u32, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_infix_u64tape(engine: Handle, scope: Handle, patterns: *const TapeU64, texts: *const TapeU64, bound: u32, distances: *mut u32, starts: *mut u32, ends: *mut u32, error: Err) -> c_int;
+    fn swh_levenshtein_infix_prepared(engine: Handle, scope: Handle, patterns: *const PreparedView, texts: *const PreparedView, bound: u32, distances: *mut u32, starts: *mut u32, ends: *mut u32, error: Err) -> c_int;
     fn swh_sharded_prepare_u32tape(scope: Handle, a: *const TapeU32, b: *const TapeU32, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_prepare_u64tape(scope: Handle, a: *const TapeU64, b: *const TapeU64, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_free(sharded: Handle) -> c_int;
@@ -444,6 +451,25 @@ impl LevenshteinDistances {
         check(unsafe { swh_levenshtein_align_prepared(self.handle, scope.handle, &va, &vb, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
                                                       offsets.as_mut_ptr(), ops.as_mut_ptr() as *mut c_char, ops.len(), &mut message) }, message)
     }
+    /// Infix search (`swh_levenshtein_infix_*`): the best approximate occurrence of `patterns[i]` in `texts[i]` -- `distances[i] = min(d, bound + 1)`,
+    /// the occurrence `texts[i][starts[i] .. ends[i])` (the smallest end that reaches d, then the shortest substring), `INFIX_NONE` in both
+    /// for a pair over the bound. The batched form of `bio::alignment::pairwise::Aligner::semiglobal` on unit costs.
+    pub fn infix_into(&self, scope: &DeviceScope, patterns: &BytesTapeView<u64>, texts: &BytesTapeView<u64>, bound: Option<u32>, distances: &mut [u32],
+                      starts: &mut [u32], ends: &mut [u32]) -> Result<(), Error> {
+        assert!(distances.len() >= patterns.len() && starts.len() >= patterns.len() && ends.len() >= patterns.len());
+        let (tp, tt) = (bytes_tape(patterns), bytes_tape(texts));
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_infix_u64tape(self.handle, scope.handle, &tp, &tt, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
+                                                     starts.as_mut_ptr(), ends.as_mut_ptr(), &mut message) }, message)
+    }
+    pub fn infix_into_prepared(&self, scope: &DeviceScope, patterns: &PreparedTape, texts: &PreparedTape, bound: Option<u32>, distances: &mut [u32],
+                               starts: &mut [u32], ends: &mut [u32]) -> Result<(), Error> {
+        assert!(distances.len() >= patterns.len() && starts.len() >= patterns.len() && ends.len() >= patterns.len());
+        let (vp, vt) = (patterns.view(), texts.view());
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_infix_prepared(self.handle, scope.handle, &vp, &vt, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
+                                                      starts.as_mut_ptr(), ends.as_mut_ptr(), &mut message) }, message)
+    }
     pub fn topk_into_prepared(&self, scope: &DeviceScope, queries: &PreparedTape, candidates: Option<&PreparedTape>, k: usize, bound: Option<u32>,
                               indices: &mut [u32], distances: &mut [u32]) -> Result<(), Error> {
         assert!(indices.len() >= queries.len() * k && distances.len() >= queries.len() * k);
@@ -505,6 +531,23 @@ impl LevenshteinDistancesUtf8 {
         let mut message = ptr::null();
         check(unsafe { swh_levenshtein_align_prepared(self.handle, scope.handle, &va, &vb, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
                                                       offsets.as_mut_ptr(), ops.as_mut_ptr() as *mut c_char, ops.len(), &mut message) }, message)
+    }
+    /// Infix search over code points (see `LevenshteinDistances::infix_into`).
+    pub fn infix_into(&self, scope: &DeviceScope, patterns: &CharsTapeView<u64>, texts: &CharsTapeView<u64>, bound: Option<u32>, distances: &mut [u32],
+                      starts: &mut [u32], ends: &mut [u32]) -> Result<(), Error> {
+        assert!(distances.len() >= patterns.len() && starts.len() >= patterns.len() && ends.len() >= patterns.len());
+        let (tp, tt) = (chars_tape(patterns), chars_tape(texts));
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_utf8_infix_u64tape(self.handle, scope.handle, &tp, &tt, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
+                                                     starts.as_mut_ptr(), ends.as_mut_ptr(), &mut message) }, message)
+    }
+    pub fn infix_into_prepared(&self, scope: &DeviceScope, patterns: &PreparedTape, texts: &PreparedTape, bound: Option<u32>, distances: &mut [u32],
+                               starts: &mut [u32], ends: &mut [u32]) -> Result<(), Error> {
+        assert!(distances.len() >= patterns.len() && starts.len() >= patterns.len() && ends.len() >= patterns.len());
+        let (vp, vt) = (patterns.view(), texts.view());
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_infix_prepared(self.handle, scope.handle, &vp, &vt, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
+                                                      starts.as_mut_ptr(), ends.as_mut_ptr(), &mut message) }, message)
     }
     /// Top-k search over code points (see `LevenshteinDistances::topk_into`).
     pub fn topk_into(&self, scope: &DeviceScope, queries: &CharsTapeView<u64>, candidates: Option<&CharsTapeView<u64>>, k: usize, bound: Option<u32>,
