@@ -308,6 +308,50 @@ swh_status_t swh_levenshtein_infix_prepared(swh_levenshtein_t engine, swh_scope_
                                             const swh_prepared_view_t *texts, uint32_t bound, uint32_t *distances, uint32_t *starts,
                                             uint32_t *ends, const char **error);
 
+/* ---- Damerau-Levenshtein (OSA) distances: a swap of two neighbouring symbols costs one edit (rapidfuzz `distance.OSA`,
+ *      `process.cdist(..., scorer=OSA.distance)`), unit costs only. -----------------------------------------------------------
+ * The optimal-string-alignment distance, also called restricted Damerau-Levenshtein: for a of m symbols and b of n symbols, D is
+ * the unit-cost Wagner-Fischer recurrence plus one case -- when i, j >= 2, a[i-1] = b[j-2] and a[i-2] = b[j-1], then also
+ * D[i][j] <= D[i-2][j-2] + 1 -- and osa(a, b) = D[m][n]. No substring is edited twice, so this is NOT the unrestricted
+ * Damerau-Levenshtein distance. ab / ba: 1; abcd / acbd: 1; kitten / sitting: 3; ca / abc: 3 (unrestricted Damerau gives 2).
+ * osa(a, b) = osa(b, a), and osa <= Levenshtein <= 2 osa.
+ * Pairs (swh_levenshtein_osa_pairs_*):
+ *  - a->count == b->count, else swh_invalid_argument_k;
+ *  - out[i] = min(osa(a_i, b_i), bound + 1); bound == SWH_UNBOUNDED means no cutoff;
+ *  - `out_stride_bytes` is the distance between consecutive results (>= 4; 0 means 4), as for swh_levenshtein_pairs_*.
+ * Cross (swh_levenshtein_osa_cross_*):
+ *  - row-major `size_t`, out[i][j] = osa(a_i, b_j), rows `row_stride_bytes` apart (0 means b->count * 8), no bound: the shape of
+ *    swh_levenshtein_cross_*;
+ *  - b == NULL means a x a: symmetric, with a zero diagonal;
+ *  - the matrix is filled in slices of whole rows, so the call's scratch memory does not grow with the matrix.
+ * Both:
+ *  - symbols are bytes, or code points in the UTF-8 variant (invalid UTF-8 -> swh_invalid_utf8_k); the prepared variant takes
+ *    what the tapes were prepared as (both of the same kind, any mix of 32- and 64-bit offsets);
+ *  - a pair whose SHORTER string has more than SWH_OSA_MAX_SHORTER symbols makes the call return swh_unsupported_length_k before
+ *    any output is written; the message names the first such pair. The longer string has no limit beyond the tapes' own;
+ *  - an engine whose costs are not (match 0, mismatch 1, open 1, extend 1) returns swh_not_implemented_k;
+ *  - `out` may be in host or device memory;
+ *  - count == 0 (an empty matrix) succeeds and writes nothing.
+ * The call is synchronous on every scope: on an asynchronous or pipelined scope it first joins the outstanding work (as
+ * swh_scope_synchronize) and returns with the results visible. With profiling on, swh_scope_last_timing describes the whole call:
+ * `cells` = sum m n; `dominant_name` is its longest kernel ("osa" for bytes, "osa_u32" for code points). */
+#define SWH_OSA_MAX_SHORTER 2048u     /* symbols of a pair's shorter string: one wave's 64 blocks of 32 rows */
+swh_status_t swh_levenshtein_osa_pairs_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                               const swh_tape_u64_t *b, uint32_t bound, uint32_t *out, size_t out_stride_bytes,
+                                               const char **error);
+swh_status_t swh_levenshtein_utf8_osa_pairs_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                    const swh_tape_u64_t *b, uint32_t bound, uint32_t *out, size_t out_stride_bytes,
+                                                    const char **error);
+swh_status_t swh_levenshtein_osa_pairs_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *a,
+                                                const swh_prepared_view_t *b, uint32_t bound, uint32_t *out, size_t out_stride_bytes,
+                                                const char **error);
+swh_status_t swh_levenshtein_osa_cross_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                               const swh_tape_u64_t *b, size_t *out, size_t row_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_utf8_osa_cross_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                    const swh_tape_u64_t *b, size_t *out, size_t row_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_osa_cross_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *a,
+                                                const swh_prepared_view_t *b, size_t *out, size_t row_stride_bytes, const char **error);
+
 /* ---- One batch over the GPUs of a multi-device scope (BASELINE config 5). --------------------------------
  * `swh_sharded_prepare_*`: HOST tapes of equal count are cut into contiguous shards balanced on the prefix sum of
  * len(a_i)*len(b_i) (DP cells, not pair counts); shard r is uploaded to and prepared on device r. The handle is the steady
@@ -413,7 +457,7 @@ swh_status_t swh_sw_pairs_sharded(swh_sw_t engine, swh_scope_t scope, swh_sharde
 const char *swh_version(void);
 /* Comma-separated capability string, e.g. "gfx950,hip,wavefront,bitparallel,banded,utf8,...";
  * "topk" when the swh_levenshtein_topk_* calls are present, "align" when the swh_levenshtein_align_* calls are,
- * "infix" when the swh_levenshtein_infix_* calls are. */
+ * "infix" when the swh_levenshtein_infix_* calls are, "osa" when the swh_levenshtein_osa_* calls are. */
 const char *swh_capabilities(void);
 
 #ifdef __cplusplus

@@ -243,6 +243,39 @@ public:
         swh_status_t status__ = swh_levenshtein_infix_prepared(handle_, scope.handle(), &vp, &vt, bound, distances, starts, ends, &err);
         check(status__, err);
     }
+    /// Damerau-Levenshtein distances in the optimal-string-alignment form (swh_levenshtein_osa_pairs_*): out[i] = min(osa(a_i, b_i), bound + 1);
+    /// a swap of two neighbouring symbols costs one edit, no substring is edited twice (ca / abc: 3). The shorter string of a pair holds
+    /// at most SWH_OSA_MAX_SHORTER symbols; `out` in host or device memory.
+    void osa(const DeviceScope &scope, const BytesTapeView &a, const BytesTapeView &b, uint32_t *out, uint32_t bound = SWH_UNBOUNDED) const {
+        const char *err = nullptr;
+        swh_tape_u64_t ta = a.c(), tb = b.c();
+        auto fn = utf8_ ? swh_levenshtein_utf8_osa_pairs_u64tape : swh_levenshtein_osa_pairs_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &ta, &tb, bound, out, 4, &err);
+        check(status__, err);
+    }
+    void osa(const DeviceScope &scope, const PreparedTape &a, const PreparedTape &b, uint32_t *out, uint32_t bound = SWH_UNBOUNDED) const {
+        const char *err = nullptr;
+        swh_prepared_view_t va = a.c(), vb = b.c();
+        swh_status_t status__ = swh_levenshtein_osa_pairs_prepared(handle_, scope.handle(), &va, &vb, bound, out, 4, &err);
+        check(status__, err);
+    }
+    /// The dense OSA matrix (swh_levenshtein_osa_cross_*): matrix[i][j] = osa(queries_i, candidates_j), row-major `size_t`;
+    /// `candidates == nullptr` is the symmetric self-product.
+    void osa_cross(const DeviceScope &scope, const BytesTapeView &queries, const BytesTapeView *candidates, size_t *matrix,
+                   size_t row_stride_bytes = 0) const {
+        const char *err = nullptr;
+        swh_tape_u64_t q = queries.c(), c = candidates ? candidates->c() : q;
+        auto fn = utf8_ ? swh_levenshtein_utf8_osa_cross_u64tape : swh_levenshtein_osa_cross_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &q, candidates ? &c : nullptr, matrix, row_stride_bytes, &err);
+        check(status__, err);
+    }
+    void osa_cross(const DeviceScope &scope, const PreparedTape &queries, const PreparedTape *candidates, size_t *matrix,
+                   size_t row_stride_bytes = 0) const {
+        const char *err = nullptr;
+        swh_prepared_view_t q = queries.c(), c = candidates ? candidates->c() : q;
+        swh_status_t status__ = swh_levenshtein_osa_cross_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, matrix, row_stride_bytes, &err);
+        check(status__, err);
+    }
     /// Top-k search (swh_levenshtein_topk_*): the k nearest candidates of every query, `indices` / `distances` of
     /// queries.count x k (host or device memory); rows ascending by (distance, index), only d <= bound, padded with 0xFFFFFFFF.
     void topk(const DeviceScope &scope, const BytesTapeView &queries, const BytesTapeView *candidates, size_t k, uint32_t *indices,

@@ -25,7 +25,7 @@ from . import _native as N
 __all__ = [
     "DeviceScope", "Strs", "DeviceTape", "PreparedTape", "ShardedPairs", "shard_cuts", "LevenshteinDistances", "LevenshteinDistancesUTF8",
     "NeedlemanWunschScores", "SmithWatermanScores", "edit_distance", "StringWarsError", "UNBOUNDED", "TOPK_MAX",
-    "ALIGN_MAX_CELLS", "Alignments", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches",
+    "ALIGN_MAX_CELLS", "Alignments", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "OSA_MAX_SHORTER",
 ]
 
 StringWarsError = N.StringWarsError
@@ -34,6 +34,7 @@ TOPK_MAX = N.TOPK_MAX
 ALIGN_MAX_CELLS = N.ALIGN_MAX_CELLS
 INFIX_MAX_PATTERN = N.INFIX_MAX_PATTERN
 INFIX_NONE = N.INFIX_NONE
+OSA_MAX_SHORTER = N.OSA_MAX_SHORTER
 
 
 def _pointer(obj) -> int:
@@ -572,13 +573,14 @@ class _Engine:
                 N.check(status, _keep[2])
         return call
 
-    def _pairs(self, fn32, fn64, a, b, scope, out, out_dtype, extra=()):
+    def _pairs(self, fn32, fn64, a, b, scope, out, out_dtype, extra=(), prepared_suffix="_pairs_prepared"):
+        """``fn32`` is None for a call family that only takes u64 tapes."""
         a, b = _as_tape(a), _as_tape(b)
         if len(a) != len(b):
             raise ValueError("pairwise scoring needs two collections of equal length")
         if isinstance(a, PreparedTape) or isinstance(b, PreparedTape):
-            return self._prepared("_pairs_prepared", a, b, scope, out, out_dtype, extra)
-        ta, a64, keep_a = _c_tape(a)
+            return self._prepared(prepared_suffix, a, b, scope, out, out_dtype, extra)
+        ta, a64, keep_a = _c_tape(a, want64=True if fn32 is None else None)
         tb, b64, keep_b = _c_tape(b, want64=a64 or None)
         if a64 != b64:
             ta, a64, keep_a = _c_tape(a, want64=True)
@@ -593,13 +595,13 @@ class _Engine:
         del keep_a, keep_b
         return out
 
-    def _cross(self, fn, queries, candidates, scope, out, out_dtype):
+    def _cross(self, fn, queries, candidates, scope, out, out_dtype, prepared_suffix="_cross_prepared"):
         queries = _as_tape(queries)
         candidates = queries if candidates is None else _as_tape(candidates)
         if isinstance(queries, PreparedTape) or isinstance(candidates, PreparedTape):
             if isinstance(out, np.ndarray) and (out.dtype.itemsize != 8 or out.shape != (len(queries), len(candidates))):
                 raise ValueError("out must be a (len(queries), len(candidates)) matrix of 64-bit integers")
-            return self._prepared("_cross_prepared", queries, candidates, scope, out, out_dtype, cross=True)
+            return self._prepared(prepared_suffix, queries, candidates, scope, out, out_dtype, cross=True)
         tq, _, keep_q = _c_tape(queries, want64=True)
         tc, _, keep_c = _c_tape(candidates, want64=True)
         if out is None:
@@ -770,6 +772,37 @@ class LevenshteinDistances(_Engine):
             del keep_p, keep_t
         N.check(status, err)
         return InfixMatches(distances, starts, ends)
+
+    def osa(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None, bound: Optional[int] = None, out=None):
+        """Damerau-Levenshtein distances in the optimal-string-alignment (OSA, restricted) form of every pair ``(a[i], b[i])``
+        (``swh_levenshtein_osa_pairs_*``): ``min(d, bound + 1)`` as uint32, where a swap of two neighbouring symbols costs one edit
+        and no substring is edited twice (``ab`` / ``ba``: 1; ``ca`` / ``abc``: 3, not the 2 of unrestricted Damerau-Levenshtein).
+        The shorter string of a pair holds at most ``OSA_MAX_SHORTER`` symbols. The two sides are tapes, or both ``PreparedTape``s.
+        rapidfuzz: ``OSA.distance(a[i], b[i], score_cutoff=bound)``."""
+        if scope is None:
+            raise ValueError("a DeviceScope is required")
+        a, b = _as_tape(a), _as_tape(b)
+        if isinstance(a, DeviceTape) or isinstance(b, DeviceTape):   # measured on the device, like the raw calls do internally
+            a = a if isinstance(a, PreparedTape) else PreparedTape(scope, a, utf8=self._utf8)
+            b = b if isinstance(b, PreparedTape) else PreparedTape(scope, b, utf8=self._utf8)
+        fn = N.lib.swh_levenshtein_utf8_osa_pairs_u64tape if self._utf8 else N.lib.swh_levenshtein_osa_pairs_u64tape
+        bound_value = N.UNBOUNDED if bound is None else int(bound)
+        return self._pairs(None, fn, a, b, scope, out, np.uint32, extra=(C.c_uint32(bound_value),), prepared_suffix="_osa_pairs_prepared")
+
+    def osa_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None, out=None):
+        """The dense OSA matrix ``out[i][j] = osa(queries[i], candidates[j])`` as uint64 (``swh_levenshtein_osa_cross_*``), the shape of
+        ``engine(queries, candidates, scope)``; ``candidates=None`` is the self-product (symmetric, zero diagonal).
+        rapidfuzz: ``process.cdist(queries, candidates, scorer=OSA.distance)``."""
+        if scope is None:
+            raise ValueError("a DeviceScope is required")
+        queries = _as_tape(queries)
+        candidates = None if candidates is None else _as_tape(candidates)
+        if isinstance(queries, DeviceTape) or isinstance(candidates, DeviceTape):
+            queries = queries if isinstance(queries, PreparedTape) else PreparedTape(scope, queries, utf8=self._utf8)
+            if candidates is not None and not isinstance(candidates, PreparedTape):
+                candidates = PreparedTape(scope, candidates, utf8=self._utf8)
+        fn = N.lib.swh_levenshtein_utf8_osa_cross_u64tape if self._utf8 else N.lib.swh_levenshtein_osa_cross_u64tape
+        return self._cross(fn, queries, candidates, scope, out, np.uint64, prepared_suffix="_osa_cross_prepared")
 
     def pairs_sharded(self, batch: "ShardedPairs", scope: DeviceScope, bound: Optional[int] = None, out=None):
         """One batch over every GPU of a multi-device scope; the distances come back gathered, in pair order."""

@@ -52,6 +52,8 @@ pub const ALIGN_MAX_CELLS: u64 = 1 << 30;
 pub const INFIX_MAX_PATTERN: u32 = 2048;
 /// `SWH_INFIX_NONE`: start / end of a pair whose best occurrence is over the bound.
 pub const INFIX_NONE: u32 = u32::MAX;
+/// `SWH_OSA_MAX_SHORTER`: symbols of a pair's shorter string an OSA call accepts.
+pub const OSA_MAX_SHORTER: u32 = 2048;
 /// `SWH_OP_*`: the op bytes of an alignment.
 pub const OP_MATCH: u8 = b'=';
 pub const OP_SUBST: u8 = b'X';
@@ -119,6 +121,12 @@ extern "C" {
     fn swh_levenshtein_infix_u64tape(engine: Handle, scope: Handle, patterns: *const TapeU64, texts: *const TapeU64, bound: u32, distances: *mut u32, starts: *mut u32, ends: *mut u32, error: Err) -> c_int;
     fn swh_levenshtein_utf8_infix_u64tape(engine: Handle, scope: Handle, patterns: *const TapeU64, texts: *const TapeU64, bound: u32, distances: *mut u32, starts: *mut u32, ends: *mut u32, error: Err) -> c_int;
     fn swh_levenshtein_infix_prepared(engine: Handle, scope: Handle, patterns: *const PreparedView, texts: *const PreparedView, bound: u32, distances: *mut u32, starts: *mut u32, ends: *mut u32, error: Err) -> c_int;
+    fn swh_levenshtein_osa_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, bound: u32, out: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_osa_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, bound: u32, out: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_osa_pairs_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, bound: u32, out: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_osa_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, out: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_osa_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, out: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_osa_cross_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, out: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_sharded_prepare_u32tape(scope: Handle, a: *const TapeU32, b: *const TapeU32, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_prepare_u64tape(scope: Handle, a: *const TapeU64, b: *const TapeU64, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_free(sharded: Handle) -> c_int;
@@ -470,6 +478,30 @@ impl LevenshteinDistances {
         check(unsafe { swh_levenshtein_infix_prepared(self.handle, scope.handle, &vp, &vt, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
                                                       starts.as_mut_ptr(), ends.as_mut_ptr(), &mut message) }, message)
     }
+    /// Damerau-Levenshtein distances in the optimal-string-alignment form (`swh_levenshtein_osa_*`, rapidfuzz `distance::osa`): `out[i] = min(osa(a[i], b[i]), bound + 1)`;
+    /// a swap of two neighbouring symbols costs one edit, no substring is edited twice (`ca` / `abc`: 3). The shorter string of a pair holds at most `OSA_MAX_SHORTER` symbols.
+    pub fn osa_into(&self, scope: &DeviceScope, a: &BytesTapeView<u64>, b: &BytesTapeView<u64>, bound: Option<u32>, out: &mut [u32]) -> Result<(), Error> {
+        assert!(out.len() >= a.len());
+        let (ta, tb) = (bytes_tape(a), bytes_tape(b));
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_osa_pairs_u64tape(self.handle, scope.handle, &ta, &tb, bound.unwrap_or(UNBOUNDED), out.as_mut_ptr(), 4, &mut message) }, message)
+    }
+    pub fn osa_into_prepared(&self, scope: &DeviceScope, a: &PreparedTape, b: &PreparedTape, bound: Option<u32>, out: &mut [u32]) -> Result<(), Error> {
+        assert!(out.len() >= a.len());
+        let (va, vb) = (a.view(), b.view());
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_osa_pairs_prepared(self.handle, scope.handle, &va, &vb, bound.unwrap_or(UNBOUNDED), out.as_mut_ptr(), 4, &mut message) }, message)
+    }
+    /// The dense OSA matrix, `matrix[i][j] = osa(queries[i], candidates[j])`; `candidates = None` is the symmetric self-product.
+    pub fn osa_cross_into(&self, scope: &DeviceScope, queries: &BytesTapeView<u64>, candidates: Option<&BytesTapeView<u64>>, matrix: &mut [usize]) -> Result<(), Error> {
+        let columns = candidates.map_or(queries.len(), |c| c.len());
+        assert!(matrix.len() >= queries.len() * columns);
+        let tq = bytes_tape(queries);
+        let tc = candidates.map(bytes_tape);
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_osa_cross_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64),
+                                                         matrix.as_mut_ptr(), columns * 8, &mut message) }, message)
+    }
     pub fn topk_into_prepared(&self, scope: &DeviceScope, queries: &PreparedTape, candidates: Option<&PreparedTape>, k: usize, bound: Option<u32>,
                               indices: &mut [u32], distances: &mut [u32]) -> Result<(), Error> {
         assert!(indices.len() >= queries.len() * k && distances.len() >= queries.len() * k);
@@ -548,6 +580,29 @@ impl LevenshteinDistancesUtf8 {
         let mut message = ptr::null();
         check(unsafe { swh_levenshtein_infix_prepared(self.handle, scope.handle, &vp, &vt, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
                                                       starts.as_mut_ptr(), ends.as_mut_ptr(), &mut message) }, message)
+    }
+    /// OSA distances over code points (see `LevenshteinDistances::osa_into`).
+    pub fn osa_into(&self, scope: &DeviceScope, a: &CharsTapeView<u64>, b: &CharsTapeView<u64>, bound: Option<u32>, out: &mut [u32]) -> Result<(), Error> {
+        assert!(out.len() >= a.len());
+        let (ta, tb) = (chars_tape(a), chars_tape(b));
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_utf8_osa_pairs_u64tape(self.handle, scope.handle, &ta, &tb, bound.unwrap_or(UNBOUNDED), out.as_mut_ptr(), 4, &mut message) }, message)
+    }
+    pub fn osa_into_prepared(&self, scope: &DeviceScope, a: &PreparedTape, b: &PreparedTape, bound: Option<u32>, out: &mut [u32]) -> Result<(), Error> {
+        assert!(out.len() >= a.len());
+        let (va, vb) = (a.view(), b.view());
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_osa_pairs_prepared(self.handle, scope.handle, &va, &vb, bound.unwrap_or(UNBOUNDED), out.as_mut_ptr(), 4, &mut message) }, message)
+    }
+    /// The dense OSA matrix, `matrix[i][j] = osa(queries[i], candidates[j])`; `candidates = None` is the symmetric self-product.
+    pub fn osa_cross_into(&self, scope: &DeviceScope, queries: &CharsTapeView<u64>, candidates: Option<&CharsTapeView<u64>>, matrix: &mut [usize]) -> Result<(), Error> {
+        let columns = candidates.map_or(queries.len(), |c| c.len());
+        assert!(matrix.len() >= queries.len() * columns);
+        let tq = chars_tape(queries);
+        let tc = candidates.map(chars_tape);
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_utf8_osa_cross_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64),
+                                                              matrix.as_mut_ptr(), columns * 8, &mut message) }, message)
     }
     /// Top-k search over code points (see `LevenshteinDistances::topk_into`).
     pub fn topk_into(&self, scope: &DeviceScope, queries: &CharsTapeView<u64>, candidates: Option<&CharsTapeView<u64>>, k: usize, bound: Option<u32>,

@@ -30,6 +30,7 @@ KERNELS = {
     "align_wide": ("swh::k_align_cross_wide<", ("alignshort.hip", "bp_window.hpp", "common.hpp")),
     "align_long": ("swh::k_align_cross_long<", ("alignshort.hip", "bp_window.hpp", "common.hpp")),
     "infix": ("swh::k_infix<", ("infix.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
+    "osa": ("swh::k_osa<", ("osa.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
 }
 
 
