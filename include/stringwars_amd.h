@@ -352,6 +352,57 @@ swh_status_t swh_levenshtein_utf8_osa_cross_u64tape(swh_levenshtein_t engine, sw
 swh_status_t swh_levenshtein_osa_cross_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *a,
                                                 const swh_prepared_view_t *b, size_t *out, size_t row_stride_bytes, const char **error);
 
+/* ---- LCS lengths and Indel distances: insertions and deletions only (rapidfuzz `distance.LCSseq`, `distance.Indel`, `fuzz.ratio`,
+ *      `process.cdist(..., scorer=ratio)`), unit costs only. ------------------------------------------------------------------
+ * For a of m symbols and b of n symbols, LCS(a, b) is the length of their longest common subsequence, and the Indel distance
+ * indel(a, b) = m + n - 2 LCS(a, b) is the least number of single-symbol insertions and deletions that turn a into b (a
+ * substitution counts as two: the Levenshtein distance at costs match 0, mismatch 2, open 1, extend 1). Both are symmetric.
+ * rapidfuzz's `fuzz.ratio` is the normalised form 100 (1 - indel / (m + n)) = 200 LCS / (m + n), and 100 where m + n = 0; callers
+ * compute it from the two outputs.
+ *   kitten / sitting: LCS 4 (ittn), indel 5, ratio 61.53...;  ab / ba: 1, 2, 50;  abc / abc: 3, 0, 100;
+ *   "" / "": 0, 0, 100;  abc / "": 0, 3, 0.
+ * Pairs (swh_levenshtein_lcs_pairs_*):
+ *  - a->count == b->count, else swh_invalid_argument_k;
+ *  - indel[i] = min(m + n - 2 LCS(a_i, b_i), bound + 1); bound == SWH_UNBOUNDED means no cutoff;
+ *  - lcs[i] = LCS(a_i, b_i), never clamped by the bound;
+ *  - either of `indel` and `lcs` may be NULL (that output is not wanted), not both: swh_invalid_argument_k;
+ *  - `out_stride_bytes` is the distance between consecutive results of either output (>= 4; 0 means 4); each output may be in host
+ *    or device memory, independently of the other.
+ * Cross (swh_levenshtein_lcs_cross_*):
+ *  - row-major `size_t`, indel[i][j] and lcs[i][j] of (a_i, b_j), rows `row_stride_bytes` apart in both matrices (0 means
+ *    b->count * 8), no bound: the shape of swh_levenshtein_osa_cross_*; either matrix may be NULL, not both;
+ *  - b == NULL means a x a: symmetric, the diagonal holds indel = 0 and lcs = len(a_i);
+ *  - the matrix is filled in slices of whole rows, so the call's scratch memory does not grow with the matrix.
+ * Both:
+ *  - symbols are bytes, or code points in the UTF-8 variant (invalid UTF-8 -> swh_invalid_utf8_k); the prepared variant takes
+ *    what the tapes were prepared as (both of the same kind, any mix of 32- and 64-bit offsets);
+ *  - a pair whose SHORTER string has more than SWH_LCS_MAX_SHORTER symbols makes the call return swh_unsupported_length_k before
+ *    any output is written; the message names the first such pair. The longer string has no limit beyond the tapes' own;
+ *  - an engine whose costs are not (match 0, mismatch 1, open 1, extend 1) returns swh_not_implemented_k;
+ *  - count == 0 (an empty matrix) succeeds and writes nothing.
+ * The call is synchronous on every scope: on an asynchronous or pipelined scope it first joins the outstanding work (as
+ * swh_scope_synchronize) and returns with the results visible. With profiling on, swh_scope_last_timing describes the whole call:
+ * `cells` = sum m n; `dominant_name` is its longest kernel ("lcs" for bytes, "lcs_u32" for code points). */
+#define SWH_LCS_MAX_SHORTER 2048u     /* symbols of a pair's shorter string: one wave's 64 blocks of 32 rows */
+swh_status_t swh_levenshtein_lcs_pairs_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                               const swh_tape_u64_t *b, uint32_t bound, uint32_t *indel, uint32_t *lcs,
+                                               size_t out_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_utf8_lcs_pairs_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                    const swh_tape_u64_t *b, uint32_t bound, uint32_t *indel, uint32_t *lcs,
+                                                    size_t out_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_lcs_pairs_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *a,
+                                                const swh_prepared_view_t *b, uint32_t bound, uint32_t *indel, uint32_t *lcs,
+                                                size_t out_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_lcs_cross_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                               const swh_tape_u64_t *b, size_t *indel, size_t *lcs, size_t row_stride_bytes,
+                                               const char **error);
+swh_status_t swh_levenshtein_utf8_lcs_cross_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                    const swh_tape_u64_t *b, size_t *indel, size_t *lcs, size_t row_stride_bytes,
+                                                    const char **error);
+swh_status_t swh_levenshtein_lcs_cross_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *a,
+                                                const swh_prepared_view_t *b, size_t *indel, size_t *lcs, size_t row_stride_bytes,
+                                                const char **error);
+
 /* ---- One batch over the GPUs of a multi-device scope (BASELINE config 5). --------------------------------
  * `swh_sharded_prepare_*`: HOST tapes of equal count are cut into contiguous shards balanced on the prefix sum of
  * len(a_i)*len(b_i) (DP cells, not pair counts); shard r is uploaded to and prepared on device r. The handle is the steady
@@ -457,7 +508,8 @@ swh_status_t swh_sw_pairs_sharded(swh_sw_t engine, swh_scope_t scope, swh_sharde
 const char *swh_version(void);
 /* Comma-separated capability string, e.g. "gfx950,hip,wavefront,bitparallel,banded,utf8,...";
  * "topk" when the swh_levenshtein_topk_* calls are present, "align" when the swh_levenshtein_align_* calls are,
- * "infix" when the swh_levenshtein_infix_* calls are, "osa" when the swh_levenshtein_osa_* calls are. */
+ * "infix" when the swh_levenshtein_infix_* calls are, "osa" when the swh_levenshtein_osa_* calls are,
+ * "lcs" when the swh_levenshtein_lcs_* calls are. */
 const char *swh_capabilities(void);
 
 #ifdef __cplusplus

@@ -276,6 +276,42 @@ public:
         swh_status_t status__ = swh_levenshtein_osa_cross_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, matrix, row_stride_bytes, &err);
         check(status__, err);
     }
+    /// LCS lengths and Indel distances (swh_levenshtein_lcs_pairs_*; rapidfuzz distance.LCSseq / distance.Indel): lcs[i] = LCS(a_i, b_i),
+    /// indel[i] = min(m + n - 2 LCS, bound + 1); either output may be nullptr, not both. fuzz.ratio is 200 lcs / (indel + 2 lcs) of an
+    /// unbounded call (100 where both strings are empty). The shorter string of a pair holds at most SWH_LCS_MAX_SHORTER symbols; the
+    /// outputs in host or device memory.
+    void lcs(const DeviceScope &scope, const BytesTapeView &a, const BytesTapeView &b, uint32_t *indel, uint32_t *lcs,
+             uint32_t bound = SWH_UNBOUNDED) const {
+        const char *err = nullptr;
+        swh_tape_u64_t ta = a.c(), tb = b.c();
+        auto fn = utf8_ ? swh_levenshtein_utf8_lcs_pairs_u64tape : swh_levenshtein_lcs_pairs_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &ta, &tb, bound, indel, lcs, 4, &err);
+        check(status__, err);
+    }
+    void lcs(const DeviceScope &scope, const PreparedTape &a, const PreparedTape &b, uint32_t *indel, uint32_t *lcs,
+             uint32_t bound = SWH_UNBOUNDED) const {
+        const char *err = nullptr;
+        swh_prepared_view_t va = a.c(), vb = b.c();
+        swh_status_t status__ = swh_levenshtein_lcs_pairs_prepared(handle_, scope.handle(), &va, &vb, bound, indel, lcs, 4, &err);
+        check(status__, err);
+    }
+    /// The dense Indel and LCS matrices (swh_levenshtein_lcs_cross_*), row-major `size_t`, either may be nullptr;
+    /// `candidates == nullptr` is the symmetric self-product.
+    void lcs_cross(const DeviceScope &scope, const BytesTapeView &queries, const BytesTapeView *candidates, size_t *indel, size_t *lcs,
+                   size_t row_stride_bytes = 0) const {
+        const char *err = nullptr;
+        swh_tape_u64_t q = queries.c(), c = candidates ? candidates->c() : q;
+        auto fn = utf8_ ? swh_levenshtein_utf8_lcs_cross_u64tape : swh_levenshtein_lcs_cross_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &q, candidates ? &c : nullptr, indel, lcs, row_stride_bytes, &err);
+        check(status__, err);
+    }
+    void lcs_cross(const DeviceScope &scope, const PreparedTape &queries, const PreparedTape *candidates, size_t *indel, size_t *lcs,
+                   size_t row_stride_bytes = 0) const {
+        const char *err = nullptr;
+        swh_prepared_view_t q = queries.c(), c = candidates ? candidates->c() : q;
+        swh_status_t status__ = swh_levenshtein_lcs_cross_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, indel, lcs, row_stride_bytes, &err);
+        check(status__, err);
+    }
     /// Top-k search (swh_levenshtein_topk_*): the k nearest candidates of every query, `indices` / `distances` of
     /// queries.count x k (host or device memory); rows ascending by (distance, index), only d <= bound, padded with 0xFFFFFFFF.
     void topk(const DeviceScope &scope, const BytesTapeView &queries, const BytesTapeView *candidates, size_t k, uint32_t *indices,

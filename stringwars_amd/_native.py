@@ -55,6 +55,7 @@ ALIGN_MAX_CELLS = 1 << 30   # SWH_ALIGN_MAX_CELLS: len(a_i) * len(b_i) an alignm
 INFIX_MAX_PATTERN = 2048   # SWH_INFIX_MAX_PATTERN: symbols per pattern an infix search accepts
 INFIX_NONE = 0xFFFFFFFF    # SWH_INFIX_NONE: start / end of a pair whose best occurrence is over the bound
 OSA_MAX_SHORTER = 2048     # SWH_OSA_MAX_SHORTER: symbols of a pair's shorter string an OSA call accepts
+LCS_MAX_SHORTER = 2048     # SWH_LCS_MAX_SHORTER: symbols of a pair's shorter string an LCS / Indel call accepts
 OP_MATCH, OP_SUBST, OP_DEL, OP_INS = ord("="), ord("X"), ord("D"), ord("I")   # SWH_OP_*: the bytes of an alignment's ops
 ALGORITHM_AUTO, ALGORITHM_WAVEFRONT, ALGORITHM_BITPARALLEL, ALGORITHM_TILED = 0, 1, 2, 3
 
@@ -191,6 +192,12 @@ SIGNATURES = {
     "swh_levenshtein_osa_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, C.c_size_t, _ERR]),
     "swh_levenshtein_utf8_osa_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, C.c_size_t, _ERR]),
     "swh_levenshtein_osa_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_lcs_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_utf8_lcs_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_lcs_pairs_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_uint32, _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_lcs_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_utf8_lcs_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_lcs_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, _P, C.c_size_t, _ERR]),
     "swh_version": (C.c_char_p, []),
     "swh_capabilities": (C.c_char_p, []),
     # harness header

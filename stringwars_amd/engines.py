@@ -25,7 +25,7 @@ from . import _native as N
 __all__ = [
     "DeviceScope", "Strs", "DeviceTape", "PreparedTape", "ShardedPairs", "shard_cuts", "LevenshteinDistances", "LevenshteinDistancesUTF8",
     "NeedlemanWunschScores", "SmithWatermanScores", "edit_distance", "StringWarsError", "UNBOUNDED", "TOPK_MAX",
-    "ALIGN_MAX_CELLS", "Alignments", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "OSA_MAX_SHORTER",
+    "ALIGN_MAX_CELLS", "Alignments", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "OSA_MAX_SHORTER", "LCS_MAX_SHORTER",
 ]
 
 StringWarsError = N.StringWarsError
@@ -35,6 +35,7 @@ ALIGN_MAX_CELLS = N.ALIGN_MAX_CELLS
 INFIX_MAX_PATTERN = N.INFIX_MAX_PATTERN
 INFIX_NONE = N.INFIX_NONE
 OSA_MAX_SHORTER = N.OSA_MAX_SHORTER
+LCS_MAX_SHORTER = N.LCS_MAX_SHORTER
 
 
 def _pointer(obj) -> int:
@@ -803,6 +804,90 @@ class LevenshteinDistances(_Engine):
                 candidates = PreparedTape(scope, candidates, utf8=self._utf8)
         fn = N.lib.swh_levenshtein_utf8_osa_cross_u64tape if self._utf8 else N.lib.swh_levenshtein_osa_cross_u64tape
         return self._cross(fn, queries, candidates, scope, out, np.uint64, prepared_suffix="_osa_cross_prepared")
+
+    def _lcs_call(self, a, b, scope, cross, bound, indel, lcs):
+        """One ``swh_levenshtein_lcs_*`` call. ``indel`` / ``lcs``: the array to fill, True for a fresh one, None where that output
+        is not wanted. Returns the two arrays (None where not wanted)."""
+        if scope is None:
+            raise ValueError("a DeviceScope is required")
+        a = _as_tape(a)
+        b = None if b is None else _as_tape(b)
+        if b is None and not cross:
+            raise ValueError("pairwise scoring needs two collections")
+        if not cross and len(a) != len(b):
+            raise ValueError("pairwise scoring needs two collections of equal length")
+        if isinstance(a, (DeviceTape, PreparedTape)) or isinstance(b, (DeviceTape, PreparedTape)):   # measured on the device
+            a = a if isinstance(a, PreparedTape) else PreparedTape(scope, a, utf8=self._utf8)
+            if b is not None and not isinstance(b, PreparedTape):
+                b = PreparedTape(scope, b, utf8=self._utf8)
+            if self._utf8 != a.utf8:
+                raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
+        shape = (len(a), len(a if b is None else b)) if cross else (len(a),)
+        dtype = np.uint64 if cross else np.uint32
+        outs = [np.zeros(shape, dtype=dtype) if out is True else out for out in (indel, lcs)]
+        strides = set()
+        for out in outs:
+            if isinstance(out, np.ndarray):
+                if out.dtype.itemsize != dtype().itemsize or out.shape != shape:
+                    raise ValueError("an output must be a %s array of %d-bit integers" % (shape, 8 * dtype().itemsize))
+                strides.add(out.strides[0] if (cross or out.size > 1) else 0)
+        if len(strides) > 1:
+            raise ValueError("the two outputs share one stride")
+        stride = strides.pop() if strides else 0
+        pointers = [C.c_void_p(None if out is None else _pointer(out)) for out in outs]
+        extra = () if cross else (C.c_uint32(N.UNBOUNDED if bound is None else int(bound)),)
+        kind = "cross" if cross else "pairs"
+        err = C.c_char_p()
+        if isinstance(a, PreparedTape):
+            va, vb = a.view(), (None if b is None else b.view())
+            fn = getattr(N.lib, "swh_levenshtein_lcs_%s_prepared" % kind)
+            status = fn(self._handle, scope.handle, C.byref(va), None if vb is None else C.byref(vb), *extra, *pointers, stride, C.byref(err))
+        else:
+            ta, _, keep_a = _c_tape(a, want64=True)
+            tb, _, keep_b = (None, None, None) if b is None else _c_tape(b, want64=True)
+            fn = getattr(N.lib, "swh_levenshtein_%slcs_%s_u64tape" % ("utf8_" if self._utf8 else "", kind))
+            status = fn(self._handle, scope.handle, C.byref(ta), None if tb is None else C.byref(tb), *extra, *pointers, stride, C.byref(err))
+            del keep_a, keep_b
+        N.check(status, err)
+        return outs[0], outs[1]
+
+    @staticmethod
+    def _ratio(indel, lcs):
+        """``200 L / (d + 2 L)`` as float64, 100 where both strings are empty: rapidfuzz's ``fuzz.ratio``, unrounded."""
+        twice = 2.0 * lcs.astype(np.float64)
+        total = indel.astype(np.float64) + twice
+        return np.where(total > 0, 100.0 * twice / np.where(total > 0, total, 1.0), 100.0)
+
+    def lcs(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None, out=None):
+        """The length of the longest common subsequence of every pair ``(a[i], b[i])`` as uint32 (``swh_levenshtein_lcs_pairs_*``).
+        The shorter string of a pair holds at most ``LCS_MAX_SHORTER`` symbols. The two sides are tapes, lists or ``PreparedTape``s.
+        rapidfuzz: ``distance.LCSseq.similarity(a[i], b[i])``."""
+        return self._lcs_call(a, b, scope, False, None, None, True if out is None else out)[1]
+
+    def indel(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None, bound: Optional[int] = None, out=None):
+        """The Indel distance of every pair, ``min(len(a[i]) + len(b[i]) - 2 LCS, bound + 1)`` as uint32: the edits between the two
+        strings when only insertions and deletions count (``kitten`` / ``sitting``: 5). rapidfuzz:
+        ``distance.Indel.distance(a[i], b[i], score_cutoff=bound)``."""
+        return self._lcs_call(a, b, scope, False, bound, True if out is None else out, None)[0]
+
+    def ratio(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None):
+        """rapidfuzz's ``fuzz.ratio(a[i], b[i])``, unrounded, as float64: ``100 (1 - indel / (m + n)) = 200 LCS / (m + n)``, and 100 for
+        two empty strings -- from one unbounded call with both outputs."""
+        return self._ratio(*self._lcs_call(a, b, scope, False, None, True, True))
+
+    def lcs_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None, out=None):
+        """The dense matrix ``out[i][j] = LCS(queries[i], candidates[j])`` as uint64 (``swh_levenshtein_lcs_cross_*``);
+        ``candidates=None`` is the self-product (symmetric, the diagonal holds the lengths)."""
+        return self._lcs_call(queries, candidates, scope, True, None, None, True if out is None else out)[1]
+
+    def indel_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None, out=None):
+        """The dense matrix of Indel distances as uint64; ``candidates=None`` is the self-product (symmetric, zero diagonal).
+        rapidfuzz: ``process.cdist(queries, candidates, scorer=distance.Indel.distance)``."""
+        return self._lcs_call(queries, candidates, scope, True, None, True if out is None else out, None)[0]
+
+    def ratio_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None):
+        """The dense float64 matrix of ``fuzz.ratio``: rapidfuzz's ``process.cdist(queries, candidates, scorer=fuzz.ratio)``, unrounded."""
+        return self._ratio(*self._lcs_call(queries, candidates, scope, True, None, True, True))
 
     def pairs_sharded(self, batch: "ShardedPairs", scope: DeviceScope, bound: Optional[int] = None, out=None):
         """One batch over every GPU of a multi-device scope; the distances come back gathered, in pair order."""

@@ -54,6 +54,8 @@ pub const INFIX_MAX_PATTERN: u32 = 2048;
 pub const INFIX_NONE: u32 = u32::MAX;
 /// `SWH_OSA_MAX_SHORTER`: symbols of a pair's shorter string an OSA call accepts.
 pub const OSA_MAX_SHORTER: u32 = 2048;
+/// `SWH_LCS_MAX_SHORTER`: symbols of a pair's shorter string an LCS / Indel call accepts.
+pub const LCS_MAX_SHORTER: u32 = 2048;
 /// `SWH_OP_*`: the op bytes of an alignment.
 pub const OP_MATCH: u8 = b'=';
 pub const OP_SUBST: u8 = b'X';
@@ -127,6 +129,12 @@ extern "C" {
     fn swh_levenshtein_osa_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, out: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_utf8_osa_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, out: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_osa_cross_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, out: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_lcs_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, bound: u32, indel: *mut u32, lcs: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_lcs_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, bound: u32, indel: *mut u32, lcs: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_lcs_pairs_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, bound: u32, indel: *mut u32, lcs: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_lcs_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, indel: *mut usize, lcs: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_lcs_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, indel: *mut usize, lcs: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_lcs_cross_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, indel: *mut usize, lcs: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_sharded_prepare_u32tape(scope: Handle, a: *const TapeU32, b: *const TapeU32, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_prepare_u64tape(scope: Handle, a: *const TapeU64, b: *const TapeU64, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_free(sharded: Handle) -> c_int;
@@ -502,6 +510,31 @@ impl LevenshteinDistances {
         check(unsafe { swh_levenshtein_osa_cross_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64),
                                                          matrix.as_mut_ptr(), columns * 8, &mut message) }, message)
     }
+    /// LCS lengths and Indel distances (`swh_levenshtein_lcs_*`, rapidfuzz `distance::lcs_seq` / `distance::indel`): `lcs[i] = LCS(a[i], b[i])`, `indel[i] = min(m + n - 2 LCS, bound + 1)`; one of the two outputs may be `None`. `fuzz::ratio` is `200 lcs / (indel + 2 lcs)`. The shorter string of a pair holds at most `LCS_MAX_SHORTER` symbols.
+    pub fn lcs_into(&self, scope: &DeviceScope, a: &BytesTapeView<u64>, b: &BytesTapeView<u64>, bound: Option<u32>, indel: Option<&mut [u32]>, lcs: Option<&mut [u32]>) -> Result<(), Error> {
+        assert!(indel.as_ref().map_or(true, |o| o.len() >= a.len()) && lcs.as_ref().map_or(true, |o| o.len() >= a.len()));
+        let (ta, tb) = (bytes_tape(a), bytes_tape(b));
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_lcs_pairs_u64tape(self.handle, scope.handle, &ta, &tb, bound.unwrap_or(UNBOUNDED), indel.map_or(ptr::null_mut(), |o| o.as_mut_ptr()),
+                          lcs.map_or(ptr::null_mut(), |o| o.as_mut_ptr()), 4, &mut message) }, message)
+    }
+    pub fn lcs_into_prepared(&self, scope: &DeviceScope, a: &PreparedTape, b: &PreparedTape, bound: Option<u32>, indel: Option<&mut [u32]>, lcs: Option<&mut [u32]>) -> Result<(), Error> {
+        assert!(indel.as_ref().map_or(true, |o| o.len() >= a.len()) && lcs.as_ref().map_or(true, |o| o.len() >= a.len()));
+        let (va, vb) = (a.view(), b.view());
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_lcs_pairs_prepared(self.handle, scope.handle, &va, &vb, bound.unwrap_or(UNBOUNDED), indel.map_or(ptr::null_mut(), |o| o.as_mut_ptr()),
+                                                          lcs.map_or(ptr::null_mut(), |o| o.as_mut_ptr()), 4, &mut message) }, message)
+    }
+    /// The dense Indel and LCS matrices of `queries` x `candidates`, either wanted or not; `candidates = None` is the symmetric self-product.
+    pub fn lcs_cross_into(&self, scope: &DeviceScope, queries: &BytesTapeView<u64>, candidates: Option<&BytesTapeView<u64>>, indel: Option<&mut [usize]>, lcs: Option<&mut [usize]>) -> Result<(), Error> {
+        let columns = candidates.map_or(queries.len(), |c| c.len());
+        assert!(indel.as_ref().map_or(true, |o| o.len() >= queries.len() * columns) && lcs.as_ref().map_or(true, |o| o.len() >= queries.len() * columns));
+        let tq = bytes_tape(queries);
+        let tc = candidates.map(bytes_tape);
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_lcs_cross_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64), indel.map_or(ptr::null_mut(), |o| o.as_mut_ptr()),
+                          lcs.map_or(ptr::null_mut(), |o| o.as_mut_ptr()), columns * 8, &mut message) }, message)
+    }
     pub fn topk_into_prepared(&self, scope: &DeviceScope, queries: &PreparedTape, candidates: Option<&PreparedTape>, k: usize, bound: Option<u32>,
                               indices: &mut [u32], distances: &mut [u32]) -> Result<(), Error> {
         assert!(indices.len() >= queries.len() * k && distances.len() >= queries.len() * k);
@@ -603,6 +636,31 @@ impl LevenshteinDistancesUtf8 {
         let mut message = ptr::null();
         check(unsafe { swh_levenshtein_utf8_osa_cross_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64),
                                                               matrix.as_mut_ptr(), columns * 8, &mut message) }, message)
+    }
+    /// LCS lengths and Indel distances over code points (see `LevenshteinDistances::lcs_into`).
+    pub fn lcs_into(&self, scope: &DeviceScope, a: &CharsTapeView<u64>, b: &CharsTapeView<u64>, bound: Option<u32>, indel: Option<&mut [u32]>, lcs: Option<&mut [u32]>) -> Result<(), Error> {
+        assert!(indel.as_ref().map_or(true, |o| o.len() >= a.len()) && lcs.as_ref().map_or(true, |o| o.len() >= a.len()));
+        let (ta, tb) = (chars_tape(a), chars_tape(b));
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_utf8_lcs_pairs_u64tape(self.handle, scope.handle, &ta, &tb, bound.unwrap_or(UNBOUNDED), indel.map_or(ptr::null_mut(), |o| o.as_mut_ptr()),
+                          lcs.map_or(ptr::null_mut(), |o| o.as_mut_ptr()), 4, &mut message) }, message)
+    }
+    pub fn lcs_into_prepared(&self, scope: &DeviceScope, a: &PreparedTape, b: &PreparedTape, bound: Option<u32>, indel: Option<&mut [u32]>, lcs: Option<&mut [u32]>) -> Result<(), Error> {
+        assert!(indel.as_ref().map_or(true, |o| o.len() >= a.len()) && lcs.as_ref().map_or(true, |o| o.len() >= a.len()));
+        let (va, vb) = (a.view(), b.view());
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_lcs_pairs_prepared(self.handle, scope.handle, &va, &vb, bound.unwrap_or(UNBOUNDED), indel.map_or(ptr::null_mut(), |o| o.as_mut_ptr()),
+                                                          lcs.map_or(ptr::null_mut(), |o| o.as_mut_ptr()), 4, &mut message) }, message)
+    }
+    /// The dense Indel and LCS matrices of `queries` x `candidates`, either wanted or not; `candidates = None` is the symmetric self-product.
+    pub fn lcs_cross_into(&self, scope: &DeviceScope, queries: &CharsTapeView<u64>, candidates: Option<&CharsTapeView<u64>>, indel: Option<&mut [usize]>, lcs: Option<&mut [usize]>) -> Result<(), Error> {
+        let columns = candidates.map_or(queries.len(), |c| c.len());
+        assert!(indel.as_ref().map_or(true, |o| o.len() >= queries.len() * columns) && lcs.as_ref().map_or(true, |o| o.len() >= queries.len() * columns));
+        let tq = chars_tape(queries);
+        let tc = candidates.map(chars_tape);
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_utf8_lcs_cross_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64), indel.map_or(ptr::null_mut(), |o| o.as_mut_ptr()),
+                          lcs.map_or(ptr::null_mut(), |o| o.as_mut_ptr()), columns * 8, &mut message) }, message)
     }
     /// Top-k search over code points (see `LevenshteinDistances::topk_into`).
     pub fn topk_into(&self, scope: &DeviceScope, queries: &CharsTapeView<u64>, candidates: Option<&CharsTapeView<u64>>, k: usize, bound: Option<u32>,

@@ -31,6 +31,7 @@ KERNELS = {
     "align_long": ("swh::k_align_cross_long<", ("alignshort.hip", "bp_window.hpp", "common.hpp")),
     "infix": ("swh::k_infix<", ("infix.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
     "osa": ("swh::k_osa<", ("osa.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
+    "lcs": ("swh::k_lcs<", ("lcs.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
 }
 
 
