@@ -403,6 +403,72 @@ swh_status_t swh_levenshtein_lcs_cross_prepared(swh_levenshtein_t engine, swh_sc
                                                 const swh_prepared_view_t *b, size_t *indel, size_t *lcs, size_t row_stride_bytes,
                                                 const char **error);
 
+/* ---- Jaro and Jaro-Winkler similarities (rapidfuzz `distance.Jaro` / `distance.JaroWinkler`, jellyfish `jaro_similarity` /
+ *      `jaro_winkler_similarity`), unit-cost engines only. The calls return the integer counts; callers evaluate the two
+ *      similarity expressions below. ---------------------------------------------------------------------------------------------
+ * Let a hold m symbols and b hold n symbols (bytes, or code points in the UTF-8 variant).
+ *  - Search range: R = max(0, max(m, n) / 2 - 1), integer division.
+ *  - Matching: a's symbols are taken in order, i = 0 .. m - 1. For each, the smallest j with max(0, i - R) <= j <= min(n - 1, i + R),
+ *    b[j] == a[i] and b[j] not yet flagged is looked for; if there is one, b[j] is flagged and a[i] is matched. This is the order
+ *    of Winkler's strcmp95 and of jellyfish: the outer loop runs over the FIRST string. The definition is one-sided -- a drives, b
+ *    is flagged -- and the library never swaps the two sides of a pair.
+ *  - Counts: M is the number of matches; h is the number of k < M at which the k-th matched symbol of a (in a's order) differs
+ *    from the k-th flagged symbol of b (in b's order); t = h / 2, floored (h can be odd: bbcaba / cab gives M = 3, h = 3, t = 1);
+ *    l is the length of the common prefix of a and b, at most 4.
+ *  - Similarities, in IEEE double, evaluated exactly as written:
+ *        jaro = 1.0 if m = n = 0;  0.0 if M = 0;  otherwise (M / m + M / n + (M - t) / M) / 3.0
+ *        jaro_winkler = jaro + l * p * (1.0 - jaro) if jaro > 0.7, else jaro;  p the prefix weight, 0 <= p <= 0.25, usually 0.1
+ *      a / b                    M  t  jaro                 jaro_winkler (p = 0.1)
+ *      MARTHA / MARHTA          6  1  0.9444444444444445   0.9611111111111111
+ *      DWAYNE / DUANE           4  0  0.8222222222222223   0.8400000000000001
+ *      DIXON / DICKSONX         4  0  0.7666666666666666   0.8133333333333332
+ *      CRATE / TRACE            3  0  0.7333333333333334   0.7333333333333334
+ *      JELLYFISH / SMELLYFISH   8  0  0.8962962962962964   0.8962962962962964  (l = 0)
+ *      ab / ba                  0  0  0.0                  0.0                 (R = 0)
+ *      a / a                    1  0  1.0                  1.0
+ *      a / b                    0  0  0.0                  0.0
+ *      "" / ""                  0  0  1.0                  1.0
+ * Pairs (swh_levenshtein_jaro_pairs_*):
+ *  - a->count == b->count, else swh_invalid_argument_k;
+ *  - matches[i] = M, transpositions[i] = t, prefix[i] = l of (a_i, b_i);
+ *  - any of the three outputs may be NULL (that output is not wanted), not all: swh_invalid_argument_k;
+ *  - `out_stride_bytes` is the distance between consecutive results of every output (a multiple of 4; 0 means 4; anything else is
+ *    swh_invalid_argument_k); each output may be in host or device memory, independently of the others.
+ * Cross (swh_levenshtein_jaro_cross_*):
+ *  - row-major `size_t`, [i][j] of (a_i, b_j) -- a_i drives, b_j is flagged --, rows `row_stride_bytes` apart in all matrices (a
+ *    multiple of 8, at least b->count * 8; 0 means b->count * 8); any matrix may be NULL, not all;
+ *  - b == NULL means a x a: the diagonal holds M = len(a_i), t = 0, l = min(len(a_i), 4);
+ *  - the matrix is filled in slices of whole rows, so the call's scratch memory does not grow with the matrix.
+ * Both:
+ *  - symbols are bytes, or code points in the UTF-8 variant (invalid UTF-8 -> swh_invalid_utf8_k); the prepared variant takes
+ *    what the tapes were prepared as (both of the same kind, any mix of 32- and 64-bit offsets);
+ *  - a pair either of whose strings has more than SWH_JARO_MAX_LENGTH symbols makes the call return swh_unsupported_length_k before
+ *    any output is written; the message names the first such pair and both lengths;
+ *  - an engine whose costs are not (match 0, mismatch 1, open 1, extend 1) returns swh_not_implemented_k;
+ *  - count == 0 (an empty matrix) succeeds and writes nothing.
+ * The call is synchronous on every scope: on an asynchronous or pipelined scope it first joins the outstanding work (as
+ * swh_scope_synchronize) and returns with the results visible. With profiling on, swh_scope_last_timing describes the whole call:
+ * `cells` = sum m n; `dominant_name` is its longest kernel ("jaro" for bytes, "jaro_u32" for code points). */
+#define SWH_JARO_MAX_LENGTH 2048u     /* symbols of either string of a pair: one wave's 64 blocks of 32 rows */
+swh_status_t swh_levenshtein_jaro_pairs_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                const swh_tape_u64_t *b, uint32_t *matches, uint32_t *transpositions,
+                                                uint32_t *prefix, size_t out_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_utf8_jaro_pairs_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                     const swh_tape_u64_t *b, uint32_t *matches, uint32_t *transpositions,
+                                                     uint32_t *prefix, size_t out_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_jaro_pairs_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *a,
+                                                 const swh_prepared_view_t *b, uint32_t *matches, uint32_t *transpositions,
+                                                 uint32_t *prefix, size_t out_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_jaro_cross_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                const swh_tape_u64_t *b, size_t *matches, size_t *transpositions, size_t *prefix,
+                                                size_t row_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_utf8_jaro_cross_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                     const swh_tape_u64_t *b, size_t *matches, size_t *transpositions, size_t *prefix,
+                                                     size_t row_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_jaro_cross_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *a,
+                                                 const swh_prepared_view_t *b, size_t *matches, size_t *transpositions, size_t *prefix,
+                                                 size_t row_stride_bytes, const char **error);
+
 /* ---- One batch over the GPUs of a multi-device scope (BASELINE config 5). --------------------------------
  * `swh_sharded_prepare_*`: HOST tapes of equal count are cut into contiguous shards balanced on the prefix sum of
  * len(a_i)*len(b_i) (DP cells, not pair counts); shard r is uploaded to and prepared on device r. The handle is the steady
@@ -509,7 +575,7 @@ const char *swh_version(void);
 /* Comma-separated capability string, e.g. "gfx950,hip,wavefront,bitparallel,banded,utf8,...";
  * "topk" when the swh_levenshtein_topk_* calls are present, "align" when the swh_levenshtein_align_* calls are,
  * "infix" when the swh_levenshtein_infix_* calls are, "osa" when the swh_levenshtein_osa_* calls are,
- * "lcs" when the swh_levenshtein_lcs_* calls are. */
+ * "lcs" when the swh_levenshtein_lcs_* calls are, "jaro" when the swh_levenshtein_jaro_* calls are. */
 const char *swh_capabilities(void);
 
 #ifdef __cplusplus

@@ -312,6 +312,44 @@ public:
         swh_status_t status__ = swh_levenshtein_lcs_cross_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, indel, lcs, row_stride_bytes, &err);
         check(status__, err);
     }
+    /// Jaro / Jaro-Winkler counts (swh_levenshtein_jaro_pairs_*; rapidfuzz distance.Jaro / distance.JaroWinkler): matches[i] = M,
+    /// transpositions[i] = t, prefix[i] = the common prefix of at most four symbols of (a_i, b_i) -- a_i drives the matching, b_i is
+    /// flagged; any output may be nullptr, not all. jaro = (M / m + M / n + (M - t) / M) / 3 (1 for two empty strings, 0 where M = 0),
+    /// jaro_winkler = jaro + prefix * p * (1 - jaro) where jaro > 0.7. Neither string holds more than SWH_JARO_MAX_LENGTH symbols;
+    /// the outputs in host or device memory.
+    void jaro(const DeviceScope &scope, const BytesTapeView &a, const BytesTapeView &b, uint32_t *matches, uint32_t *transpositions,
+              uint32_t *prefix) const {
+        const char *err = nullptr;
+        swh_tape_u64_t ta = a.c(), tb = b.c();
+        auto fn = utf8_ ? swh_levenshtein_utf8_jaro_pairs_u64tape : swh_levenshtein_jaro_pairs_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &ta, &tb, matches, transpositions, prefix, 4, &err);
+        check(status__, err);
+    }
+    void jaro(const DeviceScope &scope, const PreparedTape &a, const PreparedTape &b, uint32_t *matches, uint32_t *transpositions,
+              uint32_t *prefix) const {
+        const char *err = nullptr;
+        swh_prepared_view_t va = a.c(), vb = b.c();
+        swh_status_t status__ = swh_levenshtein_jaro_pairs_prepared(handle_, scope.handle(), &va, &vb, matches, transpositions, prefix, 4, &err);
+        check(status__, err);
+    }
+    /// The dense matrices of the three counts (swh_levenshtein_jaro_cross_*), row-major `size_t`, any may be nullptr, not all;
+    /// `candidates == nullptr` is the self-product.
+    void jaro_cross(const DeviceScope &scope, const BytesTapeView &queries, const BytesTapeView *candidates, size_t *matches,
+                    size_t *transpositions, size_t *prefix, size_t row_stride_bytes = 0) const {
+        const char *err = nullptr;
+        swh_tape_u64_t q = queries.c(), c = candidates ? candidates->c() : q;
+        auto fn = utf8_ ? swh_levenshtein_utf8_jaro_cross_u64tape : swh_levenshtein_jaro_cross_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &q, candidates ? &c : nullptr, matches, transpositions, prefix, row_stride_bytes, &err);
+        check(status__, err);
+    }
+    void jaro_cross(const DeviceScope &scope, const PreparedTape &queries, const PreparedTape *candidates, size_t *matches,
+                    size_t *transpositions, size_t *prefix, size_t row_stride_bytes = 0) const {
+        const char *err = nullptr;
+        swh_prepared_view_t q = queries.c(), c = candidates ? candidates->c() : q;
+        swh_status_t status__ = swh_levenshtein_jaro_cross_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, matches, transpositions,
+                                                                    prefix, row_stride_bytes, &err);
+        check(status__, err);
+    }
     /// Top-k search (swh_levenshtein_topk_*): the k nearest candidates of every query, `indices` / `distances` of
     /// queries.count x k (host or device memory); rows ascending by (distance, index), only d <= bound, padded with 0xFFFFFFFF.
     void topk(const DeviceScope &scope, const BytesTapeView &queries, const BytesTapeView *candidates, size_t k, uint32_t *indices,

@@ -17,6 +17,7 @@
 #include "infix.hpp"
 #include "osa.hpp"
 #include "lcs.hpp"
+#include "jaro.hpp"
 #include <algorithm>
 #include <mutex>
 #include <utility>
@@ -1175,7 +1176,7 @@ static void free_align_scratch(const Scope *scope) {
 extern "C" {
 
 const char *swh_version(void) { return "0.1.0"; }
-const char *swh_capabilities(void) { return "gfx950,hip,wavefront,bitparallel,tiled,banded,utf8,bounded,nw-linear,nw-affine,sw-linear,sw-affine,cross,prepared,topk,align,infix,osa,lcs,multi-gpu-rccl"; }
+const char *swh_capabilities(void) { return "gfx950,hip,wavefront,bitparallel,tiled,banded,utf8,bounded,nw-linear,nw-affine,sw-linear,sw-affine,cross,prepared,topk,align,infix,osa,lcs,jaro,multi-gpu-rccl"; }
 
 static swh_status_t scope_init(int device, void *stream, bool borrow, swh_scope_t *out, const char **error) {
     if (!out) return fail(error, swh_invalid_argument_k, "null scope pointer");
@@ -2906,6 +2907,240 @@ swh_status_t swh_levenshtein_utf8_lcs_cross_u64tape(swh_levenshtein_t e, swh_sco
 swh_status_t swh_levenshtein_lcs_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
                                                 size_t *indel, size_t *lcs, size_t row_stride, const char **error) {
     return lcs_prepared(e, s, a, b, true, SWH_UNBOUNDED, indel, lcs, row_stride, error);
+}
+
+// ---- Jaro and Jaro-Winkler counts (jaro.hip) -------------------------------------------------------------------------------------------
+// The phases of the LCS calls on a planner of their own: k_jaro_sizes (jaro.hip) measures the pairs and cuts them into work items by
+// the blocks of b; one read-back of the measurements decides the errors before any output is written; k_jaro counts the items' pairs
+// and writes the matches, the transpositions, the common prefix or any subset of them. A cross-product runs in slices of whole rows
+// of about kJaroChunkPairs pairs, measured as a whole first when there is more than one slice. STRINGWARS_AMD_JARO_CHUNK_PAIRS=n (test
+// library) lowers the slice. An output that lives on the host is staged slice by slice, each on its own. The scratch is the scope's
+// alignment scratch: the calls are synchronous, and they learn nothing into the scope.
+constexpr uint64_t kJaroChunkPairs = (uint64_t)1 << 21;
+static uint64_t jaro_chunk_pairs() {
+    const char *hook = test_hook("STRINGWARS_AMD_JARO_CHUNK_PAIRS");
+    const uint64_t pairs = hook ? (uint64_t)atoll(hook) : kJaroChunkPairs;
+    return std::max<uint64_t>(1, std::min<uint64_t>(pairs, kJaroChunkPairs));
+}
+
+struct JaroRequest {
+    const Prepared *pa, *pb;
+    size_t a_first, a_count, b_first, b_count;
+    bool cross;
+    void *outs[3];   // matches, transpositions, prefix: any may be null
+    size_t stride;   // bytes between consecutive results (pairs) or rows (cross), of every output
+};
+
+static swh_status_t jaro_run(Scope *scope, const JaroRequest &r, const char **error) {
+    harvest_timing(scope, false);
+    scope->stamps_used = 0;
+    scope->last_timing = swh_timing_t{};
+    const uint64_t na = r.a_count, nb = r.b_count;
+    if (na == 0 || nb == 0) return swh_success_k;
+    if (r.cross && na > ((uint64_t)1 << 40) / nb) return fail(error, swh_unsupported_length_k, "more than 2^40 pairs in one call");
+    const uint64_t total = r.cross ? na * nb : na;
+    try {
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        bool stage[3];
+        size_t staged_count = 0, wanted = 0;
+        for (int k = 0; k < 3; ++k) {
+            stage[k] = r.outs[k] && !is_device_pointer(r.outs[k]);
+            staged_count += stage[k] ? 1 : 0;
+            wanted += r.outs[k] ? 1 : 0;
+        }
+        const bool cp = r.pa->utf8;
+        OsaTapes t{};
+        t.a = prepared_view(r.pa, cp, r.a_first, na);
+        t.b = prepared_view(r.pb, cp, r.b_first, nb);
+        t.a_off64 = cp ? 1 : r.pa->off64;
+        t.b_off64 = cp ? 1 : r.pb->off64;
+        t.cp = cp ? 1 : 0;
+        t.nb = r.cross ? nb : 0;
+
+        // slices: all pairs of a pairwise call; whole rows of a cross-product
+        const uint64_t rows_per_slice = r.cross ? std::max<uint64_t>(1, jaro_chunk_pairs() / nb) : na;
+        const uint64_t slices = (na + rows_per_slice - 1) / rows_per_slice;
+        const uint64_t slice_pairs = r.cross ? std::min<uint64_t>(rows_per_slice, na) * nb : na;
+        const size_t width = r.cross ? 8 : 4;
+
+        AlignScratch *sc_entry;
+        {
+            std::lock_guard<std::mutex> hold(g_align_scratch_lock);
+            sc_entry = &g_align_scratch[scope];
+        }
+        // sizes | items | the slice's results (one array per output that lives on the host)
+        const size_t need = pad(sizeof(OsaSizes)) + pad(slice_pairs * sizeof(OsaItem)) + staged_count * pad(slice_pairs * width);
+        ensure(sc_entry->buf, sc_entry->bytes, need);
+        Carver sc{sc_entry->buf, 0, sc_entry->bytes};
+        OsaSizes *sizes = sc.take<OsaSizes>(1);
+        OsaItem *items = sc.take<OsaItem>(slice_pairs);
+        char *staged[3];
+        for (int k = 0; k < 3; ++k) staged[k] = stage[k] ? sc.take<char>(slice_pairs * width) : nullptr;
+
+        // measures pairs [row0 .. row0 + rows) x nb (or all pairs of a pairwise call) and, with `cut`, cuts them into `items`
+        auto measure = [&](uint64_t row0, uint64_t pairs, bool cut) {
+            OsaSizes init{};
+            init.first_oversize = ~0ull;
+            SWH_HIP_CHECK(hipMemcpyAsync(sizes, &init, sizeof init, hipMemcpyHostToDevice, stream));
+            t.row0 = row0; t.count = pairs;
+            launch_jaro_sizes(scope, t, sizes, cut ? items : nullptr);
+            OsaSizes got{};
+            SWH_HIP_CHECK(hipMemcpyAsync(&got, sizes, sizeof got, hipMemcpyDeviceToHost, stream));
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            return got;
+        };
+        const OsaSizes whole = measure(0, total, slices == 1);
+        if (whole.first_oversize != ~0ull) {
+            const size_t i = (size_t)(r.cross ? whole.first_oversize / nb : whole.first_oversize);
+            const size_t j = (size_t)(r.cross ? whole.first_oversize % nb : whole.first_oversize);
+            const uint64_t la = read_offset(t.a.offsets, t.a_off64, i + 1, true, stream) - read_offset(t.a.offsets, t.a_off64, i, true, stream);
+            const uint64_t lb = read_offset(t.b.offsets, t.b_off64, j + 1, true, stream) - read_offset(t.b.offsets, t.b_off64, j, true, stream);
+            scope->stamps_used = 0;
+            if (r.cross)
+                return fail(error, swh_unsupported_length_k, "pair (%zu, %zu): %llu x %llu symbols, a string exceeds SWH_JARO_MAX_LENGTH (2048)",
+                            i, j, (unsigned long long)la, (unsigned long long)lb);
+            return fail(error, swh_unsupported_length_k, "pair %zu: %llu x %llu symbols, a string exceeds SWH_JARO_MAX_LENGTH (2048)", i,
+                        (unsigned long long)la, (unsigned long long)lb);
+        }
+
+        JaroRun run{};
+        run.items = items;
+        run.wide = !cp && whole.a_total >= 16 && whole.b_total >= 16;
+        // the kernel writes its outputs at one stride: the caller's for those written in place, the packed one for those that are
+        // staged; a call with outputs of both kinds runs the slice once per kind
+        for (uint64_t q = 0; q < slices; ++q) {
+            const uint64_t row0 = q * rows_per_slice, rows = std::min<uint64_t>(rows_per_slice, na - row0);
+            const uint64_t pairs = r.cross ? rows * nb : na;
+            run.item_count = slices == 1 ? whole.items : measure(row0, pairs, true).items;
+            t.row0 = row0; t.count = pairs;
+            for (int packed = 0; packed < 2; ++packed) {
+                char *where[3];
+                bool any = false;
+                for (int k = 0; k < 3; ++k) {
+                    where[k] = nullptr;
+                    if (!r.outs[k] || stage[k] != (packed == 1)) continue;
+                    where[k] = packed ? staged[k] : (char *)r.outs[k] + (r.cross ? row0 * r.stride : 0);
+                    any = true;
+                }
+                if (!any) continue;
+                run.matches = where[0]; run.transpositions = where[1]; run.prefix = where[2];
+                run.stride = packed ? (r.cross ? nb * 8 : 4) : r.stride;
+                launch_jaro(scope, t, run);
+            }
+            for (int k = 0; k < 3; ++k) {
+                if (!stage[k]) continue;
+                if (r.cross)
+                    SWH_HIP_CHECK(hipMemcpy2DAsync((char *)r.outs[k] + row0 * r.stride, r.stride, staged[k], nb * 8, nb * 8, rows, hipMemcpyDeviceToHost, stream));
+                else if (r.stride == 4)
+                    SWH_HIP_CHECK(hipMemcpyAsync(r.outs[k], staged[k], pairs * 4, hipMemcpyDeviceToHost, stream));
+                else
+                    SWH_HIP_CHECK(hipMemcpy2DAsync(r.outs[k], r.stride, staged[k], 4, 4, pairs, hipMemcpyDeviceToHost, stream));
+            }
+            if (staged_count) SWH_HIP_CHECK(hipStreamSynchronize(stream));   // the next slice reuses the staging
+        }
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        if (scope->profiling && scope->stamps_used) {
+            collect_timing(scope);
+            add_to_totals(scope->totals, scope->last_timing);
+        }
+        scope->stamps_used = 0;
+        scope->last_timing.cells = whole.cells;
+        scope->last_timing.bytes = (cp ? 4 : 1) * whole.symbols + (na + nb + 2) * 8 + total * width * wanted;
+        return swh_success_k;
+    } catch (const HipFailure &f) {
+        return fail_hip(error, f);
+    } catch (const std::bad_alloc &) {
+        return fail(error, swh_bad_alloc_k, "host allocation failed");
+    }
+}
+
+static swh_status_t jaro_checks(swh_levenshtein_t e, size_t a_count, size_t b_count, bool cross, void *const outs[3], size_t &stride,
+                                const char **error) {
+    const Engine *engine = (const Engine *)e;
+    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (!engine->unit_costs)
+        return fail(error, swh_not_implemented_k, "Jaro and Jaro-Winkler counts are called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)");
+    if (!cross && a_count != b_count) return fail(error, swh_invalid_argument_k, "a and b must hold the same number of strings");
+    if (!outs[0] && !outs[1] && !outs[2])
+        return fail(error, swh_invalid_argument_k, "null output pointers: one of matches, transpositions and prefix is needed");
+    if (cross) {
+        if (!stride) stride = b_count * 8;
+        if (stride % 8) return fail(error, swh_invalid_argument_k, "row_stride_bytes must be 0 or a multiple of 8");
+        if (stride < b_count * 8) return fail(error, swh_invalid_argument_k, "row_stride_bytes too small");
+    } else {
+        if (!stride) stride = 4;
+        if (stride % 4) return fail(error, swh_invalid_argument_k, "out_stride_bytes must be 0 or a multiple of 4");
+    }
+    return swh_success_k;
+}
+
+static swh_status_t jaro_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, bool utf8, bool cross,
+                               void *matches, void *transpositions, void *prefix, size_t stride, const char **error) {
+    swh_status_t status = infix_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    if (!a || (!b && !cross)) return fail(error, swh_invalid_argument_k, "null tape");
+    const swh_tape_u64_t *bb = b ? b : a;
+    void *const outs[3] = {matches, transpositions, prefix};
+    status = jaro_checks(e, a->count, bb->count, cross, outs, stride, error);
+    if (status != swh_success_k) return status;
+    Scope *scope = (Scope *)s;
+    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
+    HoldSynchronous mode(scope);
+    JaroRequest r{nullptr, nullptr, 0, a->count, 0, bb->count, cross, {matches, transpositions, prefix}, stride};
+    if (a->count == 0 || bb->count == 0) return jaro_run(scope, r, error);
+    // raw tapes are made resident, measured and (UTF-8) validated and decoded for the call, as for the LCS calls
+    PreparedOwner pa, pb;
+    status = prepare_tape(scope, SWH_TAPE(a, 1), utf8, (swh_prepared_t *)&pa.p, error);
+    if (status != swh_success_k) return status;
+    if (b) {
+        status = prepare_tape(scope, SWH_TAPE(b, 1), utf8, (swh_prepared_t *)&pb.p, error);
+        if (status != swh_success_k) return status;
+    }
+    r.pa = pa.p; r.pb = b ? pb.p : pa.p;
+    return jaro_run(scope, r, error);
+}
+static swh_status_t jaro_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b, bool cross,
+                                  void *matches, void *transpositions, void *prefix, size_t stride, const char **error) {
+    if (swh_status_t status = infix_handles(e, s, error)) return status;
+    if (!a || !a->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
+    const swh_prepared_view_t *bb = (b && b->tape) ? b : (cross ? a : nullptr);
+    if (!bb) return fail(error, swh_invalid_argument_k, "null prepared view");
+    if (!view_fits(a) || !view_fits(bb)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
+    const Prepared *pa = (const Prepared *)a->tape, *pb = (const Prepared *)bb->tape;
+    void *const outs[3] = {matches, transpositions, prefix};
+    swh_status_t status = jaro_checks(e, a->count, bb->count, cross, outs, stride, error);
+    if (status != swh_success_k) return status;
+    Scope *scope = (Scope *)s;
+    if ((status = check_prepared_pair(scope, pa, pb, error)) != swh_success_k) return status;
+    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
+    HoldSynchronous mode(scope);
+    JaroRequest r{pa, pb, a->first, a->count, bb->first, bb->count, cross, {matches, transpositions, prefix}, stride};
+    return jaro_run(scope, r, error);
+}
+swh_status_t swh_levenshtein_jaro_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                uint32_t *matches, uint32_t *transpositions, uint32_t *prefix, size_t stride, const char **error) {
+    return jaro_tapes(e, s, a, b, false, false, matches, transpositions, prefix, stride, error);
+}
+swh_status_t swh_levenshtein_utf8_jaro_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                     uint32_t *matches, uint32_t *transpositions, uint32_t *prefix, size_t stride, const char **error) {
+    return jaro_tapes(e, s, a, b, true, false, matches, transpositions, prefix, stride, error);
+}
+swh_status_t swh_levenshtein_jaro_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                 uint32_t *matches, uint32_t *transpositions, uint32_t *prefix, size_t stride, const char **error) {
+    return jaro_prepared(e, s, a, b, false, matches, transpositions, prefix, stride, error);
+}
+swh_status_t swh_levenshtein_jaro_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
+    return jaro_tapes(e, s, a, b, false, true, matches, transpositions, prefix, row_stride, error);
+}
+swh_status_t swh_levenshtein_utf8_jaro_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                     size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
+    return jaro_tapes(e, s, a, b, true, true, matches, transpositions, prefix, row_stride, error);
+}
+swh_status_t swh_levenshtein_jaro_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                 size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
+    return jaro_prepared(e, s, a, b, true, matches, transpositions, prefix, row_stride, error);
 }
 
 }  // extern "C"

@@ -26,6 +26,7 @@ __all__ = [
     "DeviceScope", "Strs", "DeviceTape", "PreparedTape", "ShardedPairs", "shard_cuts", "LevenshteinDistances", "LevenshteinDistancesUTF8",
     "NeedlemanWunschScores", "SmithWatermanScores", "edit_distance", "StringWarsError", "UNBOUNDED", "TOPK_MAX",
     "ALIGN_MAX_CELLS", "Alignments", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "OSA_MAX_SHORTER", "LCS_MAX_SHORTER",
+    "JARO_MAX_LENGTH",
 ]
 
 StringWarsError = N.StringWarsError
@@ -36,6 +37,7 @@ INFIX_MAX_PATTERN = N.INFIX_MAX_PATTERN
 INFIX_NONE = N.INFIX_NONE
 OSA_MAX_SHORTER = N.OSA_MAX_SHORTER
 LCS_MAX_SHORTER = N.LCS_MAX_SHORTER
+JARO_MAX_LENGTH = N.JARO_MAX_LENGTH
 
 
 def _pointer(obj) -> int:
@@ -277,6 +279,7 @@ class PreparedTape:
         N.check(fn(scope.handle, C.byref(struct), int(bool(utf8)), C.byref(handle), C.byref(err)), err)
         self._handle, self._root, self.utf8 = handle, self, bool(utf8)
         self._keepalive = keep if isinstance(keep, DeviceTape) else None   # device tapes are used in place
+        self._source, self._lengths = tape, None   # what symbol_lengths measures, once
         self.first, self.count = 0, len(tape)
 
     def __len__(self) -> int:
@@ -304,6 +307,13 @@ class PreparedTape:
 
     def view(self) -> "N.PreparedView":
         return N.PreparedView(self._handle, self.first, self.count)
+
+    def symbol_lengths(self, scope: DeviceScope) -> np.ndarray:
+        """Symbols (bytes, or code points of a ``utf8=True`` tape) of every string of this view, as int64, on the host."""
+        root = self._root
+        if root._lengths is None:
+            root._lengths = _symbol_lengths(root._source, root.utf8, scope)
+        return root._lengths[self.first:self.first + self.count]
 
     def free(self) -> None:
         if self._root is self and getattr(self, "_handle", None) and getattr(N, "lib", None) is not None:
@@ -494,6 +504,27 @@ def _as_tape(obj: TapeLike):
     if isinstance(obj, (Strs, DeviceTape, PreparedTape)):
         return obj
     return Strs(obj)
+
+
+def _symbol_lengths(tape, utf8: bool, scope: DeviceScope) -> np.ndarray:
+    """Symbols of every string of a tape as int64: bytes, or with ``utf8`` code points (bytes that are no continuation bytes).
+    Device tapes are read back; prepared tapes remember what they were prepared from."""
+    if isinstance(tape, PreparedTape):
+        return tape.symbol_lengths(scope)
+    if isinstance(tape, DeviceTape):
+        err = C.c_char_p()
+        offsets = np.zeros(tape.count + 1, dtype=tape.offsets_dtype)
+        N.check(N.lib.swh_copy_to_host(scope.handle, offsets.ctypes.data, C.c_void_p(tape.offsets_ptr), offsets.nbytes, C.byref(err)), err)
+        data = np.zeros(int(offsets[-1]) if utf8 else 0, dtype=np.uint8)
+        if data.nbytes:
+            N.check(N.lib.swh_copy_to_host(scope.handle, data.ctypes.data, C.c_void_p(tape.data_ptr), data.nbytes, C.byref(err)), err)
+        tape = Strs(data=data, offsets=offsets)
+    if not utf8:
+        return tape.lengths
+    starts = np.zeros(len(tape.data) + 1, dtype=np.int64)
+    np.cumsum((tape.data & 0xC0) != 0x80, out=starts[1:])
+    at = starts[tape.offsets.astype(np.int64)]
+    return at[1:] - at[:-1]
 
 
 def _c_tape(tape, want64: Optional[bool] = None):
@@ -888,6 +919,110 @@ class LevenshteinDistances(_Engine):
     def ratio_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None):
         """The dense float64 matrix of ``fuzz.ratio``: rapidfuzz's ``process.cdist(queries, candidates, scorer=fuzz.ratio)``, unrounded."""
         return self._ratio(*self._lcs_call(queries, candidates, scope, True, None, True, True))
+
+    def _jaro_call(self, a, b, scope, cross, outs):
+        """One ``swh_levenshtein_jaro_*`` call. ``outs``: for matches, transpositions and prefix the array to fill, True for a fresh
+        one, None where that output is not wanted. Returns the three arrays (None where not wanted) and the two tapes as called."""
+        if scope is None:
+            raise ValueError("a DeviceScope is required")
+        a = _as_tape(a)
+        b = None if b is None else _as_tape(b)
+        if b is None and not cross:
+            raise ValueError("pairwise scoring needs two collections")
+        if not cross and len(a) != len(b):
+            raise ValueError("pairwise scoring needs two collections of equal length")
+        if isinstance(a, (DeviceTape, PreparedTape)) or isinstance(b, (DeviceTape, PreparedTape)):   # measured on the device
+            a = a if isinstance(a, PreparedTape) else PreparedTape(scope, a, utf8=self._utf8)
+            if b is not None and not isinstance(b, PreparedTape):
+                b = PreparedTape(scope, b, utf8=self._utf8)
+            if self._utf8 != a.utf8:
+                raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
+        shape = (len(a), len(a if b is None else b)) if cross else (len(a),)
+        dtype = np.uint64 if cross else np.uint32
+        outs = [np.zeros(shape, dtype=dtype) if out is True else out for out in outs]
+        strides = set()
+        for out in outs:
+            if isinstance(out, np.ndarray):
+                if out.dtype.itemsize != dtype().itemsize or out.shape != shape:
+                    raise ValueError("an output must be a %s array of %d-bit integers" % (shape, 8 * dtype().itemsize))
+                strides.add(out.strides[0] if (cross or out.size > 1) else 0)
+        if len(strides) > 1:
+            raise ValueError("the outputs share one stride")
+        stride = strides.pop() if strides else 0
+        pointers = [C.c_void_p(None if out is None else _pointer(out)) for out in outs]
+        kind = "cross" if cross else "pairs"
+        err = C.c_char_p()
+        if isinstance(a, PreparedTape):
+            va, vb = a.view(), (None if b is None else b.view())
+            fn = getattr(N.lib, "swh_levenshtein_jaro_%s_prepared" % kind)
+            status = fn(self._handle, scope.handle, C.byref(va), None if vb is None else C.byref(vb), *pointers, stride, C.byref(err))
+        else:
+            ta, _, keep_a = _c_tape(a, want64=True)
+            tb, _, keep_b = (None, None, None) if b is None else _c_tape(b, want64=True)
+            fn = getattr(N.lib, "swh_levenshtein_%sjaro_%s_u64tape" % ("utf8_" if self._utf8 else "", kind))
+            status = fn(self._handle, scope.handle, C.byref(ta), None if tb is None else C.byref(tb), *pointers, stride, C.byref(err))
+            del keep_a, keep_b
+        N.check(status, err)
+        return outs, a, (a if b is None else b)
+
+    @staticmethod
+    def _jaro(matches, transpositions, m, n):
+        """``(M / m + M / n + (M - t) / M) / 3.0`` as float64, evaluated as written; 1.0 where both strings are empty, 0.0 where
+        nothing matches. ``m`` / ``n`` broadcast against the counts."""
+        M, t = matches.astype(np.float64), transpositions.astype(np.float64)
+        m, n = np.broadcast_to(np.asarray(m, dtype=np.float64), M.shape), np.broadcast_to(np.asarray(n, dtype=np.float64), M.shape)
+        some = M > 0
+        one = np.ones_like(M)
+        Ms, ms, ns = np.where(some, M, one), np.where(some, m, one), np.where(some, n, one)
+        value = (Ms / ms + Ms / ns + (Ms - t) / Ms) / 3.0
+        return np.where(some, value, np.where((m == 0) & (n == 0), 1.0, 0.0))
+
+    @staticmethod
+    def _winkler(jaro, prefix, prefix_weight):
+        """``jaro + l * p * (1.0 - jaro)`` where ``jaro > 0.7``, else ``jaro``, evaluated as written."""
+        return np.where(jaro > 0.7, jaro + prefix.astype(np.float64) * prefix_weight * (1.0 - jaro), jaro)
+
+    def _jaro_similarity(self, a, b, scope, cross, prefix_weight):
+        if prefix_weight is not None:
+            prefix_weight = float(prefix_weight)
+            if not 0.0 <= prefix_weight <= 0.25:
+                raise ValueError("prefix_weight must lie in [0, 0.25]")
+        (matches, transpositions, prefix), a, b = self._jaro_call(a, b, scope, cross, (True, True, None if prefix_weight is None else True))
+        m, n = _symbol_lengths(a, self._utf8, scope), _symbol_lengths(b, self._utf8, scope)
+        jaro = self._jaro(matches, transpositions, m[:, None] if cross else m, n[None, :] if cross else n)
+        return jaro if prefix_weight is None else self._winkler(jaro, prefix, prefix_weight)
+
+    def jaro_counts(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None, out=None):
+        """The counts behind the Jaro similarity of every pair ``(a[i], b[i])`` as three uint32 arrays (``swh_levenshtein_jaro_pairs_*``):
+        the matches M, the transpositions t and the common prefix of at most four symbols. ``a[i]`` drives the matching and ``b[i]``
+        is flagged; neither string holds more than ``JARO_MAX_LENGTH`` symbols. ``out``: a triple of arrays to fill, None where an
+        output is not wanted (not all). The two sides are tapes, lists, device tapes or ``PreparedTape``s."""
+        return tuple(self._jaro_call(a, b, scope, False, (True, True, True) if out is None else tuple(out))[0])
+
+    def jaro_counts_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None, out=None):
+        """The three dense uint64 matrices of counts, ``[i][j]`` of ``(queries[i], candidates[j])`` (``swh_levenshtein_jaro_cross_*``);
+        ``candidates=None`` is the self-product (the diagonal holds M = len, t = 0, prefix = min(len, 4))."""
+        return tuple(self._jaro_call(queries, candidates, scope, True, (True, True, True) if out is None else tuple(out))[0])
+
+    def jaro(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None):
+        """The Jaro similarity of every pair as float64: ``(M / m + M / n + (M - t) / M) / 3``, 1 for two empty strings, 0 where nothing
+        matches (``MARTHA`` / ``MARHTA``: 0.9444...) -- from one call's counts. rapidfuzz: ``distance.Jaro.similarity(a[i], b[i])``."""
+        return self._jaro_similarity(a, b, scope, False, None)
+
+    def jaro_winkler(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None, prefix_weight: float = 0.1):
+        """The Jaro-Winkler similarity of every pair as float64: ``jaro + l p (1 - jaro)`` where ``jaro > 0.7``, ``l`` the common prefix of
+        at most four symbols and ``p = prefix_weight`` in [0, 0.25] (``MARTHA`` / ``MARHTA``: 0.9611...). rapidfuzz:
+        ``distance.JaroWinkler.similarity(a[i], b[i], prefix_weight=p)``."""
+        return self._jaro_similarity(a, b, scope, False, prefix_weight)
+
+    def jaro_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None):
+        """The dense float64 matrix of Jaro similarities: rapidfuzz's ``process.cdist(queries, candidates, scorer=distance.Jaro.similarity)``."""
+        return self._jaro_similarity(queries, candidates, scope, True, None)
+
+    def jaro_winkler_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None,
+                           prefix_weight: float = 0.1):
+        """The dense float64 matrix of Jaro-Winkler similarities."""
+        return self._jaro_similarity(queries, candidates, scope, True, prefix_weight)
 
     def pairs_sharded(self, batch: "ShardedPairs", scope: DeviceScope, bound: Optional[int] = None, out=None):
         """One batch over every GPU of a multi-device scope; the distances come back gathered, in pair order."""

@@ -56,6 +56,8 @@ pub const INFIX_NONE: u32 = u32::MAX;
 pub const OSA_MAX_SHORTER: u32 = 2048;
 /// `SWH_LCS_MAX_SHORTER`: symbols of a pair's shorter string an LCS / Indel call accepts.
 pub const LCS_MAX_SHORTER: u32 = 2048;
+/// `SWH_JARO_MAX_LENGTH`: symbols of either string of a pair a Jaro call accepts.
+pub const JARO_MAX_LENGTH: u32 = 2048;
 /// `SWH_OP_*`: the op bytes of an alignment.
 pub const OP_MATCH: u8 = b'=';
 pub const OP_SUBST: u8 = b'X';
@@ -135,6 +137,12 @@ extern "C" {
     fn swh_levenshtein_lcs_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, indel: *mut usize, lcs: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_utf8_lcs_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, indel: *mut usize, lcs: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_lcs_cross_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, indel: *mut usize, lcs: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_jaro_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, matches: *mut u32, transpositions: *mut u32, prefix: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_jaro_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, matches: *mut u32, transpositions: *mut u32, prefix: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_jaro_pairs_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, matches: *mut u32, transpositions: *mut u32, prefix: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_jaro_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, matches: *mut usize, transpositions: *mut usize, prefix: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_jaro_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, matches: *mut usize, transpositions: *mut usize, prefix: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_jaro_cross_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, matches: *mut usize, transpositions: *mut usize, prefix: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_sharded_prepare_u32tape(scope: Handle, a: *const TapeU32, b: *const TapeU32, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_prepare_u64tape(scope: Handle, a: *const TapeU64, b: *const TapeU64, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_free(sharded: Handle) -> c_int;

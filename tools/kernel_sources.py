@@ -32,6 +32,8 @@ KERNELS = {
     "infix": ("swh::k_infix<", ("infix.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
     "osa": ("swh::k_osa<", ("osa.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
     "lcs": ("swh::k_lcs<", ("lcs.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
+    "jaro": ("swh::k_jaro<unsigned char,", ("jaro.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
+    "jaro_u32": ("swh::k_jaro<unsigned int,", ("jaro.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
 }
 
 
