@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Randomized parity soak on the GPU: batches with mixed length regimes, alphabets, bounds and engines, every result
 compared with the CPU oracle bit for bit -- distances and scores, top-k rows, and alignments (validity of the whole batch, sampled
-scripts against the reference script of tests/test_align.py). Lives under tests/ (the oracle is test infrastructure) but is not collected
+scripts against the reference script of tests/test_align.py) -- and, for the calls the oracle does not know, with the numpy and
+pure-Python references of their test files: OSA distances (test_osa.py), LCS lengths and Indel distances (test_lcs.py), the three
+Jaro counts (test_jaro.py) and infix matches (test_infix.py), over bytes and code points, on raw tapes, prepared tapes and a random
+prepared sub-view, with bounds and small cross-products. Lives under tests/ (the oracle is test infrastructure) but is not collected
 by pytest: minutes, not seconds.
 
     python tests/soak.py --seconds 240 --seed 1
@@ -22,6 +25,10 @@ import stringwars_amd as sw  # noqa: E402
 import oracle  # noqa: E402
 from test_align import check_exact, check_valid_batch, code_point_tape  # noqa: E402
 from test_topk import check_rows, expected_topk, oracle_matrix  # noqa: E402
+from test_infix import NONE as INFIX_NONE, reference_infix  # noqa: E402
+from test_jaro import reference as reference_jaro  # noqa: E402
+from test_lcs import reference_indel, reference_lcs  # noqa: E402
+from test_osa import reference_osa  # noqa: E402
 
 REGIMES = [(0, 8), (0, 40), (20, 140), (100, 700), (500, 2100), (1900, 2300), (2000, 5000), (0, 5000)]
 ALPHABETS = {"acgt": [ord(c) for c in "ACGT"], "lower": list(range(97, 123)), "byte": list(range(256)),
@@ -33,13 +40,26 @@ CODE_POINT_POOLS = [SCRIPTS, SCRIPTS + list(range(0x430, 0x450)) + list(range(0x
                     SCRIPTS + list(range(0x4E00, 0x4E00 + 900)) + list(range(0x1F300, 0x1F340))]
 
 
-def random_batch(rng, utf8, budget=1.5e9):
-    regime = REGIMES[int(rng.integers(0, len(REGIMES)))]
+# OSA, LCS, Jaro and infix rounds: what the calls accept -- the shorter string of an OSA / LCS pair, both strings of a Jaro pair and an
+# infix pattern hold at most 2048 symbols -- so the regimes end there (a mutated copy may still grow past it: see similarity_round).
+SIMILARITY_KINDS = ("osa", "lcs", "jaro", "infix")
+SIMILARITY_REGIMES = [r for r in REGIMES if r[1] <= 2048] + [(500, 2048), (1900, 2048)]
+# Their references are numpy and Python, far slower than the C oracle, so a round's cells (and infix's pairs: its reference goes pair
+# by pair) are sized against the CPU. Measured on the CPU alone: the references of an `align` round (the oracle's distances at 3e8
+# cells, twelve reference scripts) take 0.46 s on average over 40 drawn rounds; those of a round of these kinds at this budget 0.51 s
+# over 12 drawn rounds of each (osa 0.72 s, lcs 0.44 s, jaro 0.34 s, infix 0.54 s), the cross-product included.
+SIMILARITY_CELLS = 4e7
+SIMILARITY_CROSS = {16: (12, 20), 64: (12, 20), 200: (8, 12), 600: (3, 5)}   # strings cut to <= key symbols: queries x candidates
+INFIX_PAIRS = 1500
+
+
+def random_batch(rng, utf8, budget=1.5e9, regimes=REGIMES):
+    regime = regimes[int(rng.integers(0, len(regimes)))]
     mixed = rng.random() < 0.3
     alphabet = np.array(CODE_POINT_POOLS[int(rng.integers(0, 3))] if utf8 else ALPHABETS[str(rng.choice(list(ALPHABETS)))], np.uint32)
     items_a, items_b, cells = [], [], 0
     while cells < budget and len(items_a) < 20000:
-        lo, hi = REGIMES[int(rng.integers(0, len(REGIMES)))] if mixed else regime
+        lo, hi = regimes[int(rng.integers(0, len(regimes)))] if mixed else regime
         la, lb = int(rng.integers(lo, hi + 1)), int(rng.integers(lo, hi + 1))
         a = alphabet[rng.integers(0, len(alphabet), la)]
         if rng.random() < 0.6 and la:
@@ -78,6 +98,66 @@ def random_search(rng, utf8):
     return queries, candidates, k, bound
 
 
+def similarity_round(rng, kind):
+    """Everything a round of OSA, LCS, Jaro or infix draws: (utf8, a, b, items of a, items of b, bound, sub-view, cross-product or None).
+    The items are what the references read: bytes, or decoded strings."""
+    utf8 = bool(rng.random() < 0.4)
+    a, b = random_batch(rng, utf8, budget=SIMILARITY_CELLS, regimes=SIMILARITY_REGIMES)
+    bound = None if kind == "jaro" or rng.random() < 0.5 else int(rng.integers(0, 141))
+    quarter = bool(rng.random() < 0.5)   # infix: patterns cut to a quarter, so that texts are the longer side
+    decode = (lambda t: [t[i].decode("utf-8") for i in range(len(t))]) if utf8 else (lambda t: [t[i] for i in range(len(t))])
+    items_a, items_b = decode(a), decode(b)
+    if kind == "jaro":   # a mutated copy of a 2048-symbol string may hold a few more
+        items_a, items_b = [x[:2048] for x in items_a], [x[:2048] for x in items_b]
+    if kind == "infix":
+        items_a, items_b = items_a[:INFIX_PAIRS], items_b[:INFIX_PAIRS]
+        items_a = [x[:len(x) // 4 if quarter else 2048] for x in items_a]
+    if kind in ("jaro", "infix"):
+        a, b = sw.Strs(items_a), sw.Strs(items_b)
+    lo = int(rng.integers(0, len(a)))
+    hi = int(rng.integers(lo, len(a) + 1))
+    cross = None
+    if kind != "infix":
+        cut = int(rng.choice(list(SIMILARITY_CROSS)))
+        cross = ([x[:cut] for x in items_a[:SIMILARITY_CROSS[cut][0]]], [x[:cut] for x in items_b[:SIMILARITY_CROSS[cut][1]]])
+    return utf8, a, b, items_a, items_b, bound, (lo, hi), cross
+
+
+def similarity_reference(kind, items_a, items_b, utf8, bound):
+    """The columns a call of `kind` returns, as int64: osa (d), lcs (LCS, indel), jaro (M, t, prefix), infix (d, start, end)."""
+    clamp = (lambda d: d) if bound is None else (lambda d: np.minimum(d, bound + 1))
+    if kind == "osa":
+        return [clamp(reference_osa(items_a, items_b, utf8=utf8))]
+    if kind == "lcs":
+        lcs = reference_lcs(items_a, items_b, utf8=utf8)
+        return [lcs, clamp(reference_indel(items_a, items_b, utf8=utf8, lcs=lcs))]
+    if kind == "jaro":
+        return list(reference_jaro(items_a, items_b, utf8=utf8).T)
+    rows = np.array([reference_infix(p, t, utf8) for p, t in zip(items_a, items_b)], dtype=np.int64).reshape(len(items_a), 3)
+    if bound is not None:
+        rows[rows[:, 0] > bound] = (bound + 1, INFIX_NONE, INFIX_NONE)
+    return list(rows.T)
+
+
+def similarity_call(kind, engine, a, b, scope, bound, cross=False):
+    if kind == "osa":
+        return [engine.osa_cross(a, b, scope)] if cross else [engine.osa(a, b, scope, bound=bound)]
+    if kind == "lcs":
+        return [engine.lcs_cross(a, b, scope), engine.indel_cross(a, b, scope)] if cross else [engine.lcs(a, b, scope), engine.indel(a, b, scope, bound=bound)]
+    if kind == "jaro":
+        return list(engine.jaro_counts_cross(a, b, scope) if cross else engine.jaro_counts(a, b, scope))
+    got = engine.infix(a, b, scope, bound=bound)
+    return [got.distances, got.starts, got.ends]
+
+
+def agree(label, got, want, part=slice(None)):
+    assert len(got) == len(want), label
+    for column, (g, w) in enumerate(zip(got, want)):
+        g, w = np.asarray(g).astype(np.int64).ravel(), np.asarray(w).astype(np.int64).ravel()[part]
+        bad = np.nonzero(g != w)[0] if g.shape == w.shape else None
+        assert bad is not None and bad.size == 0, (label, column, None if bad is None else (bad[:5], g[bad[:5]], w[bad[:5]]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=240)
@@ -94,7 +174,7 @@ def main():
     multi = sw.DeviceScope(gpu_devices=[0, 0, 0])
     t0, rounds, pairs_total = time.time(), 0, 0
     while time.time() - t0 < args.seconds or 0 <= rounds <= args.only:
-        kind = str(rng.choice(["lev", "lev", "lev_utf8", "nw", "sw", "topk", "align"]))
+        kind = str(rng.choice(["lev", "lev", "lev_utf8", "nw", "sw", "topk", "align", *SIMILARITY_KINDS]))
         selected = args.only < 0 or (args.first if args.first >= 0 else args.only) <= rounds <= args.only
         if kind == "topk":   # every random number of the round is drawn before the device is touched: a replay draws the same ones
             utf8 = bool(rng.random() < 0.5)
@@ -110,6 +190,25 @@ def main():
                 pq, pc = sw.PreparedTape(scope, a, utf8=utf8), sw.PreparedTape(scope, candidates, utf8=utf8)
                 check_rows(engine.topk(pq, pc, scope, k=k, bound=bound), want, f"topk prepared utf8={utf8} k={k} bound={bound}")
                 check_rows(engine.topk(pq[lo:], pc, scope, k=k, bound=bound), (want[0][lo:], want[1][lo:]), "topk prepared sub-view")
+        elif kind in SIMILARITY_KINDS:   # (every random number of the round is drawn by similarity_round, before the device is touched)
+            utf8, a, b, items_a, items_b, bound, (lo, hi), cross = similarity_round(rng, kind)
+            if args.verbose:
+                print(f"batch {rounds}: {kind} utf8 {utf8} pairs {len(a)} longest {int(max(a.lengths.max(), b.lengths.max()))} bound {bound} "
+                      f"sub-view {lo}:{hi} cross {None if cross is None else (len(cross[0]), len(cross[1]))}", flush=True)
+            if selected:
+                engine = (sw.LevenshteinDistancesUTF8 if utf8 else sw.LevenshteinDistances)(capabilities=scope)
+                want = similarity_reference(kind, items_a, items_b, utf8, bound)
+                agree((kind, "raw", utf8, bound), similarity_call(kind, engine, a, b, scope, bound), want)
+                pa, pb = sw.PreparedTape(scope, a, utf8=utf8), sw.PreparedTape(scope, b, utf8=utf8)
+                agree((kind, "prepared", utf8, bound), similarity_call(kind, engine, pa, pb, scope, bound), want)
+                agree((kind, "prepared sub-view", utf8, bound, lo, hi), similarity_call(kind, engine, pa[lo:hi], pb[lo:hi], scope, bound), want, slice(lo, hi))
+                if cross is not None:
+                    queries, candidates = cross
+                    flat = similarity_reference(kind, [q for q in queries for _ in candidates], [c for _ in queries for c in candidates], utf8, None)
+                    sq, sc = sw.Strs(queries), sw.Strs(candidates)
+                    agree((kind, "cross", utf8), similarity_call(kind, engine, sq, sc, scope, None, cross=True), flat)
+                    pq, pc = sw.PreparedTape(scope, sq, utf8=utf8), sw.PreparedTape(scope, sc, utf8=utf8)
+                    agree((kind, "cross prepared", utf8), similarity_call(kind, engine, pq, pc, scope, None, cross=True), flat)
         elif kind == "align":
             utf8 = bool(rng.random() < 0.3)
             a, b = random_batch(rng, utf8, budget=3e8)
