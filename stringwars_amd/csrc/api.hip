@@ -2469,246 +2469,92 @@ swh_status_t swh_levenshtein_infix_prepared(swh_levenshtein_t e, swh_scope_t s, 
     return infix_run(scope, r, error);
 }
 
-// ---- OSA distances (osa.hip) -----------------------------------------------------------------------------------------------------------
-// k_osa_sizes measures the pairs (cells, the first pair whose shorter string is over SWH_OSA_MAX_SHORTER) and cuts them into work
-// items; one read-back of the measurements decides the errors before any output is written; k_osa scores the items. A pairwise call
-// is one such round. A cross-product maps pair p to (p / nb, p % nb) and runs in slices of whole rows of about kOsaChunkPairs pairs
-// -- the item list and, for a host matrix, the staged slice are all the scratch there is, whatever the matrix size; with more than
-// one slice the whole matrix is measured first (no items), so that a refusal still comes before the first row is written.
-// STRINGWARS_AMD_OSA_CHUNK_PAIRS=n (test library) lowers the slice, to put many of them in a small test. The scratch is the scope's
-// alignment scratch: the calls are synchronous.
-constexpr uint64_t kOsaChunkPairs = (uint64_t)1 << 21;
-static uint64_t osa_chunk_pairs() {
-    const char *hook = test_hook("STRINGWARS_AMD_OSA_CHUNK_PAIRS");
-    const uint64_t pairs = hook ? (uint64_t)atoll(hook) : kOsaChunkPairs;
-    return std::max<uint64_t>(1, std::min<uint64_t>(pairs, kOsaChunkPairs));
-}
+// ---- OSA distances, LCS lengths / Indel distances, Jaro counts (osa.hip, lcs.hip, jaro.hip): one planner --------------------------------
+// The three families score pairs on the same phases. A sizes kernel measures the pairs (cells, symbols, the first pair over the
+// family's length limit) and cuts them into work items; one read-back of the measurements decides the errors before any output is
+// written; the family's kernel scores the items and writes whichever of its outputs the caller asked for. A pairwise call is one such
+// round. A cross-product maps pair p to (p / nb, p % nb) and runs in slices of whole rows of about kScoredChunkPairs pairs -- the item
+// list and, per output that lives on the host, the staged slice are all the scratch there is, whatever the matrix size; with more
+// than one slice the whole matrix is measured first (no items), so that a refusal still comes before the first row is written. The
+// family's test hook (test library) lowers the slice, to put many of them in a small test. The scratch is the scope's alignment
+// scratch: the calls are synchronous, and they learn nothing into the scope.
+// What a family brings is its ScoredFamily: the two launchers, its words, and the few argument rules that differ.
+//  - OSA: k_osa_sizes cuts the items by the blocks of a pair's shorter string, which holds at most SWH_OSA_MAX_SHORTER symbols; one output.
+//  - LCS / Indel: OSA's sizes kernel and limit as they stand (SWH_LCS_MAX_SHORTER); two outputs, indel and lcs.
+//  - Jaro: k_jaro_sizes cuts the items by the blocks of b, and neither string holds more than SWH_JARO_MAX_LENGTH symbols; three
+//    outputs, matches, transpositions and prefix, and the only family that holds strides to multiples of the element.
+constexpr uint64_t kScoredChunkPairs = (uint64_t)1 << 21;
+constexpr int kScoredOutputs = 3;
 
-struct OsaRequest {
-    const Prepared *pa, *pb;
-    size_t a_first, a_count, b_first, b_count;
-    bool cross;
-    uint32_t bound;
-    void *out;
-    size_t stride;   // bytes between consecutive results (pairs) or rows (cross)
+struct ScoredFamily {
+    int outputs;   // of kScoredOutputs
+    void (*sizes)(Scope *scope, const OsaTapes &t, OsaSizes *sizes, OsaItem *items);
+    // scores the items into where[0 .. outputs), null where an output is not written by this launch, all at `stride`
+    void (*launch)(Scope *scope, const OsaTapes &t, const OsaItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride,
+                   uint32_t bound, bool wide);
+    const char *chunk_hook;      // the test hook that lowers the slice
+    const char *oversize;        // how the refusal of a pair over the length limit ends
+    const char *unit_costs;      // the refusal of a general-cost engine
+    const char *null_outputs;    // the refusal of a call that wants no output ...
+    bool null_outputs_on_empty;  // ... which a call without pairs meets too
+    bool element_strides;        // strides are multiples of the element (4 bytes pairwise, 8 cross), not merely large enough
 };
 
-static swh_status_t osa_run(Scope *scope, const OsaRequest &r, const char **error) {
-    harvest_timing(scope, false);
-    scope->stamps_used = 0;
-    scope->last_timing = swh_timing_t{};
-    const uint64_t na = r.a_count, nb = r.b_count;
-    if (na == 0 || nb == 0) return swh_success_k;
-    if (r.cross && na > ((uint64_t)1 << 40) / nb) return fail(error, swh_unsupported_length_k, "more than 2^40 pairs in one call");
-    const uint64_t total = r.cross ? na * nb : na;
-    try {
-        SWH_HIP_CHECK(hipSetDevice(scope->device));
-        hipStream_t stream = scope->stream;
-        const bool dev_out = is_device_pointer(r.out);
-        const bool cp = r.pa->utf8;
-        OsaTapes t{};
-        t.a = prepared_view(r.pa, cp, r.a_first, na);
-        t.b = prepared_view(r.pb, cp, r.b_first, nb);
-        t.a_off64 = cp ? 1 : r.pa->off64;
-        t.b_off64 = cp ? 1 : r.pb->off64;
-        t.cp = cp ? 1 : 0;
-        t.nb = r.cross ? nb : 0;
-
-        // slices: all pairs of a pairwise call; whole rows of a cross-product
-        const uint64_t rows_per_slice = r.cross ? std::max<uint64_t>(1, osa_chunk_pairs() / nb) : na;
-        const uint64_t slices = (na + rows_per_slice - 1) / rows_per_slice;
-        const uint64_t slice_pairs = r.cross ? std::min<uint64_t>(rows_per_slice, na) * nb : na;
-        const size_t width = r.cross ? 8 : 4;
-
-        AlignScratch *sc_entry;
-        {
-            std::lock_guard<std::mutex> hold(g_align_scratch_lock);
-            sc_entry = &g_align_scratch[scope];
-        }
-        // sizes | items | the slice's results (only where the caller's array lives on the host)
-        const size_t need = pad(sizeof(OsaSizes)) + pad(slice_pairs * sizeof(OsaItem)) + (dev_out ? 0 : pad(slice_pairs * width));
-        ensure(sc_entry->buf, sc_entry->bytes, need);
-        Carver sc{sc_entry->buf, 0, sc_entry->bytes};
-        OsaSizes *sizes = sc.take<OsaSizes>(1);
-        OsaItem *items = sc.take<OsaItem>(slice_pairs);
-        char *staged = dev_out ? nullptr : sc.take<char>(slice_pairs * width);
-
-        // measures pairs [row0 .. row0 + rows) x nb (or all pairs of a pairwise call) and, with `cut`, cuts them into `items`
-        auto measure = [&](uint64_t row0, uint64_t pairs, bool cut) {
-            OsaSizes init{};
-            init.first_oversize = ~0ull;
-            SWH_HIP_CHECK(hipMemcpyAsync(sizes, &init, sizeof init, hipMemcpyHostToDevice, stream));
-            t.row0 = row0; t.count = pairs;
-            launch_osa_sizes(scope, t, sizes, cut ? items : nullptr);
-            OsaSizes got{};
-            SWH_HIP_CHECK(hipMemcpyAsync(&got, sizes, sizeof got, hipMemcpyDeviceToHost, stream));
-            SWH_HIP_CHECK(hipStreamSynchronize(stream));
-            return got;
-        };
-        const OsaSizes whole = measure(0, total, slices == 1);
-        if (whole.first_oversize != ~0ull) {
-            const size_t i = (size_t)(r.cross ? whole.first_oversize / nb : whole.first_oversize);
-            const size_t j = (size_t)(r.cross ? whole.first_oversize % nb : whole.first_oversize);
-            const uint64_t la = read_offset(t.a.offsets, t.a_off64, i + 1, true, stream) - read_offset(t.a.offsets, t.a_off64, i, true, stream);
-            const uint64_t lb = read_offset(t.b.offsets, t.b_off64, j + 1, true, stream) - read_offset(t.b.offsets, t.b_off64, j, true, stream);
-            scope->stamps_used = 0;
-            if (r.cross)
-                return fail(error, swh_unsupported_length_k, "pair (%zu, %zu): %llu x %llu symbols, the shorter string exceeds SWH_OSA_MAX_SHORTER (2048)",
-                            i, j, (unsigned long long)la, (unsigned long long)lb);
-            return fail(error, swh_unsupported_length_k, "pair %zu: %llu x %llu symbols, the shorter string exceeds SWH_OSA_MAX_SHORTER (2048)", i,
-                        (unsigned long long)la, (unsigned long long)lb);
-        }
-
+static const ScoredFamily kOsaFamily = {
+    1, launch_osa_sizes,
+    [](Scope *scope, const OsaTapes &t, const OsaItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
+       bool wide) {
         OsaRun run{};
-        run.items = items;
-        run.bound = r.bound;
-        run.wide = !cp && whole.a_total >= 16 && whole.b_total >= 16;
-        for (uint64_t q = 0; q < slices; ++q) {
-            const uint64_t row0 = q * rows_per_slice, rows = std::min<uint64_t>(rows_per_slice, na - row0);
-            const uint64_t pairs = r.cross ? rows * nb : na;
-            run.item_count = slices == 1 ? whole.items : measure(row0, pairs, true).items;
-            t.row0 = row0; t.count = pairs;
-            if (dev_out) {
-                run.out = (char *)r.out + (r.cross ? row0 * r.stride : 0);
-                run.stride = r.stride;
-            } else {
-                run.out = staged;
-                run.stride = r.cross ? nb * 8 : 4;
-            }
-            launch_osa(scope, t, run);
-            if (!dev_out) {
-                if (r.cross)
-                    SWH_HIP_CHECK(hipMemcpy2DAsync((char *)r.out + row0 * r.stride, r.stride, staged, nb * 8, nb * 8, rows, hipMemcpyDeviceToHost, stream));
-                else if (r.stride == 4)
-                    SWH_HIP_CHECK(hipMemcpyAsync(r.out, staged, pairs * 4, hipMemcpyDeviceToHost, stream));
-                else
-                    SWH_HIP_CHECK(hipMemcpy2DAsync(r.out, r.stride, staged, 4, 4, pairs, hipMemcpyDeviceToHost, stream));
-                SWH_HIP_CHECK(hipStreamSynchronize(stream));   // the next slice reuses the staging
-            }
-        }
-        SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        if (scope->profiling && scope->stamps_used) {
-            collect_timing(scope);
-            add_to_totals(scope->totals, scope->last_timing);
-        }
-        scope->stamps_used = 0;
-        scope->last_timing.cells = whole.cells;
-        scope->last_timing.bytes = (cp ? 4 : 1) * whole.symbols + (na + nb + 2) * 8 + total * width;
-        return swh_success_k;
-    } catch (const HipFailure &f) {
-        return fail_hip(error, f);
-    } catch (const std::bad_alloc &) {
-        return fail(error, swh_bad_alloc_k, "host allocation failed");
-    }
+        run.items = items; run.item_count = item_count;
+        run.out = where[0];
+        run.stride = stride; run.bound = bound; run.wide = wide;
+        launch_osa(scope, t, run);
+    },
+    "STRINGWARS_AMD_OSA_CHUNK_PAIRS", "the shorter string exceeds SWH_OSA_MAX_SHORTER (2048)",
+    "OSA distances need unit costs (match 0, mismatch 1, open 1, extend 1)", "null output pointer", false, false};
+static const ScoredFamily kLcsFamily = {
+    2, launch_osa_sizes,
+    [](Scope *scope, const OsaTapes &t, const OsaItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
+       bool wide) {
+        LcsRun run{};
+        run.items = items; run.item_count = item_count;
+        run.indel = where[0]; run.lcs = where[1];
+        run.stride = stride; run.bound = bound; run.wide = wide;
+        launch_lcs(scope, t, run);
+    },
+    "STRINGWARS_AMD_LCS_CHUNK_PAIRS", "the shorter string exceeds SWH_LCS_MAX_SHORTER (2048)",
+    "LCS lengths and Indel distances are called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)",
+    "null output pointers: one of indel and lcs is needed", true, false};
+static const ScoredFamily kJaroFamily = {
+    3, launch_jaro_sizes,
+    [](Scope *scope, const OsaTapes &t, const OsaItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t,
+       bool wide) {
+        JaroRun run{};
+        run.items = items; run.item_count = item_count;
+        run.matches = where[0]; run.transpositions = where[1]; run.prefix = where[2];
+        run.stride = stride; run.wide = wide;
+        launch_jaro(scope, t, run);
+    },
+    "STRINGWARS_AMD_JARO_CHUNK_PAIRS", "a string exceeds SWH_JARO_MAX_LENGTH (2048)",
+    "Jaro and Jaro-Winkler counts are called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)",
+    "null output pointers: one of matches, transpositions and prefix is needed", true, true};
+
+static uint64_t scored_chunk_pairs(const ScoredFamily &f) {
+    const char *hook = test_hook(f.chunk_hook);
+    const uint64_t pairs = hook ? (uint64_t)atoll(hook) : kScoredChunkPairs;
+    return std::max<uint64_t>(1, std::min<uint64_t>(pairs, kScoredChunkPairs));
 }
 
-static swh_status_t osa_checks(swh_levenshtein_t e, size_t a_count, size_t b_count, bool cross, const void *out, size_t &stride,
-                               const char **error) {
-    const Engine *engine = (const Engine *)e;
-    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
-    if (!engine->unit_costs) return fail(error, swh_not_implemented_k, "OSA distances need unit costs (match 0, mismatch 1, open 1, extend 1)");
-    if (!cross && a_count != b_count) return fail(error, swh_invalid_argument_k, "a and b must hold the same number of strings");
-    if (a_count && b_count && !out) return fail(error, swh_invalid_argument_k, "null output pointer");
-    if (cross) {
-        if (!stride) stride = b_count * 8;
-        if (stride < b_count * 8) return fail(error, swh_invalid_argument_k, "row_stride_bytes too small");
-    } else {
-        if (!stride) stride = 4;
-        if (stride < 4) return fail(error, swh_invalid_argument_k, "out_stride_bytes must be >= 4");
-    }
-    return swh_success_k;
-}
-
-static swh_status_t osa_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, bool utf8, bool cross,
-                              uint32_t bound, void *out, size_t stride, const char **error) {
-    swh_status_t status = infix_handles(e, s, error);
-    if (status != swh_success_k) return status;
-    if (!a || (!b && !cross)) return fail(error, swh_invalid_argument_k, "null tape");
-    const swh_tape_u64_t *bb = b ? b : a;
-    status = osa_checks(e, a->count, bb->count, cross, out, stride, error);
-    if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
-    HoldSynchronous mode(scope);
-    OsaRequest r{nullptr, nullptr, 0, a->count, 0, bb->count, cross, bound, out, stride};
-    if (a->count == 0 || bb->count == 0) return osa_run(scope, r, error);
-    // raw tapes are made resident, measured and (UTF-8) validated and decoded for the call, as for top-k, alignments and infix search
-    PreparedOwner pa, pb;
-    status = prepare_tape(scope, SWH_TAPE(a, 1), utf8, (swh_prepared_t *)&pa.p, error);
-    if (status != swh_success_k) return status;
-    if (b) {
-        status = prepare_tape(scope, SWH_TAPE(b, 1), utf8, (swh_prepared_t *)&pb.p, error);
-        if (status != swh_success_k) return status;
-    }
-    r.pa = pa.p; r.pb = b ? pb.p : pa.p;
-    return osa_run(scope, r, error);
-}
-static swh_status_t osa_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b, bool cross,
-                                 uint32_t bound, void *out, size_t stride, const char **error) {
-    if (swh_status_t status = infix_handles(e, s, error)) return status;
-    if (!a || !a->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
-    const swh_prepared_view_t *bb = (b && b->tape) ? b : (cross ? a : nullptr);
-    if (!bb) return fail(error, swh_invalid_argument_k, "null prepared view");
-    if (!view_fits(a) || !view_fits(bb)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
-    const Prepared *pa = (const Prepared *)a->tape, *pb = (const Prepared *)bb->tape;
-    swh_status_t status = osa_checks(e, a->count, bb->count, cross, out, stride, error);
-    if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = check_prepared_pair(scope, pa, pb, error)) != swh_success_k) return status;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
-    HoldSynchronous mode(scope);
-    OsaRequest r{pa, pb, a->first, a->count, bb->first, bb->count, cross, bound, out, stride};
-    return osa_run(scope, r, error);
-}
-swh_status_t swh_levenshtein_osa_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,
-                                               uint32_t *out, size_t stride, const char **error) {
-    return osa_tapes(e, s, a, b, false, false, bound, out, stride, error);
-}
-swh_status_t swh_levenshtein_utf8_osa_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                                    uint32_t bound, uint32_t *out, size_t stride, const char **error) {
-    return osa_tapes(e, s, a, b, true, false, bound, out, stride, error);
-}
-swh_status_t swh_levenshtein_osa_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
-                                                uint32_t bound, uint32_t *out, size_t stride, const char **error) {
-    return osa_prepared(e, s, a, b, false, bound, out, stride, error);
-}
-swh_status_t swh_levenshtein_osa_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, size_t *out,
-                                               size_t row_stride, const char **error) {
-    return osa_tapes(e, s, a, b, false, true, SWH_UNBOUNDED, out, row_stride, error);
-}
-swh_status_t swh_levenshtein_utf8_osa_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                                    size_t *out, size_t row_stride, const char **error) {
-    return osa_tapes(e, s, a, b, true, true, SWH_UNBOUNDED, out, row_stride, error);
-}
-swh_status_t swh_levenshtein_osa_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
-                                                size_t *out, size_t row_stride, const char **error) {
-    return osa_prepared(e, s, a, b, true, SWH_UNBOUNDED, out, row_stride, error);
-}
-
-// ---- LCS lengths and Indel distances (lcs.hip) -----------------------------------------------------------------------------------------
-// The phases of the OSA calls, on the OSA calls' planner: k_osa_sizes (osa.hip) measures the pairs and cuts them into work items; one
-// read-back of the measurements decides the errors before any output is written; k_lcs scores the items and writes the Indel
-// distance, the LCS length or both. A cross-product runs in slices of whole rows of about kLcsChunkPairs pairs, measured as a whole
-// first when there is more than one slice. STRINGWARS_AMD_LCS_CHUNK_PAIRS=n (test library) lowers the slice. An output that lives on
-// the host is staged slice by slice, each on its own. The scratch is the scope's alignment scratch: the calls are synchronous, and
-// they learn nothing into the scope.
-constexpr uint64_t kLcsChunkPairs = (uint64_t)1 << 21;
-static uint64_t lcs_chunk_pairs() {
-    const char *hook = test_hook("STRINGWARS_AMD_LCS_CHUNK_PAIRS");
-    const uint64_t pairs = hook ? (uint64_t)atoll(hook) : kLcsChunkPairs;
-    return std::max<uint64_t>(1, std::min<uint64_t>(pairs, kLcsChunkPairs));
-}
-
-struct LcsRequest {
+struct ScoredRequest {
     const Prepared *pa, *pb;
     size_t a_first, a_count, b_first, b_count;
     bool cross;
     uint32_t bound;
-    void *indel, *lcs;   // either may be null
-    size_t stride;       // bytes between consecutive results (pairs) or rows (cross), of both outputs
+    void *outs[kScoredOutputs];   // the family's outputs in the order of its exports: any may be null, those past its count are
+    size_t stride;                // bytes between consecutive results (pairs) or rows (cross), of every output
 };
 
-static swh_status_t lcs_run(Scope *scope, const LcsRequest &r, const char **error) {
+static swh_status_t scored_run(Scope *scope, const ScoredFamily &f, const ScoredRequest &r, const char **error) {
     harvest_timing(scope, false);
     scope->stamps_used = 0;
     scope->last_timing = swh_timing_t{};
@@ -2719,232 +2565,9 @@ static swh_status_t lcs_run(Scope *scope, const LcsRequest &r, const char **erro
     try {
         SWH_HIP_CHECK(hipSetDevice(scope->device));
         hipStream_t stream = scope->stream;
-        void *const outs[2] = {r.indel, r.lcs};
-        const bool stage[2] = {r.indel && !is_device_pointer(r.indel), r.lcs && !is_device_pointer(r.lcs)};
-        const bool cp = r.pa->utf8;
-        OsaTapes t{};
-        t.a = prepared_view(r.pa, cp, r.a_first, na);
-        t.b = prepared_view(r.pb, cp, r.b_first, nb);
-        t.a_off64 = cp ? 1 : r.pa->off64;
-        t.b_off64 = cp ? 1 : r.pb->off64;
-        t.cp = cp ? 1 : 0;
-        t.nb = r.cross ? nb : 0;
-
-        // slices: all pairs of a pairwise call; whole rows of a cross-product
-        const uint64_t rows_per_slice = r.cross ? std::max<uint64_t>(1, lcs_chunk_pairs() / nb) : na;
-        const uint64_t slices = (na + rows_per_slice - 1) / rows_per_slice;
-        const uint64_t slice_pairs = r.cross ? std::min<uint64_t>(rows_per_slice, na) * nb : na;
-        const size_t width = r.cross ? 8 : 4;
-
-        AlignScratch *sc_entry;
-        {
-            std::lock_guard<std::mutex> hold(g_align_scratch_lock);
-            sc_entry = &g_align_scratch[scope];
-        }
-        // sizes | items | the slice's results (one array per output that lives on the host)
-        const size_t need = pad(sizeof(OsaSizes)) + pad(slice_pairs * sizeof(OsaItem)) + ((size_t)stage[0] + stage[1]) * pad(slice_pairs * width);
-        ensure(sc_entry->buf, sc_entry->bytes, need);
-        Carver sc{sc_entry->buf, 0, sc_entry->bytes};
-        OsaSizes *sizes = sc.take<OsaSizes>(1);
-        OsaItem *items = sc.take<OsaItem>(slice_pairs);
-        char *staged[2];
-        for (int k = 0; k < 2; ++k) staged[k] = stage[k] ? sc.take<char>(slice_pairs * width) : nullptr;
-
-        // measures pairs [row0 .. row0 + rows) x nb (or all pairs of a pairwise call) and, with `cut`, cuts them into `items`
-        auto measure = [&](uint64_t row0, uint64_t pairs, bool cut) {
-            OsaSizes init{};
-            init.first_oversize = ~0ull;
-            SWH_HIP_CHECK(hipMemcpyAsync(sizes, &init, sizeof init, hipMemcpyHostToDevice, stream));
-            t.row0 = row0; t.count = pairs;
-            launch_osa_sizes(scope, t, sizes, cut ? items : nullptr);
-            OsaSizes got{};
-            SWH_HIP_CHECK(hipMemcpyAsync(&got, sizes, sizeof got, hipMemcpyDeviceToHost, stream));
-            SWH_HIP_CHECK(hipStreamSynchronize(stream));
-            return got;
-        };
-        const OsaSizes whole = measure(0, total, slices == 1);
-        if (whole.first_oversize != ~0ull) {
-            const size_t i = (size_t)(r.cross ? whole.first_oversize / nb : whole.first_oversize);
-            const size_t j = (size_t)(r.cross ? whole.first_oversize % nb : whole.first_oversize);
-            const uint64_t la = read_offset(t.a.offsets, t.a_off64, i + 1, true, stream) - read_offset(t.a.offsets, t.a_off64, i, true, stream);
-            const uint64_t lb = read_offset(t.b.offsets, t.b_off64, j + 1, true, stream) - read_offset(t.b.offsets, t.b_off64, j, true, stream);
-            scope->stamps_used = 0;
-            if (r.cross)
-                return fail(error, swh_unsupported_length_k, "pair (%zu, %zu): %llu x %llu symbols, the shorter string exceeds SWH_LCS_MAX_SHORTER (2048)",
-                            i, j, (unsigned long long)la, (unsigned long long)lb);
-            return fail(error, swh_unsupported_length_k, "pair %zu: %llu x %llu symbols, the shorter string exceeds SWH_LCS_MAX_SHORTER (2048)", i,
-                        (unsigned long long)la, (unsigned long long)lb);
-        }
-
-        LcsRun run{};
-        run.items = items;
-        run.bound = r.bound;
-        run.wide = !cp && whole.a_total >= 16 && whole.b_total >= 16;
-        // the kernel writes both outputs at one stride: the caller's where both are written in place, the packed one where both
-        // are staged; a call with one output of each kind runs the slice once per output
-        const bool split = outs[0] && outs[1] && stage[0] != stage[1];
-        for (uint64_t q = 0; q < slices; ++q) {
-            const uint64_t row0 = q * rows_per_slice, rows = std::min<uint64_t>(rows_per_slice, na - row0);
-            const uint64_t pairs = r.cross ? rows * nb : na;
-            run.item_count = slices == 1 ? whole.items : measure(row0, pairs, true).items;
-            t.row0 = row0; t.count = pairs;
-            char *where[2];
-            for (int k = 0; k < 2; ++k)
-                where[k] = !outs[k] ? nullptr : stage[k] ? staged[k] : (char *)outs[k] + (r.cross ? row0 * r.stride : 0);
-            for (int pass = 0; pass < (split ? 2 : 1); ++pass) {
-                run.indel = (!split || pass == 0) ? where[0] : nullptr;
-                run.lcs = (!split || pass == 1) ? where[1] : nullptr;
-                const bool packed = split ? stage[pass] : (stage[0] || stage[1]);
-                run.stride = packed ? (r.cross ? nb * 8 : 4) : r.stride;
-                launch_lcs(scope, t, run);
-            }
-            for (int k = 0; k < 2; ++k) {
-                if (!stage[k]) continue;
-                if (r.cross)
-                    SWH_HIP_CHECK(hipMemcpy2DAsync((char *)outs[k] + row0 * r.stride, r.stride, staged[k], nb * 8, nb * 8, rows, hipMemcpyDeviceToHost, stream));
-                else if (r.stride == 4)
-                    SWH_HIP_CHECK(hipMemcpyAsync(outs[k], staged[k], pairs * 4, hipMemcpyDeviceToHost, stream));
-                else
-                    SWH_HIP_CHECK(hipMemcpy2DAsync(outs[k], r.stride, staged[k], 4, 4, pairs, hipMemcpyDeviceToHost, stream));
-            }
-            if (stage[0] || stage[1]) SWH_HIP_CHECK(hipStreamSynchronize(stream));   // the next slice reuses the staging
-        }
-        SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        if (scope->profiling && scope->stamps_used) {
-            collect_timing(scope);
-            add_to_totals(scope->totals, scope->last_timing);
-        }
-        scope->stamps_used = 0;
-        scope->last_timing.cells = whole.cells;
-        scope->last_timing.bytes = (cp ? 4 : 1) * whole.symbols + (na + nb + 2) * 8 + total * width * ((outs[0] ? 1 : 0) + (outs[1] ? 1 : 0));
-        return swh_success_k;
-    } catch (const HipFailure &f) {
-        return fail_hip(error, f);
-    } catch (const std::bad_alloc &) {
-        return fail(error, swh_bad_alloc_k, "host allocation failed");
-    }
-}
-
-static swh_status_t lcs_checks(swh_levenshtein_t e, size_t a_count, size_t b_count, bool cross, const void *indel, const void *lcs, size_t &stride,
-                               const char **error) {
-    const Engine *engine = (const Engine *)e;
-    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
-    if (!engine->unit_costs)
-        return fail(error, swh_not_implemented_k, "LCS lengths and Indel distances are called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)");
-    if (!cross && a_count != b_count) return fail(error, swh_invalid_argument_k, "a and b must hold the same number of strings");
-    if (!indel && !lcs) return fail(error, swh_invalid_argument_k, "null output pointers: one of indel and lcs is needed");
-    if (cross) {
-        if (!stride) stride = b_count * 8;
-        if (stride < b_count * 8) return fail(error, swh_invalid_argument_k, "row_stride_bytes too small");
-    } else {
-        if (!stride) stride = 4;
-        if (stride < 4) return fail(error, swh_invalid_argument_k, "out_stride_bytes must be >= 4");
-    }
-    return swh_success_k;
-}
-
-static swh_status_t lcs_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, bool utf8, bool cross,
-                              uint32_t bound, void *indel, void *lcs, size_t stride, const char **error) {
-    swh_status_t status = infix_handles(e, s, error);
-    if (status != swh_success_k) return status;
-    if (!a || (!b && !cross)) return fail(error, swh_invalid_argument_k, "null tape");
-    const swh_tape_u64_t *bb = b ? b : a;
-    status = lcs_checks(e, a->count, bb->count, cross, indel, lcs, stride, error);
-    if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
-    HoldSynchronous mode(scope);
-    LcsRequest r{nullptr, nullptr, 0, a->count, 0, bb->count, cross, bound, indel, lcs, stride};
-    if (a->count == 0 || bb->count == 0) return lcs_run(scope, r, error);
-    // raw tapes are made resident, measured and (UTF-8) validated and decoded for the call, as for the OSA calls
-    PreparedOwner pa, pb;
-    status = prepare_tape(scope, SWH_TAPE(a, 1), utf8, (swh_prepared_t *)&pa.p, error);
-    if (status != swh_success_k) return status;
-    if (b) {
-        status = prepare_tape(scope, SWH_TAPE(b, 1), utf8, (swh_prepared_t *)&pb.p, error);
-        if (status != swh_success_k) return status;
-    }
-    r.pa = pa.p; r.pb = b ? pb.p : pa.p;
-    return lcs_run(scope, r, error);
-}
-static swh_status_t lcs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b, bool cross,
-                                 uint32_t bound, void *indel, void *lcs, size_t stride, const char **error) {
-    if (swh_status_t status = infix_handles(e, s, error)) return status;
-    if (!a || !a->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
-    const swh_prepared_view_t *bb = (b && b->tape) ? b : (cross ? a : nullptr);
-    if (!bb) return fail(error, swh_invalid_argument_k, "null prepared view");
-    if (!view_fits(a) || !view_fits(bb)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
-    const Prepared *pa = (const Prepared *)a->tape, *pb = (const Prepared *)bb->tape;
-    swh_status_t status = lcs_checks(e, a->count, bb->count, cross, indel, lcs, stride, error);
-    if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = check_prepared_pair(scope, pa, pb, error)) != swh_success_k) return status;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
-    HoldSynchronous mode(scope);
-    LcsRequest r{pa, pb, a->first, a->count, bb->first, bb->count, cross, bound, indel, lcs, stride};
-    return lcs_run(scope, r, error);
-}
-swh_status_t swh_levenshtein_lcs_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,
-                                               uint32_t *indel, uint32_t *lcs, size_t stride, const char **error) {
-    return lcs_tapes(e, s, a, b, false, false, bound, indel, lcs, stride, error);
-}
-swh_status_t swh_levenshtein_utf8_lcs_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                                    uint32_t bound, uint32_t *indel, uint32_t *lcs, size_t stride, const char **error) {
-    return lcs_tapes(e, s, a, b, true, false, bound, indel, lcs, stride, error);
-}
-swh_status_t swh_levenshtein_lcs_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
-                                                uint32_t bound, uint32_t *indel, uint32_t *lcs, size_t stride, const char **error) {
-    return lcs_prepared(e, s, a, b, false, bound, indel, lcs, stride, error);
-}
-swh_status_t swh_levenshtein_lcs_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, size_t *indel,
-                                               size_t *lcs, size_t row_stride, const char **error) {
-    return lcs_tapes(e, s, a, b, false, true, SWH_UNBOUNDED, indel, lcs, row_stride, error);
-}
-swh_status_t swh_levenshtein_utf8_lcs_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                                    size_t *indel, size_t *lcs, size_t row_stride, const char **error) {
-    return lcs_tapes(e, s, a, b, true, true, SWH_UNBOUNDED, indel, lcs, row_stride, error);
-}
-swh_status_t swh_levenshtein_lcs_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
-                                                size_t *indel, size_t *lcs, size_t row_stride, const char **error) {
-    return lcs_prepared(e, s, a, b, true, SWH_UNBOUNDED, indel, lcs, row_stride, error);
-}
-
-// ---- Jaro and Jaro-Winkler counts (jaro.hip) -------------------------------------------------------------------------------------------
-// The phases of the LCS calls on a planner of their own: k_jaro_sizes (jaro.hip) measures the pairs and cuts them into work items by
-// the blocks of b; one read-back of the measurements decides the errors before any output is written; k_jaro counts the items' pairs
-// and writes the matches, the transpositions, the common prefix or any subset of them. A cross-product runs in slices of whole rows
-// of about kJaroChunkPairs pairs, measured as a whole first when there is more than one slice. STRINGWARS_AMD_JARO_CHUNK_PAIRS=n (test
-// library) lowers the slice. An output that lives on the host is staged slice by slice, each on its own. The scratch is the scope's
-// alignment scratch: the calls are synchronous, and they learn nothing into the scope.
-constexpr uint64_t kJaroChunkPairs = (uint64_t)1 << 21;
-static uint64_t jaro_chunk_pairs() {
-    const char *hook = test_hook("STRINGWARS_AMD_JARO_CHUNK_PAIRS");
-    const uint64_t pairs = hook ? (uint64_t)atoll(hook) : kJaroChunkPairs;
-    return std::max<uint64_t>(1, std::min<uint64_t>(pairs, kJaroChunkPairs));
-}
-
-struct JaroRequest {
-    const Prepared *pa, *pb;
-    size_t a_first, a_count, b_first, b_count;
-    bool cross;
-    void *outs[3];   // matches, transpositions, prefix: any may be null
-    size_t stride;   // bytes between consecutive results (pairs) or rows (cross), of every output
-};
-
-static swh_status_t jaro_run(Scope *scope, const JaroRequest &r, const char **error) {
-    harvest_timing(scope, false);
-    scope->stamps_used = 0;
-    scope->last_timing = swh_timing_t{};
-    const uint64_t na = r.a_count, nb = r.b_count;
-    if (na == 0 || nb == 0) return swh_success_k;
-    if (r.cross && na > ((uint64_t)1 << 40) / nb) return fail(error, swh_unsupported_length_k, "more than 2^40 pairs in one call");
-    const uint64_t total = r.cross ? na * nb : na;
-    try {
-        SWH_HIP_CHECK(hipSetDevice(scope->device));
-        hipStream_t stream = scope->stream;
-        bool stage[3];
+        bool stage[kScoredOutputs];
         size_t staged_count = 0, wanted = 0;
-        for (int k = 0; k < 3; ++k) {
+        for (int k = 0; k < f.outputs; ++k) {
             stage[k] = r.outs[k] && !is_device_pointer(r.outs[k]);
             staged_count += stage[k] ? 1 : 0;
             wanted += r.outs[k] ? 1 : 0;
@@ -2959,7 +2582,7 @@ static swh_status_t jaro_run(Scope *scope, const JaroRequest &r, const char **er
         t.nb = r.cross ? nb : 0;
 
         // slices: all pairs of a pairwise call; whole rows of a cross-product
-        const uint64_t rows_per_slice = r.cross ? std::max<uint64_t>(1, jaro_chunk_pairs() / nb) : na;
+        const uint64_t rows_per_slice = r.cross ? std::max<uint64_t>(1, scored_chunk_pairs(f) / nb) : na;
         const uint64_t slices = (na + rows_per_slice - 1) / rows_per_slice;
         const uint64_t slice_pairs = r.cross ? std::min<uint64_t>(rows_per_slice, na) * nb : na;
         const size_t width = r.cross ? 8 : 4;
@@ -2975,8 +2598,8 @@ static swh_status_t jaro_run(Scope *scope, const JaroRequest &r, const char **er
         Carver sc{sc_entry->buf, 0, sc_entry->bytes};
         OsaSizes *sizes = sc.take<OsaSizes>(1);
         OsaItem *items = sc.take<OsaItem>(slice_pairs);
-        char *staged[3];
-        for (int k = 0; k < 3; ++k) staged[k] = stage[k] ? sc.take<char>(slice_pairs * width) : nullptr;
+        char *staged[kScoredOutputs];
+        for (int k = 0; k < f.outputs; ++k) staged[k] = stage[k] ? sc.take<char>(slice_pairs * width) : nullptr;
 
         // measures pairs [row0 .. row0 + rows) x nb (or all pairs of a pairwise call) and, with `cut`, cuts them into `items`
         auto measure = [&](uint64_t row0, uint64_t pairs, bool cut) {
@@ -2984,7 +2607,7 @@ static swh_status_t jaro_run(Scope *scope, const JaroRequest &r, const char **er
             init.first_oversize = ~0ull;
             SWH_HIP_CHECK(hipMemcpyAsync(sizes, &init, sizeof init, hipMemcpyHostToDevice, stream));
             t.row0 = row0; t.count = pairs;
-            launch_jaro_sizes(scope, t, sizes, cut ? items : nullptr);
+            f.sizes(scope, t, sizes, cut ? items : nullptr);
             OsaSizes got{};
             SWH_HIP_CHECK(hipMemcpyAsync(&got, sizes, sizeof got, hipMemcpyDeviceToHost, stream));
             SWH_HIP_CHECK(hipStreamSynchronize(stream));
@@ -2998,37 +2621,31 @@ static swh_status_t jaro_run(Scope *scope, const JaroRequest &r, const char **er
             const uint64_t lb = read_offset(t.b.offsets, t.b_off64, j + 1, true, stream) - read_offset(t.b.offsets, t.b_off64, j, true, stream);
             scope->stamps_used = 0;
             if (r.cross)
-                return fail(error, swh_unsupported_length_k, "pair (%zu, %zu): %llu x %llu symbols, a string exceeds SWH_JARO_MAX_LENGTH (2048)",
-                            i, j, (unsigned long long)la, (unsigned long long)lb);
-            return fail(error, swh_unsupported_length_k, "pair %zu: %llu x %llu symbols, a string exceeds SWH_JARO_MAX_LENGTH (2048)", i,
-                        (unsigned long long)la, (unsigned long long)lb);
+                return fail(error, swh_unsupported_length_k, "pair (%zu, %zu): %llu x %llu symbols, %s", i, j, (unsigned long long)la,
+                            (unsigned long long)lb, f.oversize);
+            return fail(error, swh_unsupported_length_k, "pair %zu: %llu x %llu symbols, %s", i, (unsigned long long)la, (unsigned long long)lb,
+                        f.oversize);
         }
 
-        JaroRun run{};
-        run.items = items;
-        run.wide = !cp && whole.a_total >= 16 && whole.b_total >= 16;
+        const bool wide = !cp && whole.a_total >= 16 && whole.b_total >= 16;
         // the kernel writes its outputs at one stride: the caller's for those written in place, the packed one for those that are
         // staged; a call with outputs of both kinds runs the slice once per kind
         for (uint64_t q = 0; q < slices; ++q) {
             const uint64_t row0 = q * rows_per_slice, rows = std::min<uint64_t>(rows_per_slice, na - row0);
             const uint64_t pairs = r.cross ? rows * nb : na;
-            run.item_count = slices == 1 ? whole.items : measure(row0, pairs, true).items;
+            const uint64_t item_count = slices == 1 ? whole.items : measure(row0, pairs, true).items;
             t.row0 = row0; t.count = pairs;
             for (int packed = 0; packed < 2; ++packed) {
-                char *where[3];
+                char *where[kScoredOutputs] = {};
                 bool any = false;
-                for (int k = 0; k < 3; ++k) {
-                    where[k] = nullptr;
+                for (int k = 0; k < f.outputs; ++k) {
                     if (!r.outs[k] || stage[k] != (packed == 1)) continue;
                     where[k] = packed ? staged[k] : (char *)r.outs[k] + (r.cross ? row0 * r.stride : 0);
                     any = true;
                 }
-                if (!any) continue;
-                run.matches = where[0]; run.transpositions = where[1]; run.prefix = where[2];
-                run.stride = packed ? (r.cross ? nb * 8 : 4) : r.stride;
-                launch_jaro(scope, t, run);
+                if (any) f.launch(scope, t, items, item_count, where, packed ? (r.cross ? nb * 8 : 4) : r.stride, r.bound, wide);
             }
-            for (int k = 0; k < 3; ++k) {
+            for (int k = 0; k < f.outputs; ++k) {
                 if (!stage[k]) continue;
                 if (r.cross)
                     SWH_HIP_CHECK(hipMemcpy2DAsync((char *)r.outs[k] + row0 * r.stride, r.stride, staged[k], nb * 8, nb * 8, rows, hipMemcpyDeviceToHost, stream));
@@ -3048,48 +2665,49 @@ static swh_status_t jaro_run(Scope *scope, const JaroRequest &r, const char **er
         scope->last_timing.cells = whole.cells;
         scope->last_timing.bytes = (cp ? 4 : 1) * whole.symbols + (na + nb + 2) * 8 + total * width * wanted;
         return swh_success_k;
-    } catch (const HipFailure &f) {
-        return fail_hip(error, f);
+    } catch (const HipFailure &failure) {
+        return fail_hip(error, failure);
     } catch (const std::bad_alloc &) {
         return fail(error, swh_bad_alloc_k, "host allocation failed");
     }
 }
 
-static swh_status_t jaro_checks(swh_levenshtein_t e, size_t a_count, size_t b_count, bool cross, void *const outs[3], size_t &stride,
-                                const char **error) {
+// the argument rules; a stride of 0 becomes the packed one
+static swh_status_t scored_checks(const ScoredFamily &f, swh_levenshtein_t e, size_t a_count, size_t b_count, bool cross,
+                                  void *const (&outs)[kScoredOutputs], size_t &stride, const char **error) {
     const Engine *engine = (const Engine *)e;
     if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
-    if (!engine->unit_costs)
-        return fail(error, swh_not_implemented_k, "Jaro and Jaro-Winkler counts are called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)");
+    if (!engine->unit_costs) return fail(error, swh_not_implemented_k, "%s", f.unit_costs);
     if (!cross && a_count != b_count) return fail(error, swh_invalid_argument_k, "a and b must hold the same number of strings");
-    if (!outs[0] && !outs[1] && !outs[2])
-        return fail(error, swh_invalid_argument_k, "null output pointers: one of matches, transpositions and prefix is needed");
+    bool wanted = false;
+    for (int k = 0; k < f.outputs; ++k) wanted = wanted || outs[k];
+    if (!wanted && (f.null_outputs_on_empty || (a_count && b_count))) return fail(error, swh_invalid_argument_k, "%s", f.null_outputs);
     if (cross) {
         if (!stride) stride = b_count * 8;
-        if (stride % 8) return fail(error, swh_invalid_argument_k, "row_stride_bytes must be 0 or a multiple of 8");
+        if (f.element_strides && stride % 8) return fail(error, swh_invalid_argument_k, "row_stride_bytes must be 0 or a multiple of 8");
         if (stride < b_count * 8) return fail(error, swh_invalid_argument_k, "row_stride_bytes too small");
     } else {
         if (!stride) stride = 4;
-        if (stride % 4) return fail(error, swh_invalid_argument_k, "out_stride_bytes must be 0 or a multiple of 4");
+        if (f.element_strides && stride % 4) return fail(error, swh_invalid_argument_k, "out_stride_bytes must be 0 or a multiple of 4");
+        if (stride < 4) return fail(error, swh_invalid_argument_k, "out_stride_bytes must be >= 4");
     }
     return swh_success_k;
 }
 
-static swh_status_t jaro_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, bool utf8, bool cross,
-                               void *matches, void *transpositions, void *prefix, size_t stride, const char **error) {
+static swh_status_t scored_tapes(const ScoredFamily &f, swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                 bool utf8, bool cross, uint32_t bound, void *const (&outs)[kScoredOutputs], size_t stride, const char **error) {
     swh_status_t status = infix_handles(e, s, error);
     if (status != swh_success_k) return status;
     if (!a || (!b && !cross)) return fail(error, swh_invalid_argument_k, "null tape");
-    const swh_tape_u64_t *bb = b ? b : a;
-    void *const outs[3] = {matches, transpositions, prefix};
-    status = jaro_checks(e, a->count, bb->count, cross, outs, stride, error);
+    const swh_tape_u64_t *bb = b ? b : a;   // a cross-product without b: the self-product
+    status = scored_checks(f, e, a->count, bb->count, cross, outs, stride, error);
     if (status != swh_success_k) return status;
     Scope *scope = (Scope *)s;
     if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
     HoldSynchronous mode(scope);
-    JaroRequest r{nullptr, nullptr, 0, a->count, 0, bb->count, cross, {matches, transpositions, prefix}, stride};
-    if (a->count == 0 || bb->count == 0) return jaro_run(scope, r, error);
-    // raw tapes are made resident, measured and (UTF-8) validated and decoded for the call, as for the LCS calls
+    ScoredRequest r{nullptr, nullptr, 0, a->count, 0, bb->count, cross, bound, {outs[0], outs[1], outs[2]}, stride};
+    if (a->count == 0 || bb->count == 0) return scored_run(scope, f, r, error);
+    // raw tapes are made resident, measured and (UTF-8) validated and decoded for the call, as for top-k, alignments and infix search
     PreparedOwner pa, pb;
     status = prepare_tape(scope, SWH_TAPE(a, 1), utf8, (swh_prepared_t *)&pa.p, error);
     if (status != swh_success_k) return status;
@@ -3098,49 +2716,101 @@ static swh_status_t jaro_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tap
         if (status != swh_success_k) return status;
     }
     r.pa = pa.p; r.pb = b ? pb.p : pa.p;
-    return jaro_run(scope, r, error);
+    return scored_run(scope, f, r, error);
 }
-static swh_status_t jaro_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b, bool cross,
-                                  void *matches, void *transpositions, void *prefix, size_t stride, const char **error) {
+static swh_status_t scored_prepared(const ScoredFamily &f, swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a,
+                                    const swh_prepared_view_t *b, bool cross, uint32_t bound, void *const (&outs)[kScoredOutputs], size_t stride,
+                                    const char **error) {
     if (swh_status_t status = infix_handles(e, s, error)) return status;
     if (!a || !a->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
     const swh_prepared_view_t *bb = (b && b->tape) ? b : (cross ? a : nullptr);
     if (!bb) return fail(error, swh_invalid_argument_k, "null prepared view");
     if (!view_fits(a) || !view_fits(bb)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
     const Prepared *pa = (const Prepared *)a->tape, *pb = (const Prepared *)bb->tape;
-    void *const outs[3] = {matches, transpositions, prefix};
-    swh_status_t status = jaro_checks(e, a->count, bb->count, cross, outs, stride, error);
+    swh_status_t status = scored_checks(f, e, a->count, bb->count, cross, outs, stride, error);
     if (status != swh_success_k) return status;
     Scope *scope = (Scope *)s;
     if ((status = check_prepared_pair(scope, pa, pb, error)) != swh_success_k) return status;
     if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
     HoldSynchronous mode(scope);
-    JaroRequest r{pa, pb, a->first, a->count, bb->first, bb->count, cross, {matches, transpositions, prefix}, stride};
-    return jaro_run(scope, r, error);
+    ScoredRequest r{pa, pb, a->first, a->count, bb->first, bb->count, cross, bound, {outs[0], outs[1], outs[2]}, stride};
+    return scored_run(scope, f, r, error);
 }
+
+swh_status_t swh_levenshtein_osa_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,
+                                               uint32_t *out, size_t stride, const char **error) {
+    return scored_tapes(kOsaFamily, e, s, a, b, false, false, bound, {out}, stride, error);
+}
+swh_status_t swh_levenshtein_utf8_osa_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                    uint32_t bound, uint32_t *out, size_t stride, const char **error) {
+    return scored_tapes(kOsaFamily, e, s, a, b, true, false, bound, {out}, stride, error);
+}
+swh_status_t swh_levenshtein_osa_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                uint32_t bound, uint32_t *out, size_t stride, const char **error) {
+    return scored_prepared(kOsaFamily, e, s, a, b, false, bound, {out}, stride, error);
+}
+swh_status_t swh_levenshtein_osa_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, size_t *out,
+                                               size_t row_stride, const char **error) {
+    return scored_tapes(kOsaFamily, e, s, a, b, false, true, SWH_UNBOUNDED, {out}, row_stride, error);
+}
+swh_status_t swh_levenshtein_utf8_osa_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                    size_t *out, size_t row_stride, const char **error) {
+    return scored_tapes(kOsaFamily, e, s, a, b, true, true, SWH_UNBOUNDED, {out}, row_stride, error);
+}
+swh_status_t swh_levenshtein_osa_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                size_t *out, size_t row_stride, const char **error) {
+    return scored_prepared(kOsaFamily, e, s, a, b, true, SWH_UNBOUNDED, {out}, row_stride, error);
+}
+
+swh_status_t swh_levenshtein_lcs_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,
+                                               uint32_t *indel, uint32_t *lcs, size_t stride, const char **error) {
+    return scored_tapes(kLcsFamily, e, s, a, b, false, false, bound, {indel, lcs}, stride, error);
+}
+swh_status_t swh_levenshtein_utf8_lcs_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                    uint32_t bound, uint32_t *indel, uint32_t *lcs, size_t stride, const char **error) {
+    return scored_tapes(kLcsFamily, e, s, a, b, true, false, bound, {indel, lcs}, stride, error);
+}
+swh_status_t swh_levenshtein_lcs_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                uint32_t bound, uint32_t *indel, uint32_t *lcs, size_t stride, const char **error) {
+    return scored_prepared(kLcsFamily, e, s, a, b, false, bound, {indel, lcs}, stride, error);
+}
+swh_status_t swh_levenshtein_lcs_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, size_t *indel,
+                                               size_t *lcs, size_t row_stride, const char **error) {
+    return scored_tapes(kLcsFamily, e, s, a, b, false, true, SWH_UNBOUNDED, {indel, lcs}, row_stride, error);
+}
+swh_status_t swh_levenshtein_utf8_lcs_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                    size_t *indel, size_t *lcs, size_t row_stride, const char **error) {
+    return scored_tapes(kLcsFamily, e, s, a, b, true, true, SWH_UNBOUNDED, {indel, lcs}, row_stride, error);
+}
+swh_status_t swh_levenshtein_lcs_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                size_t *indel, size_t *lcs, size_t row_stride, const char **error) {
+    return scored_prepared(kLcsFamily, e, s, a, b, true, SWH_UNBOUNDED, {indel, lcs}, row_stride, error);
+}
+
+// (the Jaro kernel takes no bound)
 swh_status_t swh_levenshtein_jaro_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
                                                 uint32_t *matches, uint32_t *transpositions, uint32_t *prefix, size_t stride, const char **error) {
-    return jaro_tapes(e, s, a, b, false, false, matches, transpositions, prefix, stride, error);
+    return scored_tapes(kJaroFamily, e, s, a, b, false, false, SWH_UNBOUNDED, {matches, transpositions, prefix}, stride, error);
 }
 swh_status_t swh_levenshtein_utf8_jaro_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
                                                      uint32_t *matches, uint32_t *transpositions, uint32_t *prefix, size_t stride, const char **error) {
-    return jaro_tapes(e, s, a, b, true, false, matches, transpositions, prefix, stride, error);
+    return scored_tapes(kJaroFamily, e, s, a, b, true, false, SWH_UNBOUNDED, {matches, transpositions, prefix}, stride, error);
 }
 swh_status_t swh_levenshtein_jaro_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
                                                  uint32_t *matches, uint32_t *transpositions, uint32_t *prefix, size_t stride, const char **error) {
-    return jaro_prepared(e, s, a, b, false, matches, transpositions, prefix, stride, error);
+    return scored_prepared(kJaroFamily, e, s, a, b, false, SWH_UNBOUNDED, {matches, transpositions, prefix}, stride, error);
 }
 swh_status_t swh_levenshtein_jaro_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
                                                 size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
-    return jaro_tapes(e, s, a, b, false, true, matches, transpositions, prefix, row_stride, error);
+    return scored_tapes(kJaroFamily, e, s, a, b, false, true, SWH_UNBOUNDED, {matches, transpositions, prefix}, row_stride, error);
 }
 swh_status_t swh_levenshtein_utf8_jaro_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
                                                      size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
-    return jaro_tapes(e, s, a, b, true, true, matches, transpositions, prefix, row_stride, error);
+    return scored_tapes(kJaroFamily, e, s, a, b, true, true, SWH_UNBOUNDED, {matches, transpositions, prefix}, row_stride, error);
 }
 swh_status_t swh_levenshtein_jaro_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
                                                  size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
-    return jaro_prepared(e, s, a, b, true, matches, transpositions, prefix, row_stride, error);
+    return scored_prepared(kJaroFamily, e, s, a, b, true, SWH_UNBOUNDED, {matches, transpositions, prefix}, row_stride, error);
 }
 
 }  // extern "C"

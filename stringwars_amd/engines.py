@@ -836,9 +836,10 @@ class LevenshteinDistances(_Engine):
         fn = N.lib.swh_levenshtein_utf8_osa_cross_u64tape if self._utf8 else N.lib.swh_levenshtein_osa_cross_u64tape
         return self._cross(fn, queries, candidates, scope, out, np.uint64, prepared_suffix="_osa_cross_prepared")
 
-    def _lcs_call(self, a, b, scope, cross, bound, indel, lcs):
-        """One ``swh_levenshtein_lcs_*`` call. ``indel`` / ``lcs``: the array to fill, True for a fresh one, None where that output
-        is not wanted. Returns the two arrays (None where not wanted)."""
+    def _scored_call(self, family, a, b, scope, cross, outs, extra=()):
+        """One ``swh_levenshtein_{lcs,jaro}_*`` call. ``outs``: for each output of the family, in the order of its exports, the array
+        to fill, True for a fresh one, None where that output is not wanted; ``extra``: the C arguments between the tapes and the
+        outputs (the bound of the pairwise LCS calls). Returns the arrays (None where not wanted) and the two tapes as called."""
         if scope is None:
             raise ValueError("a DeviceScope is required")
         a = _as_tape(a)
@@ -855,7 +856,7 @@ class LevenshteinDistances(_Engine):
                 raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
         shape = (len(a), len(a if b is None else b)) if cross else (len(a),)
         dtype = np.uint64 if cross else np.uint32
-        outs = [np.zeros(shape, dtype=dtype) if out is True else out for out in (indel, lcs)]
+        outs = [np.zeros(shape, dtype=dtype) if out is True else out for out in outs]
         strides = set()
         for out in outs:
             if isinstance(out, np.ndarray):
@@ -863,24 +864,28 @@ class LevenshteinDistances(_Engine):
                     raise ValueError("an output must be a %s array of %d-bit integers" % (shape, 8 * dtype().itemsize))
                 strides.add(out.strides[0] if (cross or out.size > 1) else 0)
         if len(strides) > 1:
-            raise ValueError("the two outputs share one stride")
+            raise ValueError("the outputs share one stride")
         stride = strides.pop() if strides else 0
         pointers = [C.c_void_p(None if out is None else _pointer(out)) for out in outs]
-        extra = () if cross else (C.c_uint32(N.UNBOUNDED if bound is None else int(bound)),)
         kind = "cross" if cross else "pairs"
         err = C.c_char_p()
         if isinstance(a, PreparedTape):
             va, vb = a.view(), (None if b is None else b.view())
-            fn = getattr(N.lib, "swh_levenshtein_lcs_%s_prepared" % kind)
+            fn = getattr(N.lib, "swh_levenshtein_%s_%s_prepared" % (family, kind))
             status = fn(self._handle, scope.handle, C.byref(va), None if vb is None else C.byref(vb), *extra, *pointers, stride, C.byref(err))
         else:
             ta, _, keep_a = _c_tape(a, want64=True)
             tb, _, keep_b = (None, None, None) if b is None else _c_tape(b, want64=True)
-            fn = getattr(N.lib, "swh_levenshtein_%slcs_%s_u64tape" % ("utf8_" if self._utf8 else "", kind))
+            fn = getattr(N.lib, "swh_levenshtein_%s%s_%s_u64tape" % ("utf8_" if self._utf8 else "", family, kind))
             status = fn(self._handle, scope.handle, C.byref(ta), None if tb is None else C.byref(tb), *extra, *pointers, stride, C.byref(err))
             del keep_a, keep_b
         N.check(status, err)
-        return outs[0], outs[1]
+        return outs, a, (a if b is None else b)
+
+    def _lcs_call(self, a, b, scope, cross, bound, indel, lcs):
+        """The Indel distances and the LCS lengths of one ``swh_levenshtein_lcs_*`` call, each as ``_scored_call`` takes and returns it."""
+        extra = () if cross else (C.c_uint32(N.UNBOUNDED if bound is None else int(bound)),)
+        return self._scored_call("lcs", a, b, scope, cross, (indel, lcs), extra)[0]
 
     @staticmethod
     def _ratio(indel, lcs):
@@ -920,51 +925,6 @@ class LevenshteinDistances(_Engine):
         """The dense float64 matrix of ``fuzz.ratio``: rapidfuzz's ``process.cdist(queries, candidates, scorer=fuzz.ratio)``, unrounded."""
         return self._ratio(*self._lcs_call(queries, candidates, scope, True, None, True, True))
 
-    def _jaro_call(self, a, b, scope, cross, outs):
-        """One ``swh_levenshtein_jaro_*`` call. ``outs``: for matches, transpositions and prefix the array to fill, True for a fresh
-        one, None where that output is not wanted. Returns the three arrays (None where not wanted) and the two tapes as called."""
-        if scope is None:
-            raise ValueError("a DeviceScope is required")
-        a = _as_tape(a)
-        b = None if b is None else _as_tape(b)
-        if b is None and not cross:
-            raise ValueError("pairwise scoring needs two collections")
-        if not cross and len(a) != len(b):
-            raise ValueError("pairwise scoring needs two collections of equal length")
-        if isinstance(a, (DeviceTape, PreparedTape)) or isinstance(b, (DeviceTape, PreparedTape)):   # measured on the device
-            a = a if isinstance(a, PreparedTape) else PreparedTape(scope, a, utf8=self._utf8)
-            if b is not None and not isinstance(b, PreparedTape):
-                b = PreparedTape(scope, b, utf8=self._utf8)
-            if self._utf8 != a.utf8:
-                raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
-        shape = (len(a), len(a if b is None else b)) if cross else (len(a),)
-        dtype = np.uint64 if cross else np.uint32
-        outs = [np.zeros(shape, dtype=dtype) if out is True else out for out in outs]
-        strides = set()
-        for out in outs:
-            if isinstance(out, np.ndarray):
-                if out.dtype.itemsize != dtype().itemsize or out.shape != shape:
-                    raise ValueError("an output must be a %s array of %d-bit integers" % (shape, 8 * dtype().itemsize))
-                strides.add(out.strides[0] if (cross or out.size > 1) else 0)
-        if len(strides) > 1:
-            raise ValueError("the outputs share one stride")
-        stride = strides.pop() if strides else 0
-        pointers = [C.c_void_p(None if out is None else _pointer(out)) for out in outs]
-        kind = "cross" if cross else "pairs"
-        err = C.c_char_p()
-        if isinstance(a, PreparedTape):
-            va, vb = a.view(), (None if b is None else b.view())
-            fn = getattr(N.lib, "swh_levenshtein_jaro_%s_prepared" % kind)
-            status = fn(self._handle, scope.handle, C.byref(va), None if vb is None else C.byref(vb), *pointers, stride, C.byref(err))
-        else:
-            ta, _, keep_a = _c_tape(a, want64=True)
-            tb, _, keep_b = (None, None, None) if b is None else _c_tape(b, want64=True)
-            fn = getattr(N.lib, "swh_levenshtein_%sjaro_%s_u64tape" % ("utf8_" if self._utf8 else "", kind))
-            status = fn(self._handle, scope.handle, C.byref(ta), None if tb is None else C.byref(tb), *pointers, stride, C.byref(err))
-            del keep_a, keep_b
-        N.check(status, err)
-        return outs, a, (a if b is None else b)
-
     @staticmethod
     def _jaro(matches, transpositions, m, n):
         """``(M / m + M / n + (M - t) / M) / 3.0`` as float64, evaluated as written; 1.0 where both strings are empty, 0.0 where
@@ -987,7 +947,7 @@ class LevenshteinDistances(_Engine):
             prefix_weight = float(prefix_weight)
             if not 0.0 <= prefix_weight <= 0.25:
                 raise ValueError("prefix_weight must lie in [0, 0.25]")
-        (matches, transpositions, prefix), a, b = self._jaro_call(a, b, scope, cross, (True, True, None if prefix_weight is None else True))
+        (matches, transpositions, prefix), a, b = self._scored_call("jaro", a, b, scope, cross, (True, True, None if prefix_weight is None else True))
         m, n = _symbol_lengths(a, self._utf8, scope), _symbol_lengths(b, self._utf8, scope)
         jaro = self._jaro(matches, transpositions, m[:, None] if cross else m, n[None, :] if cross else n)
         return jaro if prefix_weight is None else self._winkler(jaro, prefix, prefix_weight)
@@ -997,12 +957,12 @@ class LevenshteinDistances(_Engine):
         the matches M, the transpositions t and the common prefix of at most four symbols. ``a[i]`` drives the matching and ``b[i]``
         is flagged; neither string holds more than ``JARO_MAX_LENGTH`` symbols. ``out``: a triple of arrays to fill, None where an
         output is not wanted (not all). The two sides are tapes, lists, device tapes or ``PreparedTape``s."""
-        return tuple(self._jaro_call(a, b, scope, False, (True, True, True) if out is None else tuple(out))[0])
+        return tuple(self._scored_call("jaro", a, b, scope, False, (True, True, True) if out is None else tuple(out))[0])
 
     def jaro_counts_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None, out=None):
         """The three dense uint64 matrices of counts, ``[i][j]`` of ``(queries[i], candidates[j])`` (``swh_levenshtein_jaro_cross_*``);
         ``candidates=None`` is the self-product (the diagonal holds M = len, t = 0, prefix = min(len, 4))."""
-        return tuple(self._jaro_call(queries, candidates, scope, True, (True, True, True) if out is None else tuple(out))[0])
+        return tuple(self._scored_call("jaro", queries, candidates, scope, True, (True, True, True) if out is None else tuple(out))[0])
 
     def jaro(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None):
         """The Jaro similarity of every pair as float64: ``(M / m + M / n + (M - t) / M) / 3``, 1 for two empty strings, 0 where nothing

@@ -12,7 +12,11 @@ The sizes below straddle 4 and 16 on either tape independently, with the first a
 
 Every comparison is exact, against the references of test_osa.py, test_lcs.py, test_jaro.py and test_infix.py; each pair's reference
 is computed once (`expected` remembers it) and shared by the tests. The one CPU test runs the generators alone and asserts what the
-sweeps are meant to contain."""
+sweeps are meant to contain.
+
+OSA, LCS and Jaro share their host path (api.hip: scored_run and its front ends); section f holds each of them to its own argument
+rules and error texts at the C ABI, from one table."""
+import ctypes as C
 import functools
 from collections import namedtuple
 
@@ -509,7 +513,147 @@ def test_neighbours_never_show(sw, scope, lev, lev8, call, utf8):
     assert sizes == {True, False}
 
 
-# ---- f. what the sweeps hold, and what the references are worth: no GPU -------------------------------------------------------------
+# ---- f. the argument rules of the three scored families, family by family ----------------------------------------------------------
+UNIT_COSTS = " (match 0, mismatch 1, open 1, extend 1)"
+# What differs between the families at the C ABI. `outputs`: in ABI order, as columns of `expected`; `bound`: the pairwise calls take one;
+# `null_on_empty`: what a call with every output null says on empty tapes (None: success); `stride_2` / `stride_6`: a pairwise
+# out_stride_bytes of 2 / 6 (None: accepted); `row_plus_4`: a row_stride_bytes of nb * 8 + 4; `oversize_cross`: the first refused pair
+# of OVERSIZE_A x OVERSIZE_B in row order, with its lengths.
+FAMILY_RULES = {
+    "osa": dict(outputs=(0,), bound=True,
+                unit_costs="OSA distances need unit costs" + UNIT_COSTS,
+                null="null output pointer", null_on_empty=None,
+                stride_2="out_stride_bytes must be >= 4", stride_6=None, row_plus_4=None,
+                tail="the shorter string exceeds SWH_OSA_MAX_SHORTER (2048)", oversize_cross=(1, 1, 2049, 2049)),
+    "lcs": dict(outputs=(1, 0), bound=True,
+                unit_costs="LCS lengths and Indel distances are called on a unit-cost engine" + UNIT_COSTS,
+                null="null output pointers: one of indel and lcs is needed",
+                null_on_empty="null output pointers: one of indel and lcs is needed",
+                stride_2="out_stride_bytes must be >= 4", stride_6=None, row_plus_4=None,
+                tail="the shorter string exceeds SWH_LCS_MAX_SHORTER (2048)", oversize_cross=(1, 1, 2049, 2049)),
+    "jaro": dict(outputs=(0, 1, 2), bound=False,
+                 unit_costs="Jaro and Jaro-Winkler counts are called on a unit-cost engine" + UNIT_COSTS,
+                 null="null output pointers: one of matches, transpositions and prefix is needed",
+                 null_on_empty="null output pointers: one of matches, transpositions and prefix is needed",
+                 stride_2="out_stride_bytes must be 0 or a multiple of 4", stride_6="out_stride_bytes must be 0 or a multiple of 4",
+                 row_plus_4="row_stride_bytes must be 0 or a multiple of 8",
+                 tail="a string exceeds SWH_JARO_MAX_LENGTH (2048)", oversize_cross=(0, 1, 2, 2049)),
+}
+RULE_A, RULE_B = [b"ab", b"ca"], [b"ba", b"ac"]
+OVERSIZE_A, OVERSIZE_B = [b"ab", b"a" * 2049], [b"ba", b"b" * 2049]
+SENTINEL = 0x4D
+
+
+def raw_scored(sw, call, kind, engine_handle, scope, a, b, outs, stride):
+    """One of the 18 scored exports as it stands: `a` / `b` are both Strs or both PreparedTape (b None: a null pointer), `outs` the
+    family's output pointers (None: null). Returns (status name, message)."""
+    from stringwars_amd import _native as N
+    if isinstance(a, sw.PreparedTape):
+        sides, form = [None if x is None else x.view() for x in (a, b)], "prepared"
+    else:
+        kept = [None if x is None else sw.engines._c_tape(x, want64=True) for x in (a, b)]
+        sides, form = [None if k is None else k[0] for k in kept], "u64tape"
+    extra = (C.c_uint32(N.UNBOUNDED),) if kind == "pairs" and FAMILY_RULES[call]["bound"] else ()
+    err = C.c_char_p()
+    status = getattr(N.lib, "swh_levenshtein_%s_%s_%s" % (call, kind, form))(
+        engine_handle, scope.handle, *(None if x is None else C.byref(x) for x in sides), *extra, *(C.c_void_p(p) for p in outs), stride, C.byref(err))
+    return N.STATUS_NAMES[status], (err.value or b"").decode() if status else ""
+
+
+@gpu
+@pytest.mark.parametrize("call", CROSS_CALLS)
+def test_each_family_keeps_its_own_argument_rules(sw, scope, lev, call):
+    """OSA, LCS and Jaro go through one set of host checks, and each keeps the rules and the words it had: the status and the whole
+    message of every refusal, on raw and on prepared tapes, with not a byte of the outputs written; and the results of the strides
+    that one family accepts and another refuses, at those strides. Two pairs of two-byte strings; one pair of 2049 symbols for the
+    length limit."""
+    rules = FAMILY_RULES[call]
+    outputs = len(rules["outputs"])
+    costly = sw.LevenshteinDistances(0, 2, 1, 1, capabilities=scope)
+    global_scores = sw.NeedlemanWunschScores(substitution_matrix=sw.substitution_matrix(42), open=-4, extend=-4, capabilities=scope)
+    want = {"pairs": expected(call, RULE_A, RULE_B, False)[:, rules["outputs"]],
+            "cross": expected(call, *expanded(RULE_A, RULE_B), False)[:, rules["outputs"]],
+            "self": expected(call, *expanded(RULE_A, RULE_A), False)[:, rules["outputs"]]}
+    room = 64   # bytes per output: two results at a stride of 12, two rows at a stride of 20
+
+    def fresh():
+        return [np.full(room, SENTINEL, np.uint8) for _ in range(outputs)]
+
+    def pointers(buffers):
+        return [x.ctypes.data for x in buffers]
+
+    def refused(status, message, kind, engine, a, b, outs, stride, buffers=()):
+        got = raw_scored(sw, call, kind, engine._handle, scope, a, b, outs, stride)
+        assert got == (status, message), (call, kind, type(a).__name__, stride, got)
+        assert all((x == SENTINEL).all() for x in buffers), (call, kind, message)
+
+    def accepted(kind, a, b, stride, want_rows, nb=1):
+        """The call's results lie at `stride` (of results for pairs, of rows of `nb` for cross) and nothing else is written."""
+        buffers = fresh()
+        got = raw_scored(sw, call, kind, lev._handle, scope, a, b, pointers(buffers), stride)
+        assert got == ("success", ""), (call, kind, stride, got)
+        width = 4 if kind == "pairs" else 8
+        for column, buffer in enumerate(buffers):
+            written = np.zeros(room, bool)
+            for k, value in enumerate(want_rows[:, column]):
+                at = (k // nb) * stride + (k % nb) * width if kind == "cross" else k * stride
+                assert int.from_bytes(buffer[at:at + width].tobytes(), "little") == value, (call, kind, stride, column, k)
+                written[at:at + width] = True
+            assert (buffer[~written] == SENTINEL).all(), (call, kind, stride, column)
+
+    sa, sb = sw.Strs(RULE_A), sw.Strs(RULE_B)
+    pa, pb = sw.PreparedTape(scope, sa), sw.PreparedTape(scope, sb)
+    for a, b in ((sa, sb), (pa, pb)):
+        for kind in ("pairs", "cross"):
+            buffers = fresh()
+            outs = pointers(buffers)
+            # the engine: general costs, and a handle of another kind
+            refused("not_implemented", rules["unit_costs"], kind, costly, a, b, outs, 0, buffers)
+            refused("invalid_argument", "not a Levenshtein engine", kind, global_scores, a, b, outs, 0, buffers)
+            # every output null: on two pairs, and on no pairs at all
+            refused("invalid_argument", rules["null"], kind, lev, a, b, [None] * outputs, 0)
+            none = (sw.Strs([]), sw.Strs([])) if a is sa else (pa[0:0], pb[0:0])
+            if rules["null_on_empty"] is None:
+                assert raw_scored(sw, call, kind, lev._handle, scope, *none, [None] * outputs, 0) == ("success", "")
+            else:
+                refused("invalid_argument", rules["null_on_empty"], kind, lev, *none, [None] * outputs, 0)
+        # pairwise: the counts, and strides of 2, 6 and 12 bytes
+        buffers = fresh()
+        outs = pointers(buffers)
+        refused("invalid_argument", "a and b must hold the same number of strings", "pairs", lev, a, sw.Strs(RULE_B[:1]) if a is sa else pb[0:1],
+                outs, 0, buffers)
+        refused("invalid_argument", rules["stride_2"], "pairs", lev, a, b, outs, 2, buffers)
+        if rules["stride_6"] is None:
+            accepted("pairs", a, b, 6, want["pairs"])
+        else:
+            refused("invalid_argument", rules["stride_6"], "pairs", lev, a, b, outs, 6, buffers)
+        accepted("pairs", a, b, 12, want["pairs"])
+        # cross: rows of nb * 8 - 8 and of nb * 8 + 4 bytes
+        nb = len(RULE_B)
+        refused("invalid_argument", "row_stride_bytes too small", "cross", lev, a, b, outs, nb * 8 - 8, buffers)
+        if rules["row_plus_4"] is None:
+            accepted("cross", a, b, nb * 8 + 4, want["cross"], nb)
+        else:
+            refused("invalid_argument", rules["row_plus_4"], "cross", lev, a, b, outs, nb * 8 + 4, buffers)
+        accepted("cross", a, b, nb * 8 + 8, want["cross"], nb)
+    # the length limit: the pair, its lengths and the family's own words, before anything is written
+    la, lb = sw.Strs(OVERSIZE_A), sw.Strs(OVERSIZE_B)
+    i, j, m, n = rules["oversize_cross"]
+    for a, b in ((la, lb), (sw.PreparedTape(scope, la), sw.PreparedTape(scope, lb))):
+        buffers = fresh()
+        refused("unsupported_length", "pair 1: 2049 x 2049 symbols, " + rules["tail"], "pairs", lev, a, b, pointers(buffers), 0, buffers)
+        refused("unsupported_length", "pair (%d, %d): %d x %d symbols, %s" % (i, j, m, n, rules["tail"]), "cross", lev, a, b, pointers(buffers), 0,
+                buffers)
+    # prepared views: a null b is the self-product of a cross call, and an error of a pairwise one
+    accepted("cross", pa, None, 16, want["self"], len(RULE_A))
+    accepted("cross", pa, pa, 16, want["self"], len(RULE_A))
+    assert (want["self"] != want["cross"]).any()
+    buffers = fresh()
+    refused("invalid_argument", "null prepared view", "pairs", lev, pa, None, pointers(buffers), 0, buffers)
+    refused("invalid_argument", "null tape", "pairs", lev, sa, None, pointers(buffers), 0, buffers)
+
+
+# ---- g. what the sweeps hold, and what the references are worth: no GPU -------------------------------------------------------------
 def test_sweeps_hold_what_they_are_meant_to():
     """The generators alone. Every (total_a, total_b) is there twice, the totals lie on both sides of 4 and of 16 on either tape,
     the forced empty-edge trials exist on both sides, every lopsided length is present; and on a sample of the sweep the imported
