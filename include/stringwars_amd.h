@@ -234,6 +234,40 @@ swh_status_t swh_levenshtein_topk_prepared(swh_levenshtein_t engine, swh_scope_t
                                            const swh_prepared_view_t *candidates, size_t k, uint32_t bound,
                                            uint32_t *indices, uint32_t *distances, const char **error);
 
+/* ---- Range search: EVERY candidate within `bound` edits of every query, as CSR (rapidfuzz `process.extract(query, choices,
+ *      score_cutoff=bound, limit=None)` / `process.cdist(..., score_cutoff=bound)` with the Levenshtein distance as the scorer). ----
+ * Engines, symbols, tapes and the self-product are those of the top-k calls above; what differs is the result:
+ *  - row i holds every candidate j with d(q_i, c_j) <= bound, in ASCENDING j, at entries [row_offsets[i], row_offsets[i + 1]) of
+ *    `indices` and `distances`; `distances` holds the true distance, never clamped;
+ *  - `row_offsets` has queries->count + 1 entries, row_offsets[0] = 0; the output is bit-for-bit deterministic;
+ *  - candidates == NULL means queries x queries, diagonal and both orientations included;
+ *  - bound == SWH_UNBOUNDED returns swh_invalid_argument_k (that is the dense cross-product); a bound at or above every possible
+ *    distance is accepted and returns every pair;
+ *  - counting protocol: `row_offsets` is ALWAYS written in full, with the true counts. `indices` and `distances` (`capacity` entries
+ *    each) are written only if row_offsets[count] <= capacity; otherwise they are left untouched and the call still returns
+ *    swh_success_k -- the caller compares row_offsets[count] with `capacity`. indices == NULL && distances == NULL && capacity == 0 is
+ *    the counting call. One of the two arrays NULL and the other not, both NULL with a capacity, or a NULL `row_offsets`, is
+ *    swh_invalid_argument_k and nothing is written;
+ *  - candidates->count must be below 0xFFFFFFFF; queries->count x candidates->count has NO 2^32 limit and the hit total is a size_t;
+ *    queries->count == 0 writes row_offsets[0] = 0 only; candidates->count == 0 makes every row empty;
+ *  - each of the three outputs may be host or device memory, independently;
+ *  - two prepared byte tapes must share one offset width, as for top-k; multi-device scopes are treated as top-k treats them.
+ * The call is synchronous on every scope (outstanding asynchronous / pipelined work is joined first). The pairs are walked twice --
+ * counted, then, if the arrays hold them, stored -- and nothing is kept between the walks but the counts. With profiling on,
+ * swh_scope_last_timing describes the whole search: `cells` = sum len(q) len(c) over all pairs, counted once although the pairs of
+ * a filled call are walked twice; `dominant_name` is "cross_within" for the fused word-sized kernel, or "within_select/<kernel>"
+ * for the general path (<kernel> the longest scoring kernel); on the fused route `bytes` = the two tapes + 12 bytes for every
+ * (query, candidate slice) count + the row offsets + 8 bytes per stored hit. */
+swh_status_t swh_levenshtein_within_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *queries,
+                                            const swh_tape_u64_t *candidates, uint32_t bound, size_t *row_offsets,
+                                            uint32_t *indices, uint32_t *distances, size_t capacity, const char **error);
+swh_status_t swh_levenshtein_utf8_within_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *queries,
+                                                 const swh_tape_u64_t *candidates, uint32_t bound, size_t *row_offsets,
+                                                 uint32_t *indices, uint32_t *distances, size_t capacity, const char **error);
+swh_status_t swh_levenshtein_within_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *queries,
+                                             const swh_prepared_view_t *candidates, uint32_t bound, size_t *row_offsets,
+                                             uint32_t *indices, uint32_t *distances, size_t capacity, const char **error);
+
 /* ---- Alignments: the edit operations of every pair (rapidfuzz `Levenshtein.editops`, edlib `task="path"`, bio
  *      `Aligner::global(a, b).operations`), unit costs only. -------------------------------------------------------------
  * For every pair i of a pairwise batch (a->count == b->count, else swh_invalid_argument_k):
@@ -573,7 +607,7 @@ swh_status_t swh_sw_pairs_sharded(swh_sw_t engine, swh_scope_t scope, swh_sharde
 /* ---- Introspection: `log_stringzilla_metadata` (utils.rs:78-92). --------------------------- */
 const char *swh_version(void);
 /* Comma-separated capability string, e.g. "gfx950,hip,wavefront,bitparallel,banded,utf8,...";
- * "topk" when the swh_levenshtein_topk_* calls are present, "align" when the swh_levenshtein_align_* calls are,
+ * "topk" when the swh_levenshtein_topk_* calls are present, "within" when the swh_levenshtein_within_* calls are, "align" when the swh_levenshtein_align_* calls are,
  * "infix" when the swh_levenshtein_infix_* calls are, "osa" when the swh_levenshtein_osa_* calls are,
  * "lcs" when the swh_levenshtein_lcs_* calls are, "jaro" when the swh_levenshtein_jaro_* calls are. */
 const char *swh_capabilities(void);

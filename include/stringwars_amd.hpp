@@ -367,6 +367,26 @@ public:
         swh_status_t status__ = swh_levenshtein_topk_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, k, bound, indices, distances, &err);
         check(status__, err);
     }
+    /// Range search (swh_levenshtein_within_*): every candidate with d <= bound of every query, as CSR -- row i at entries
+    /// [row_offsets[i], row_offsets[i + 1]) of `indices` / `distances`, ascending by candidate. `row_offsets` (queries.count + 1, host or
+    /// device) is always written; the arrays (`capacity` entries each, host or device) only if the total fits: a caller compares
+    /// row_offsets[count] with `capacity` and calls again with larger arrays. nullptr, nullptr, 0 is the counting call.
+    void within(const DeviceScope &scope, const BytesTapeView &queries, const BytesTapeView *candidates, uint32_t bound, size_t *row_offsets,
+                uint32_t *indices, uint32_t *distances, size_t capacity) const {
+        const char *err = nullptr;
+        swh_tape_u64_t q = queries.c(), c = candidates ? candidates->c() : q;
+        auto fn = utf8_ ? swh_levenshtein_utf8_within_u64tape : swh_levenshtein_within_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &q, candidates ? &c : nullptr, bound, row_offsets, indices, distances, capacity, &err);
+        check(status__, err);
+    }
+    void within(const DeviceScope &scope, const PreparedTape &queries, const PreparedTape *candidates, uint32_t bound, size_t *row_offsets,
+                uint32_t *indices, uint32_t *distances, size_t capacity) const {
+        const char *err = nullptr;
+        swh_prepared_view_t q = queries.c(), c = candidates ? candidates->c() : q;
+        swh_status_t status__ = swh_levenshtein_within_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, bound, row_offsets, indices,
+                                                                distances, capacity, &err);
+        check(status__, err);
+    }
     /// `compute_into` over every GPU of a multi-device scope: each device fills its rows of the matrix.
     void compute_into(const DeviceScope &scope, const ShardedCross &product, size_t *matrix, size_t row_stride_bytes = 0) const {
         const char *err = nullptr;

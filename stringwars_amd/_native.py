@@ -181,6 +181,9 @@ SIGNATURES = {
     "swh_levenshtein_topk_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_size_t, C.c_uint32, _P, _P, _ERR]),
     "swh_levenshtein_utf8_topk_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_size_t, C.c_uint32, _P, _P, _ERR]),
     "swh_levenshtein_topk_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_size_t, C.c_uint32, _P, _P, _ERR]),
+    "swh_levenshtein_within_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_utf8_within_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_within_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_uint32, _P, _P, _P, C.c_size_t, _ERR]),
     "swh_levenshtein_align_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, _P, C.c_size_t, _ERR]),
     "swh_levenshtein_utf8_align_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, _P, C.c_size_t, _ERR]),
     "swh_levenshtein_align_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_uint32, _P, _P, _P, C.c_size_t, _ERR]),

@@ -13,6 +13,7 @@
 #include <new>
 
 #include "common.hpp"
+#include "within.hpp"
 #include "align.hpp"
 #include "infix.hpp"
 #include "osa.hpp"
@@ -1176,7 +1177,7 @@ static void free_align_scratch(const Scope *scope) {
 extern "C" {
 
 const char *swh_version(void) { return "0.1.0"; }
-const char *swh_capabilities(void) { return "gfx950,hip,wavefront,bitparallel,tiled,banded,utf8,bounded,nw-linear,nw-affine,sw-linear,sw-affine,cross,prepared,topk,align,infix,osa,lcs,jaro,multi-gpu-rccl"; }
+const char *swh_capabilities(void) { return "gfx950,hip,wavefront,bitparallel,tiled,banded,utf8,bounded,nw-linear,nw-affine,sw-linear,sw-affine,cross,prepared,topk,within,align,infix,osa,lcs,jaro,multi-gpu-rccl"; }
 
 static swh_status_t scope_init(int device, void *stream, bool borrow, swh_scope_t *out, const char **error) {
     if (!out) return fail(error, swh_invalid_argument_k, "null scope pointer");
@@ -1258,6 +1259,7 @@ swh_status_t swh_scope_free(swh_scope_t handle) {
     if (scope->stage) (void)hipFree(scope->stage);
     if (scope->boundary) (void)hipFree(scope->boundary);
     if (scope->topk_scratch) (void)hipFree(scope->topk_scratch);
+    if (scope->within_out) (void)hipFree(scope->within_out);
     free_align_scratch(scope);
     if (scope->plan_host) (void)hipHostFree(scope->plan_host);
     if (scope->summary_host) (void)hipHostFree(scope->summary_host);
@@ -2082,6 +2084,283 @@ swh_status_t swh_levenshtein_topk_prepared(swh_levenshtein_t e, swh_scope_t s, c
     HoldSynchronous mode(scope);
     TopkRequest r{pq, pc, queries->first, queries->count, cc->first, cc->count, (uint32_t)k, bound, indices, distances};
     return topk_run(scope, (Engine *)e, r, error);
+}
+
+// ---- range search (within.hip) ---------------------------------------------------------------------------------------------------------
+// Every candidate within `bound` of every query, as CSR. The routes are top-k's: word-sized byte strings on unit costs run the fused
+// kernel (k_cross_within, the calls top-k gives to k_cross_topk), everything else the general path (slices of a dense matrix scored by the
+// ordinary cross-product routes). Both count first, scan the counts into the row offsets on the device, read the total (8 bytes) and
+// fill only if the caller's arrays hold it.
+// STRINGWARS_AMD_WITHIN_PRUNE=0 (test library): the fused kernel walks every chunk, also those the length gap rules out
+static uint32_t within_prune() {
+    static const uint32_t on = [] { const char *e = test_hook("STRINGWARS_AMD_WITHIN_PRUNE"); return !e || atoi(e) != 0 ? 1u : 0u; }();
+    return on;
+}
+// STRINGWARS_AMD_WITHIN_ROUTE=select (test library): every search on the general path
+static bool within_force_select() {
+    static const bool on = [] { const char *e = test_hook("STRINGWARS_AMD_WITHIN_ROUTE"); return e && !strcmp(e, "select"); }();
+    return on;
+}
+// STRINGWARS_AMD_WITHIN_SLICES=n (test library): the fused kernel's candidate slices per query block (at most one per chunk)
+static uint64_t within_slices_hook() {
+    static const uint64_t n = [] { const char *e = test_hook("STRINGWARS_AMD_WITHIN_SLICES"); return e && atoll(e) > 0 ? (uint64_t)atoll(e) : 0; }();
+    return n;
+}
+
+struct WithinRequest {
+    const Prepared *pq, *pc;
+    size_t q_first, q_count, c_first, c_count;
+    uint32_t bound;
+    size_t *row_offsets;
+    uint32_t *indices, *distances;
+    size_t capacity;
+};
+
+static swh_status_t within_run(Scope *scope, const Engine *engine, const WithinRequest &r, const char **error) {
+    static_assert(sizeof(size_t) == sizeof(uint64_t), "row offsets are scanned as 64-bit words");
+    harvest_timing(scope, false);
+    scope->stamps_used = 0;
+    scope->last_timing = swh_timing_t{};
+    const uint64_t nq = r.q_count, nc = r.c_count;
+    try {
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        const bool dev_o = is_device_pointer(r.row_offsets), dev_i = is_device_pointer(r.indices), dev_d = is_device_pointer(r.distances);
+        if (nq == 0 || nc == 0) {   // no row, or every row empty
+            const size_t bytes = (nq + 1) * sizeof(size_t);
+            if (dev_o) {
+                SWH_HIP_CHECK(hipMemsetAsync(r.row_offsets, 0, bytes, stream));
+                SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            } else {
+                memset(r.row_offsets, 0, bytes);
+            }
+            return swh_success_k;
+        }
+        const bool utf8 = r.pq->utf8 && !(r.pq->ascii && r.pc->ascii && r.pq->off64 == r.pc->off64);
+        const size_t ow = r.pq->off64 ? 8 : 4;
+        // the offsets are complete on the device: the total decides the fill, the rest goes to a host caller
+        auto read_total = [&](const uint64_t *offs) {
+            uint64_t total = 0;
+            SWH_HIP_CHECK(hipMemcpyAsync(&total, offs + nq, sizeof total, hipMemcpyDeviceToHost, stream));
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            return total;
+        };
+        auto finish_offsets = [&](const uint64_t *offs) {
+            if (!dev_o) SWH_HIP_CHECK(hipMemcpyAsync(r.row_offsets, offs, (nq + 1) * sizeof(size_t), hipMemcpyDeviceToHost, stream));
+        };
+        // where the fill pass writes: the caller's device arrays, or staging for its host arrays
+        uint32_t *ind = nullptr, *dist = nullptr;
+        auto stage_outputs = [&](uint64_t total) {
+            const size_t need = (dev_i ? 0 : pad(total * 4)) + (dev_d ? 0 : pad(total * 4));
+            ensure(scope->within_out, scope->within_out_bytes, need);
+            Carver oc{scope->within_out, 0, scope->within_out_bytes};
+            ind = dev_i ? r.indices : oc.take<uint32_t>(total);
+            dist = dev_d ? r.distances : oc.take<uint32_t>(total);
+        };
+        auto finish_outputs = [&](uint64_t total) {
+            if (!dev_i) SWH_HIP_CHECK(hipMemcpyAsync(r.indices, ind, total * 4, hipMemcpyDeviceToHost, stream));
+            if (!dev_d) SWH_HIP_CHECK(hipMemcpyAsync(r.distances, dist, total * 4, hipMemcpyDeviceToHost, stream));
+        };
+
+        CallSpec whole{};   // the dense cross-product of the two views, as run_call_on would route it
+        whole.a.count = nq; whole.b.count = nc; whole.cross = true; whole.bound = r.bound; whole.pa = r.pq; whole.pb = r.pc;
+        const bool fused = !within_force_select() && !utf8 && engine->algorithm == swh_algorithm_auto_k && r.pq->off64 == r.pc->off64 &&
+                           pick_route(scope, engine, whole, false, dev_i, call_lengths(scope, engine, whole, false)).route == kRouteCrossShort;
+        if (fused) {
+            // ---- fused: top-k's slicing (~32 items per compute unit); a count and a start per (row, slice) stay under 256 MB -----------
+            const uint64_t qblocks = (nq + 15) / 16, chunks = (nc + 63) / 64;
+            const uint64_t target = (uint64_t)scope->compute_units * 32;
+            uint64_t slices = std::min<uint64_t>(std::max<uint64_t>((target + qblocks - 1) / qblocks, 1), chunks);
+            slices = std::max<uint64_t>(1, std::min<uint64_t>(slices, ((uint64_t)256 << 20) / (nq * 12)));
+            if (within_slices_hook()) slices = std::min<uint64_t>(within_slices_hook(), chunks);
+            const uint64_t slice_chunks = (chunks + slices - 1) / slices;
+            slices = (chunks + slice_chunks - 1) / slice_chunks;
+            const uint64_t n_counts = nq * slices, tiles = (n_counts + kWithinScanTile - 1) / kWithinScanTile;
+            const size_t need = pad(n_counts * 4) + pad(n_counts * 8) + pad(tiles * 8) + (dev_o ? 0 : pad((nq + 1) * 8));
+            ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
+            Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
+            WithinLaunch w{};
+            w.a = prepared_view(r.pq, false, r.q_first, nq); w.b = prepared_view(r.pc, false, r.c_first, nc);
+            w.off64 = r.pq->off64; w.slices = (uint32_t)slices; w.bound = r.bound; w.prune = within_prune(); w.slice_chunks = slice_chunks;
+            w.counts = sc.take<uint32_t>(n_counts);
+            uint64_t *starts = sc.take<uint64_t>(n_counts), *block_sums = sc.take<uint64_t>(tiles);
+            uint64_t *offs = dev_o ? (uint64_t *)r.row_offsets : sc.take<uint64_t>(nq + 1);
+            w.starts = starts;
+            scope->summary_slot = 0;
+            launch_cross_within(scope, w, false);
+            launch_within_offsets(scope, w.counts, nq, (uint32_t)slices, block_sums, starts, offs);
+            const uint64_t total = read_total(offs);
+            const CallSummary sm = scope->summary_host[0];
+            if (!sm.violation) {
+                finish_offsets(offs);
+                if (total && total <= r.capacity) {
+                    stage_outputs(total);
+                    w.total = total; w.indices = ind; w.distances = dist;
+                    launch_cross_within(scope, w, true);
+                    finish_outputs(total);
+                }
+                SWH_HIP_CHECK(hipStreamSynchronize(stream));
+                if (scope->profiling && scope->stamps_used) {
+                    collect_timing(scope);
+                    // the search is named after its walk, also where a tiny call's scan takes longer: the longer of the two passes
+                    swh_timing_t &t = scope->last_timing;
+                    t.dominant_ms = 0;
+                    for (size_t i = 0; i < scope->stamps_used; ++i) {
+                        float ms = 0;
+                        if (!strcmp(scope->stamps[i].name, "cross_within")) (void)hipEventElapsedTime(&ms, scope->stamps[i].start, scope->stamps[i].stop);
+                        if (ms > t.dominant_ms) t.dominant_ms = ms;
+                    }
+                    snprintf(t.dominant_name, sizeof t.dominant_name, "cross_within");
+                    add_to_totals(scope->totals, scope->last_timing);
+                }
+                scope->last_timing.cells = sm.cells;
+                // the tapes, a count and a start per (row, slice), the row offsets and the hits
+                scope->last_timing.bytes = r.pq->total_bytes + r.pc->total_bytes + (nq + nc) * ow + n_counts * 12 + (nq + 1) * 8 +
+                                           (total <= r.capacity ? total * 8 : 0);
+                return swh_success_k;
+            }
+            // a string longer than the kernel takes (the memory of a prepared tape changed since it was measured): the general path
+            scope->stamps_used = 0;
+            scope->last_timing = swh_timing_t{};
+        }
+
+        // ---- general path: top-k's blocking -- query blocks of at most 2^18 rows x candidate slices of at most 2^26 pairs, scored twice ------
+        const uint64_t q_step = std::min<uint64_t>(nq, (uint64_t)1 << 18);
+        const uint64_t c_step = std::max<uint64_t>(1, std::min<uint64_t>(nc, ((uint64_t)1 << 26) / q_step));
+        const uint64_t tiles = (nq + kWithinScanTile - 1) / kWithinScanTile;
+        const size_t need = pad(q_step * c_step * 4) + pad(nq * 4) + pad(nq * 8) + pad(tiles * 8) + (dev_o ? 0 : pad((nq + 1) * 8));
+        ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
+        Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
+        uint32_t *matrix = sc.take<uint32_t>(q_step * c_step);
+        uint32_t *counts = sc.take<uint32_t>(nq);
+        uint64_t *cursors = sc.take<uint64_t>(nq), *block_sums = sc.take<uint64_t>(tiles);
+        uint64_t *offs = dev_o ? (uint64_t *)r.row_offsets : sc.take<uint64_t>(nq + 1);
+        const swh_timing_totals_t totals_before = scope->totals;
+        swh_timing_t sum{};
+        char scoring_name[64] = "";
+        uint64_t total = 0;
+        auto time_own_kernels = [&](uint32_t launched) {   // the compaction kernels launched since the last scoring call
+            if (!scope->profiling) return;
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            collect_timing(scope);
+            sum.total_ms += scope->last_timing.total_ms; sum.compute_ms += scope->last_timing.compute_ms; sum.kernels += launched;
+            scope->stamps_used = 0;
+        };
+        auto sweep = [&](bool fill) -> swh_status_t {
+            for (uint64_t q0 = 0; q0 < nq; q0 += q_step) {
+                const uint64_t rows = std::min<uint64_t>(q_step, nq - q0);
+                for (uint64_t c0 = 0; c0 < nc; c0 += c_step) {
+                    const uint64_t columns = std::min<uint64_t>(c_step, nc - c0);
+                    CallSpec spec{};
+                    spec.a = HostTape{nullptr, nullptr, (size_t)rows, 0};
+                    spec.b = HostTape{nullptr, nullptr, (size_t)columns, 0};
+                    spec.cross = true; spec.utf8 = r.pq->utf8; spec.bound = r.bound;
+                    spec.out = matrix; spec.out_stride = 4; spec.row_stride = columns * 4; spec.out64 = false;
+                    spec.pa = r.pq; spec.pb = r.pc; spec.a_first = r.q_first + q0; spec.b_first = r.c_first + c0;
+                    const swh_status_t status = run_call_on(scope, engine, spec, error);
+                    if (status != swh_success_k) return status;
+                    const swh_timing_t &dp = scope->last_timing;
+                    if (!fill) { sum.cells += dp.cells; sum.bytes += dp.bytes; }   // (the second walk of the same pairs is not counted again)
+                    sum.total_ms += dp.total_ms; sum.compute_ms += dp.compute_ms; sum.kernels += dp.kernels;
+                    if (dp.dominant_ms > sum.dominant_ms) { sum.dominant_ms = dp.dominant_ms; snprintf(scoring_name, sizeof scoring_name, "%s", dp.dominant_name); }
+                    scope->stamps_used = 0;
+                    scope->stamps_pending = false;
+                    if (fill) launch_within_fill(scope, matrix, rows, columns, c0, r.bound, cursors + q0, total, ind, dist);
+                    else launch_within_count(scope, matrix, rows, columns, r.bound, counts + q0);
+                    time_own_kernels(1);
+                }
+            }
+            return swh_success_k;
+        };
+        SWH_HIP_CHECK(hipMemsetAsync(counts, 0, nq * 4, stream));
+        swh_status_t status = sweep(false);
+        if (status != swh_success_k) return status;
+        launch_within_offsets(scope, counts, nq, 1, block_sums, cursors, offs);
+        time_own_kernels(2);
+        total = read_total(offs);
+        finish_offsets(offs);
+        if (total && total <= r.capacity) {
+            stage_outputs(total);
+            if ((status = sweep(true)) != swh_success_k) return status;
+            finish_outputs(total);
+        }
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        scope->summary_pending = false;
+        scope->stamps_pending = false;
+        // the search as one call: its name says which path ran and which kernel scored the pairs
+        snprintf(sum.dominant_name, sizeof sum.dominant_name, "within_select/%s", scoring_name);
+        scope->last_timing = sum;
+        if (scope->profiling) {
+            scope->totals = totals_before;
+            add_to_totals(scope->totals, sum);
+        }
+        return swh_success_k;
+    } catch (const HipFailure &f) {
+        return fail_hip(error, f);
+    } catch (const std::bad_alloc &) {
+        return fail(error, swh_bad_alloc_k, "host allocation failed");
+    }
+}
+
+static swh_status_t within_checks(swh_levenshtein_t e, swh_scope_t s, size_t candidates, uint32_t bound, const size_t *row_offsets,
+                                  const uint32_t *indices, const uint32_t *distances, size_t capacity, const char **error) {
+    if (!s || !e) return fail(error, swh_invalid_argument_k, "null scope or engine");
+    if (((Engine *)e)->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (bound == SWH_UNBOUNDED) return fail(error, swh_invalid_argument_k, "a range search needs a bound: without one it is the dense cross-product");
+    if (candidates >= 0xFFFFFFFFull) return fail(error, swh_unsupported_length_k, "2^32 - 1 candidates or more");
+    if (!row_offsets) return fail(error, swh_invalid_argument_k, "null row_offsets");
+    if (!indices != !distances) return fail(error, swh_invalid_argument_k, "indices and distances must both be given, or neither");
+    if (!indices && capacity) return fail(error, swh_invalid_argument_k, "a capacity without arrays: the counting call passes NULL, NULL, 0");
+    return swh_success_k;
+}
+
+static swh_status_t within_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *q, const swh_tape_u64_t *c, bool utf8, uint32_t bound,
+                                 size_t *row_offsets, uint32_t *indices, uint32_t *distances, size_t capacity, const char **error) {
+    if (!q) return fail(error, swh_invalid_argument_k, "null tape");
+    const swh_tape_u64_t *cc = c ? c : q;
+    swh_status_t status = within_checks(e, s, cc->count, bound, row_offsets, indices, distances, capacity, error);
+    if (status != swh_success_k) return status;
+    Scope *scope = (Scope *)s;
+    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
+    HoldSynchronous mode(scope);
+    // raw tapes are made resident and measured for the call, as for top-k: the route is chosen on lengths that are known
+    PreparedOwner pq, pc;
+    if (q->count) {
+        status = prepare_tape(scope, SWH_TAPE(q, 1), utf8, (swh_prepared_t *)&pq.p, error);
+        if (status != swh_success_k) return status;
+        if (c && c->count) {
+            status = prepare_tape(scope, SWH_TAPE(c, 1), utf8, (swh_prepared_t *)&pc.p, error);
+            if (status != swh_success_k) return status;
+        }
+    }
+    WithinRequest r{pq.p, c ? pc.p : pq.p, 0, q->count, 0, cc->count, bound, row_offsets, indices, distances, capacity};
+    return within_run(scope, (Engine *)e, r, error);
+}
+swh_status_t swh_levenshtein_within_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries, const swh_tape_u64_t *candidates,
+                                            uint32_t bound, size_t *row_offsets, uint32_t *indices, uint32_t *distances, size_t capacity,
+                                            const char **error) {
+    return within_tapes(e, s, queries, candidates, false, bound, row_offsets, indices, distances, capacity, error);
+}
+swh_status_t swh_levenshtein_utf8_within_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries,
+                                                 const swh_tape_u64_t *candidates, uint32_t bound, size_t *row_offsets, uint32_t *indices,
+                                                 uint32_t *distances, size_t capacity, const char **error) {
+    return within_tapes(e, s, queries, candidates, true, bound, row_offsets, indices, distances, capacity, error);
+}
+swh_status_t swh_levenshtein_within_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *queries,
+                                             const swh_prepared_view_t *candidates, uint32_t bound, size_t *row_offsets, uint32_t *indices,
+                                             uint32_t *distances, size_t capacity, const char **error) {
+    if (!queries || !queries->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
+    const swh_prepared_view_t *cc = (candidates && candidates->tape) ? candidates : queries;
+    if (!view_fits(queries) || !view_fits(cc)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
+    const Prepared *pq = (const Prepared *)queries->tape, *pc = (const Prepared *)cc->tape;
+    swh_status_t status = within_checks(e, s, cc->count, bound, row_offsets, indices, distances, capacity, error);
+    if (status != swh_success_k) return status;
+    Scope *scope = (Scope *)s;
+    if ((status = check_prepared_pair(scope, pq, pc, error)) != swh_success_k) return status;
+    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
+    HoldSynchronous mode(scope);
+    WithinRequest r{pq, pc, queries->first, queries->count, cc->first, cc->count, bound, row_offsets, indices, distances, capacity};
+    return within_run(scope, (Engine *)e, r, error);
 }
 
 // ---- alignments (align.hip) ----------------------------------------------------------------------------------------------------------

@@ -394,6 +394,10 @@ struct Scope {
     // cross-product calls of a search's general path carve for themselves
     char *topk_scratch = nullptr;
     size_t topk_scratch_bytes = 0;
+    // range searches (within.hip) share topk_scratch for their counts and matrices; `within_out` stages the hits of a call whose
+    // `indices` / `distances` are host memory -- sized once the count pass has given the total, while topk_scratch is in use
+    char *within_out = nullptr;
+    size_t within_out_bytes = 0;
     Plan *plan_host = nullptr;  // pinned
     char *plan_area = nullptr;  // device: hist | cursor | partials | plan, zeroed once (the scan kernel re-zeroes hist)
     uint32_t *plan_hist = nullptr, *plan_cursor = nullptr, *plan_leftover = nullptr;   // carved from plan_area at scope creation

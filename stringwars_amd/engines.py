@@ -25,7 +25,7 @@ from . import _native as N
 __all__ = [
     "DeviceScope", "Strs", "DeviceTape", "PreparedTape", "ShardedPairs", "shard_cuts", "LevenshteinDistances", "LevenshteinDistancesUTF8",
     "NeedlemanWunschScores", "SmithWatermanScores", "edit_distance", "StringWarsError", "UNBOUNDED", "TOPK_MAX",
-    "ALIGN_MAX_CELLS", "Alignments", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "OSA_MAX_SHORTER", "LCS_MAX_SHORTER",
+    "ALIGN_MAX_CELLS", "Alignments", "RangeMatches", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "OSA_MAX_SHORTER", "LCS_MAX_SHORTER",
     "JARO_MAX_LENGTH",
 ]
 
@@ -405,6 +405,60 @@ class ShardedCross:
 TapeLike = Union[Strs, DeviceTape, PreparedTape, Sequence[Union[bytes, str]]]
 
 
+class RangeMatches:
+    """The result of ``LevenshteinDistances.within``: for every query the candidates within the bound, as CSR.
+
+    Row ``i`` is ``indices[offsets[i]:offsets[i + 1]]`` with the true distances in ``distances`` at the same places, ascending by
+    candidate index (callers who want them by distance sort a row, or use ``topk``). ``offsets`` is uint64 with one entry more than
+    there are queries. Arrays that live on the device (``out=`` tensors) are brought to the host when a row or the pairs are asked for.
+    The result of a counting call (``out=(offsets, None, None)``) has ``offsets`` and ``counts`` only: ``indices`` and ``distances`` are None."""
+
+    def __init__(self, offsets, indices, distances):
+        self.offsets, self.indices, self.distances = offsets, indices, distances
+        if len(offsets) < 1 or (indices is None) != (distances is None) or (indices is not None and len(indices) != len(distances)):
+            raise ValueError("offsets needs at least one entry, indices and distances the same length (or both None: counted, not filled)")
+
+    @staticmethod
+    def _host(array, dtype):
+        if hasattr(array, "cpu"):   # torch.Tensor
+            array = array.cpu().numpy()
+        array = np.asarray(array)   # (a signed tensor of the same width holds the same bits: torch has no uint64 arithmetic)
+        return array.view(dtype) if array.dtype.itemsize == np.dtype(dtype).itemsize else array.astype(dtype)
+
+    def __len__(self) -> int:
+        """The number of queries (rows)."""
+        return len(self.offsets) - 1
+
+    @property
+    def counts(self) -> np.ndarray:
+        """Hits per query."""
+        return np.diff(self._host(self.offsets, np.uint64)).astype(np.uint64)
+
+    def row(self, i: int):
+        """``(indices, distances)`` of query ``i``."""
+        if not -len(self) <= i < len(self):
+            raise IndexError("query index out of range")
+        i %= len(self)
+        if self.indices is None:
+            raise ValueError("a counting call holds no rows")
+        offsets = self._host(self.offsets, np.uint64)
+        first, last = int(offsets[i]), int(offsets[i + 1])
+        return self._host(self.indices, np.uint32)[first:last], self._host(self.distances, np.uint32)[first:last]
+
+    def pairs(self, upper: bool = False):
+        """Flat ``(i, j, d)`` arrays of every hit, in row order. ``upper=True`` keeps ``i < j``: each unordered pair of a self-search
+        once and no string with itself, which is what deduplication wants."""
+        if self.indices is None:
+            raise ValueError("a counting call holds no pairs")
+        total = int(self._host(self.offsets, np.uint64)[-1])
+        i = np.repeat(np.arange(len(self), dtype=np.uint64), self.counts.astype(np.int64))
+        j, d = self._host(self.indices, np.uint32)[:total], self._host(self.distances, np.uint32)[:total]
+        if upper:
+            keep = i < j
+            return i[keep], j[keep], d[keep]
+        return i, j, d
+
+
 class Alignments:
     """The result of ``LevenshteinDistances.align``: a tape of edit operations, one string of op bytes per pair.
 
@@ -726,6 +780,76 @@ class LevenshteinDistances(_Engine):
             del keep_q, keep_c
         N.check(status, err)
         return indices, distances
+
+    def within(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None, *, bound: int,
+               capacity: Optional[int] = None, out=None) -> "RangeMatches":
+        """Every candidate within ``bound`` edits of every query (``swh_levenshtein_within_*``): a :class:`RangeMatches`, rows in
+        candidate order with the true distances. ``candidates=None`` searches the queries themselves (diagonal and both orientations
+        included; ``pairs(upper=True)`` of the result is the deduplication form). Nobody knows the number of hits in advance: the
+        first call is made with room for ``capacity`` hits (default ``max(1024, 4 * (len(queries) + len(candidates)))``) and, only
+        if they did not fit, a second with the exact size the first one counted. ``out=(offsets, indices, distances)`` fills given
+        arrays or device tensors instead (``len(queries) + 1`` 64-bit offsets; 32-bit indices and distances of equal size); if they
+        are too small the offsets are still written and ``ValueError`` is raised; ``out=(offsets, None, None)`` is the counting
+        call (one walk, the offsets alone). Tapes are handled as in ``topk``.
+        rapidfuzz: ``process.extract(q, candidates, scorer=Levenshtein.distance, score_cutoff=bound, limit=None)`` per query."""
+        if scope is None:
+            raise ValueError("a DeviceScope is required")
+        if bound is None or not 0 <= int(bound) < N.UNBOUNDED:
+            raise ValueError("a range search needs a bound; the unbounded form is the dense cross-product")
+        queries = _as_tape(queries)
+        if candidates is not None:
+            candidates = _as_tape(candidates)
+        count = len(queries)
+        prepared = isinstance(queries, PreparedTape) or isinstance(candidates, PreparedTape)
+        if prepared:
+            if not isinstance(queries, PreparedTape) or not (candidates is None or isinstance(candidates, PreparedTape)):
+                raise TypeError("both tapes of a call must be prepared, or neither")
+            if self._utf8 != queries.utf8:
+                raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
+            vq, vc = queries.view(), (candidates.view() if candidates is not None else None)
+        else:
+            tq, _, keep_q = _c_tape(queries, want64=True)
+            tc, _, keep_c = _c_tape(candidates, want64=True) if candidates is not None else (None, None, None)
+
+        def call(offsets, indices, distances, room):
+            err = C.c_char_p()
+            tail = (C.c_uint32(int(bound)), C.c_void_p(_pointer(offsets)), C.c_void_p(_pointer(indices)), C.c_void_p(_pointer(distances)),
+                    int(room), C.byref(err))
+            if prepared:
+                status = N.lib.swh_levenshtein_within_prepared(self._handle, scope.handle, C.byref(vq), C.byref(vc) if vc is not None else None, *tail)
+            else:
+                fn = N.lib.swh_levenshtein_utf8_within_u64tape if self._utf8 else N.lib.swh_levenshtein_within_u64tape
+                status = fn(self._handle, scope.handle, C.byref(tq), C.byref(tc) if tc is not None else None, *tail)
+            N.check(status, err)
+            return int(offsets[count])
+
+        if out is not None:
+            offsets, indices, distances = out
+            room = 0 if indices is None else int(indices.numel() if hasattr(indices, "numel") else indices.size)
+            for array, width, entries in ((offsets, 8, count + 1), (indices, 4, room), (distances, 4, room)):
+                if array is None:
+                    continue
+                size = int(array.numel() if hasattr(array, "numel") else array.size)
+                itemsize = array.element_size() if hasattr(array, "element_size") else array.dtype.itemsize
+                contiguous = array.is_contiguous() if hasattr(array, "is_contiguous") else array.flags.c_contiguous
+                if itemsize != width or size != entries or not contiguous:
+                    raise ValueError("out needs len(queries) + 1 64-bit offsets and two contiguous 32-bit arrays of one size")
+            if (indices is None) != (distances is None):
+                raise ValueError("out needs both arrays, or None for both (the counting call)")
+            total = call(offsets, indices, distances, room)
+            if indices is None:
+                return RangeMatches(offsets, None, None)
+            if total > room:
+                raise ValueError("out holds %d hits, the search found %d (the offsets are written)" % (room, total))
+            return RangeMatches(offsets, indices[:total], distances[:total])
+        room = max(1024, 4 * (count + len(candidates if candidates is not None else queries))) if capacity is None else max(int(capacity), 1)
+        offsets = np.zeros(count + 1, dtype=np.uint64)
+        indices, distances = np.empty(room, dtype=np.uint32), np.empty(room, dtype=np.uint32)
+        total = call(offsets, indices, distances, room)
+        if total > room:
+            indices, distances = np.empty(total, dtype=np.uint32), np.empty(total, dtype=np.uint32)
+            call(offsets, indices, distances, total)
+        return RangeMatches(offsets, indices[:total], distances[:total])
 
     def align(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None, bound: Optional[int] = None) -> "Alignments":
         """The edit operations of every pair ``(a[i], b[i])`` on unit costs (``swh_levenshtein_align_*``): an :class:`Alignments` with

@@ -119,6 +119,9 @@ extern "C" {
     fn swh_levenshtein_topk_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, k: usize, bound: u32, indices: *mut u32, distances: *mut u32, error: Err) -> c_int;
     fn swh_levenshtein_utf8_topk_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, k: usize, bound: u32, indices: *mut u32, distances: *mut u32, error: Err) -> c_int;
     fn swh_levenshtein_topk_prepared(engine: Handle, scope: Handle, queries: *const PreparedView, candidates: *const PreparedView, k: usize, bound: u32, indices: *mut u32, distances: *mut u32, error: Err) -> c_int;
+    fn swh_levenshtein_within_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, bound: u32, row_offsets: *mut usize, indices: *mut u32, distances: *mut u32, capacity: usize, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_within_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, bound: u32, row_offsets: *mut usize, indices: *mut u32, distances: *mut u32, capacity: usize, error: Err) -> c_int;
+    fn swh_levenshtein_within_prepared(engine: Handle, scope: Handle, queries: *const PreparedView, candidates: *const PreparedView, bound: u32, row_offsets: *mut usize, indices: *mut u32, distances: *mut u32, capacity: usize, error: Err) -> c_int;
     fn swh_levenshtein_align_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, bound: u32, distances: *mut u32, ops_offsets: *mut usize, ops: *mut c_char, ops_capacity: usize, error: Err) -> c_int;
     fn swh_levenshtein_utf8_align_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, bound: u32, distances: *mut u32, ops_offsets: *mut usize, ops: *mut c_char, ops_capacity: usize, error: Err) -> c_int;
     fn swh_levenshtein_align_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, bound: u32, distances: *mut u32, ops_offsets: *mut usize, ops: *mut c_char, ops_capacity: usize, error: Err) -> c_int;
@@ -455,6 +458,22 @@ impl LevenshteinDistances {
         let mut message = ptr::null();
         check(unsafe { swh_levenshtein_topk_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64), k,
                                                     bound.unwrap_or(UNBOUNDED), indices.as_mut_ptr(), distances.as_mut_ptr(), &mut message) }, message)
+    }
+    /// Range search: every candidate within `bound` edits of every query (`process.extract(score_cutoff = bound, limit = None)` per
+    /// query), as CSR: row i is `indices` / `distances` `[row_offsets[i] .. row_offsets[i + 1])`, ascending by candidate; `None` = q x q.
+    /// `row_offsets` (`queries.len() + 1` entries) is always filled; the two arrays only if the total fits them. Returns the total:
+    /// a caller who gets more than `indices.len()` back calls again with larger arrays (two empty slices make the counting call).
+    pub fn within_into(&self, scope: &DeviceScope, queries: &BytesTapeView<u64>, candidates: Option<&BytesTapeView<u64>>, bound: u32,
+                       row_offsets: &mut [usize], indices: &mut [u32], distances: &mut [u32]) -> Result<usize, Error> {
+        assert!(row_offsets.len() > queries.len() && indices.len() == distances.len());
+        let tq = bytes_tape(queries);
+        let tc = candidates.map(bytes_tape);
+        let capacity = indices.len();
+        let (ind, dist) = if capacity == 0 { (ptr::null_mut(), ptr::null_mut()) } else { (indices.as_mut_ptr(), distances.as_mut_ptr()) };
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_within_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64), bound,
+                                                      row_offsets.as_mut_ptr(), ind, dist, capacity, &mut message) }, message)?;
+        Ok(row_offsets[queries.len()])
     }
     /// Alignments (`swh_levenshtein_align_*`): pair i's canonical edit script is `ops[offsets[i] .. offsets[i + 1])`, one `OP_*` byte per
     /// op, `distances[i] = min(d, bound + 1)`; `offsets` holds `a.len() + 1` entries and `ops` at least the two tapes' symbols.

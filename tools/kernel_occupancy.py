@@ -31,7 +31,9 @@ def waves_per_simd(vgprs, agprs=0):
 def kernels_of(obj):
     with tempfile.TemporaryDirectory() as tmp:
         fat, co = os.path.join(tmp, "fat"), os.path.join(tmp, "co")
-        done = subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", obj], capture_output=True, text=True)
+        # (with an output file: llvm-objcopy given the input alone rewrites it in place, and an object newer than an edited header is not rebuilt)
+        done = subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", obj, os.path.join(tmp, "copy.o")],
+                              capture_output=True, text=True)
         if done.returncode != 0 or not os.path.exists(fat) or os.path.getsize(fat) == 0:
             return {}
         subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}",
