@@ -1863,11 +1863,189 @@ swh_status_t swh_sw_cross_prepared(swh_sw_t e, swh_scope_t s, const swh_prepared
     return prepared_call(e, 2, s, a, b, true, SWH_UNBOUNDED, out, row_stride, error);
 }
 
+}  // extern "C"
+
+// ---- the synchronous two-tape calls: one front end ------------------------------------------------------------------------------------
+// Top-k and range searches, alignments, infix search and the scored families (OSA, LCS, Jaro) are synchronous on every scope:
+// outstanding asynchronous / pipelined work is joined first, and the call runs on the scope itself (not on a pipeline lane) with the
+// asynchronous mode held off until it returns. Every export runs its own null tests and argument checks in its own order -- which
+// refusal wins is its contract (DESIGN.md lists where the calls differ on purpose) -- and between them resolves its two sides here,
+// into the TapePair its *_run takes.
+struct TapePair {
+    const Prepared *pa = nullptr, *pb = nullptr;   // null where a raw call prepared nothing: every *_run returns before it looks at them
+    size_t a_first = 0, a_count = 0, b_first = 0, b_count = 0;
+};
+struct PreparedOwner {
+    Prepared *p = nullptr;
+    ~PreparedOwner() { free_prepared(p); }
+};
+static swh_status_t join_outstanding(Scope *scope, const char **error) {
+    if (!scope->async && !scope->pipelined) return swh_success_k;
+    return swh_scope_synchronize((swh_scope_t)scope, error);
+}
+
+struct HoldSynchronous {
+    Scope *scope = nullptr;
+    bool async = false, pipelined = false;
+    void hold(Scope *s) { scope = s; async = s->async; pipelined = s->pipelined; s->async = false; s->pipelined = false; }
+    ~HoldSynchronous() {
+        if (scope) { scope->async = async; scope->pipelined = pipelined; }
+    }
+};
+struct TwoTapeCall {
+    HoldSynchronous mode;             // declared first, so the scope's mode comes back last: after what the call prepared is freed
+    Scope *scope = nullptr;           // set once the call has begun
+    PreparedOwner owned_a, owned_b;   // what a raw call prepared: it lives as long as the call
+    TapePair pair;
+
+    // joins what is outstanding and holds the scope synchronous until the call returns
+    swh_status_t begin(swh_scope_t s, const char **error) {
+        const swh_status_t status = join_outstanding((Scope *)s, error);
+        if (status != swh_success_k) return status;
+        scope = (Scope *)s;
+        mode.hold(scope);
+        return swh_success_k;
+    }
+    // Raw tapes, after begin(): the sides named are made resident and measured for the call (prepare_tape: device tapes in place, host
+    // tapes uploaded; UTF-8 validated and decoded), so the route is chosen on lengths that are known, not believed. Without `b` the
+    // second side is the first. A call without pairs names no side: its pair keeps the counts and null tapes.
+    swh_status_t prepare(const swh_tape_u64_t *a, const swh_tape_u64_t *b, bool utf8, bool prepare_a, bool prepare_b, const char **error) {
+        pair = TapePair{nullptr, nullptr, 0, a->count, 0, (b ? b : a)->count};
+        swh_status_t status = swh_success_k;
+        if (prepare_a && (status = prepare_tape(scope, SWH_TAPE(a, 1), utf8, (swh_prepared_t *)&owned_a.p, error)) != swh_success_k) return status;
+        if (b && prepare_b && (status = prepare_tape(scope, SWH_TAPE(b, 1), utf8, (swh_prepared_t *)&owned_b.p, error)) != swh_success_k) return status;
+        pair.pa = owned_a.p; pair.pb = b ? owned_b.p : owned_a.p;
+        return swh_success_k;
+    }
+    // Prepared views, before the call's own checks: the null tests and the bounds of both. A missing b is a (the self-search, the
+    // self-product) where `b_optional`.
+    swh_status_t views(const swh_prepared_view_t *a, const swh_prepared_view_t *b, bool b_optional, const char **error) {
+        if (!a || !a->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
+        const swh_prepared_view_t *bb = (b && b->tape) ? b : (b_optional ? a : nullptr);
+        if (!bb) return fail(error, swh_invalid_argument_k, "null prepared view");
+        if (!view_fits(a) || !view_fits(bb)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
+        pair = TapePair{(const Prepared *)a->tape, (const Prepared *)bb->tape, a->first, a->count, bb->first, bb->count};
+        return swh_success_k;
+    }
+    // ... and after them: the two tapes go together and live on the scope's device, and the call begins
+    swh_status_t begin_on_views(swh_scope_t s, const char **error) {
+        const swh_status_t status = check_prepared_pair((Scope *)s, pair.pa, pair.pb, error);
+        return status != swh_success_k ? status : begin(s, error);
+    }
+};
+
+// What every *_run is wrapped in: the previous call's timing is harvested and this call's begins empty; a HIP or allocation failure
+// anywhere in `body` becomes the call's status.
+template <typename Body> static swh_status_t synchronous_run(Scope *scope, const char **error, Body body) {
+    harvest_timing(scope, false);
+    scope->stamps_used = 0;
+    scope->last_timing = swh_timing_t{};
+    try {
+        return body();
+    } catch (const HipFailure &f) {
+        return fail_hip(error, f);
+    } catch (const std::bad_alloc &) {
+        return fail(error, swh_bad_alloc_k, "host allocation failed");
+    }
+}
+
+// ---- the search planner: what top-k and the range search decide alike ---------------------------------------------------------------
+// Both searches run word-sized byte strings on unit costs through a fused kernel of their own (k_cross_topk, k_cross_within): the
+// searches a dense cross-product of the same views would run on k_cross_short (pick_route for prepared tapes). Everything else takes
+// the general path: the candidates in slices, each slice scored by the ordinary cross-product routes into a u32 matrix in scratch
+// (with the caller's bound, so long strings may take the banded kernel) and handed to the search's own kernels. What differs between
+// the two comes in as a value or a callback.
+// `force_select`: the search's STRINGWARS_AMD_*_ROUTE=select hook; `dev_out`: its results go to device memory
+static bool search_is_fused(const Scope *scope, const Engine *engine, const TapePair &p, uint32_t bound, bool force_select, bool dev_out) {
+    const bool utf8 = p.pa->utf8 && !(p.pa->ascii && p.pb->ascii && p.pa->off64 == p.pb->off64);
+    CallSpec whole{};   // the dense cross-product of the two views, as run_call_on would route it
+    whole.a.count = p.a_count; whole.b.count = p.b_count; whole.cross = true; whole.bound = bound; whole.pa = p.pa; whole.pb = p.pb;
+    return !force_select && !utf8 && engine->algorithm == swh_algorithm_auto_k && p.pa->off64 == p.pb->off64 &&
+           pick_route(scope, engine, whole, false, dev_out, call_lengths(scope, engine, whole, false)).route == kRouteCrossShort;
+}
+
+// The fused kernels' candidate slices per block of 16 queries: enough for ~32 items per compute unit (a few rounds of its 12 wave
+// slots: 65 536 x 1 M words ran top-k at 4.6 TCUPS with 16, 5.9 with 32), while what the search keeps per (row, slice) --
+// `row_slice_bytes` -- stays under 256 MB; at most one per chunk of 64 candidates. `forced`: a test hook's count, 0 without one.
+struct SearchSlices { uint64_t slices, slice_chunks; };
+static SearchSlices search_slices(uint64_t nq, uint64_t nc, uint64_t compute_units, uint64_t row_slice_bytes, uint64_t forced) {
+    const uint64_t qblocks = (nq + 15) / 16, chunks = (nc + 63) / 64;
+    const uint64_t target = compute_units * 32;
+    uint64_t slices = std::min<uint64_t>(std::max<uint64_t>((target + qblocks - 1) / qblocks, 1), chunks);
+    slices = std::max<uint64_t>(1, std::min<uint64_t>(slices, ((uint64_t)256 << 20) / (nq * row_slice_bytes)));
+    if (forced) slices = std::min<uint64_t>(forced, chunks);
+    const uint64_t slice_chunks = (chunks + slices - 1) / slices;
+    return SearchSlices{(chunks + slice_chunks - 1) / slice_chunks, slice_chunks};
+}
+
+// The general path: query blocks of at most 2^18 rows x candidate slices of at most 2^26 pairs (a 256 MB u32 matrix), and the search
+// reported as one call whose name says which path ran and which kernel scored the pairs.
+struct SearchSweep {
+    Scope *scope; const Engine *engine; const TapePair &pair; uint32_t bound;
+    uint64_t q_step, c_step;
+    swh_timing_totals_t totals_before;
+    swh_timing_t sum{};
+    char scoring_name[64] = "";
+
+    SearchSweep(Scope *s, const Engine *e, const TapePair &p, uint32_t bound_)
+        : scope(s), engine(e), pair(p), bound(bound_), q_step(std::min<uint64_t>(p.a_count, (uint64_t)1 << 18)),
+          c_step(std::max<uint64_t>(1, std::min<uint64_t>(p.b_count, ((uint64_t)1 << 26) / q_step))), totals_before(s->totals) {}
+
+    // One walk over the blocks. rows_begin(q0, rows) opens every block of queries, before its first slice is scored; each slice is then
+    // scored into `matrix` (q_step * c_step entries) and handed to block(q0, rows, c0, columns, last_slice) with the stamps reset.
+    // `counted`: the walk's cells and bytes go into the sum (a second walk of the same pairs: not again).
+    template <typename Rows, typename Block>
+    swh_status_t walk(uint32_t *matrix, bool counted, const char **error, Rows rows_begin, Block block) {
+        const uint64_t nq = pair.a_count, nc = pair.b_count;
+        for (uint64_t q0 = 0; q0 < nq; q0 += q_step) {
+            const uint64_t rows = std::min<uint64_t>(q_step, nq - q0);
+            rows_begin(q0, rows);
+            for (uint64_t c0 = 0; c0 < nc; c0 += c_step) {
+                const uint64_t columns = std::min<uint64_t>(c_step, nc - c0);
+                CallSpec spec{};
+                spec.a = HostTape{nullptr, nullptr, (size_t)rows, 0};
+                spec.b = HostTape{nullptr, nullptr, (size_t)columns, 0};
+                spec.cross = true; spec.utf8 = pair.pa->utf8; spec.bound = bound;
+                spec.out = matrix; spec.out_stride = 4; spec.row_stride = columns * 4; spec.out64 = false;
+                spec.pa = pair.pa; spec.pb = pair.pb; spec.a_first = pair.a_first + q0; spec.b_first = pair.b_first + c0;
+                const swh_status_t status = run_call_on(scope, engine, spec, error);
+                if (status != swh_success_k) return status;
+                const swh_timing_t &dp = scope->last_timing;
+                if (counted) { sum.cells += dp.cells; sum.bytes += dp.bytes; }
+                sum.total_ms += dp.total_ms; sum.compute_ms += dp.compute_ms; sum.kernels += dp.kernels;
+                if (dp.dominant_ms > sum.dominant_ms) { sum.dominant_ms = dp.dominant_ms; snprintf(scoring_name, sizeof scoring_name, "%s", dp.dominant_name); }
+                scope->stamps_used = 0;
+                scope->stamps_pending = false;
+                block(q0, rows, c0, columns, c0 + columns == nc);
+            }
+        }
+        return swh_success_k;
+    }
+    // with profiling on, the time of the `launched` kernels of the search's own since the last scoring call
+    void time_own_kernels(uint32_t launched) {
+        if (!scope->profiling) return;
+        SWH_HIP_CHECK(hipStreamSynchronize(scope->stream));
+        collect_timing(scope);
+        sum.total_ms += scope->last_timing.total_ms; sum.compute_ms += scope->last_timing.compute_ms; sum.kernels += launched;
+        scope->stamps_used = 0;
+    }
+    // the search as one call, "<search>_select/<scoring kernel>", once in the scope's totals
+    void close(const char *search) {
+        scope->summary_pending = false;
+        scope->stamps_pending = false;
+        snprintf(sum.dominant_name, sizeof sum.dominant_name, "%s_select/%s", search, scoring_name);
+        scope->last_timing = sum;
+        if (scope->profiling) {
+            scope->totals = totals_before;
+            add_to_totals(scope->totals, sum);
+        }
+    }
+};
+
+extern "C" {
 // ---- top-k search (topk.hip) ----------------------------------------------------------------------------------------------------------
-// Word-sized byte strings on unit costs run the fused kernel (k_cross_topk): the search a dense cross-product of the same views would run
-// on k_cross_short (pick_route for prepared tapes). Everything else takes the general path: the candidates in slices, each slice scored
-// by the ordinary cross-product routes into a u32 matrix in scratch (with the caller's bound, so long strings may take the banded
-// kernel), then folded into the running lists by k_topk_select.
+// The fused kernel keeps a list of k per (row, slice) and merges them; the general path folds each scored slice into the running
+// lists with k_topk_select.
 // STRINGWARS_AMD_TOPK_PRUNE=0 (test library): the fused kernel walks every chunk, also those the length bound rules out (the comparison knob)
 static uint32_t topk_prune() {
     static const uint32_t on = [] { const char *e = test_hook("STRINGWARS_AMD_TOPK_PRUNE"); return !e || atoi(e) != 0 ? 1u : 0u; }();
@@ -1879,62 +2057,43 @@ static bool topk_force_select() {
     return on;
 }
 
-struct TopkRequest {
-    const Prepared *pq, *pc;
-    size_t q_first, q_count, c_first, c_count;
-    uint32_t k, bound;
-    uint32_t *indices, *distances;
-};
-
-static swh_status_t topk_run(Scope *scope, const Engine *engine, const TopkRequest &r, const char **error) {
-    harvest_timing(scope, false);
-    scope->stamps_used = 0;
-    scope->last_timing = swh_timing_t{};
-    const uint64_t nq = r.q_count, nc = r.c_count, k = r.k;
-    if (nq == 0) return swh_success_k;
-    const bool utf8 = r.pq->utf8 && !(r.pq->ascii && r.pc->ascii && r.pq->off64 == r.pc->off64);
-    const uint64_t cap = r.bound == SWH_UNBOUNDED ? ~0ull : ((uint64_t)r.bound + 1) << 32;
-    const size_t out_bytes = nq * k * sizeof(uint32_t);
-    try {
+static swh_status_t topk_run(Scope *scope, const Engine *engine, const TapePair &p, uint32_t k32, uint32_t bound, uint32_t *indices,
+                             uint32_t *distances, const char **error) {
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t nq = p.a_count, nc = p.b_count, k = k32;
+        if (nq == 0) return swh_success_k;
+        const uint64_t cap = bound == SWH_UNBOUNDED ? ~0ull : ((uint64_t)bound + 1) << 32;
+        const size_t out_bytes = nq * k * sizeof(uint32_t);
         SWH_HIP_CHECK(hipSetDevice(scope->device));
         hipStream_t stream = scope->stream;
-        const bool dev_i = is_device_pointer(r.indices), dev_d = is_device_pointer(r.distances);
+        const bool dev_i = is_device_pointer(indices), dev_d = is_device_pointer(distances);
         if (nc == 0) {   // every row is padding
-            if (dev_i) SWH_HIP_CHECK(hipMemsetAsync(r.indices, 0xFF, out_bytes, stream)); else memset(r.indices, 0xFF, out_bytes);
-            if (dev_d) SWH_HIP_CHECK(hipMemsetAsync(r.distances, 0xFF, out_bytes, stream)); else memset(r.distances, 0xFF, out_bytes);
+            if (dev_i) SWH_HIP_CHECK(hipMemsetAsync(indices, 0xFF, out_bytes, stream)); else memset(indices, 0xFF, out_bytes);
+            if (dev_d) SWH_HIP_CHECK(hipMemsetAsync(distances, 0xFF, out_bytes, stream)); else memset(distances, 0xFF, out_bytes);
             SWH_HIP_CHECK(hipStreamSynchronize(stream));
             return swh_success_k;
         }
-        const size_t ow = r.pq->off64 ? 8 : 4;
+        const size_t ow = p.pa->off64 ? 8 : 4;
         auto finish_outputs = [&](uint32_t *ind, uint32_t *dist) {
-            if (!dev_i) SWH_HIP_CHECK(hipMemcpyAsync(r.indices, ind, out_bytes, hipMemcpyDeviceToHost, stream));
-            if (!dev_d) SWH_HIP_CHECK(hipMemcpyAsync(r.distances, dist, out_bytes, hipMemcpyDeviceToHost, stream));
+            if (!dev_i) SWH_HIP_CHECK(hipMemcpyAsync(indices, ind, out_bytes, hipMemcpyDeviceToHost, stream));
+            if (!dev_d) SWH_HIP_CHECK(hipMemcpyAsync(distances, dist, out_bytes, hipMemcpyDeviceToHost, stream));
             SWH_HIP_CHECK(hipStreamSynchronize(stream));
         };
 
-        CallSpec whole{};   // the dense cross-product of the two views, as run_call_on would route it
-        whole.a.count = nq; whole.b.count = nc; whole.cross = true; whole.bound = r.bound; whole.pa = r.pq; whole.pb = r.pc;
-        const bool fused = !topk_force_select() && !utf8 && engine->algorithm == swh_algorithm_auto_k && r.pq->off64 == r.pc->off64 &&
-                           pick_route(scope, engine, whole, false, dev_i, call_lengths(scope, engine, whole, false)).route == kRouteCrossShort;
-        if (fused) {
-            // ---- fused: slices enough for ~32 items per compute unit (a few rounds of its 12 wave slots: 65 536 x 1 M words ran at 4.6
-            // TCUPS with 16, 5.9 with 32); the partial lists stay under 256 MB ------------------------------------------------------------
-            const uint64_t qblocks = (nq + 15) / 16, chunks = (nc + 63) / 64;
-            const uint64_t target = (uint64_t)scope->compute_units * 32;
-            uint64_t slices = std::min<uint64_t>(std::max<uint64_t>((target + qblocks - 1) / qblocks, 1), chunks);
-            slices = std::max<uint64_t>(1, std::min<uint64_t>(slices, ((uint64_t)256 << 20) / (nq * k * 8)));
-            const uint64_t slice_chunks = (chunks + slices - 1) / slices;
-            slices = (chunks + slice_chunks - 1) / slice_chunks;
+        if (search_is_fused(scope, engine, p, bound, topk_force_select(), dev_i)) {
+            // ---- fused: a partial list of k (index, distance) words per (row, slice) ------------------------------------------------------
+            const SearchSlices cut = search_slices(nq, nc, scope->compute_units, k * 8, 0);
+            const uint64_t slices = cut.slices;
             const size_t need = (slices > 1 ? pad(nq * slices * k * 8) : 0) + (dev_i ? 0 : pad(out_bytes)) + (dev_d ? 0 : pad(out_bytes));
             ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
             Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
             TopkLaunch t{};
-            t.a = prepared_view(r.pq, false, r.q_first, nq); t.b = prepared_view(r.pc, false, r.c_first, nc);
-            t.off64 = r.pq->off64; t.k = (uint32_t)k; t.slices = (uint32_t)slices; t.prune = topk_prune();
-            t.slice_chunks = slice_chunks; t.cap = cap;
+            t.a = prepared_view(p.pa, false, p.a_first, nq); t.b = prepared_view(p.pb, false, p.b_first, nc);
+            t.off64 = p.pa->off64; t.k = (uint32_t)k; t.slices = (uint32_t)slices; t.prune = topk_prune();
+            t.slice_chunks = cut.slice_chunks; t.cap = cap;
             t.partial = slices > 1 ? sc.take<uint64_t>(nq * slices * k) : nullptr;
-            t.indices = dev_i ? r.indices : sc.take<uint32_t>(nq * k);
-            t.distances = dev_d ? r.distances : sc.take<uint32_t>(nq * k);
+            t.indices = dev_i ? indices : sc.take<uint32_t>(nq * k);
+            t.distances = dev_d ? distances : sc.take<uint32_t>(nq * k);
             scope->summary_slot = 0;
             launch_cross_topk(scope, t);
             finish_outputs(t.indices, t.distances);
@@ -1945,7 +2104,7 @@ static swh_status_t topk_run(Scope *scope, const Engine *engine, const TopkReque
                     add_to_totals(scope->totals, scope->last_timing);
                 }
                 scope->last_timing.cells = sm.cells;
-                scope->last_timing.bytes = r.pq->total_bytes + r.pc->total_bytes + (nq + nc) * ow + 2 * out_bytes;
+                scope->last_timing.bytes = p.pa->total_bytes + p.pb->total_bytes + (nq + nc) * ow + 2 * out_bytes;
                 return swh_success_k;
             }
             // a string longer than the kernel takes (the memory of a prepared tape changed since it was measured): the general path
@@ -1953,76 +2112,26 @@ static swh_status_t topk_run(Scope *scope, const Engine *engine, const TopkReque
             scope->last_timing = swh_timing_t{};
         }
 
-        // ---- general path: query blocks of at most 2^18 rows x candidate slices of at most 2^26 pairs (a 256 MB u32 matrix) ----------------
-        const uint64_t q_step = std::min<uint64_t>(nq, (uint64_t)1 << 18);
-        const uint64_t c_step = std::max<uint64_t>(1, std::min<uint64_t>(nc, ((uint64_t)1 << 26) / q_step));
-        const size_t need = pad(q_step * c_step * 4) + pad(q_step * k * 8) + (dev_i ? 0 : pad(out_bytes)) + (dev_d ? 0 : pad(out_bytes));
+        // ---- general path: each slice folded into the block's running lists ---------------------------------------------------------------
+        SearchSweep sweep(scope, engine, p, bound);
+        const size_t need = pad(sweep.q_step * sweep.c_step * 4) + pad(sweep.q_step * k * 8) + (dev_i ? 0 : pad(out_bytes)) + (dev_d ? 0 : pad(out_bytes));
         ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
         Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
-        uint32_t *matrix = sc.take<uint32_t>(q_step * c_step);
-        uint64_t *lists = sc.take<uint64_t>(q_step * k);
-        uint32_t *ind = dev_i ? r.indices : sc.take<uint32_t>(nq * k);
-        uint32_t *dist = dev_d ? r.distances : sc.take<uint32_t>(nq * k);
-        const swh_timing_totals_t totals_before = scope->totals;
-        swh_timing_t sum{};
-        char scoring_name[64] = "";
-        for (uint64_t q0 = 0; q0 < nq; q0 += q_step) {
-            const uint64_t rows = std::min<uint64_t>(q_step, nq - q0);
-            SWH_HIP_CHECK(hipMemsetAsync(lists, 0xFF, rows * k * 8, stream));
-            for (uint64_t c0 = 0; c0 < nc; c0 += c_step) {
-                const uint64_t columns = std::min<uint64_t>(c_step, nc - c0);
-                CallSpec spec{};
-                spec.a = HostTape{nullptr, nullptr, (size_t)rows, 0};
-                spec.b = HostTape{nullptr, nullptr, (size_t)columns, 0};
-                spec.cross = true; spec.utf8 = r.pq->utf8; spec.bound = r.bound;
-                spec.out = matrix; spec.out_stride = 4; spec.row_stride = columns * 4; spec.out64 = false;
-                spec.pa = r.pq; spec.pb = r.pc; spec.a_first = r.q_first + q0; spec.b_first = r.c_first + c0;
-                const swh_status_t status = run_call_on(scope, engine, spec, error);
-                if (status != swh_success_k) return status;
-                const swh_timing_t &dp = scope->last_timing;
-                sum.cells += dp.cells; sum.bytes += dp.bytes;
-                sum.total_ms += dp.total_ms; sum.compute_ms += dp.compute_ms; sum.kernels += dp.kernels;
-                if (dp.dominant_ms > sum.dominant_ms) { sum.dominant_ms = dp.dominant_ms; snprintf(scoring_name, sizeof scoring_name, "%s", dp.dominant_name); }
-                scope->stamps_used = 0;
-                scope->stamps_pending = false;
-                launch_topk_select(scope, matrix, rows, columns, q0, c0, (uint32_t)k, cap, lists, c0 + columns == nc, ind, dist);
-                if (scope->profiling) {
-                    SWH_HIP_CHECK(hipStreamSynchronize(stream));
-                    collect_timing(scope);
-                    sum.total_ms += scope->last_timing.total_ms; sum.compute_ms += scope->last_timing.compute_ms; sum.kernels += 1;
-                    scope->stamps_used = 0;
-                }
-            }
-        }
+        uint32_t *matrix = sc.take<uint32_t>(sweep.q_step * sweep.c_step);
+        uint64_t *lists = sc.take<uint64_t>(sweep.q_step * k);
+        uint32_t *ind = dev_i ? indices : sc.take<uint32_t>(nq * k);
+        uint32_t *dist = dev_d ? distances : sc.take<uint32_t>(nq * k);
+        auto pad_lists = [&](uint64_t, uint64_t rows) { SWH_HIP_CHECK(hipMemsetAsync(lists, 0xFF, rows * k * 8, stream)); };   // every row is padding
+        const swh_status_t status = sweep.walk(matrix, true, error, pad_lists, [&](uint64_t q0, uint64_t rows, uint64_t c0, uint64_t columns, bool last_slice) {
+            launch_topk_select(scope, matrix, rows, columns, q0, c0, (uint32_t)k, cap, lists, last_slice, ind, dist);
+            sweep.time_own_kernels(1);
+        });
+        if (status != swh_success_k) return status;
         finish_outputs(ind, dist);
-        scope->summary_pending = false;
-        scope->stamps_pending = false;
-        // the search as one call: its name says which path ran and which kernel scored the pairs
-        snprintf(sum.dominant_name, sizeof sum.dominant_name, "topk_select/%s", scoring_name);
-        scope->last_timing = sum;
-        if (scope->profiling) {
-            scope->totals = totals_before;
-            add_to_totals(scope->totals, sum);
-        }
+        sweep.close("topk");
         return swh_success_k;
-    } catch (const HipFailure &f) {
-        return fail_hip(error, f);
-    } catch (const std::bad_alloc &) {
-        return fail(error, swh_bad_alloc_k, "host allocation failed");
-    }
+    });
 }
-
-// Top-k searches and alignments are synchronous on every scope: outstanding asynchronous / pipelined work is joined first, and the call
-// runs on the scope itself (not on a pipeline lane) with the asynchronous mode held off until it returns.
-struct HoldSynchronous {
-    Scope *scope; bool async, pipelined;
-    explicit HoldSynchronous(Scope *s) : scope(s), async(s->async), pipelined(s->pipelined) { s->async = false; s->pipelined = false; }
-    ~HoldSynchronous() { scope->async = async; scope->pipelined = pipelined; }
-};
-struct PreparedOwner {
-    Prepared *p = nullptr;
-    ~PreparedOwner() { free_prepared(p); }
-};
 
 static swh_status_t topk_checks(swh_levenshtein_t e, swh_scope_t s, size_t k, size_t queries, size_t candidates, const uint32_t *indices,
                                 const uint32_t *distances, const char **error) {
@@ -2033,32 +2142,17 @@ static swh_status_t topk_checks(swh_levenshtein_t e, swh_scope_t s, size_t k, si
     if (queries && (!indices || !distances)) return fail(error, swh_invalid_argument_k, "null output pointer");
     return swh_success_k;
 }
-static swh_status_t join_outstanding(Scope *scope, const char **error) {
-    if (!scope->async && !scope->pipelined) return swh_success_k;
-    return swh_scope_synchronize((swh_scope_t)scope, error);
-}
 
 static swh_status_t topk_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *q, const swh_tape_u64_t *c, bool utf8, size_t k,
                                uint32_t bound, uint32_t *indices, uint32_t *distances, const char **error) {
     if (!q) return fail(error, swh_invalid_argument_k, "null tape");
-    const swh_tape_u64_t *cc = c ? c : q;
-    swh_status_t status = topk_checks(e, s, k, q->count, cc->count, indices, distances, error);
+    swh_status_t status = topk_checks(e, s, k, q->count, (c ? c : q)->count, indices, distances, error);
     if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
     if (q->count == 0) return swh_success_k;
-    HoldSynchronous mode(scope);
-    // raw tapes are made resident and measured for the call (prepare_tape: device tapes in place, host tapes uploaded; UTF-8 validated and
-    // decoded): the route is then chosen on lengths that are known, not believed
-    PreparedOwner pq, pc;
-    status = prepare_tape(scope, SWH_TAPE(q, 1), utf8, (swh_prepared_t *)&pq.p, error);
-    if (status != swh_success_k) return status;
-    if (c) {
-        status = prepare_tape(scope, SWH_TAPE(c, 1), utf8, (swh_prepared_t *)&pc.p, error);
-        if (status != swh_success_k) return status;
-    }
-    TopkRequest r{pq.p, c ? pc.p : pq.p, 0, q->count, 0, cc->count, (uint32_t)k, bound, indices, distances};
-    return topk_run(scope, (Engine *)e, r, error);
+    if ((status = call.prepare(q, c, utf8, true, true, error)) != swh_success_k) return status;
+    return topk_run(call.scope, (Engine *)e, call.pair, (uint32_t)k, bound, indices, distances, error);
 }
 swh_status_t swh_levenshtein_topk_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries, const swh_tape_u64_t *candidates,
                                           size_t k, uint32_t bound, uint32_t *indices, uint32_t *distances, const char **error) {
@@ -2072,25 +2166,17 @@ swh_status_t swh_levenshtein_utf8_topk_u64tape(swh_levenshtein_t e, swh_scope_t 
 swh_status_t swh_levenshtein_topk_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *queries,
                                            const swh_prepared_view_t *candidates, size_t k, uint32_t bound, uint32_t *indices,
                                            uint32_t *distances, const char **error) {
-    if (!queries || !queries->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
-    const swh_prepared_view_t *cc = (candidates && candidates->tape) ? candidates : queries;
-    if (!view_fits(queries) || !view_fits(cc)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
-    const Prepared *pq = (const Prepared *)queries->tape, *pc = (const Prepared *)cc->tape;
-    swh_status_t status = topk_checks(e, s, k, queries->count, cc->count, indices, distances, error);
+    TwoTapeCall call;
+    swh_status_t status = call.views(queries, candidates, true, error);
     if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = check_prepared_pair(scope, pq, pc, error)) != swh_success_k) return status;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
-    HoldSynchronous mode(scope);
-    TopkRequest r{pq, pc, queries->first, queries->count, cc->first, cc->count, (uint32_t)k, bound, indices, distances};
-    return topk_run(scope, (Engine *)e, r, error);
+    if ((status = topk_checks(e, s, k, call.pair.a_count, call.pair.b_count, indices, distances, error)) != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return topk_run(call.scope, (Engine *)e, call.pair, (uint32_t)k, bound, indices, distances, error);
 }
 
 // ---- range search (within.hip) ---------------------------------------------------------------------------------------------------------
-// Every candidate within `bound` of every query, as CSR. The routes are top-k's: word-sized byte strings on unit costs run the fused
-// kernel (k_cross_within, the calls top-k gives to k_cross_topk), everything else the general path (slices of a dense matrix scored by the
-// ordinary cross-product routes). Both count first, scan the counts into the row offsets on the device, read the total (8 bytes) and
-// fill only if the caller's arrays hold it.
+// Every candidate within `bound` of every query, as CSR, on the search planner's routes. Both count first, scan the counts into the row
+// offsets on the device, read the total (8 bytes) and fill only if the caller's arrays hold it.
 // STRINGWARS_AMD_WITHIN_PRUNE=0 (test library): the fused kernel walks every chunk, also those the length gap rules out
 static uint32_t within_prune() {
     static const uint32_t on = [] { const char *e = test_hook("STRINGWARS_AMD_WITHIN_PRUNE"); return !e || atoi(e) != 0 ? 1u : 0u; }();
@@ -2107,22 +2193,16 @@ static uint64_t within_slices_hook() {
     return n;
 }
 
-struct WithinRequest {
-    const Prepared *pq, *pc;
-    size_t q_first, q_count, c_first, c_count;
-    uint32_t bound;
+struct WithinOutputs {
     size_t *row_offsets;
     uint32_t *indices, *distances;
     size_t capacity;
 };
 
-static swh_status_t within_run(Scope *scope, const Engine *engine, const WithinRequest &r, const char **error) {
+static swh_status_t within_run(Scope *scope, const Engine *engine, const TapePair &p, uint32_t bound, const WithinOutputs &r, const char **error) {
     static_assert(sizeof(size_t) == sizeof(uint64_t), "row offsets are scanned as 64-bit words");
-    harvest_timing(scope, false);
-    scope->stamps_used = 0;
-    scope->last_timing = swh_timing_t{};
-    const uint64_t nq = r.q_count, nc = r.c_count;
-    try {
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t nq = p.a_count, nc = p.b_count;
         SWH_HIP_CHECK(hipSetDevice(scope->device));
         hipStream_t stream = scope->stream;
         const bool dev_o = is_device_pointer(r.row_offsets), dev_i = is_device_pointer(r.indices), dev_d = is_device_pointer(r.distances);
@@ -2136,8 +2216,7 @@ static swh_status_t within_run(Scope *scope, const Engine *engine, const WithinR
             }
             return swh_success_k;
         }
-        const bool utf8 = r.pq->utf8 && !(r.pq->ascii && r.pc->ascii && r.pq->off64 == r.pc->off64);
-        const size_t ow = r.pq->off64 ? 8 : 4;
+        const size_t ow = p.pa->off64 ? 8 : 4;
         // the offsets are complete on the device: the total decides the fill, the rest goes to a host caller
         auto read_total = [&](const uint64_t *offs) {
             uint64_t total = 0;
@@ -2162,26 +2241,17 @@ static swh_status_t within_run(Scope *scope, const Engine *engine, const WithinR
             if (!dev_d) SWH_HIP_CHECK(hipMemcpyAsync(r.distances, dist, total * 4, hipMemcpyDeviceToHost, stream));
         };
 
-        CallSpec whole{};   // the dense cross-product of the two views, as run_call_on would route it
-        whole.a.count = nq; whole.b.count = nc; whole.cross = true; whole.bound = r.bound; whole.pa = r.pq; whole.pb = r.pc;
-        const bool fused = !within_force_select() && !utf8 && engine->algorithm == swh_algorithm_auto_k && r.pq->off64 == r.pc->off64 &&
-                           pick_route(scope, engine, whole, false, dev_i, call_lengths(scope, engine, whole, false)).route == kRouteCrossShort;
-        if (fused) {
-            // ---- fused: top-k's slicing (~32 items per compute unit); a count and a start per (row, slice) stay under 256 MB -----------
-            const uint64_t qblocks = (nq + 15) / 16, chunks = (nc + 63) / 64;
-            const uint64_t target = (uint64_t)scope->compute_units * 32;
-            uint64_t slices = std::min<uint64_t>(std::max<uint64_t>((target + qblocks - 1) / qblocks, 1), chunks);
-            slices = std::max<uint64_t>(1, std::min<uint64_t>(slices, ((uint64_t)256 << 20) / (nq * 12)));
-            if (within_slices_hook()) slices = std::min<uint64_t>(within_slices_hook(), chunks);
-            const uint64_t slice_chunks = (chunks + slices - 1) / slices;
-            slices = (chunks + slice_chunks - 1) / slice_chunks;
+        if (search_is_fused(scope, engine, p, bound, within_force_select(), dev_i)) {
+            // ---- fused: a count (4 bytes) and a start (8) per (row, slice) ----------------------------------------------------------------
+            const SearchSlices cut = search_slices(nq, nc, scope->compute_units, 12, within_slices_hook());
+            const uint64_t slices = cut.slices;
             const uint64_t n_counts = nq * slices, tiles = (n_counts + kWithinScanTile - 1) / kWithinScanTile;
             const size_t need = pad(n_counts * 4) + pad(n_counts * 8) + pad(tiles * 8) + (dev_o ? 0 : pad((nq + 1) * 8));
             ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
             Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
             WithinLaunch w{};
-            w.a = prepared_view(r.pq, false, r.q_first, nq); w.b = prepared_view(r.pc, false, r.c_first, nc);
-            w.off64 = r.pq->off64; w.slices = (uint32_t)slices; w.bound = r.bound; w.prune = within_prune(); w.slice_chunks = slice_chunks;
+            w.a = prepared_view(p.pa, false, p.a_first, nq); w.b = prepared_view(p.pb, false, p.b_first, nc);
+            w.off64 = p.pa->off64; w.slices = (uint32_t)slices; w.bound = bound; w.prune = within_prune(); w.slice_chunks = cut.slice_chunks;
             w.counts = sc.take<uint32_t>(n_counts);
             uint64_t *starts = sc.take<uint64_t>(n_counts), *block_sums = sc.take<uint64_t>(tiles);
             uint64_t *offs = dev_o ? (uint64_t *)r.row_offsets : sc.take<uint64_t>(nq + 1);
@@ -2215,7 +2285,7 @@ static swh_status_t within_run(Scope *scope, const Engine *engine, const WithinR
                 }
                 scope->last_timing.cells = sm.cells;
                 // the tapes, a count and a start per (row, slice), the row offsets and the hits
-                scope->last_timing.bytes = r.pq->total_bytes + r.pc->total_bytes + (nq + nc) * ow + n_counts * 12 + (nq + 1) * 8 +
+                scope->last_timing.bytes = p.pa->total_bytes + p.pb->total_bytes + (nq + nc) * ow + n_counts * 12 + (nq + 1) * 8 +
                                            (total <= r.capacity ? total * 8 : 0);
                 return swh_success_k;
             }
@@ -2224,82 +2294,40 @@ static swh_status_t within_run(Scope *scope, const Engine *engine, const WithinR
             scope->last_timing = swh_timing_t{};
         }
 
-        // ---- general path: top-k's blocking -- query blocks of at most 2^18 rows x candidate slices of at most 2^26 pairs, scored twice ------
-        const uint64_t q_step = std::min<uint64_t>(nq, (uint64_t)1 << 18);
-        const uint64_t c_step = std::max<uint64_t>(1, std::min<uint64_t>(nc, ((uint64_t)1 << 26) / q_step));
+        // ---- general path: every block scored twice, once to count and once to fill -------------------------------------------------------
+        SearchSweep sweep(scope, engine, p, bound);
         const uint64_t tiles = (nq + kWithinScanTile - 1) / kWithinScanTile;
-        const size_t need = pad(q_step * c_step * 4) + pad(nq * 4) + pad(nq * 8) + pad(tiles * 8) + (dev_o ? 0 : pad((nq + 1) * 8));
+        const size_t need = pad(sweep.q_step * sweep.c_step * 4) + pad(nq * 4) + pad(nq * 8) + pad(tiles * 8) + (dev_o ? 0 : pad((nq + 1) * 8));
         ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
         Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
-        uint32_t *matrix = sc.take<uint32_t>(q_step * c_step);
+        uint32_t *matrix = sc.take<uint32_t>(sweep.q_step * sweep.c_step);
         uint32_t *counts = sc.take<uint32_t>(nq);
         uint64_t *cursors = sc.take<uint64_t>(nq), *block_sums = sc.take<uint64_t>(tiles);
         uint64_t *offs = dev_o ? (uint64_t *)r.row_offsets : sc.take<uint64_t>(nq + 1);
-        const swh_timing_totals_t totals_before = scope->totals;
-        swh_timing_t sum{};
-        char scoring_name[64] = "";
-        uint64_t total = 0;
-        auto time_own_kernels = [&](uint32_t launched) {   // the compaction kernels launched since the last scoring call
-            if (!scope->profiling) return;
-            SWH_HIP_CHECK(hipStreamSynchronize(stream));
-            collect_timing(scope);
-            sum.total_ms += scope->last_timing.total_ms; sum.compute_ms += scope->last_timing.compute_ms; sum.kernels += launched;
-            scope->stamps_used = 0;
-        };
-        auto sweep = [&](bool fill) -> swh_status_t {
-            for (uint64_t q0 = 0; q0 < nq; q0 += q_step) {
-                const uint64_t rows = std::min<uint64_t>(q_step, nq - q0);
-                for (uint64_t c0 = 0; c0 < nc; c0 += c_step) {
-                    const uint64_t columns = std::min<uint64_t>(c_step, nc - c0);
-                    CallSpec spec{};
-                    spec.a = HostTape{nullptr, nullptr, (size_t)rows, 0};
-                    spec.b = HostTape{nullptr, nullptr, (size_t)columns, 0};
-                    spec.cross = true; spec.utf8 = r.pq->utf8; spec.bound = r.bound;
-                    spec.out = matrix; spec.out_stride = 4; spec.row_stride = columns * 4; spec.out64 = false;
-                    spec.pa = r.pq; spec.pb = r.pc; spec.a_first = r.q_first + q0; spec.b_first = r.c_first + c0;
-                    const swh_status_t status = run_call_on(scope, engine, spec, error);
-                    if (status != swh_success_k) return status;
-                    const swh_timing_t &dp = scope->last_timing;
-                    if (!fill) { sum.cells += dp.cells; sum.bytes += dp.bytes; }   // (the second walk of the same pairs is not counted again)
-                    sum.total_ms += dp.total_ms; sum.compute_ms += dp.compute_ms; sum.kernels += dp.kernels;
-                    if (dp.dominant_ms > sum.dominant_ms) { sum.dominant_ms = dp.dominant_ms; snprintf(scoring_name, sizeof scoring_name, "%s", dp.dominant_name); }
-                    scope->stamps_used = 0;
-                    scope->stamps_pending = false;
-                    if (fill) launch_within_fill(scope, matrix, rows, columns, c0, r.bound, cursors + q0, total, ind, dist);
-                    else launch_within_count(scope, matrix, rows, columns, r.bound, counts + q0);
-                    time_own_kernels(1);
-                }
-            }
-            return swh_success_k;
-        };
         SWH_HIP_CHECK(hipMemsetAsync(counts, 0, nq * 4, stream));
-        swh_status_t status = sweep(false);
+        auto no_rows_begin = [](uint64_t, uint64_t) {};   // (counts and cursors span all queries: nothing to open per block)
+        swh_status_t status = sweep.walk(matrix, true, error, no_rows_begin, [&](uint64_t q0, uint64_t rows, uint64_t, uint64_t columns, bool) {
+            launch_within_count(scope, matrix, rows, columns, bound, counts + q0);
+            sweep.time_own_kernels(1);
+        });
         if (status != swh_success_k) return status;
         launch_within_offsets(scope, counts, nq, 1, block_sums, cursors, offs);
-        time_own_kernels(2);
-        total = read_total(offs);
+        sweep.time_own_kernels(2);
+        const uint64_t total = read_total(offs);
         finish_offsets(offs);
         if (total && total <= r.capacity) {
             stage_outputs(total);
-            if ((status = sweep(true)) != swh_success_k) return status;
+            status = sweep.walk(matrix, false, error, no_rows_begin, [&](uint64_t q0, uint64_t rows, uint64_t c0, uint64_t columns, bool) {
+                launch_within_fill(scope, matrix, rows, columns, c0, bound, cursors + q0, total, ind, dist);
+                sweep.time_own_kernels(1);
+            });
+            if (status != swh_success_k) return status;
             finish_outputs(total);
         }
         SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        scope->summary_pending = false;
-        scope->stamps_pending = false;
-        // the search as one call: its name says which path ran and which kernel scored the pairs
-        snprintf(sum.dominant_name, sizeof sum.dominant_name, "within_select/%s", scoring_name);
-        scope->last_timing = sum;
-        if (scope->profiling) {
-            scope->totals = totals_before;
-            add_to_totals(scope->totals, sum);
-        }
+        sweep.close("within");
         return swh_success_k;
-    } catch (const HipFailure &f) {
-        return fail_hip(error, f);
-    } catch (const std::bad_alloc &) {
-        return fail(error, swh_bad_alloc_k, "host allocation failed");
-    }
+    });
 }
 
 static swh_status_t within_checks(swh_levenshtein_t e, swh_scope_t s, size_t candidates, uint32_t bound, const size_t *row_offsets,
@@ -2315,52 +2343,36 @@ static swh_status_t within_checks(swh_levenshtein_t e, swh_scope_t s, size_t can
 }
 
 static swh_status_t within_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *q, const swh_tape_u64_t *c, bool utf8, uint32_t bound,
-                                 size_t *row_offsets, uint32_t *indices, uint32_t *distances, size_t capacity, const char **error) {
+                                 const WithinOutputs &outs, const char **error) {
     if (!q) return fail(error, swh_invalid_argument_k, "null tape");
-    const swh_tape_u64_t *cc = c ? c : q;
-    swh_status_t status = within_checks(e, s, cc->count, bound, row_offsets, indices, distances, capacity, error);
+    const size_t candidates = (c ? c : q)->count;
+    swh_status_t status = within_checks(e, s, candidates, bound, outs.row_offsets, outs.indices, outs.distances, outs.capacity, error);
     if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
-    HoldSynchronous mode(scope);
-    // raw tapes are made resident and measured for the call, as for top-k: the route is chosen on lengths that are known
-    PreparedOwner pq, pc;
-    if (q->count) {
-        status = prepare_tape(scope, SWH_TAPE(q, 1), utf8, (swh_prepared_t *)&pq.p, error);
-        if (status != swh_success_k) return status;
-        if (c && c->count) {
-            status = prepare_tape(scope, SWH_TAPE(c, 1), utf8, (swh_prepared_t *)&pc.p, error);
-            if (status != swh_success_k) return status;
-        }
-    }
-    WithinRequest r{pq.p, c ? pc.p : pq.p, 0, q->count, 0, cc->count, bound, row_offsets, indices, distances, capacity};
-    return within_run(scope, (Engine *)e, r, error);
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    // (a search without queries prepares nothing, one without candidates the queries alone: the offsets are still written)
+    if ((status = call.prepare(q, c, utf8, q->count != 0, q->count && candidates, error)) != swh_success_k) return status;
+    return within_run(call.scope, (Engine *)e, call.pair, bound, outs, error);
 }
 swh_status_t swh_levenshtein_within_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries, const swh_tape_u64_t *candidates,
                                             uint32_t bound, size_t *row_offsets, uint32_t *indices, uint32_t *distances, size_t capacity,
                                             const char **error) {
-    return within_tapes(e, s, queries, candidates, false, bound, row_offsets, indices, distances, capacity, error);
+    return within_tapes(e, s, queries, candidates, false, bound, WithinOutputs{row_offsets, indices, distances, capacity}, error);
 }
 swh_status_t swh_levenshtein_utf8_within_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries,
                                                  const swh_tape_u64_t *candidates, uint32_t bound, size_t *row_offsets, uint32_t *indices,
                                                  uint32_t *distances, size_t capacity, const char **error) {
-    return within_tapes(e, s, queries, candidates, true, bound, row_offsets, indices, distances, capacity, error);
+    return within_tapes(e, s, queries, candidates, true, bound, WithinOutputs{row_offsets, indices, distances, capacity}, error);
 }
 swh_status_t swh_levenshtein_within_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *queries,
                                              const swh_prepared_view_t *candidates, uint32_t bound, size_t *row_offsets, uint32_t *indices,
                                              uint32_t *distances, size_t capacity, const char **error) {
-    if (!queries || !queries->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
-    const swh_prepared_view_t *cc = (candidates && candidates->tape) ? candidates : queries;
-    if (!view_fits(queries) || !view_fits(cc)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
-    const Prepared *pq = (const Prepared *)queries->tape, *pc = (const Prepared *)cc->tape;
-    swh_status_t status = within_checks(e, s, cc->count, bound, row_offsets, indices, distances, capacity, error);
+    TwoTapeCall call;
+    swh_status_t status = call.views(queries, candidates, true, error);
     if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = check_prepared_pair(scope, pq, pc, error)) != swh_success_k) return status;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
-    HoldSynchronous mode(scope);
-    WithinRequest r{pq, pc, queries->first, queries->count, cc->first, cc->count, bound, row_offsets, indices, distances, capacity};
-    return within_run(scope, (Engine *)e, r, error);
+    if ((status = within_checks(e, s, call.pair.b_count, bound, row_offsets, indices, distances, capacity, error)) != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return within_run(call.scope, (Engine *)e, call.pair, bound, WithinOutputs{row_offsets, indices, distances, capacity}, error);
 }
 
 // ---- alignments (align.hip) ----------------------------------------------------------------------------------------------------------
@@ -2390,22 +2402,16 @@ static uint64_t align_chunk_pairs(const Scope *scope, uint64_t count, uint64_t s
     return std::max<uint64_t>(1, std::min<uint64_t>(pairs, count));
 }
 
-struct AlignRequest {
-    const Prepared *pa, *pb;
-    size_t a_first, b_first, count;
-    uint32_t bound;
+struct AlignOutputs {
     uint32_t *distances;
     uint64_t *offsets;
     uint8_t *ops;
     size_t capacity;
 };
 
-static swh_status_t align_run(Scope *scope, const AlignRequest &r, const char **error) {
-    harvest_timing(scope, false);
-    scope->stamps_used = 0;
-    scope->last_timing = swh_timing_t{};
-    const uint64_t count = r.count;
-    try {
+static swh_status_t align_run(Scope *scope, const TapePair &p, uint32_t bound, const AlignOutputs &r, const char **error) {
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t count = p.a_count;
         SWH_HIP_CHECK(hipSetDevice(scope->device));
         hipStream_t stream = scope->stream;
         const bool dev_d = is_device_pointer(r.distances), dev_o = is_device_pointer(r.offsets), dev_ops = is_device_pointer(r.ops);
@@ -2415,12 +2421,12 @@ static swh_status_t align_run(Scope *scope, const AlignRequest &r, const char **
             SWH_HIP_CHECK(hipStreamSynchronize(stream));
             return swh_success_k;
         }
-        const bool cp = r.pa->utf8;
+        const bool cp = p.pa->utf8;
         AlignTapes t{};
-        t.a = prepared_view(r.pa, cp, r.a_first, count);
-        t.b = prepared_view(r.pb, cp, r.b_first, count);
-        t.a_off64 = cp ? 1 : r.pa->off64;
-        t.b_off64 = cp ? 1 : r.pb->off64;
+        t.a = prepared_view(p.pa, cp, p.a_first, count);
+        t.b = prepared_view(p.pb, cp, p.b_first, count);
+        t.a_off64 = cp ? 1 : p.pa->off64;
+        t.b_off64 = cp ? 1 : p.pb->off64;
         t.cp = cp ? 1 : 0;
         t.count = count;
 
@@ -2503,7 +2509,7 @@ static swh_status_t align_run(Scope *scope, const AlignRequest &r, const char **
 
         AlignChunk c{};
         c.store_base = store_base; c.slot_base = slot_base; c.store = store; c.slots = slots;
-        c.counts = counts; c.distances = distances; c.bound = r.bound;
+        c.counts = counts; c.distances = distances; c.bound = bound;
         for (uint64_t q = 0; q < chunks; ++q) {
             c.pair_first = q * per_chunk;
             c.pair_end = std::min<uint64_t>(count, (q + 1) * per_chunk);
@@ -2529,11 +2535,7 @@ static swh_status_t align_run(Scope *scope, const AlignRequest &r, const char **
         scope->last_timing.cells = got.cells;
         scope->last_timing.bytes = (cp ? 4 : 1) * got.symbols + 2 * (count + 1) * 8 + count * 4 + got.symbols;
         return swh_success_k;
-    } catch (const HipFailure &f) {
-        return fail_hip(error, f);
-    } catch (const std::bad_alloc &) {
-        return fail(error, swh_bad_alloc_k, "host allocation failed");
-    }
+    });
 }
 
 static swh_status_t align_checks(swh_levenshtein_t e, swh_scope_t s, size_t a_count, size_t b_count, const uint32_t *distances,
@@ -2548,51 +2550,35 @@ static swh_status_t align_checks(swh_levenshtein_t e, swh_scope_t s, size_t a_co
 }
 
 static swh_status_t align_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, bool utf8, uint32_t bound,
-                                uint32_t *distances, uint64_t *offsets, uint8_t *ops, size_t capacity, const char **error) {
+                                const AlignOutputs &outs, const char **error) {
     if (!a || !b) return fail(error, swh_invalid_argument_k, "null tape");
-    swh_status_t status = align_checks(e, s, a->count, b->count, distances, offsets, ops, error);
+    swh_status_t status = align_checks(e, s, a->count, b->count, outs.distances, outs.offsets, outs.ops, error);
     if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
-    HoldSynchronous mode(scope);
-    AlignRequest r{nullptr, nullptr, 0, 0, a->count, bound, distances, offsets, ops, capacity};
-    if (a->count == 0) {
-        Prepared none;
-        r.pa = r.pb = &none;
-        return align_run(scope, r, error);
-    }
-    // raw tapes are made resident, measured and (UTF-8) validated and decoded for the call, as for top-k
-    PreparedOwner pa, pb;
-    status = prepare_tape(scope, SWH_TAPE(a, 1), utf8, (swh_prepared_t *)&pa.p, error);
-    if (status != swh_success_k) return status;
-    status = prepare_tape(scope, SWH_TAPE(b, 1), utf8, (swh_prepared_t *)&pb.p, error);
-    if (status != swh_success_k) return status;
-    r.pa = pa.p; r.pb = pb.p;
-    return align_run(scope, r, error);
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    const bool pairs = a->count != 0;
+    if ((status = call.prepare(a, b, utf8, pairs, pairs, error)) != swh_success_k) return status;
+    return align_run(call.scope, call.pair, bound, outs, error);
 }
 swh_status_t swh_levenshtein_align_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,
                                            uint32_t *distances, size_t *ops_offsets, char *ops, size_t ops_capacity, const char **error) {
-    return align_tapes(e, s, a, b, false, bound, distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity, error);
+    return align_tapes(e, s, a, b, false, bound, AlignOutputs{distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity}, error);
 }
 swh_status_t swh_levenshtein_utf8_align_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
                                                 uint32_t bound, uint32_t *distances, size_t *ops_offsets, char *ops, size_t ops_capacity,
                                                 const char **error) {
-    return align_tapes(e, s, a, b, true, bound, distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity, error);
+    return align_tapes(e, s, a, b, true, bound, AlignOutputs{distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity}, error);
 }
 swh_status_t swh_levenshtein_align_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
                                             uint32_t bound, uint32_t *distances, size_t *ops_offsets, char *ops, size_t ops_capacity,
                                             const char **error) {
-    if (!a || !a->tape || !b || !b->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
-    if (!view_fits(a) || !view_fits(b)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
-    const Prepared *pa = (const Prepared *)a->tape, *pb = (const Prepared *)b->tape;
-    swh_status_t status = align_checks(e, s, a->count, b->count, distances, (const uint64_t *)ops_offsets, (const uint8_t *)ops, error);
+    const AlignOutputs outs{distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity};
+    TwoTapeCall call;
+    swh_status_t status = call.views(a, b, false, error);
     if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = check_prepared_pair(scope, pa, pb, error)) != swh_success_k) return status;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
-    HoldSynchronous mode(scope);
-    AlignRequest r{pa, pb, a->first, b->first, a->count, bound, distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity};
-    return align_run(scope, r, error);
+    if ((status = align_checks(e, s, call.pair.a_count, call.pair.b_count, outs.distances, outs.offsets, outs.ops, error)) != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return align_run(call.scope, call.pair, bound, outs, error);
 }
 
 // ---- infix search (infix.hip) ---------------------------------------------------------------------------------------------------------
@@ -2600,29 +2586,21 @@ swh_status_t swh_levenshtein_align_prepared(swh_levenshtein_t e, swh_scope_t s, 
 // the measurements decides the errors before any output is written. Then the forward pass (distance and end of every pair) and the
 // start pass (the starts, the bound) over the same items, and the copy-out of outputs that live on the host. The scratch -- the item
 // list and, for host outputs, the three result arrays -- is the scope's alignment scratch: both calls are synchronous.
-struct InfixRequest {
-    const Prepared *pp, *pt;
-    size_t p_first, t_first, count;
-    uint32_t bound;
-    uint32_t *distances, *starts, *ends;
-};
+struct InfixOutputs { uint32_t *distances, *starts, *ends; };
 
-static swh_status_t infix_run(Scope *scope, const InfixRequest &r, const char **error) {
-    harvest_timing(scope, false);
-    scope->stamps_used = 0;
-    scope->last_timing = swh_timing_t{};
-    const uint64_t count = r.count;
-    if (count == 0) return swh_success_k;
-    try {
+static swh_status_t infix_run(Scope *scope, const TapePair &p, uint32_t bound, const InfixOutputs &r, const char **error) {
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t count = p.a_count;
+        if (count == 0) return swh_success_k;
         SWH_HIP_CHECK(hipSetDevice(scope->device));
         hipStream_t stream = scope->stream;
         const bool dev_d = is_device_pointer(r.distances), dev_s = is_device_pointer(r.starts), dev_e = is_device_pointer(r.ends);
-        const bool cp = r.pp->utf8;
+        const bool cp = p.pa->utf8;
         InfixTapes t{};
-        t.patterns = prepared_view(r.pp, cp, r.p_first, count);
-        t.texts = prepared_view(r.pt, cp, r.t_first, count);
-        t.p_off64 = cp ? 1 : r.pp->off64;
-        t.t_off64 = cp ? 1 : r.pt->off64;
+        t.patterns = prepared_view(p.pa, cp, p.a_first, count);
+        t.texts = prepared_view(p.pb, cp, p.b_first, count);
+        t.p_off64 = cp ? 1 : p.pa->off64;
+        t.t_off64 = cp ? 1 : p.pb->off64;
         t.cp = cp ? 1 : 0;
         t.count = count;
 
@@ -2659,7 +2637,7 @@ static swh_status_t infix_run(Scope *scope, const InfixRequest &r, const char **
         InfixRun run{};
         run.items = items; run.item_count = got.items;
         run.distances = distances; run.starts = starts; run.ends = ends;
-        run.bound = r.bound;
+        run.bound = bound;
         run.wide_text = !cp && got.text_symbols >= 16;
         launch_infix_forward(scope, t, run);
         launch_infix_starts(scope, t, run);
@@ -2675,15 +2653,12 @@ static swh_status_t infix_run(Scope *scope, const InfixRequest &r, const char **
         scope->last_timing.cells = got.cells;
         scope->last_timing.bytes = (cp ? 4 : 1) * got.symbols + 2 * (count + 1) * 8 + 3 * count * 4;
         return swh_success_k;
-    } catch (const HipFailure &f) {
-        return fail_hip(error, f);
-    } catch (const std::bad_alloc &) {
-        return fail(error, swh_bad_alloc_k, "host allocation failed");
-    }
+    });
 }
 
-// no scope or engine can exist without a device: a call that gets none says so, as scope creation does
-static swh_status_t infix_handles(swh_levenshtein_t e, swh_scope_t s, const char **error) {
+// no scope or engine can exist without a device: a call that gets a null handle says so where there is none, as scope creation does
+// (infix search and the scored families ask; top-k, within and align answer "null scope or engine" without the probe)
+static swh_status_t probe_null_handles(swh_levenshtein_t e, swh_scope_t s, const char **error) {
     if (s && e) return swh_success_k;
     int devices = 0;
     if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0) {
@@ -2703,49 +2678,36 @@ static swh_status_t infix_checks(swh_levenshtein_t e, swh_scope_t s, size_t p_co
 }
 
 static swh_status_t infix_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts, bool utf8,
-                                uint32_t bound, uint32_t *distances, uint32_t *starts, uint32_t *ends, const char **error) {
-    swh_status_t status = infix_handles(e, s, error);
+                                uint32_t bound, const InfixOutputs &outs, const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
     if (status != swh_success_k) return status;
     if (!patterns || !texts) return fail(error, swh_invalid_argument_k, "null tape");
-    status = infix_checks(e, s, patterns->count, texts->count, distances, starts, ends, error);
+    status = infix_checks(e, s, patterns->count, texts->count, outs.distances, outs.starts, outs.ends, error);
     if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
-    HoldSynchronous mode(scope);
-    InfixRequest r{nullptr, nullptr, 0, 0, patterns->count, bound, distances, starts, ends};
-    if (patterns->count == 0) return infix_run(scope, r, error);
-    // raw tapes are made resident, measured and (UTF-8) validated and decoded for the call, as for top-k and alignments
-    PreparedOwner pp, pt;
-    status = prepare_tape(scope, SWH_TAPE(patterns, 1), utf8, (swh_prepared_t *)&pp.p, error);
-    if (status != swh_success_k) return status;
-    status = prepare_tape(scope, SWH_TAPE(texts, 1), utf8, (swh_prepared_t *)&pt.p, error);
-    if (status != swh_success_k) return status;
-    r.pp = pp.p; r.pt = pt.p;
-    return infix_run(scope, r, error);
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    const bool pairs = patterns->count != 0;
+    if ((status = call.prepare(patterns, texts, utf8, pairs, pairs, error)) != swh_success_k) return status;
+    return infix_run(call.scope, call.pair, bound, outs, error);
 }
 swh_status_t swh_levenshtein_infix_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts,
                                            uint32_t bound, uint32_t *distances, uint32_t *starts, uint32_t *ends, const char **error) {
-    return infix_tapes(e, s, patterns, texts, false, bound, distances, starts, ends, error);
+    return infix_tapes(e, s, patterns, texts, false, bound, InfixOutputs{distances, starts, ends}, error);
 }
 swh_status_t swh_levenshtein_utf8_infix_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts,
                                                 uint32_t bound, uint32_t *distances, uint32_t *starts, uint32_t *ends, const char **error) {
-    return infix_tapes(e, s, patterns, texts, true, bound, distances, starts, ends, error);
+    return infix_tapes(e, s, patterns, texts, true, bound, InfixOutputs{distances, starts, ends}, error);
 }
 swh_status_t swh_levenshtein_infix_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *patterns,
                                             const swh_prepared_view_t *texts, uint32_t bound, uint32_t *distances, uint32_t *starts,
                                             uint32_t *ends, const char **error) {
-    if (swh_status_t status = infix_handles(e, s, error)) return status;
-    if (!patterns || !patterns->tape || !texts || !texts->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
-    if (!view_fits(patterns) || !view_fits(texts)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
-    const Prepared *pp = (const Prepared *)patterns->tape, *pt = (const Prepared *)texts->tape;
-    swh_status_t status = infix_checks(e, s, patterns->count, texts->count, distances, starts, ends, error);
+    swh_status_t status = probe_null_handles(e, s, error);
     if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = check_prepared_pair(scope, pp, pt, error)) != swh_success_k) return status;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
-    HoldSynchronous mode(scope);
-    InfixRequest r{pp, pt, patterns->first, texts->first, patterns->count, bound, distances, starts, ends};
-    return infix_run(scope, r, error);
+    TwoTapeCall call;
+    if ((status = call.views(patterns, texts, false, error)) != swh_success_k) return status;
+    if ((status = infix_checks(e, s, call.pair.a_count, call.pair.b_count, distances, starts, ends, error)) != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return infix_run(call.scope, call.pair, bound, InfixOutputs{distances, starts, ends}, error);
 }
 
 // ---- OSA distances, LCS lengths / Indel distances, Jaro counts (osa.hip, lcs.hip, jaro.hip): one planner --------------------------------
@@ -2825,23 +2787,18 @@ static uint64_t scored_chunk_pairs(const ScoredFamily &f) {
 }
 
 struct ScoredRequest {
-    const Prepared *pa, *pb;
-    size_t a_first, a_count, b_first, b_count;
     bool cross;
     uint32_t bound;
     void *outs[kScoredOutputs];   // the family's outputs in the order of its exports: any may be null, those past its count are
     size_t stride;                // bytes between consecutive results (pairs) or rows (cross), of every output
 };
 
-static swh_status_t scored_run(Scope *scope, const ScoredFamily &f, const ScoredRequest &r, const char **error) {
-    harvest_timing(scope, false);
-    scope->stamps_used = 0;
-    scope->last_timing = swh_timing_t{};
-    const uint64_t na = r.a_count, nb = r.b_count;
-    if (na == 0 || nb == 0) return swh_success_k;
-    if (r.cross && na > ((uint64_t)1 << 40) / nb) return fail(error, swh_unsupported_length_k, "more than 2^40 pairs in one call");
-    const uint64_t total = r.cross ? na * nb : na;
-    try {
+static swh_status_t scored_run(Scope *scope, const ScoredFamily &f, const TapePair &p, const ScoredRequest &r, const char **error) {
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t na = p.a_count, nb = p.b_count;
+        if (na == 0 || nb == 0) return swh_success_k;
+        if (r.cross && na > ((uint64_t)1 << 40) / nb) return fail(error, swh_unsupported_length_k, "more than 2^40 pairs in one call");
+        const uint64_t total = r.cross ? na * nb : na;
         SWH_HIP_CHECK(hipSetDevice(scope->device));
         hipStream_t stream = scope->stream;
         bool stage[kScoredOutputs];
@@ -2851,12 +2808,12 @@ static swh_status_t scored_run(Scope *scope, const ScoredFamily &f, const Scored
             staged_count += stage[k] ? 1 : 0;
             wanted += r.outs[k] ? 1 : 0;
         }
-        const bool cp = r.pa->utf8;
+        const bool cp = p.pa->utf8;
         OsaTapes t{};
-        t.a = prepared_view(r.pa, cp, r.a_first, na);
-        t.b = prepared_view(r.pb, cp, r.b_first, nb);
-        t.a_off64 = cp ? 1 : r.pa->off64;
-        t.b_off64 = cp ? 1 : r.pb->off64;
+        t.a = prepared_view(p.pa, cp, p.a_first, na);
+        t.b = prepared_view(p.pb, cp, p.b_first, nb);
+        t.a_off64 = cp ? 1 : p.pa->off64;
+        t.b_off64 = cp ? 1 : p.pb->off64;
         t.cp = cp ? 1 : 0;
         t.nb = r.cross ? nb : 0;
 
@@ -2944,11 +2901,7 @@ static swh_status_t scored_run(Scope *scope, const ScoredFamily &f, const Scored
         scope->last_timing.cells = whole.cells;
         scope->last_timing.bytes = (cp ? 4 : 1) * whole.symbols + (na + nb + 2) * 8 + total * width * wanted;
         return swh_success_k;
-    } catch (const HipFailure &failure) {
-        return fail_hip(error, failure);
-    } catch (const std::bad_alloc &) {
-        return fail(error, swh_bad_alloc_k, "host allocation failed");
-    }
+    });
 }
 
 // the argument rules; a stride of 0 becomes the packed one
@@ -2975,45 +2928,28 @@ static swh_status_t scored_checks(const ScoredFamily &f, swh_levenshtein_t e, si
 
 static swh_status_t scored_tapes(const ScoredFamily &f, swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
                                  bool utf8, bool cross, uint32_t bound, void *const (&outs)[kScoredOutputs], size_t stride, const char **error) {
-    swh_status_t status = infix_handles(e, s, error);
+    swh_status_t status = probe_null_handles(e, s, error);
     if (status != swh_success_k) return status;
     if (!a || (!b && !cross)) return fail(error, swh_invalid_argument_k, "null tape");
-    const swh_tape_u64_t *bb = b ? b : a;   // a cross-product without b: the self-product
-    status = scored_checks(f, e, a->count, bb->count, cross, outs, stride, error);
+    const size_t b_count = (b ? b : a)->count;   // a cross-product without b: the self-product
+    status = scored_checks(f, e, a->count, b_count, cross, outs, stride, error);
     if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
-    HoldSynchronous mode(scope);
-    ScoredRequest r{nullptr, nullptr, 0, a->count, 0, bb->count, cross, bound, {outs[0], outs[1], outs[2]}, stride};
-    if (a->count == 0 || bb->count == 0) return scored_run(scope, f, r, error);
-    // raw tapes are made resident, measured and (UTF-8) validated and decoded for the call, as for top-k, alignments and infix search
-    PreparedOwner pa, pb;
-    status = prepare_tape(scope, SWH_TAPE(a, 1), utf8, (swh_prepared_t *)&pa.p, error);
-    if (status != swh_success_k) return status;
-    if (b) {
-        status = prepare_tape(scope, SWH_TAPE(b, 1), utf8, (swh_prepared_t *)&pb.p, error);
-        if (status != swh_success_k) return status;
-    }
-    r.pa = pa.p; r.pb = b ? pb.p : pa.p;
-    return scored_run(scope, f, r, error);
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    const bool pairs = a->count && b_count;
+    if ((status = call.prepare(a, b, utf8, pairs, pairs, error)) != swh_success_k) return status;
+    return scored_run(call.scope, f, call.pair, ScoredRequest{cross, bound, {outs[0], outs[1], outs[2]}, stride}, error);
 }
 static swh_status_t scored_prepared(const ScoredFamily &f, swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a,
                                     const swh_prepared_view_t *b, bool cross, uint32_t bound, void *const (&outs)[kScoredOutputs], size_t stride,
                                     const char **error) {
-    if (swh_status_t status = infix_handles(e, s, error)) return status;
-    if (!a || !a->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
-    const swh_prepared_view_t *bb = (b && b->tape) ? b : (cross ? a : nullptr);
-    if (!bb) return fail(error, swh_invalid_argument_k, "null prepared view");
-    if (!view_fits(a) || !view_fits(bb)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
-    const Prepared *pa = (const Prepared *)a->tape, *pb = (const Prepared *)bb->tape;
-    swh_status_t status = scored_checks(f, e, a->count, bb->count, cross, outs, stride, error);
+    swh_status_t status = probe_null_handles(e, s, error);
     if (status != swh_success_k) return status;
-    Scope *scope = (Scope *)s;
-    if ((status = check_prepared_pair(scope, pa, pb, error)) != swh_success_k) return status;
-    if ((status = join_outstanding(scope, error)) != swh_success_k) return status;
-    HoldSynchronous mode(scope);
-    ScoredRequest r{pa, pb, a->first, a->count, bb->first, bb->count, cross, bound, {outs[0], outs[1], outs[2]}, stride};
-    return scored_run(scope, f, r, error);
+    TwoTapeCall call;
+    if ((status = call.views(a, b, cross, error)) != swh_success_k) return status;
+    if ((status = scored_checks(f, e, call.pair.a_count, call.pair.b_count, cross, outs, stride, error)) != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return scored_run(call.scope, f, call.pair, ScoredRequest{cross, bound, {outs[0], outs[1], outs[2]}, stride}, error);
 }
 
 swh_status_t swh_levenshtein_osa_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,

@@ -16,6 +16,7 @@ CUDA tensors); device-resident inputs are used in place.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from typing import Iterable, Optional, Sequence, Union
 
 import numpy as np
@@ -596,6 +597,9 @@ def _c_tape(tape, want64: Optional[bool] = None):
     return struct, is64, tape
 
 
+_EXPORTS = {}   # (engine type, stem, prepared) -> the export, as _Engine._two_tapes found it
+
+
 class _Engine:
     _utf8 = False
     _abi_prefix = "swh_levenshtein"
@@ -603,24 +607,55 @@ class _Engine:
     def __init__(self):
         self._handle = None
 
-    def _prepared(self, suffix, a, b, scope, out, out_dtype, extra=(), cross=False):
-        """The ``*_prepared`` twin of a call: both sides are PreparedTape views."""
-        if not isinstance(a, PreparedTape) or not (b is None or isinstance(b, PreparedTape)):
-            raise TypeError("both tapes of a call must be prepared, or neither")
-        if self._utf8 != a.utf8:
+    def _promoted(self, a, b, scope, at=()):
+        """Both tapes as PreparedTapes where either is of a type in ``at`` (measured on the device, like the raw calls do internally);
+        as they are otherwise. ``b`` may be None."""
+        a = _as_tape(a)
+        b = None if b is None else _as_tape(b)
+        if isinstance(a, at) or isinstance(b, at):
+            a = a if isinstance(a, PreparedTape) else PreparedTape(scope, a, utf8=self._utf8)
+            if b is not None and not isinstance(b, PreparedTape):
+                b = PreparedTape(scope, b, utf8=self._utf8)
+        return a, b
+
+    def _need_mode(self, tape: "PreparedTape") -> None:
+        if self._utf8 != tape.utf8:
             raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
-        va, vb = a.view(), (b.view() if b is not None else None)
+
+    def _two_tapes(self, a, b, scope, stem):
+        """The two sides of one ``<prefix>_<stem>_prepared`` / ``<prefix>_[utf8_]<stem>_u64tape`` call: both prepared (the first in the
+        engine's mode), or neither; ``b`` None is a null pointer. Returns ``call``: ``call(*tail, byref(err))`` passes the engine, the
+        scope, the two sides and the C arguments ``tail``, keeps the tapes alive meanwhile and returns the status for ``N.check``.
+        A search of 2048 x 2048 words takes ~100 us, so a prepared call is held to what the inline calls cost (0.3 us more, on a
+        stub export): the export is looked up by name once per (engine type, stem, form), and ``call`` is a ``partial`` of the export
+        itself -- no Python frame between the caller and the library."""
+        prepared = isinstance(a, PreparedTape) or isinstance(b, PreparedTape)
+        key = (type(self), stem, prepared)
+        fn = _EXPORTS.get(key)
+        if fn is None:
+            form = "%s_prepared" % stem if prepared else "%s%s_u64tape" % ("utf8_" if self._utf8 else "", stem)
+            fn = _EXPORTS[key] = getattr(N.lib, "%s_%s" % (self._abi_prefix, form))
+        if prepared:
+            if not isinstance(a, PreparedTape) or not (b is None or isinstance(b, PreparedTape)):
+                raise TypeError("both tapes of a call must be prepared, or neither")
+            self._need_mode(a)
+            return functools.partial(fn, self._handle, scope.handle, C.byref(a.view()), None if b is None else C.byref(b.view()))
+        kept = (_c_tape(a, want64=True), None if b is None else _c_tape(b, want64=True))
+        call = functools.partial(fn, self._handle, scope.handle, C.byref(kept[0][0]), None if b is None else C.byref(kept[1][0]))
+        call.kept = kept   # (the structs hold bare pointers into these arrays; prepared tapes are the caller's own arguments)
+        return call
+
+    def _prepared(self, stem, a, b, scope, out, out_dtype, extra=(), cross=False):
+        """The ``*_prepared`` twin of a call: both sides are PreparedTape views."""
+        call = self._two_tapes(a, b, scope, stem)
         if out is None:
             shape = (len(a), len(b if b is not None else a)) if cross else (len(a),)
             out = np.zeros(shape, dtype=out_dtype)
         stride = 0
         if isinstance(out, np.ndarray):
             stride = out.strides[0] if (cross or out.size > 1) else 0
-        fn = getattr(N.lib, self._abi_prefix + suffix)
         err = C.c_char_p()
-        status = fn(self._handle, scope.handle, C.byref(va), C.byref(vb) if vb is not None else None, *extra,
-                    C.c_void_p(_pointer(out)), stride, C.byref(err))
-        N.check(status, err)
+        N.check(call(*extra, C.c_void_p(_pointer(out)), stride, C.byref(err)), err)
         return out
 
     def cross_sharded(self, product: "ShardedCross", scope: DeviceScope, out=None):
@@ -659,13 +694,13 @@ class _Engine:
                 N.check(status, _keep[2])
         return call
 
-    def _pairs(self, fn32, fn64, a, b, scope, out, out_dtype, extra=(), prepared_suffix="_pairs_prepared"):
+    def _pairs(self, fn32, fn64, a, b, scope, out, out_dtype, extra=(), prepared_stem="pairs"):
         """``fn32`` is None for a call family that only takes u64 tapes."""
         a, b = _as_tape(a), _as_tape(b)
         if len(a) != len(b):
             raise ValueError("pairwise scoring needs two collections of equal length")
         if isinstance(a, PreparedTape) or isinstance(b, PreparedTape):
-            return self._prepared(prepared_suffix, a, b, scope, out, out_dtype, extra)
+            return self._prepared(prepared_stem, a, b, scope, out, out_dtype, extra)
         ta, a64, keep_a = _c_tape(a, want64=True if fn32 is None else None)
         tb, b64, keep_b = _c_tape(b, want64=a64 or None)
         if a64 != b64:
@@ -681,13 +716,13 @@ class _Engine:
         del keep_a, keep_b
         return out
 
-    def _cross(self, fn, queries, candidates, scope, out, out_dtype, prepared_suffix="_cross_prepared"):
+    def _cross(self, fn, queries, candidates, scope, out, out_dtype, prepared_stem="cross"):
         queries = _as_tape(queries)
         candidates = queries if candidates is None else _as_tape(candidates)
         if isinstance(queries, PreparedTape) or isinstance(candidates, PreparedTape):
             if isinstance(out, np.ndarray) and (out.dtype.itemsize != 8 or out.shape != (len(queries), len(candidates))):
                 raise ValueError("out must be a (len(queries), len(candidates)) matrix of 64-bit integers")
-            return self._prepared(prepared_suffix, queries, candidates, scope, out, out_dtype, cross=True)
+            return self._prepared(prepared_stem, queries, candidates, scope, out, out_dtype, cross=True)
         tq, _, keep_q = _c_tape(queries, want64=True)
         tc, _, keep_c = _c_tape(candidates, want64=True)
         if out is None:
@@ -763,22 +798,8 @@ class LevenshteinDistances(_Engine):
                     raise ValueError("out arrays must be contiguous (len(queries), k) arrays of 32-bit integers")
         bound_value = C.c_uint32(N.UNBOUNDED if bound is None else int(bound))
         err = C.c_char_p()
-        if isinstance(queries, PreparedTape) or isinstance(candidates, PreparedTape):
-            if not isinstance(queries, PreparedTape) or not (candidates is None or isinstance(candidates, PreparedTape)):
-                raise TypeError("both tapes of a call must be prepared, or neither")
-            if self._utf8 != queries.utf8:
-                raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
-            vq, vc = queries.view(), (candidates.view() if candidates is not None else None)
-            status = N.lib.swh_levenshtein_topk_prepared(self._handle, scope.handle, C.byref(vq), C.byref(vc) if vc is not None else None,
-                                                         int(k), bound_value, C.c_void_p(_pointer(indices)), C.c_void_p(_pointer(distances)), C.byref(err))
-        else:
-            tq, _, keep_q = _c_tape(queries, want64=True)
-            tc, _, keep_c = _c_tape(candidates, want64=True) if candidates is not None else (None, None, None)
-            fn = N.lib.swh_levenshtein_utf8_topk_u64tape if self._utf8 else N.lib.swh_levenshtein_topk_u64tape
-            status = fn(self._handle, scope.handle, C.byref(tq), C.byref(tc) if tc is not None else None, int(k), bound_value,
-                        C.c_void_p(_pointer(indices)), C.c_void_p(_pointer(distances)), C.byref(err))
-            del keep_q, keep_c
-        N.check(status, err)
+        N.check(self._two_tapes(queries, candidates, scope, "topk")(int(k), bound_value, C.c_void_p(_pointer(indices)),
+                                                                    C.c_void_p(_pointer(distances)), C.byref(err)), err)
         return indices, distances
 
     def within(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None, *, bound: int,
@@ -800,27 +821,12 @@ class LevenshteinDistances(_Engine):
         if candidates is not None:
             candidates = _as_tape(candidates)
         count = len(queries)
-        prepared = isinstance(queries, PreparedTape) or isinstance(candidates, PreparedTape)
-        if prepared:
-            if not isinstance(queries, PreparedTape) or not (candidates is None or isinstance(candidates, PreparedTape)):
-                raise TypeError("both tapes of a call must be prepared, or neither")
-            if self._utf8 != queries.utf8:
-                raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
-            vq, vc = queries.view(), (candidates.view() if candidates is not None else None)
-        else:
-            tq, _, keep_q = _c_tape(queries, want64=True)
-            tc, _, keep_c = _c_tape(candidates, want64=True) if candidates is not None else (None, None, None)
+        search = self._two_tapes(queries, candidates, scope, "within")
 
         def call(offsets, indices, distances, room):
             err = C.c_char_p()
-            tail = (C.c_uint32(int(bound)), C.c_void_p(_pointer(offsets)), C.c_void_p(_pointer(indices)), C.c_void_p(_pointer(distances)),
-                    int(room), C.byref(err))
-            if prepared:
-                status = N.lib.swh_levenshtein_within_prepared(self._handle, scope.handle, C.byref(vq), C.byref(vc) if vc is not None else None, *tail)
-            else:
-                fn = N.lib.swh_levenshtein_utf8_within_u64tape if self._utf8 else N.lib.swh_levenshtein_within_u64tape
-                status = fn(self._handle, scope.handle, C.byref(tq), C.byref(tc) if tc is not None else None, *tail)
-            N.check(status, err)
+            N.check(search(C.c_uint32(int(bound)), C.c_void_p(_pointer(offsets)), C.c_void_p(_pointer(indices)), C.c_void_p(_pointer(distances)),
+                           int(room), C.byref(err)), err)
             return int(offsets[count])
 
         if out is not None:
@@ -858,40 +864,25 @@ class LevenshteinDistances(_Engine):
         rapidfuzz: ``Levenshtein.editops(a[i], b[i])`` up to the choice among optimal scripts."""
         if scope is None:
             raise ValueError("a DeviceScope is required")
-        a, b = _as_tape(a), _as_tape(b)
-        if isinstance(a, DeviceTape) or isinstance(b, DeviceTape):   # measured on the device, like the raw calls do internally
-            a = a if isinstance(a, PreparedTape) else PreparedTape(scope, a, utf8=self._utf8)
-            b = b if isinstance(b, PreparedTape) else PreparedTape(scope, b, utf8=self._utf8)
+        a, b = self._promoted(a, b, scope, at=DeviceTape)
         if len(a) != len(b):
             raise ValueError("a and b must hold the same number of strings")
         count = len(a)
         bound_value = C.c_uint32(N.UNBOUNDED if bound is None else int(bound))
         distances = np.empty(count, dtype=np.uint32)
         offsets = np.zeros(count + 1, dtype=np.uint64)
-        err = C.c_char_p()
-        if isinstance(a, PreparedTape) or isinstance(b, PreparedTape):
-            if not (isinstance(a, PreparedTape) and isinstance(b, PreparedTape)):
-                raise TypeError("both tapes of a call must be prepared, or neither")
-            if self._utf8 != a.utf8 or self._utf8 != b.utf8:
-                raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
+        call = self._two_tapes(a, b, scope, "align")
+        if isinstance(a, PreparedTape):
+            self._need_mode(b)
             # the symbols of a sub-view are not known on the host: the whole tapes' bound the view's, and np.empty only reserves the
             # pages -- the call writes (and touches) the view's ops alone; a result much smaller than the buffer is copied out below
             capacity = a._root.info["symbols"] + b._root.info["symbols"]
-            ops = np.empty(max(capacity, 1), dtype=np.uint8)
-            va, vb = a.view(), b.view()
-            status = N.lib.swh_levenshtein_align_prepared(self._handle, scope.handle, C.byref(va), C.byref(vb), bound_value,
-                                                          C.c_void_p(distances.ctypes.data), C.c_void_p(offsets.ctypes.data),
-                                                          C.c_void_p(ops.ctypes.data), capacity, C.byref(err))
-        else:
-            ta, _, keep_a = _c_tape(a, want64=True)
-            tb, _, keep_b = _c_tape(b, want64=True)
-            capacity = int(keep_a.offsets[-1]) - int(keep_a.offsets[0]) + int(keep_b.offsets[-1]) - int(keep_b.offsets[0]) if count else 0
-            ops = np.empty(max(capacity, 1), dtype=np.uint8)
-            fn = N.lib.swh_levenshtein_utf8_align_u64tape if self._utf8 else N.lib.swh_levenshtein_align_u64tape
-            status = fn(self._handle, scope.handle, C.byref(ta), C.byref(tb), bound_value, C.c_void_p(distances.ctypes.data),
-                        C.c_void_p(offsets.ctypes.data), C.c_void_p(ops.ctypes.data), capacity, C.byref(err))
-            del keep_a, keep_b
-        N.check(status, err)
+        else:   # both are Strs: _promoted has prepared every DeviceTape, and widening the offsets for the call changes no value
+            capacity = int(a.offsets[-1]) - int(a.offsets[0]) + int(b.offsets[-1]) - int(b.offsets[0]) if count else 0
+        ops = np.empty(max(capacity, 1), dtype=np.uint8)
+        err = C.c_char_p()
+        N.check(call(bound_value, C.c_void_p(distances.ctypes.data), C.c_void_p(offsets.ctypes.data), C.c_void_p(ops.ctypes.data), capacity,
+                     C.byref(err)), err)
         used = int(offsets[-1])
         return Alignments(distances, offsets, ops[:used].copy() if 2 * used < len(ops) else ops[:used])
 
@@ -902,31 +893,17 @@ class LevenshteinDistances(_Engine):
         inclusive end); rapidfuzz: ``partial_ratio_alignment`` (``dest_start`` / ``dest_end``)."""
         if scope is None:
             raise ValueError("a DeviceScope is required")
-        patterns, texts = _as_tape(patterns), _as_tape(texts)
-        if isinstance(patterns, DeviceTape) or isinstance(texts, DeviceTape):   # measured on the device, like the raw calls do internally
-            patterns = patterns if isinstance(patterns, PreparedTape) else PreparedTape(scope, patterns, utf8=self._utf8)
-            texts = texts if isinstance(texts, PreparedTape) else PreparedTape(scope, texts, utf8=self._utf8)
+        patterns, texts = self._promoted(patterns, texts, scope, at=DeviceTape)
         if len(patterns) != len(texts):
             raise ValueError("patterns and texts must hold the same number of strings")
         count = len(patterns)
         bound_value = C.c_uint32(N.UNBOUNDED if bound is None else int(bound))
         distances, starts, ends = (np.empty(count, dtype=np.uint32) for _ in range(3))
-        outs = tuple(C.c_void_p(array.ctypes.data) for array in (distances, starts, ends))
+        call = self._two_tapes(patterns, texts, scope, "infix")
+        if isinstance(patterns, PreparedTape):
+            self._need_mode(texts)
         err = C.c_char_p()
-        if isinstance(patterns, PreparedTape) or isinstance(texts, PreparedTape):
-            if not (isinstance(patterns, PreparedTape) and isinstance(texts, PreparedTape)):
-                raise TypeError("both tapes of a call must be prepared, or neither")
-            if self._utf8 != patterns.utf8 or self._utf8 != texts.utf8:
-                raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
-            vp, vt = patterns.view(), texts.view()
-            status = N.lib.swh_levenshtein_infix_prepared(self._handle, scope.handle, C.byref(vp), C.byref(vt), bound_value, *outs, C.byref(err))
-        else:
-            tp, _, keep_p = _c_tape(patterns, want64=True)
-            tt, _, keep_t = _c_tape(texts, want64=True)
-            fn = N.lib.swh_levenshtein_utf8_infix_u64tape if self._utf8 else N.lib.swh_levenshtein_infix_u64tape
-            status = fn(self._handle, scope.handle, C.byref(tp), C.byref(tt), bound_value, *outs, C.byref(err))
-            del keep_p, keep_t
-        N.check(status, err)
+        N.check(call(bound_value, *(C.c_void_p(array.ctypes.data) for array in (distances, starts, ends)), C.byref(err)), err)
         return InfixMatches(distances, starts, ends)
 
     def osa(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None, bound: Optional[int] = None, out=None):
@@ -937,13 +914,10 @@ class LevenshteinDistances(_Engine):
         rapidfuzz: ``OSA.distance(a[i], b[i], score_cutoff=bound)``."""
         if scope is None:
             raise ValueError("a DeviceScope is required")
-        a, b = _as_tape(a), _as_tape(b)
-        if isinstance(a, DeviceTape) or isinstance(b, DeviceTape):   # measured on the device, like the raw calls do internally
-            a = a if isinstance(a, PreparedTape) else PreparedTape(scope, a, utf8=self._utf8)
-            b = b if isinstance(b, PreparedTape) else PreparedTape(scope, b, utf8=self._utf8)
+        a, b = self._promoted(a, b, scope, at=DeviceTape)
         fn = N.lib.swh_levenshtein_utf8_osa_pairs_u64tape if self._utf8 else N.lib.swh_levenshtein_osa_pairs_u64tape
         bound_value = N.UNBOUNDED if bound is None else int(bound)
-        return self._pairs(None, fn, a, b, scope, out, np.uint32, extra=(C.c_uint32(bound_value),), prepared_suffix="_osa_pairs_prepared")
+        return self._pairs(None, fn, a, b, scope, out, np.uint32, extra=(C.c_uint32(bound_value),), prepared_stem="osa_pairs")
 
     def osa_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None, out=None):
         """The dense OSA matrix ``out[i][j] = osa(queries[i], candidates[j])`` as uint64 (``swh_levenshtein_osa_cross_*``), the shape of
@@ -951,14 +925,9 @@ class LevenshteinDistances(_Engine):
         rapidfuzz: ``process.cdist(queries, candidates, scorer=OSA.distance)``."""
         if scope is None:
             raise ValueError("a DeviceScope is required")
-        queries = _as_tape(queries)
-        candidates = None if candidates is None else _as_tape(candidates)
-        if isinstance(queries, DeviceTape) or isinstance(candidates, DeviceTape):
-            queries = queries if isinstance(queries, PreparedTape) else PreparedTape(scope, queries, utf8=self._utf8)
-            if candidates is not None and not isinstance(candidates, PreparedTape):
-                candidates = PreparedTape(scope, candidates, utf8=self._utf8)
+        queries, candidates = self._promoted(queries, candidates, scope, at=DeviceTape)
         fn = N.lib.swh_levenshtein_utf8_osa_cross_u64tape if self._utf8 else N.lib.swh_levenshtein_osa_cross_u64tape
-        return self._cross(fn, queries, candidates, scope, out, np.uint64, prepared_suffix="_osa_cross_prepared")
+        return self._cross(fn, queries, candidates, scope, out, np.uint64, prepared_stem="osa_cross")
 
     def _scored_call(self, family, a, b, scope, cross, outs, extra=()):
         """One ``swh_levenshtein_{lcs,jaro}_*`` call. ``outs``: for each output of the family, in the order of its exports, the array
@@ -972,12 +941,9 @@ class LevenshteinDistances(_Engine):
             raise ValueError("pairwise scoring needs two collections")
         if not cross and len(a) != len(b):
             raise ValueError("pairwise scoring needs two collections of equal length")
-        if isinstance(a, (DeviceTape, PreparedTape)) or isinstance(b, (DeviceTape, PreparedTape)):   # measured on the device
-            a = a if isinstance(a, PreparedTape) else PreparedTape(scope, a, utf8=self._utf8)
-            if b is not None and not isinstance(b, PreparedTape):
-                b = PreparedTape(scope, b, utf8=self._utf8)
-            if self._utf8 != a.utf8:
-                raise ValueError("a %s engine needs tapes prepared with utf8=%s" % (type(self).__name__, self._utf8))
+        a, b = self._promoted(a, b, scope, at=(DeviceTape, PreparedTape))
+        if isinstance(a, PreparedTape):
+            self._need_mode(a)   # (_two_tapes asks again below: here the refusal comes before those of the outputs, as it always did)
         shape = (len(a), len(a if b is None else b)) if cross else (len(a),)
         dtype = np.uint64 if cross else np.uint32
         outs = [np.zeros(shape, dtype=dtype) if out is True else out for out in outs]
@@ -990,20 +956,9 @@ class LevenshteinDistances(_Engine):
         if len(strides) > 1:
             raise ValueError("the outputs share one stride")
         stride = strides.pop() if strides else 0
-        pointers = [C.c_void_p(None if out is None else _pointer(out)) for out in outs]
-        kind = "cross" if cross else "pairs"
+        call = self._two_tapes(a, b, scope, "%s_%s" % (family, "cross" if cross else "pairs"))
         err = C.c_char_p()
-        if isinstance(a, PreparedTape):
-            va, vb = a.view(), (None if b is None else b.view())
-            fn = getattr(N.lib, "swh_levenshtein_%s_%s_prepared" % (family, kind))
-            status = fn(self._handle, scope.handle, C.byref(va), None if vb is None else C.byref(vb), *extra, *pointers, stride, C.byref(err))
-        else:
-            ta, _, keep_a = _c_tape(a, want64=True)
-            tb, _, keep_b = (None, None, None) if b is None else _c_tape(b, want64=True)
-            fn = getattr(N.lib, "swh_levenshtein_%s%s_%s_u64tape" % ("utf8_" if self._utf8 else "", family, kind))
-            status = fn(self._handle, scope.handle, C.byref(ta), None if tb is None else C.byref(tb), *extra, *pointers, stride, C.byref(err))
-            del keep_a, keep_b
-        N.check(status, err)
+        N.check(call(*extra, *(C.c_void_p(None if out is None else _pointer(out)) for out in outs), stride, C.byref(err)), err)
         return outs, a, (a if b is None else b)
 
     def _lcs_call(self, a, b, scope, cross, bound, indel, lcs):

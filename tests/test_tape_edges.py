@@ -653,6 +653,230 @@ def test_each_family_keeps_its_own_argument_rules(sw, scope, lev, call):
     refused("invalid_argument", "null tape", "pairs", lev, sa, None, pointers(buffers), 0, buffers)
 
 
+# ---- f2. the argument rules of top-k, within, align and infix, call by call ---------------------------------------------------------
+TWO_TAPE_CALLS = ("topk", "within", "align", "infix")
+UNBOUNDED = 0xFFFFFFFF
+# What differs between the four calls at the C ABI. `bad`: an argument of the call's own that it refuses, and the words it has for it
+# (a view beyond its tape wins over it, it wins over a UTF-8 tape next to a byte tape); `null_b`: what a null second side is;
+# `tape_first`: a null tape is tested before a null engine.
+CALL_RULES = {
+    "topk": dict(bad=dict(k=0), bad_says="k must lie in [1, SWH_TOPK_MAX]", null_b="self", tape_first=True, costs=None),
+    "within": dict(bad=dict(bound=UNBOUNDED), bad_says="a range search needs a bound: without one it is the dense cross-product", null_b="self",
+                   tape_first=True, costs=None),
+    "align": dict(bad=dict(null=(1,)), bad_says="null output pointer", null_b="null", tape_first=True,
+                  costs="alignments need unit costs" + UNIT_COSTS, counts="a and b must hold the same number of strings"),
+    "infix": dict(bad=dict(null=(0,)), bad_says="null output pointer", null_b="null", tape_first=False,
+                  costs="infix search needs unit costs" + UNIT_COSTS, counts="patterns and texts must hold the same number of strings"),
+}
+ROOM = 64   # bytes per output
+
+
+def raw_two_tape(sw, call, engine, scope, a, b, tail, form=None):
+    """One of the twelve exports as it stands. `a` / `b`: a Strs, a PreparedTape, a PreparedView passed as it is, or None (a null
+    pointer; `form` then says which export); `engine` None: a null handle; `tail`: the C arguments between the tapes and the error.
+    Returns (status name, message)."""
+    from stringwars_amd import _native as N
+    sides, kept = [], []
+    for x in (a, b):
+        if isinstance(x, sw.PreparedTape):
+            x = x.view()
+        elif isinstance(x, sw.Strs):
+            kept.append(sw.engines._c_tape(x, want64=True))
+            x = kept[-1][0]
+        sides.append(x)
+    if form is None:
+        form = "prepared" if isinstance(sides[0], N.PreparedView) else "u64tape"
+    err = C.c_char_p()
+    status = getattr(N.lib, "swh_levenshtein_%s_%s" % (call, form))(
+        None if engine is None else engine._handle, scope.handle, *(None if x is None else C.byref(x) for x in sides), *tail, C.byref(err))
+    return N.STATUS_NAMES[status], (err.value or b"").decode() if status else ""
+
+
+def two_tape_tail(call, buffers, k=2, bound=None, capacity=ROOM // 4, null=()):
+    """The call's own arguments in ABI order. `buffers`: its outputs in ABI order (top-k: indices, distances; within: row_offsets,
+    indices, distances; align: distances, ops_offsets, ops; infix: distances, starts, ends); `null`: which of them are passed as null."""
+    outs = [None if i in null else x.ctypes.data for i, x in enumerate(buffers)]
+    if call == "topk":
+        return (k, UNBOUNDED if bound is None else bound, *outs)
+    if call == "within":
+        return (1 if bound is None else bound, *outs, capacity)
+    if call == "align":
+        return (UNBOUNDED if bound is None else bound, *outs, capacity)
+    return (UNBOUNDED if bound is None else bound, *outs)
+
+
+def fresh_outputs(call):
+    return [np.full(ROOM, SENTINEL, np.uint8) for _ in range(2 if call == "topk" else 3)]
+
+
+def words(buffer, dtype, count):
+    return buffer[:count * np.dtype(dtype).itemsize].view(dtype)
+
+
+def topk_of(d, k):
+    """(indices, distances) of the k smallest of every row of a dense matrix, ties by candidate index."""
+    order = np.argsort(d, axis=1, kind="stable")[:, :k]
+    return order.astype(np.uint32), np.take_along_axis(d, order, axis=1).astype(np.uint32)
+
+
+def csr_of(d, bound):
+    hits = d <= bound
+    offsets = np.concatenate([[0], np.cumsum(hits.sum(axis=1))]).astype(np.uint64)
+    return offsets, np.nonzero(hits)[1].astype(np.uint32), d[hits].astype(np.uint32)
+
+
+@gpu
+@pytest.mark.parametrize("call", TWO_TAPE_CALLS)
+def test_each_two_tape_call_keeps_its_own_argument_rules(sw, scope, lev, call):
+    """Top-k, within, align and infix resolve their tapes through one front end, and each keeps the rules, the order and the words it
+    had: the status and the whole message of every refusal, which refusal wins where two apply, on raw and on prepared tapes, with
+    not a byte of the outputs written; what an empty call writes; and the searches' self-search and general-cost results. Two strings
+    of two bytes a side."""
+    from stringwars_amd import _native as N
+    rules = CALL_RULES[call]
+    costly = sw.LevenshteinDistances(0, 2, 1, 1, capabilities=scope)
+    global_scores = sw.NeedlemanWunschScores(substitution_matrix=sw.substitution_matrix(42), open=-4, extend=-4, capabilities=scope)
+    sa, sb = sw.Strs(RULE_A), sw.Strs(RULE_B)
+    pa, pb = sw.PreparedTape(scope, sa), sw.PreparedTape(scope, sb)
+    pb8 = sw.PreparedTape(scope, sb, utf8=True)
+
+    def refused(status, message, engine, a, b, form=None, **tail):
+        buffers = fresh_outputs(call)
+        got = raw_two_tape(sw, call, engine, scope, a, b, two_tape_tail(call, buffers, **tail), form)
+        assert got == (status, message), (call, type(a).__name__, tail, got)
+        assert all((x == SENTINEL).all() for x in buffers), (call, message)
+
+    def accepted(engine, a, b, form=None, **tail):
+        buffers = fresh_outputs(call)
+        got = raw_two_tape(sw, call, engine, scope, a, b, two_tape_tail(call, buffers, **tail), form)
+        assert got == ("success", ""), (call, type(a).__name__, tail, got)
+        return buffers
+
+    def untouched(buffer, written=0):
+        assert (buffer[written:] == SENTINEL).all(), call
+
+    for a, b, one, none, form in ((sa, sb, sw.Strs(RULE_B[:1]), sw.Strs([]), "u64tape"), (pa, pb, pb[0:1], pa[0:0], "prepared")):
+        null_says = "null prepared view" if form == "prepared" else "null tape"
+        # ---- what all four share -------------------------------------------------------------------------------------------------------
+        refused("invalid_argument", "not a Levenshtein engine", global_scores, a, b)
+        refused("invalid_argument", "null scope or engine", None, a, b)
+        refused("invalid_argument", null_says if rules["tape_first"] else "null scope or engine", None, None, b, form)
+        refused("invalid_argument", null_says, lev, None, b, form)
+        refused("invalid_argument", rules["bad_says"], lev, a, b, **rules["bad"])
+        if form == "prepared":
+            beyond = N.PreparedView(pa._handle, 1, 2)
+            for x, y in ((beyond, b.view()), (a.view(), beyond)):
+                refused("invalid_argument", "view exceeds the prepared tape", lev, x, y)
+                refused("invalid_argument", "view exceeds the prepared tape", lev, x, y, **rules["bad"])
+            refused("invalid_argument", "one tape was prepared as UTF-8, the other as bytes", lev, pa, pb8)
+            refused("invalid_argument", rules["bad_says"], lev, pa, pb8, **rules["bad"])
+        # ---- a null second side, general costs, the counts ----------------------------------------------------------------------------
+        no_tape = N.PreparedView(None, 0, 0)
+        if rules["null_b"] == "null":
+            refused("invalid_argument", null_says, lev, a, None)
+            if form == "prepared":
+                refused("invalid_argument", null_says, lev, a, no_tape)
+                refused("invalid_argument", null_says, lev, no_tape, b)
+            refused("not_implemented", rules["costs"], costly, a, b)
+            refused("invalid_argument", rules["counts"], lev, a, one)
+        else:
+            twice = accepted(lev, a, a)
+            for nothing in (None,) + ((no_tape,) if form == "prepared" else ()):
+                assert all((x == y).all() for x, y in zip(accepted(lev, a, nothing), twice)), (call, form)
+            assert any((x != y).any() for x, y in zip(accepted(lev, a, b), twice)), call
+
+        # ---- each call's own ----------------------------------------------------------------------------------------------------------
+        if call == "topk":
+            refused("invalid_argument", rules["bad_says"], lev, a, b, k=N.TOPK_MAX + 1)
+            refused("invalid_argument", "null output pointer", lev, a, b, null=(0,))
+            refused("invalid_argument", "null output pointer", lev, a, b, null=(1,))
+            for buffer in accepted(lev, none, b, null=(0, 1)) + accepted(lev, none, b):
+                untouched(buffer)
+            for engine in (lev, costly):
+                indices, distances = accepted(engine, a, b)
+                want = topk_of(np.asarray(engine(sa, sb, scope)), 2)
+                assert (words(indices, np.uint32, 4) == want[0].ravel()).all() and (words(distances, np.uint32, 4) == want[1].ravel()).all(), (call, form)
+                untouched(indices, 16), untouched(distances, 16)
+        elif call == "within":
+            refused("invalid_argument", "null row_offsets", lev, a, b, null=(0,))
+            refused("invalid_argument", "indices and distances must both be given, or neither", lev, a, b, null=(1,))
+            refused("invalid_argument", "indices and distances must both be given, or neither", lev, a, b, null=(2,))
+            refused("invalid_argument", "a capacity without arrays: the counting call passes NULL, NULL, 0", lev, a, b, null=(1, 2), capacity=1)
+            offsets, indices, distances = accepted(lev, none, b)
+            assert (words(offsets, np.uint64, 1) == 0).all()
+            untouched(offsets, 8), untouched(indices), untouched(distances)
+            offsets, indices, distances = accepted(lev, a, none)
+            assert (words(offsets, np.uint64, 3) == 0).all()
+            untouched(offsets, 24), untouched(indices), untouched(distances)
+            for engine, bound in ((lev, 1), (costly, 2)):
+                offsets, indices, distances = accepted(engine, a, b, bound=bound)
+                want = csr_of(np.asarray(engine(sa, sb, scope)), bound)
+                total = int(want[0][-1])
+                assert total and (words(offsets, np.uint64, 3) == want[0]).all(), (call, form)
+                assert (words(indices, np.uint32, total) == want[1]).all() and (words(distances, np.uint32, total) == want[2]).all(), (call, form)
+                untouched(offsets, 24), untouched(indices, 4 * total), untouched(distances, 4 * total)
+            offsets, indices, distances = accepted(lev, a, b, null=(1, 2), capacity=0)   # the counting call
+            assert (words(offsets, np.uint64, 3) == csr_of(np.asarray(lev(sa, sb, scope)), 1)[0]).all()
+        elif call == "align":
+            refused("invalid_argument", "null output pointer", lev, a, b, null=(0,))
+            refused("invalid_argument", "null output pointer", lev, a, b, null=(2,))
+            refused("invalid_argument", "null output pointer", lev, none, none, null=(1,))
+            for null in ((), (0, 2)):
+                distances, offsets, ops = accepted(lev, none, none, null=null)
+                assert (words(offsets, np.uint64, 1) == 0).all()
+                untouched(distances), untouched(offsets, 8), untouched(ops)
+        else:
+            for null in ((0,), (1,), (2,)):
+                refused("invalid_argument", "null output pointer", lev, a, b, null=null)
+            for buffer in accepted(lev, none, none, null=(0, 1, 2)) + accepted(lev, none, none):
+                untouched(buffer)
+
+
+@gpu
+def test_two_tape_calls_refuse_mixed_and_mismatched_tapes_in_python(sw, scope, lev, lev8):
+    """The wrapper's own refusals of topk, within, align and infix, before any C call: a prepared tape next to a raw one is a TypeError,
+    byte-prepared tapes on a UTF-8 engine a ValueError. A UTF-8 tape as the second side only: align and infix say so themselves, the
+    two searches leave it to the library."""
+    sa, sb = sw.Strs(RULE_A), sw.Strs(RULE_B)
+    pa, pb, pb8 = sw.PreparedTape(scope, sa), sw.PreparedTape(scope, sb), sw.PreparedTape(scope, sb, utf8=True)
+    calls = {"topk": lambda e, a, b: e.topk(a, b, scope, k=1), "within": lambda e, a, b: e.within(a, b, scope, bound=1),
+             "align": lambda e, a, b: e.align(a, b, scope), "infix": lambda e, a, b: e.infix(a, b, scope)}
+    needs = "a %s engine needs tapes prepared with utf8=%s"
+    for name, call in calls.items():
+        for a, b in ((pa, sb), (sa, pb)):
+            with pytest.raises(TypeError, match="^both tapes of a call must be prepared, or neither$"):
+                call(lev, a, b)
+        with pytest.raises(ValueError, match="^" + needs % ("LevenshteinDistancesUTF8", True) + "$"):
+            call(lev8, pa, pb)
+        if name in ("align", "infix"):
+            with pytest.raises(ValueError, match="^" + needs % ("LevenshteinDistances", False) + "$"):
+                call(lev, pa, pb8)
+        else:
+            with pytest.raises(sw.StringWarsError, match="^invalid_argument: one tape was prepared as UTF-8, the other as bytes$"):
+                call(lev, pa, pb8)
+
+
+@gpu
+def test_topk_and_within_score_the_general_path_alike(sw, scope, lev8):
+    """One sweep scores the blocks of both searches: on the same views, bound and scope, the general path (code points: never the fused
+    kernel's) names the same scoring kernel after `topk_select/` and `within_select/`, and top-k and the counting call of within count
+    the same cells. 300 x 200 words."""
+    rng = np.random.default_rng(11)
+    items = ["".join(rng.choice(list("abé中"), int(rng.integers(1, 12)))) for _ in range(500)]
+    pq, pc = sw.PreparedTape(scope, sw.Strs(items[:300]), utf8=True), sw.PreparedTape(scope, sw.Strs(items[300:]), utf8=True)
+    scope.set_profiling(True)
+    try:
+        lev8.topk(pq, pc, scope, k=3, bound=4)
+        top = scope.last_timing()
+        lev8.within(pq, pc, scope, bound=4, out=(np.zeros(301, np.uint64), None, None))
+        counted = scope.last_timing()
+    finally:
+        scope.set_profiling(False)
+    assert top["dominant_name"].startswith("topk_select/") and counted["dominant_name"].startswith("within_select/"), (top, counted)
+    assert top["dominant_name"].split("/", 1)[1] == counted["dominant_name"].split("/", 1)[1] != "", (top, counted)
+    assert top["cells"] == counted["cells"] > 0, (top, counted)
+
+
 # ---- g. what the sweeps hold, and what the references are worth: no GPU -------------------------------------------------------------
 def test_sweeps_hold_what_they_are_meant_to():
     """The generators alone. Every (total_a, total_b) is there twice, the totals lie on both sides of 4 and of 16 on either tape,
