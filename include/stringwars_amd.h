@@ -133,7 +133,18 @@ swh_status_t swh_copy_to_host(swh_scope_t scope, void *host_dst, const void *dev
                               const char **error);
 
 /* ---- Tapes: `BytesTapeView<u64>` / `AnyBytesTape::View64` (bench.rs:62, :134-143, :292-306). */
-/* Arrow-style: `offsets` has `count + 1` entries, string i is data[offsets[i] .. offsets[i+1]). */
+/* Arrow-style: `offsets` has `count + 1` entries, string i is data[offsets[i] .. offsets[i+1]).
+ *  - offsets[0] may be non-zero: a tape may be a window of a larger buffer (`BytesTapeView::subview`, bench.rs:134-139) -- `data`
+ *    is then the BUFFER's first byte, not the window's.
+ *  - data[0 .. offsets[count]) must be readable, the bytes in front of offsets[0] included: the kernels read in wide, clamped
+ *    windows around a string, never outside [0, offsets[count]), and a raw UTF-8 call or `swh_tape_prepare_*(utf8 = 1)` validates and
+ *    decodes that whole range (so the bytes in front of a window must be valid UTF-8 as well).
+ *  - Totals are 64-bit with u64 offsets, and up to 2^32 - 1 with u32 offsets (entries at or above 2^31 are plain unsigned values).
+ *  - One string holds fewer than 2^30 bytes (hence fewer than 2^30 symbols). A longer one is refused with
+ *    swh_unsupported_length_k: by `swh_tape_prepare_*` (and so by every call that prepares its raw tapes: top-k, within, align,
+ *    infix, OSA, LCS, Jaro) on the offsets alone, and by the pairwise and cross-product calls on raw tapes as soon as they have
+ *    measured the batch (lengths are measured as 64-bit differences: an entry of 2^32 bytes or more does not wrap into a short
+ *    one) -- no kernel scores a pair with such a string; the call's outputs may have been written and mean nothing. */
 typedef struct swh_tape_u32_t { const uint8_t *data; const uint32_t *offsets; size_t count; } swh_tape_u32_t;
 typedef struct swh_tape_u64_t { const uint8_t *data; const uint64_t *offsets; size_t count; } swh_tape_u64_t;
 

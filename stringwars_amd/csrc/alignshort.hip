@@ -42,7 +42,7 @@ struct AlignShortArgs {
 };
 
 __device__ __forceinline__ void align_extent(const void *offsets, uint32_t off64, uint64_t i, uint64_t &start, uint32_t &len) {
-    if (off64) { const uint64_t *o = (const uint64_t *)offsets; const uint64_t x0 = o[i], x1 = o[i + 1]; start = x0; len = (uint32_t)(x1 - x0); }
+    if (off64) { const uint64_t *o = (const uint64_t *)offsets; const uint64_t x0 = o[i], x1 = o[i + 1]; start = x0; len = extent_length<uint64_t>(x0, x1); }
     else { const uint32_t *o = (const uint32_t *)offsets; const uint32_t x0 = o[i], x1 = o[i + 1]; start = x0; len = (uint32_t)(x1 - x0); }
 }
 

@@ -229,7 +229,8 @@ struct Prepared {
     uint32_t off64 = 0;          // width of the byte tape's offsets
     TapeRef bytes{};             // device: u8 data, u32/u64 offsets
     TapeRef symbols{};           // utf8: u32 code points + u64 code-point offsets; otherwise unused
-    uint64_t total_bytes = 0, total_symbols = 0;
+    uint64_t total_bytes = 0, total_symbols = 0;   // offsets[count]: the end of the last string (and, of the symbols, how many were decoded)
+    uint64_t first_byte = 0;     // offsets[0]: a tape may be a window of a larger buffer
     uint32_t longest_bytes = 0, longest_symbols = 0;
     std::vector<void *> owned;   // device buffers that go with the handle
 };
@@ -437,9 +438,9 @@ static Lengths call_lengths(const Scope *scope, const Engine *engine, const Call
         l.known = l.guaranteed = true;
         l.la_max = utf8 ? spec.pa->longest_symbols : spec.pa->longest_bytes;
         l.lb_max = utf8 ? spec.pb->longest_symbols : spec.pb->longest_bytes;
-        const uint64_t ma = spec.pa->bytes.count ? spec.pa->total_bytes * 16 / spec.pa->bytes.count : 0;
-        const uint64_t mb = spec.pb->bytes.count ? spec.pb->total_bytes * 16 / spec.pb->bytes.count : 0;
-        l.prepared_mean_x16 = std::max(ma, mb);
+        const uint64_t ma = spec.pa->bytes.count ? (spec.pa->total_bytes - spec.pa->first_byte) * 16 / spec.pa->bytes.count : 0;
+        const uint64_t mb = spec.pb->bytes.count ? (spec.pb->total_bytes - spec.pb->first_byte) * 16 / spec.pb->bytes.count : 0;
+        l.prepared_mean_x16 = std::max(ma, mb);   // (of the WHOLE tapes, whatever the view: a view's own bytes would cost a read of its two offsets per call)
     } else if (scope->hint_lengths) {
         l.known = true;
         l.la_max = scope->hint_max_la; l.lb_max = scope->hint_max_lb;
@@ -951,6 +952,16 @@ struct Call {
         else SWH_HIP_CHECK(hipStreamSynchronize(stream));
         if (*invalid_host) return utf8_flagged();
         learn_ascii();
+        if (scope->summary_host[0].max_la >= kStringLimit || scope->summary_host[0].max_lb >= kStringLimit) {
+            // A string the windows cannot index (common.hpp: kStringLimit). The kernels of these routes leave its pair alone, or -- where
+            // they finish the pairs that lengths alone decide (k_direct_short) -- store a value that means nothing: the call is refused
+            // here as the planned path refuses it, and the scope believes nothing about this batch.
+            scope->summary_pending = false;
+            scope->stamps_pending = false;
+            scope->hint_lengths = false;
+            return fail(error, swh_unsupported_length_k, "a string of 2^30 symbols or more (the longest: %u x %u symbols)",
+                        scope->summary_host[0].max_la, scope->summary_host[0].max_lb);
+        }
         if (scope->summary_host[0].violation) {
             // the belief about the lengths was wrong (it came from an earlier batch): redo on the planned path
             scope->hint_lengths = false;
@@ -1036,6 +1047,11 @@ struct Call {
             SWH_HIP_CHECK(hipStreamSynchronize(stream));
             scope->fused_disabled = true;
             return redo_with(spec);
+        }
+        if (plan.max_la >= kStringLimit || plan.max_lb >= kStringLimit) {
+            // (the planner filed the pairs of such strings as done: nothing walks them; the other pairs' results may have been written)
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            return fail(error, swh_unsupported_length_k, "a string of 2^30 symbols or more (the longest: %u x %u symbols)", plan.max_la, plan.max_lb);
         }
         // enqueue k_direct_short next time only if short pairs are a real share of the batch (it sweeps all offsets)
         scope->hint_short = (uint64_t)plan.short_pairs * 4 >= pairs;
@@ -1487,6 +1503,24 @@ static swh_status_t prepare_tape(Scope *scope, const HostTape &tape, bool utf8, 
         SWH_HIP_CHECK(hipMemsetAsync(words, 0, (4 + kUtf8FlagWords) * sizeof(uint32_t), stream));
         launch_tape_longest(scope, offsets, p->off64, tape.count, words);
         uint64_t total_symbols = p->total_bytes;
+        // offsets[0], for the mean string of a tape that is a window into a larger buffer (call_lengths): it travels with the words read
+        // back below, under the synchronisation they need anyway
+        uint64_t first_byte = 0;
+        if (tape.count) {
+            if (dev_off) SWH_HIP_CHECK(hipMemcpyAsync(&first_byte, tape.offsets, ow, hipMemcpyDeviceToHost, stream));
+            else memcpy(&first_byte, tape.offsets, ow);
+        }
+        if (p->total_bytes >= kStringLimit) {
+            // only such a tape can hold a string the windows cannot index (common.hpp: kStringLimit); it is refused on its offsets alone,
+            // before anything is decoded -- in bytes, which bound the code points (k_tape_longest saturates at 2^32 - 1)
+            uint32_t longest = 0;
+            SWH_HIP_CHECK(hipMemcpyAsync(&longest, words, sizeof longest, hipMemcpyDeviceToHost, stream));
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            if (longest >= kStringLimit) {
+                free_prepared(p);
+                return fail(error, swh_unsupported_length_k, "a string of %u bytes: one string holds fewer than 2^30", longest);
+            }
+        }
         if (utf8) {
             // validate + decode once: `CharsTapeView::try_from` (bench.rs:303-306)
             Utf8Args u{};
@@ -1522,6 +1556,9 @@ static swh_status_t prepare_tape(Scope *scope, const HostTape &tape, bool utf8, 
             p->symbols = p->bytes;
         }
         p->total_symbols = total_symbols;
+        // (offsets that do not ascend are the caller's error and every kernel's reads stay clamped into the tape regardless; the mean only
+        // sizes short.hip's chunks, so all it needs from such a tape is a difference that does not wrap)
+        p->first_byte = std::min(first_byte, p->total_bytes);
         *out = (swh_prepared_t)p;
         return swh_success_k;
     } catch (const HipFailure &f) {

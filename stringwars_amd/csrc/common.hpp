@@ -67,15 +67,33 @@ __device__ __forceinline__ void cross_split(const Job &job, uint64_t p, uint64_t
     ib = n - q * (uint32_t)job.b_count;
 }
 
+// A string's length as the kernels hold it: 32 bits, SATURATED wherever a length is JUDGED. On a u64 tape an entry of 2^32 bytes or
+// more must not wrap into a short string (2^32 + 5 -> 5) that a kernel would then score: at 2^32 - 1 it is above kStringLimit for
+// the planner, the plan-free kernels' own limits and k_tape_longest, and the call is refused. The readers of the plan-free kernels
+// and of the calls on prepared tapes go through here, and so does the planner.
 template <typename Off>
+__device__ __forceinline__ uint32_t extent_length(Off x0, Off x1) {
+    if constexpr (sizeof(Off) == 8) {
+        const uint64_t d = (uint64_t)(x1 - x0);
+        return (d >> 32) ? 0xFFFFFFFFu : (uint32_t)d;
+    } else {
+        return (uint32_t)(x1 - x0);
+    }
+}
+
+// kJudge: the caller decides what becomes of the pair (prepass.hip's planners, tiled.hip's tile plan): saturated lengths. The kernels
+// that score what the planner filed under their classes (bitparallel, banded, wavefront, nwprofile) never meet a pair with a string
+// of kStringLimit symbols or more -- it is filed as done -- and keep the plain difference (and their registers).
+template <typename Off, bool kJudge = false>
 __device__ __forceinline__ void pair_extent(const Job &job, uint64_t p, uint64_t &a0, uint32_t &la, uint64_t &b0,
                                             uint32_t &lb) {
     uint64_t ia = p, ib = p;
     if (job.cross) cross_split(job, p, ia, ib);
     const Off *oa = (const Off *)job.a.offsets + (ia << job.a.gap), *ob = (const Off *)job.b.offsets + (ib << job.b.gap);
     Off x0 = oa[0], x1 = oa[1], y0 = ob[0], y1 = ob[1];
-    a0 = (uint64_t)x0; la = (uint32_t)(x1 - x0);
-    b0 = (uint64_t)y0; lb = (uint32_t)(y1 - y0);
+    a0 = (uint64_t)x0; b0 = (uint64_t)y0;
+    if constexpr (kJudge) { la = extent_length<Off>(x0, x1); lb = extent_length<Off>(y0, y1); }
+    else { la = (uint32_t)(x1 - x0); lb = (uint32_t)(y1 - y0); }
 }
 
 // A result leaves as an agent-scope atomic store (`global_store ... sc1`): written through to where every XCD -- and a copy engine --
@@ -192,6 +210,11 @@ __host__ __device__ __forceinline__ uint32_t band_cost(uint32_t bound) {
     const uint32_t base = 3 * (bound + 1) + 45;
     return bound <= 63 ? base : base + 85;
 }
+
+// One string holds fewer than 2^30 symbols: the windows (bp_window.hpp, bp_item.hpp, wavefront.hip) clamp their `int` indices to
+// +-2^30 around a string's start, whatever the tape's total. A longer string is refused with swh_unsupported_length_k: when its tape
+// is prepared, or -- raw tapes -- once the host has the plan; the planner files its pair as done, so that no kernel walks it.
+constexpr uint32_t kStringLimit = 1u << 30;
 
 // Levenshtein results honour the cutoff convention out = min(d, bound + 1).
 __device__ __forceinline__ uint32_t clamp_bound(uint32_t d, uint32_t bound) {

@@ -35,7 +35,7 @@ template <typename Off>
 __device__ __forceinline__ void tape_extent(const void *offsets, uint64_t i, uint64_t &start, uint32_t &len) {
     const Off *o = (const Off *)offsets;
     const Off x0 = o[i], x1 = o[i + 1];
-    start = (uint64_t)x0; len = (uint32_t)(x1 - x0);
+    start = (uint64_t)x0; len = extent_length<Off>(x0, x1);
 }
 
 // Between LDS operations of ONE wave only program order has to be kept: a wave's DS instructions are queued and executed

@@ -32,7 +32,7 @@ __device__ __forceinline__ void infix_extent(const TapeRef &t, uint64_t i, uint6
     const Off *o = (const Off *)t.offsets;
     const Off x0 = o[i], x1 = o[i + 1];
     start = (uint64_t)x0;
-    len = (uint32_t)(x1 - x0);
+    len = extent_length<Off>(x0, x1);
 }
 __device__ __forceinline__ void infix_extent(const TapeRef &t, uint32_t off64, uint64_t i, uint64_t &start, uint32_t &len) {
     if (off64) infix_extent<uint64_t>(t, i, start, len);

@@ -82,7 +82,7 @@ template <typename Off>
 __device__ __forceinline__ PairInfo pair_info(const PrepassArgs &args, uint64_t p, int gap_open, int gap_extend,
                                               bool levenshtein_unit) {
     PairInfo info;
-    pair_extent<Off>(args.job, p, info.a0, info.la, info.b0, info.lb);
+    pair_extent<Off, true>(args.job, p, info.a0, info.la, info.b0, info.lb);
     classify_trivial(args, info, gap_open, gap_extend, levenshtein_unit);
     return info;
 }
@@ -92,7 +92,9 @@ __device__ __forceinline__ void classify_trivial(const PrepassArgs &args, PairIn
     info.trivial = false;
     info.trivial_value = 0;
     uint32_t la = info.la, lb = info.lb;
-    if (la == 0 || lb == 0) {
+    if ((la | lb) >= kStringLimit) {   // (either has bit 30 or 31 set) the call is refused once the host has the plan: no kernel walks this pair
+        info.trivial = true;
+    } else if (la == 0 || lb == 0) {
         uint32_t len = la + lb;
         info.trivial = true;
         // gap(k) = open + (k-1)*extend; a pair of empty strings scores 0.
@@ -340,7 +342,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_fused(PrepassArgs args, F
         for (int k = 0; k < kFusedPer; ++k) {
             const uint64_t p = first + (uint64_t)k * kPlanThreads + threadIdx.x;
             uint64_t a0, b0;
-            pair_extent<Off>(args.job, p < args.job.pairs ? p : args.job.pairs - 1, a0, las[k], b0, lbs[k]);
+            pair_extent<Off, true>(args.job, p < args.job.pairs ? p : args.job.pairs - 1, a0, las[k], b0, lbs[k]);
         }
 #pragma unroll
         for (int k = 0; k < kFusedPer; ++k) {

@@ -144,8 +144,8 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
             const int k = kb + j;
             const uint64_t p = base + (uint32_t)k * kThreads + threadIdx.x;
             const uint64_t pc = p < args.job.pairs ? p : args.job.pairs - 1;
-            if (args.off64) pair_extent<uint64_t>(args.job, pc, a0s[j], las[j], b0s[j], lbs[j]);
-            else pair_extent<uint32_t>(args.job, pc, a0s[j], las[j], b0s[j], lbs[j]);
+            if (args.off64) pair_extent<uint64_t, true>(args.job, pc, a0s[j], las[j], b0s[j], lbs[j]);
+            else pair_extent<uint32_t, true>(args.job, pc, a0s[j], las[j], b0s[j], lbs[j]);
             affix[k] = 0;
         }
         if constexpr (sizeof(Sym) == 1 && kWide) {
@@ -191,6 +191,9 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
                 maxa = la > maxa ? la : maxa;
                 maxb = lb > maxb ? lb : maxb;
                 shorts += (la <= 32 && lb <= 32) ? 1u : 0u;
+                // (a string the windows cannot index, common.hpp: a short pattern would otherwise walk it as its text. The redo plans the
+                // call, and the planned path refuses it)
+                if ((la | lb) >= kStringLimit) { misfit = 1; continue; }
                 const uint32_t diff = la > lb ? la - lb : lb - la;
                 const uint32_t shared = (affix[k] & 63u) + (affix[k] >> 6);
                 la -= shared; lb -= shared;
@@ -339,8 +342,8 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
                 if (have) {
                     const uint32_t entry = tl.sorted[cstart + pidx];
                     p = base + (entry & (uint32_t)(kTileMax - 1));
-                    if (args.off64) pair_extent<uint64_t>(args.job, p, a0, la, b0, lb);
-                    else pair_extent<uint32_t>(args.job, p, a0, la, b0, lb);
+                    if (args.off64) pair_extent<uint64_t, true>(args.job, p, a0, la, b0, lb);
+                    else pair_extent<uint32_t, true>(args.job, p, a0, la, b0, lb);
                     const uint32_t pre = (entry >> kTileIndexBits) & 63u, both = pre + (entry >> (kTileIndexBits + 6));   // what the pair shares at both ends (step B)
                     a0 += pre; b0 += pre; la -= both; lb -= both;
                 }
