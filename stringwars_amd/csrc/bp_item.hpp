@@ -121,6 +121,42 @@ struct BpWave {
     }
 };
 
+// Sixteen bytes at any alignment from GLOBAL memory, through a base that was put together from integers (a wave-uniform register
+// pair, read_first_lane'd): said in the pointer's type, or the loads come out as flat ones.
+typedef uint32_t bp_u32x4 __attribute__((ext_vector_type(4)));
+typedef bp_u32x4 bp_u32x4_unaligned __attribute__((aligned(1)));
+typedef const __attribute__((address_space(1))) uint8_t *bp_global_bytes;
+__device__ __forceinline__ bp_u32x4 bp_load16(bp_global_bytes base, uint32_t offset) {
+    return *(const __attribute__((address_space(1))) bp_u32x4_unaligned *)(base + offset);
+}
+
+// What tiled.hip hands an item besides the pair (kBpFromTile, kBpInterior): what it knows per lane and tile already.
+struct BpTileItem {
+    uint32_t slot = 0, blk = 0;     // lane / G, lane % G
+    bool a_is_pattern = false;      // bp_pattern_is_a of the pair, as step B of the tile plan found it
+    // kBpInterior: both tapes are read through ONE wave-uniform base and a 32-bit offset per lane
+    bp_global_bytes base = nullptr;
+    uint32_t a_off = 0, b_off = 0;      // tape data - base (mod 2^32: a string's start + this is below 2^31)
+    uint32_t a_last = 0, b_last = 0;    // highest offset at which a 16-byte window of that tape may start
+};
+enum BpItemMode { kBpAlone = 0, kBpFromTile = 1, kBpInterior = 2 };
+
+// The interior variant's margins. Around every string of an INTERIOR tile (tiled.hip decides per tile) lie at least kBpMarginLo
+// readable bytes of its tape before the tile's lowest start and kBpMarginHi after its highest end, so an item reads without
+// clamping its windows into the tape:
+//   - a text window starts at s0 - blk, blk <= 63 bytes before the string's start:                       kBpMarginLo >= 63;
+//   - a pattern block is the 32 bytes row0 .. row0 + 31 and is used only if row0 < m, so it starts at or before the string's last
+//     byte and ends at most 31 bytes past the string's end:                                              kBpMarginHi >= 31;
+//   - a 16-byte text window with a column in range starts before the string's end:                       kBpMarginHi >= 15.
+// What starts later than that -- the prefetch one super-step past n_eff, the columns of a longer text in the same item, the blocks
+// of a class wider than the pair needs -- is held at the tape's last allowed window with ONE v_min_u32 (`*_last`): such a window
+// lies wholly behind the lane's own string, where every column fails the range test and every row is masked out of the table.
+// Bytes read outside a pair's own strings are harmless by construction, here as with the clamped windows, which return the
+// neighbours' bytes too: text past n is masked by the range test of `column`; pattern rows past m only enter zero bits, sit in rows
+// that are masked out of the popcount, and never propagate downward (the recurrence carries upward, from low rows to high).
+constexpr uint32_t kBpMarginLo = 64, kBpMarginHi = 32;
+static_assert(kBpMarginLo >= 63 && kBpMarginHi >= 31 && kBpMarginHi >= 16, "see the derivation above: 64 lanes per wave, 32-row blocks, 16-byte windows");
+
 // kWide: byte tapes of at least 16 bytes each, read with 128-bit loads (bp_window.hpp). A compile-time switch, because
 // a run-time one inside the loops makes the two variants' registers merge right after the loads, i.e. puts a full
 // memory wait next to every prefetch.
@@ -128,28 +164,55 @@ struct BpWave {
 // (p, a0, la, b0, lb). G may exceed the blocks a pair needs (lanes past the pattern idle).
 // `staged` (optional): an LDS array of 16-bit slots the caller drains later -- the distance of pair p goes to staged[p - staged_base]
 // instead of straight to the output (tiled.hip writes a tile's results as one coalesced sweep).
-template <typename Sym, bool kWide>
+// kMode: kBpAlone derives slot, block and pattern side itself; kBpFromTile takes them from `ti`; kBpInterior (bytes, kWide) also
+// reads both strings through ti's unclamped windows.
+template <typename Sym, bool kWide, int kMode = kBpAlone>
 __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv, const uint32_t G, const bool have, const uint64_t p,
                                         const uint64_t a0, const uint32_t la, const uint64_t b0, const uint32_t lb,
-                                        uint16_t *staged = nullptr, const uint64_t staged_base = 0) {
+                                        uint16_t *staged = nullptr, const uint64_t staged_base = 0, const BpTileItem &ti = BpTileItem{}) {
     constexpr bool kBytes = sizeof(Sym) == 1;
     constexpr bool wide_tapes = kWide;
+    constexpr bool kInterior = kMode == kBpInterior;
+    static_assert(!kInterior || (kBytes && kWide), "the interior variant is for byte tapes read with 128-bit loads");
     const int lane = wv.lane;
     uint32_t *const table = wv.table;
     uint32_t *const acc = wv.acc;
     [[maybe_unused]] const NibbleTables &nib = wv.nib;
     [[maybe_unused]] const GroupTables3 &grp = wv.grp;
-    const uint64_t a_total = wv.a_total, b_total = wv.b_total;
-    const uint32_t slot = (uint32_t)lane / G, blk = (uint32_t)lane - slot * G;
-    // pattern = rows / bits / lanes, text = columns / steps: the cheaper of the two assignments (common.hpp)
-    const bool a_is_pattern = bp_pattern_is_a(la, lb);
+    uint32_t slot, blk;
+    bool a_is_pattern;
+    if constexpr (kMode == kBpAlone) {
+        slot = (uint32_t)lane / G; blk = (uint32_t)lane - slot * G;
+        // pattern = rows / bits / lanes, text = columns / steps: the cheaper of the two assignments (common.hpp)
+        a_is_pattern = bp_pattern_is_a(la, lb);
+    } else {
+        slot = ti.slot; blk = ti.blk; a_is_pattern = ti.a_is_pattern;
+    }
     const uint32_t m = a_is_pattern ? la : lb, n = a_is_pattern ? lb : la;
     using Window = typename std::conditional<kBytes, ByteWindow, SymWindow32>::type;
-    Window pat, txt;
-    pat.init((const Sym *)(a_is_pattern ? args.job.a.data : args.job.b.data), a_is_pattern ? a0 : b0,
-             a_is_pattern ? a_total : b_total);
-    txt.init((const Sym *)(a_is_pattern ? args.job.b.data : args.job.a.data), a_is_pattern ? b0 : a0,
-             a_is_pattern ? b_total : a_total);
+    [[maybe_unused]] Window pat, txt;
+    // (interior) offsets of my pattern block and of my text's column 0 - blk from ti.base; a lane without a pair stays on the
+    // margin in front of the tile. Such a lane has a0 = b0 = 0, so its offsets are ti.a_off / ti.b_off themselves (tape data - base,
+    // which wraps modulo 2^32 when the tape begins below the base) plus blk * 32 or minus blk: anything from a few bytes to nearly
+    // 2^32. The UNSIGNED minimum against kBpMarginLo catches both: a wrapped (huge) offset becomes kBpMarginLo, a small one stays
+    // below it, and either way the lane's windows start within base .. base + kBpMarginLo, the readable margin in front of the tile
+    // (32 pattern bytes or 16 text bytes from there end by base + kBpMarginLo + 32, that is the tile's lowest start + kBpMarginHi,
+    // which the interior test found readable).
+    [[maybe_unused]] uint32_t pat_off = 0, txt_off = 0, txt_last = 0;
+    if constexpr (kInterior) {
+        const uint32_t oa = (uint32_t)a0 + ti.a_off, ob = (uint32_t)b0 + ti.b_off;
+        const uint32_t pat_last = have ? (a_is_pattern ? ti.a_last : ti.b_last) - 16u : kBpMarginLo;
+        txt_last = have ? (a_is_pattern ? ti.b_last : ti.a_last) : kBpMarginLo;
+        pat_off = (a_is_pattern ? oa : ob) + blk * 32u;
+        pat_off = pat_off < pat_last ? pat_off : pat_last;
+        txt_off = (a_is_pattern ? ob : oa) - blk;
+    } else {
+        const uint64_t a_total = wv.a_total, b_total = wv.b_total;
+        pat.init((const Sym *)(a_is_pattern ? args.job.a.data : args.job.b.data), a_is_pattern ? a0 : b0,
+                 a_is_pattern ? a_total : b_total);
+        txt.init((const Sym *)(a_is_pattern ? args.job.b.data : args.job.a.data), a_is_pattern ? b0 : a0,
+                 a_is_pattern ? b_total : a_total);
+    }
 
     // rows of my block
     const uint32_t row0 = blk * 32;
@@ -162,7 +225,11 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
     uint32_t tnxt[kTextRegs];
     int tshift[kBytes ? 4 : 1];
     auto fetch_text = [&](int first) {
-        if constexpr (kBytes) {
+        if constexpr (kInterior) {
+            const uint32_t at = txt_off + (uint32_t)first;   // `first` counts from column 0 - blk here
+            const bp_u32x4 v = bp_load16(ti.base, at < txt_last ? at : txt_last);
+            tnxt[0] = v.x; tnxt[1] = v.y; tnxt[2] = v.z; tnxt[3] = v.w;
+        } else if constexpr (kBytes) {
             if (wide_tapes) {
                 tshift[0] = txt.fetch16_raw(first, tnxt);   // [0] = distance the clamp moved the window
             } else {
@@ -179,7 +246,7 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
             }
         }
     };
-    fetch_text(0 - (int)blk);
+    fetch_text(kInterior ? 0 : 0 - (int)blk);
     [[maybe_unused]] uint32_t groups = 7;   // (code points) 3-bit groups of the tables this item uses
 
     // ---- build the match tables of my block -------------------------------------------------
@@ -188,7 +255,13 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
         // latency per item instead of one per word
         uint32_t praw[8];
         int pshift[8];
-        if (wide_tapes) {
+        if constexpr (kInterior) {
+            const bp_u32x4 v[2] = {bp_load16(ti.base, pat_off), bp_load16(ti.base, pat_off + 16)};
+#pragma unroll
+            for (int q = 0; q < 2; ++q) { praw[4 * q] = v[q].x; praw[4 * q + 1] = v[q].y; praw[4 * q + 2] = v[q].z; praw[4 * q + 3] = v[q].w; }
+#pragma unroll
+            for (int q = 0; q < 8; ++q) pshift[q] = 24;
+        } else if (wide_tapes) {
             uint32_t half[2][4];
             const int moved0 = pat.fetch16_raw((int)row0, half[0]), moved1 = pat.fetch16_raw((int)row0 + 16, half[1]);
             pat.fix16((int)row0, moved0, half[0]);
@@ -276,7 +349,10 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
     [[maybe_unused]] constexpr int NG = decltype(ng_tag)::value;
     for (uint32_t s0 = 0; s0 < steps; s0 += 16) {
         uint32_t tcur[kTextRegs];
-        if constexpr (kBytes) {
+        if constexpr (kInterior) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) tcur[q] = tnxt[q];
+        } else if constexpr (kBytes) {
             if (wide_tapes) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) tcur[q] = tnxt[q];
@@ -291,7 +367,7 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
         }
         // unconditional: clamped addresses are always readable, and a branch around the loads would make the
         // compiler wait for them right there (their registers merge with the skipped path's)
-        fetch_text((int)s0 + 16 - (int)blk);
+        fetch_text(kInterior ? (int)s0 + 16 : (int)s0 + 16 - (int)blk);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const uint32_t gs = s0 + q * 4;

@@ -7,7 +7,8 @@
 //   B. classifies them: pattern side, G = blocks of 32 rows, text length n; finishes the trivial ones;
 //   C. moves a class's few left-over pairs up into the next class when that saves a mostly empty work item;
 //   D-F. counting-sorts the tile by (G, n bucket) into a u16 index list;
-//   G. runs the work items of bp_item.hpp on it, longest first, waves taking items from an LDS ticket.
+//   G. runs the work items of bp_item.hpp on it, longest first, waves taking items from an LDS ticket -- for a tile away from both ends
+//      of both tapes (step B finds out) the item that reads its strings without clamping its windows into the tape.
 // Pairs of one item are consecutive in the sorted tile, so the lanes of a wave finish together just as with the global
 // sort; what is lost is one partly filled item per class and tile. What is gained: one launch per call, no host
 // round trip, no permutation / key arrays in HBM, and results that land in a 4 KB window per tile instead of being
@@ -44,15 +45,31 @@ constexpr int kTileBins = kTileClasses * kTileBuckets;
 // 16 KB index list, 8 KB of counters / staged distances) -- sixteen waves on one ticket finish together: 29.6 -> 31.1 TCUPS.
 template <int kTileMax>
 struct TileLds {
-    uint32_t sorted[kTileMax];            // tile-local pair indices (| prefix << kIndexBits | suffix << (kIndexBits + 6)), sorted by (class, text-length bucket)
+    uint32_t sorted[kTileMax];            // tile-local pair indices (| prefix << kIndexBits | suffix << (kIndexBits + 6) | "a is the pattern" << (kIndexBits + 12)), sorted by (class, text-length bucket)
     uint32_t bins[kTileBins / 2 > kTileMax / 2 ? kTileBins / 2 : kTileMax / 2];   // two u16 counters per word: counts, then exclusive prefixes; later a tile's distances, 16 bits each
     uint32_t class_count[kTileClasses];   // pairs per natural class; after step C: per final class
     uint16_t class_thr[kTileClasses];     // ranks >= thr move up to class_tgt
-    uint16_t class_tgt[kTileClasses];
+    uint16_t class_tgt[kTileClasses];     // after step F: floor(65535 / G) of class G - 1 (lane_over())
     uint32_t item_prefix[kTileClasses + 1];
-    uint32_t wave_sums[16];
+    union {
+        uint32_t wave_sums[16];           // step E
+        struct { unsigned long long lo_a, hi_a, lo_b, hi_b; } span;   // steps A - B: the bytes of either tape this tile's strings lie in
+    };
     uint32_t ticket;
 };
+static_assert(sizeof(TileLds<4096>::span) <= sizeof(TileLds<4096>::wave_sums), "the tile's span borrows the scan's wave sums");
+
+// x / G for x <= 64 and a wave-uniform G in 1 .. 64 without a division: ceil(2^16 / G) = floor(65535 / G) + 1 as a 16-bit magic (the
+// table entry is the floor: G = 1 would not fit otherwise), exact because x (magic - 2^16 / G) < 65 < 2^16 / G.
+__host__ __device__ constexpr uint32_t lane_over(uint32_t x, uint32_t floor_magic) { return (x * floor_magic + x) >> 16; }
+constexpr bool lane_over_is_exact() {
+    for (uint32_t g = 1; g <= 64; ++g)
+        for (uint32_t x = 0; x <= 64; ++x)
+            if (lane_over(x, 65535u / g) != x / g) return false;
+    return true;
+}
+static_assert(lane_over_is_exact(), "lane / G and 64 / G by multiplication");
+
 struct TileTail {   // after the last tile the counters' space serves the call summary
     unsigned long long cells, syms;
     uint32_t maxa, maxb, shorts, misfit;
@@ -89,19 +106,32 @@ struct TiledArgs {
     uint32_t tiles;
     uint32_t shift;         // text-length bucket = min(n >> shift, kTileBuckets - 1)
     uint32_t cut_affixes;   // byte strings: cut what a pair shares at both ends before classifying it
+    uint32_t no_interior;   // comparison knob: every tile runs the clamped item
     PlanPartial *partials;  // per-workgroup work-unit sums (cells, symbols, maxima, "met a pair that does not fit")
     uint32_t *done_counter;
     CallSummary *summary;   // host-mapped: the last workgroup reports (common.hpp: report_call_summary)
 };
 
-template <typename Sym, int kWaves, bool kWide>
+// kPlain: the launch's shape is known when the kernel is compiled -- 32-bit offsets, pairwise, unbounded (what launch_tiled_sym sends
+// there) -- so the per-pair tests of offset width, cross-product split and bound fold away.
+template <typename Sym, int kWaves, bool kWide, bool kPlain = false>
 __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, const uint64_t a_total, const uint64_t b_total) {
     constexpr int kThreads = kWaves * 64, kTableWords = bp_table_words<Sym>();
     // pairs per thread and tile, rounded UP: ten-wave workgroups (code points) have 640 threads, and 1024 / 640 = 1 left the
     // pairs 640 .. 1023 of a full tile unclassified (every use below is guarded by idx < count)
     constexpr int kTileMax = tile_max(kWaves), kTileIndexBits = tile_index_bits(kWaves);
     constexpr int kPer = (kTileMax + kThreads - 1) / kThreads;
-    const KernelArgs &args = targs.k;
+    // tiles away from the tapes' ends run the unclamped item (not the four-wave workgroup, a test shape that holds eight pairs per
+    // thread while it classifies: the extents' four registers would make it spill)
+    constexpr bool kInteriorTiles = sizeof(Sym) == 1 && kWide && kWaves >= 8;
+    [[maybe_unused]] KernelArgs shaped;
+    const KernelArgs *shaped_or_sent = &targs.k;
+    if constexpr (kPlain) {
+        shaped = targs.k;
+        shaped.off64 = 0; shaped.job.cross = 0; shaped.job.bound = 0xFFFFFFFFu;
+        shaped_or_sent = &shaped;
+    }
+    const KernelArgs &args = *shaped_or_sent;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     BpWave<Sym> wv;
     wv.init((uint32_t *)smem + (size_t)wave * kTableWords, (uint32_t *)smem + (size_t)kWaves * kTableWords + wave * 64, lane,
@@ -121,7 +151,7 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
         __builtin_amdgcn_s_setprio(3);   // planning is a chain of round trips and barriers: it goes first, the work items of other workgroups fill the gaps
         for (int i = threadIdx.x; i < kTileBins / 2; i += kThreads) tl.bins[i] = 0;
         if (threadIdx.x < kTileClasses) tl.class_count[threadIdx.x] = 0;
-        if (threadIdx.x == 0) tl.ticket = 0;
+        if (threadIdx.x == 0) { tl.ticket = 0; tl.span.lo_a = tl.span.lo_b = ~0ull; tl.span.hi_a = tl.span.hi_b = 0; }
         __syncthreads();
         // ---- B: classify my pairs ---------------------------------------------------------------------------------
         // Every load a thread needs here is requested in two batches (indices clamped into the batch, no branch between the
@@ -129,6 +159,7 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
         // pair. What a pair shares at both ends is cut off before it is classified (the first thing rapidfuzz's Levenshtein
         // does, too): up to kAffixCap symbols each, kept in the upper bits of the pair's entry in the tile's index list.
         uint32_t cls[kPer], txt[kPer], rank[kPer], affix[kPer];
+        [[maybe_unused]] unsigned long long lo_a = ~0ull, hi_a = 0, lo_b = ~0ull, hi_b = 0;   // where my pairs' strings lie (whole strings, affixes included)
         // (two pairs per thread at a time: a pair's four 16-byte windows are 16 registers while they are in flight)
 #ifndef SWH_TILE_BATCH
 #define SWH_TILE_BATCH 2
@@ -186,6 +217,10 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
             if (idx < count) {
                 const uint64_t p = base + idx;
                 uint32_t la = las[j], lb = lbs[j];
+                if constexpr (kInteriorTiles) {
+                    lo_a = a0s[j] < lo_a ? a0s[j] : lo_a; hi_a = a0s[j] + la > hi_a ? a0s[j] + la : hi_a;
+                    lo_b = b0s[j] < lo_b ? b0s[j] : lo_b; hi_b = b0s[j] + lb > hi_b ? b0s[j] + lb : hi_b;
+                }
                 cells += (unsigned long long)la * lb;
                 syms += (unsigned long long)la + lb;
                 maxa = la > maxa ? la : maxa;
@@ -210,13 +245,56 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
                     } else {
                         cls[k] = g - 1;
                         txt[k] = n;
+                        affix[k] |= pattern_is_a ? 1u << 12 : 0u;
                         rank[k] = atomicAdd(&tl.class_count[g - 1], 1u);
                     }
                 }
             }
         }
         }
+        if constexpr (kInteriorTiles) {
+            if (!args.off64) {   // 32-bit offsets: four DPP reductions (the minima as maxima of the complements)
+                lo_a = (uint32_t)~wave_max_u32(~(uint32_t)lo_a); hi_a = wave_max_u32((uint32_t)hi_a);
+                lo_b = (uint32_t)~wave_max_u32(~(uint32_t)lo_b); hi_b = wave_max_u32((uint32_t)hi_b);
+            } else {
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) {
+                    const unsigned long long la_ = __shfl_xor(lo_a, off), ha_ = __shfl_xor(hi_a, off), lb_ = __shfl_xor(lo_b, off), hb_ = __shfl_xor(hi_b, off);
+                    lo_a = la_ < lo_a ? la_ : lo_a; hi_a = ha_ > hi_a ? ha_ : hi_a;
+                    lo_b = lb_ < lo_b ? lb_ : lo_b; hi_b = hb_ > hi_b ? hb_ : hi_b;
+                }
+            }
+            if (lane == 0) {
+                atomicMin(&tl.span.lo_a, lo_a); atomicMax(&tl.span.hi_a, hi_a);
+                atomicMin(&tl.span.lo_b, lo_b); atomicMax(&tl.span.hi_b, hi_b);
+            }
+        }
         __syncthreads();
+        // Is this an INTERIOR tile -- may its items read both tapes without clamping their windows (bp_item.hpp: kBpInterior)? On both
+        // tapes the lowest start of the tile's strings lies kBpMarginLo bytes or more behind the tape's start and their highest end
+        // kBpMarginHi or more before its end (the ACTUAL extents: a cross-product tile's candidates are scattered over their tape),
+        // and the two windows, margins included, lie within 2^31 bytes of address space, so that one base and a 32-bit offset reach
+        // both. Only the tiles that hold a tape's first or last strings fail the first test; a tile that fails either runs the
+        // clamped item, as do tapes shorter than the margins. Workgroup-uniform, read once per tile (wave_sums is next written in step E).
+        [[maybe_unused]] bool interior = false;
+        [[maybe_unused]] BpTileItem ti;
+        if constexpr (kInteriorTiles) {
+            const unsigned long long s_lo_a = tl.span.lo_a, s_hi_a = tl.span.hi_a, s_lo_b = tl.span.lo_b, s_hi_b = tl.span.hi_b;
+            const bool inside = !targs.no_interior && s_lo_a <= s_hi_a && s_lo_b <= s_hi_b && s_lo_a >= kBpMarginLo && s_lo_b >= kBpMarginLo &&
+                                s_hi_a <= a_total && s_hi_b <= b_total && a_total - s_hi_a >= kBpMarginHi && b_total - s_hi_b >= kBpMarginHi;
+            const unsigned long long da = (unsigned long long)(uintptr_t)args.job.a.data, db = (unsigned long long)(uintptr_t)args.job.b.data;
+            const unsigned long long low = (da + s_lo_a < db + s_lo_b ? da + s_lo_a : db + s_lo_b) - kBpMarginLo;
+            const unsigned long long top = (da + s_hi_a > db + s_hi_b ? da + s_hi_a : db + s_hi_b) + kBpMarginHi;
+            interior = __builtin_amdgcn_readfirstlane((int)(inside && top - low <= (1ull << 31))) != 0;
+            if (interior) {
+                const uint32_t base_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)low), base_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(low >> 32));
+                ti.base = (bp_global_bytes)(uintptr_t)(((unsigned long long)base_hi << 32) | base_lo);
+                ti.a_off = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(da - low));
+                ti.b_off = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(db - low));
+                ti.a_last = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(da + s_hi_a + kBpMarginHi - 16 - low));
+                ti.b_last = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(db + s_hi_b + kBpMarginHi - 16 - low));
+            }
+        }
         // ---- C: left-overs move up; work items per class (wave 0) -------------------------------------------------
         if (wave == 0) {
             const uint32_t mine = tl.class_count[lane];
@@ -302,7 +380,7 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
             if (key[k] != 0xFFFFFFFFu) {
                 const uint32_t word = tl.bins[key[k] >> 1];
                 const uint32_t start = (key[k] & 1u) ? word >> 16 : word & 0xFFFFu;
-                tl.sorted[start + rank[k]] = ((uint32_t)k * kThreads + threadIdx.x) | (affix[k] << kTileIndexBits);   // index | prefix << 11 | suffix << 17
+                tl.sorted[start + rank[k]] = ((uint32_t)k * kThreads + threadIdx.x) | (affix[k] << kTileIndexBits);   // index | prefix << 11 | suffix << 17 | pattern side << 23
             }
         }
         __syncthreads();
@@ -313,7 +391,11 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
         // The key counters have done their work: keep the 64 class starts (class_thr is free since step D), then the
         // 4 KB they occupied stage the tile's distances -- one coalesced sweep at the end instead of 4-byte stores
         // scattered over the tile's window (which reached HBM as one 32-byte sector each: 6x the result bytes).
-        if (threadIdx.x < kTileClasses) tl.class_thr[threadIdx.x] = (uint16_t)(tl.bins[(threadIdx.x * kTileBuckets) >> 1] & 0xFFFFu);
+        // (class_tgt has been free since step D too: the multiplier that stands for a division by the class's G, lane_over())
+        if (threadIdx.x < kTileClasses) {
+            tl.class_thr[threadIdx.x] = (uint16_t)(tl.bins[(threadIdx.x * kTileBuckets) >> 1] & 0xFFFFu);
+            tl.class_tgt[threadIdx.x] = (uint16_t)(65535u / (threadIdx.x + 1u));
+        }
         __syncthreads();
         static_assert(sizeof(tl.bins) >= (size_t)kTileMax * 2, "the key counters' space holds a tile's distances as 16-bit slots");
         uint16_t *const staged = (uint16_t *)tl.bins;
@@ -321,7 +403,10 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
         __syncthreads();
         // ---- G: work items, heaviest first (high class, long text), dealt by an LDS ticket --------------------------------
         __builtin_amdgcn_s_setprio(0);
-        {
+        // The item loop exists once per item mode, chosen per tile OUTSIDE the loop for kWide's reason (bp_item.hpp): the interior
+        // tiles' unclamped item, the clamped one for the tiles at a tape's edges; code points keep the item that derives everything itself.
+        auto run_items = [&](auto mode_tag) {
+            constexpr int kMode = decltype(mode_tag)::value;
             const uint32_t items_total = tl.item_prefix[64];
             const uint32_t my_prefix = tl.item_prefix[lane];
             for (;;) {
@@ -331,27 +416,39 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
                 if (t >= items_total) break;
                 const uint32_t item = items_total - 1 - t;
                 const uint32_t G = (uint32_t)__popcll(__ballot(my_prefix <= item));   // class = prefix entries <= item
-                const uint32_t per = 64 / G;
+                const uint32_t over_g = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)tl.class_tgt[G - 1]);
+                const uint32_t per = lane_over(64, over_g);
                 const uint32_t chunk = item - tl.item_prefix[G - 1];
                 const uint32_t cstart = tl.class_thr[G - 1], ccount = tl.class_count[G - 1];
-                const uint32_t slot = (uint32_t)lane / G;
+                const uint32_t slot = lane_over((uint32_t)lane, over_g);
                 const uint32_t pidx = chunk * per + slot;
                 const bool have = slot < per && pidx < ccount;
                 uint64_t p = 0, a0 = 0, b0 = 0;
                 uint32_t la = 0, lb = 0;
+                BpTileItem mine = ti;
+                mine.slot = slot; mine.blk = (uint32_t)lane - slot * G;
                 if (have) {
                     const uint32_t entry = tl.sorted[cstart + pidx];
                     p = base + (entry & (uint32_t)(kTileMax - 1));
                     if (args.off64) pair_extent<uint64_t, true>(args.job, p, a0, la, b0, lb);
                     else pair_extent<uint32_t, true>(args.job, p, a0, la, b0, lb);
-                    const uint32_t pre = (entry >> kTileIndexBits) & 63u, both = pre + (entry >> (kTileIndexBits + 6));   // what the pair shares at both ends (step B)
+                    const uint32_t pre = (entry >> kTileIndexBits) & 63u, both = pre + ((entry >> (kTileIndexBits + 6)) & 63u);   // what the pair shares at both ends (step B)
                     a0 += pre; b0 += pre; la -= both; lb -= both;
+                    mine.a_is_pattern = (entry >> (kTileIndexBits + 12)) & 1u;   // step B's bp_pattern_is_a of the same cut lengths
                 }
-                bp_item<Sym, kWide>(args, wv, G, have, p, a0, la, b0, lb, staged, base);
+                bp_item<Sym, kWide, kMode>(args, wv, G, have, p, a0, la, b0, lb, staged, base, mine);
 #ifdef SWH_TILE_PROFILE
                 ++items_done;
 #endif
             }
+        };
+        if constexpr (kInteriorTiles) {
+            if (interior) run_items(std::integral_constant<int, kBpInterior>{});
+            else run_items(std::integral_constant<int, kBpFromTile>{});
+        } else if constexpr (sizeof(Sym) == 1) {
+            run_items(std::integral_constant<int, kBpFromTile>{});
+        } else {
+            run_items(std::integral_constant<int, kBpAlone>{});
         }
         TILE_STAMP(1);   // work items
         __syncthreads();
@@ -402,17 +499,17 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
     }
 }
 
-template <typename Sym, int kWaves>
+template <typename Sym, int kWaves, bool kPlain = false>
 __global__ __launch_bounds__(kWaves * 64, BpTraits<Sym>::kMinWavesPerSimd) void k_bitparallel_tiled(TiledArgs targs) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const KernelArgs &args = targs.k;
     const uint64_t a_total = tape_total(args.job.a, args.off64);
     const uint64_t b_total = tape_total(args.job.b, args.off64);
     if constexpr (sizeof(Sym) == 1) {
-        if (a_total >= 16 && b_total >= 16) tiled_run<Sym, kWaves, true>(targs, smem, a_total, b_total);
-        else tiled_run<Sym, kWaves, false>(targs, smem, a_total, b_total);
+        if (a_total >= 16 && b_total >= 16) tiled_run<Sym, kWaves, true, kPlain>(targs, smem, a_total, b_total);
+        else tiled_run<Sym, kWaves, false, kPlain>(targs, smem, a_total, b_total);
     } else {
-        tiled_run<Sym, kWaves, false>(targs, smem, a_total, b_total);
+        tiled_run<Sym, kWaves, false, kPlain>(targs, smem, a_total, b_total);
     }
 }
 
@@ -448,19 +545,26 @@ static void launch_tiled_sym(Scope *scope, const KernelArgs &args, uint64_t pair
     t.tile = tp.tile; t.tiles = tp.tiles; t.shift = tp.shift;
     static const bool no_affix = [] { const char *e = test_hook("STRINGWARS_AMD_AFFIX"); return e && atoi(e) == 0; }();   // comparison knob
     t.cut_affixes = sizeof(Sym) == 1 && !no_affix ? 1u : 0u;
+    static const bool no_interior = [] { const char *e = test_hook("STRINGWARS_AMD_INTERIOR"); return e && atoi(e) == 0; }();   // comparison knob
+    t.no_interior = no_interior ? 1u : 0u;
     t.partials = scope->plan_partials;
     t.done_counter = scope->done_counter;
     t.summary = scope->summary_target();
-    opt_in_dynamic_lds(scope, (const void *)k_bitparallel_tiled<Sym, kWaves>, lds);
+    // the headline shape (bytes, sixteen waves, 32-bit offsets, pairwise, unbounded) has a kernel of its own
+    void (*kernel)(TiledArgs) = k_bitparallel_tiled<Sym, kWaves>;
+    if constexpr (sizeof(Sym) == 1 && kWaves == 16) {
+        if (!args.off64 && !args.job.cross && args.job.bound == 0xFFFFFFFFu) kernel = k_bitparallel_tiled<Sym, kWaves, true>;
+    }
+    opt_in_dynamic_lds(scope, (const void *)kernel, lds);
     static const bool debug = test_hook("STRINGWARS_AMD_DEBUG") != nullptr;
     if (debug) {
         int per_cu = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bitparallel_tiled<Sym, kWaves>, kWaves * 64, lds);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kWaves * 64, lds);
         fprintf(stderr, "[swh] tiled: pairs %llu tile %u tiles %u blocks %u shift %u lds %zu -> %d workgroups per CU\n",
                 (unsigned long long)pairs, tp.tile, tp.tiles, tp.blocks, tp.shift, lds, per_cu);
     }
     StampGuard guard(scope, sizeof(Sym) == 1 ? "bitparallel_tiled" : "bitparallel_tiled_u32");
-    hipLaunchKernelGGL((k_bitparallel_tiled<Sym, kWaves>), dim3(tp.blocks), dim3(kWaves * 64), lds, scope->stream, t);
+    hipLaunchKernelGGL(kernel, dim3(tp.blocks), dim3(kWaves * 64), lds, scope->stream, t);
     SWH_HIP_CHECK(hipGetLastError());
 }
 
