@@ -17,6 +17,18 @@
  * output in device memory: every result has been written through to memory and acknowledged, any
  * stream, device or copy may read it; the scope's own stream may still be retiring the kernel
  * (the call returns on the kernel's summary, not on the stream: DESIGN.md section 3).
+ *
+ * Null handles and a missing device. No scope, engine or prepared tape can exist without a gfx950 device: `swh_scope_init_gpu`,
+ * `swh_scope_init_gpu_stream` and `swh_scope_init_gpus` return swh_no_device_k and leave `*scope` NULL. What a caller then holds is a
+ * NULL handle, and every call refuses one, writes none of its outputs and, where it has an `error` parameter, sets a message:
+ *  - a NULL scope or engine (or a prepared view whose `tape` is NULL) is swh_invalid_argument_k;
+ *  - the infix, OSA, LCS and Jaro calls first ask whether a device is visible and return swh_no_device_k for a NULL scope or engine
+ *    where there is none (swh_invalid_argument_k where there is one);
+ *  - the `*_free` calls accept NULL and return swh_success_k; `swh_device_count` returns swh_success_k and a count of 0;
+ *  - `swh_version` and `swh_capabilities` need no device.
+ * The calls without an `error` parameter (`swh_scope_set_async`, `swh_scope_forget`, `swh_scope_describe`, the timing getters, ...)
+ * return the status alone. `swh_scope_describe` with `capacity` below the length of the text returns swh_success_k and writes the first
+ * `capacity - 1` characters and a NUL, nothing behind them; a NULL `text` or a `capacity` of 0 is swh_invalid_argument_k.
  */
 #ifndef STRINGWARS_AMD_H_
 #define STRINGWARS_AMD_H_
