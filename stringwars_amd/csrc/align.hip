@@ -13,24 +13,12 @@
 // The ops come out back to front and are written from the end of the pair's slot, so they sit there in forward order;
 // k_align_emit moves them to their compact place once the counts are scanned.
 #include "align.hpp"
-#include "bp_item.hpp"
+#include "bp_lanes.hpp"   // the offset reader
 
 namespace swh {
 
 constexpr int kAlignWaves = 4;
 constexpr uint32_t kAlignRun = 16;   // columns of the forward pass whose inputs are loaded together
-
-template <typename Off>
-__device__ __forceinline__ void align_extent(const TapeRef &t, uint64_t i, uint64_t &start, uint32_t &len) {
-    const Off *o = (const Off *)t.offsets;
-    const Off x0 = o[i], x1 = o[i + 1];
-    start = (uint64_t)x0;
-    len = extent_length<Off>(x0, x1);
-}
-__device__ __forceinline__ void align_extent(const TapeRef &t, uint32_t off64, uint64_t i, uint64_t &start, uint32_t &len) {
-    if (off64) align_extent<uint64_t>(t, i, start, len);
-    else align_extent<uint32_t>(t, i, start, len);
-}
 
 // stored bytes of one pair: Pv / Mv per (pattern block, text column), then the bottom scores of all blocks but the last;
 // the pattern is the longer string
@@ -48,8 +36,8 @@ __global__ void __launch_bounds__(256) k_align_sizes(AlignTapes t, uint64_t *sto
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < t.count; i += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t a0, b0;
         uint32_t m, n;
-        align_extent(t.a, t.a_off64, i, a0, m);
-        align_extent(t.b, t.b_off64, i, b0, n);
+        tape_extent(t.a, t.a_off64, i, a0, m);
+        tape_extent(t.b, t.b_off64, i, b0, n);
         const uint64_t bytes = align_store_bytes(m, n), c = (uint64_t)m * n;
         store += bytes;
         symbols += (uint64_t)m + n;
@@ -198,8 +186,8 @@ __global__ void __launch_bounds__(kAlignWaves * 64) k_align(AlignTapes t, AlignC
     if (p >= c.pair_end) return;
     uint64_t a0, b0;
     uint32_t m, n;
-    align_extent<OffA>(t.a, p, a0, m);
-    align_extent<OffB>(t.b, p, b0, n);
+    tape_extent<OffA>(t.a, p, a0, m);
+    tape_extent<OffB>(t.b, p, b0, n);
     const Sym *a = (const Sym *)t.a.data + a0, *b = (const Sym *)t.b.data + b0;
     uint8_t *slot_end = c.slots + c.slot_base[p] + m + n;
 

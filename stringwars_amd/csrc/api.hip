@@ -2647,11 +2647,11 @@ static swh_status_t infix_run(Scope *scope, const TapePair &p, uint32_t bound, c
             sc_entry = &g_align_scratch[scope];
         }
         // sizes | items | distances | starts | ends (the last three only where the caller's array lives on the host)
-        const size_t need = pad(sizeof(InfixSizes)) + pad(count * sizeof(InfixItem)) + ((dev_d ? 0 : 1) + (dev_s ? 0 : 1) + (dev_e ? 0 : 1)) * pad(count * 4);
+        const size_t need = pad(sizeof(InfixSizes)) + pad(count * sizeof(LaneItem)) + ((dev_d ? 0 : 1) + (dev_s ? 0 : 1) + (dev_e ? 0 : 1)) * pad(count * 4);
         ensure(sc_entry->buf, sc_entry->bytes, need);
         Carver sc{sc_entry->buf, 0, sc_entry->bytes};
         InfixSizes *sizes = sc.take<InfixSizes>(1);
-        InfixItem *items = sc.take<InfixItem>(count);
+        LaneItem *items = sc.take<LaneItem>(count);
         uint32_t *distances = dev_d ? r.distances : sc.take<uint32_t>(count);
         uint32_t *starts = dev_s ? r.starts : sc.take<uint32_t>(count);
         uint32_t *ends = dev_e ? r.ends : sc.take<uint32_t>(count);
@@ -2766,9 +2766,9 @@ constexpr int kScoredOutputs = 3;
 
 struct ScoredFamily {
     int outputs;   // of kScoredOutputs
-    void (*sizes)(Scope *scope, const OsaTapes &t, OsaSizes *sizes, OsaItem *items);
+    void (*sizes)(Scope *scope, const OsaTapes &t, OsaSizes *sizes, LaneItem *items);
     // scores the items into where[0 .. outputs), null where an output is not written by this launch, all at `stride`
-    void (*launch)(Scope *scope, const OsaTapes &t, const OsaItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride,
+    void (*launch)(Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride,
                    uint32_t bound, bool wide);
     const char *chunk_hook;      // the test hook that lowers the slice
     const char *oversize;        // how the refusal of a pair over the length limit ends
@@ -2780,7 +2780,7 @@ struct ScoredFamily {
 
 static const ScoredFamily kOsaFamily = {
     1, launch_osa_sizes,
-    [](Scope *scope, const OsaTapes &t, const OsaItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
+    [](Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
        bool wide) {
         OsaRun run{};
         run.items = items; run.item_count = item_count;
@@ -2792,7 +2792,7 @@ static const ScoredFamily kOsaFamily = {
     "OSA distances need unit costs (match 0, mismatch 1, open 1, extend 1)", "null output pointer", false, false};
 static const ScoredFamily kLcsFamily = {
     2, launch_osa_sizes,
-    [](Scope *scope, const OsaTapes &t, const OsaItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
+    [](Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
        bool wide) {
         LcsRun run{};
         run.items = items; run.item_count = item_count;
@@ -2805,7 +2805,7 @@ static const ScoredFamily kLcsFamily = {
     "null output pointers: one of indel and lcs is needed", true, false};
 static const ScoredFamily kJaroFamily = {
     3, launch_jaro_sizes,
-    [](Scope *scope, const OsaTapes &t, const OsaItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t,
+    [](Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t,
        bool wide) {
         JaroRun run{};
         run.items = items; run.item_count = item_count;
@@ -2866,11 +2866,11 @@ static swh_status_t scored_run(Scope *scope, const ScoredFamily &f, const TapePa
             sc_entry = &g_align_scratch[scope];
         }
         // sizes | items | the slice's results (one array per output that lives on the host)
-        const size_t need = pad(sizeof(OsaSizes)) + pad(slice_pairs * sizeof(OsaItem)) + staged_count * pad(slice_pairs * width);
+        const size_t need = pad(sizeof(OsaSizes)) + pad(slice_pairs * sizeof(LaneItem)) + staged_count * pad(slice_pairs * width);
         ensure(sc_entry->buf, sc_entry->bytes, need);
         Carver sc{sc_entry->buf, 0, sc_entry->bytes};
         OsaSizes *sizes = sc.take<OsaSizes>(1);
-        OsaItem *items = sc.take<OsaItem>(slice_pairs);
+        LaneItem *items = sc.take<LaneItem>(slice_pairs);
         char *staged[kScoredOutputs];
         for (int k = 0; k < f.outputs; ++k) staged[k] = stage[k] ? sc.take<char>(slice_pairs * width) : nullptr;
 

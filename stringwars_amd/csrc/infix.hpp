@@ -1,7 +1,7 @@
 // infix.hpp -- launchers of the Levenshtein infix-search kernels (infix.hip), called by api.hip.
 // Kept apart from common.hpp, which every kernel family's profile stamp hashes (tools/kernel_sources.py).
 #pragma once
-#include "common.hpp"
+#include "osa.hpp"   // LaneItem: the work items of the two passes
 
 namespace swh {
 
@@ -22,19 +22,13 @@ struct InfixSizes {
     unsigned long long text_symbols;     // symbols the text tape (the view of it the call sees) holds
 };
 
-// A work item of the two passes: `pairs` consecutive pairs from `first` on, `blocks` lanes (32-row blocks) each; pairs * blocks <= 64.
-struct InfixItem {
-    uint64_t first;
-    uint32_t pairs, blocks;
-};
-
 // Measures the batch into `sizes` (zeroed by the caller, first_oversize set to ~0) and cuts it into items (`items`: room for `count`).
-void launch_infix_sizes(Scope *scope, const InfixTapes &t, InfixSizes *sizes, InfixItem *items);
+void launch_infix_sizes(Scope *scope, const InfixTapes &t, InfixSizes *sizes, LaneItem *items);
 
 // The forward pass writes every pair's distance and end (unclamped) to `distances` / `ends`; the start pass reads them, finds the
 // starts of the pairs within the bound and writes all three arrays in their final form (the bound applied).
 struct InfixRun {
-    const InfixItem *items;
+    const LaneItem *items;
     uint64_t item_count;
     uint32_t *distances, *starts, *ends;
     uint32_t bound;

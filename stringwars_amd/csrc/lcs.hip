@@ -13,65 +13,43 @@
 // blocks of popcount(~V) with no mask at the end; the lane of the last block collects the sum in G - 1 more wave_shr:1 steps (G is
 // no power of two) and writes the results.
 //
-// Work items: osa.hip's k_osa_sizes measures the pairs and cuts them (launch_osa_sizes, OsaTapes / OsaItem / OsaSizes), the shorter
+// The layout's shared text is bp_lanes.hpp's BpLanes. Work items: osa.hip's k_osa_sizes measures the pairs and cuts them
+// (launch_osa_sizes, OsaTapes / LaneItem / OsaSizes), the shorter
 // string at most SWH_LCS_MAX_SHORTER = SWH_OSA_MAX_SHORTER symbols. The same kernel serves the pairwise calls and, in slices of
 // whole rows, the cross-products. The bound only clamps the Indel distance.
 #include "lcs.hpp"
-#include "bp_item.hpp"
+#include "bp_lanes.hpp"
 
 namespace swh {
 
 static_assert(SWH_LCS_MAX_SHORTER == SWH_OSA_MAX_SHORTER, "the work items are cut by k_osa_sizes");
 
-template <typename Off>
-__device__ __forceinline__ void lcs_extent(const TapeRef &t, uint64_t i, uint64_t &start, uint32_t &len) {
-    const Off *o = (const Off *)t.offsets;
-    const Off x0 = o[i], x1 = o[i + 1];
-    start = (uint64_t)x0;
-    len = extent_length<Off>(x0, x1);
-}
-__device__ __forceinline__ void lcs_extent(const TapeRef &t, uint32_t off64, uint64_t i, uint64_t &start, uint32_t &len) {
-    if (off64) lcs_extent<uint64_t>(t, i, start, len);
-    else lcs_extent<uint32_t>(t, i, start, len);
-}
-__device__ __forceinline__ uint32_t lcs_blocks(uint32_t m) { return m ? (m + 31) >> 5 : 1u; }
-// the strings of the launch's pair p
-__device__ __forceinline__ void lcs_pair(const OsaTapes &t, uint64_t p, uint64_t &ia, uint64_t &ib) {
-    if (t.nb) { const uint64_t row = p / t.nb; ia = t.row0 + row; ib = p - row * t.nb; }
-    else { ia = p; ib = p; }
-}
-
 template <typename Sym, bool kWide>
 __global__ void __launch_bounds__(BpTraits<Sym>::kWaves * 64, BpTraits<Sym>::kMinWavesPerSimd) k_lcs(OsaTapes t, LcsRun run) {
-    constexpr bool kBytes = sizeof(Sym) == 1;
-    static_assert(kBytes || !kWide, "128-bit reads of the columns' string are a byte-tape variant");
+    using Lanes = BpLanes<Sym, kWide>;
     constexpr int kWaves = BpTraits<Sym>::kWaves, kEntries = BpTraits<Sym>::kEntries;
     // the wave's tables: 8 KB (bytes) or 14 KB (code points) apart, from LDS address 0 -- the layout NibbleTables / GroupTables3 need
     __shared__ __attribute__((aligned(8192))) uint32_t tables[kWaves * kEntries * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t *const table = tables + wave * kEntries * 64;
-    [[maybe_unused]] NibbleTables nib;
-    [[maybe_unused]] GroupTables3 grp;
-    if constexpr (kBytes) nib.init(table, lane);
-    else grp.init(table, lane);
+    Lanes lanes;
+    lanes.init(tables + wave * kEntries * 64, lane);
     const uint64_t a_total = tape_total(t.a, t.a_off64), b_total = tape_total(t.b, t.b_off64);
-    using Window = typename std::conditional<kBytes, ByteWindow, SymWindow32>::type;
 
     for (uint64_t item = (uint64_t)blockIdx.x * kWaves + wave; item < run.item_count; item += (uint64_t)gridDim.x * kWaves) {
-        const OsaItem it = run.items[item];
+        const LaneItem it = run.items[item];
         const uint32_t G = it.blocks;
         const uint32_t slot = (uint32_t)lane / G, blk = (uint32_t)lane - slot * G;
         const bool have = slot < it.pairs;
         const uint64_t p = it.first + (have ? slot : 0);
         uint64_t ia, ib, a0, b0;
         uint32_t la, lb;
-        lcs_pair(t, p, ia, ib);
-        lcs_extent(t.a, t.a_off64, ia, a0, la);
-        lcs_extent(t.b, t.b_off64, ib, b0, lb);
+        lane_pair(t, p, ia, ib);
+        tape_extent(t.a, t.a_off64, ia, a0, la);
+        tape_extent(t.b, t.b_off64, ib, b0, lb);
         // rows / bits / lanes: the shorter string; columns / steps: the longer one
         const bool a_is_rows = la <= lb;
         const uint32_t m = a_is_rows ? la : lb, n = a_is_rows ? lb : la;
-        const uint32_t last = lcs_blocks(m) - 1;   // the block whose lane collects the pair's count
+        const uint32_t last = lane_blocks(m) - 1;   // the block whose lane collects the pair's count
         const bool keeper = have && blk == last;
         const uint32_t columns = (have && m) ? n : 0;
         // lanes that start a pair take no carry
@@ -84,70 +62,11 @@ __global__ void __launch_bounds__(BpTraits<Sym>::kWaves * 64, BpTraits<Sym>::kMi
         const uint32_t n_eff = wave_max_u32(columns ? columns + last : 0);
         if (n_eff) {   // (so both tapes hold symbols: the clamped windows below have something to read)
             const uint32_t steps = (n_eff + 15) & ~15u;
-            Window pat, txt;
+            typename Lanes::Window pat, txt;
             pat.init((const Sym *)(a_is_rows ? t.a.data : t.b.data), a_is_rows ? a0 : b0, a_is_rows ? a_total : b_total);
             txt.init((const Sym *)(a_is_rows ? t.b.data : t.a.data), a_is_rows ? b0 : a0, a_is_rows ? b_total : a_total);
-
-            // text prefetch: 16 symbols per super-step, one super-step ahead (bytes: 4 dwords; code points: 16)
-            constexpr int kTextRegs = kBytes ? 4 : 16;
-            uint32_t tnxt[kTextRegs];
-            int tshift[kBytes ? 4 : 1];
-            auto fetch_text = [&](int first) {
-                if constexpr (kBytes) {
-                    if constexpr (kWide) {
-                        tshift[0] = txt.fetch16_raw(first, tnxt);
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) tnxt[q] = txt.fetch4_raw(first + q * 4, tshift[q]);
-                    }
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 16; q += 4) {
-                        uint32_t four[4];
-                        txt.fetch4(first + q, four);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) tnxt[q + r] = four[r];
-                    }
-                }
-            };
-            fetch_text(0 - (int)blk);
-
-            // ---- the match tables of my block ----
-            const uint32_t row0 = blk * 32;
-            const uint32_t brows = columns ? (m > row0 ? (m - row0 < 32 ? m - row0 : 32) : 0) : 0;
-            const uint32_t row_mask = brows >= 32 ? 0xFFFFFFFFu : ((1u << brows) - 1u);
-#pragma unroll
-            for (int k = 0; k < kEntries; ++k) table[k * 64 + lane] = 0;
-            wave_lds_fence();
-            if constexpr (kBytes) {
-                uint32_t praw[8];
-                int pshift[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) praw[q] = pat.fetch4_raw((int)row0 + q * 4, pshift[q]);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    if (brows > (uint32_t)q * 4) {
-                        const uint32_t dw = ByteWindow::realign(praw[q], pshift[q]);
-                        nib.template insert<0>(dw, row_mask & (1u << (q * 4 + 0)));
-                        nib.template insert<1>(dw, row_mask & (1u << (q * 4 + 1)));
-                        nib.template insert<2>(dw, row_mask & (1u << (q * 4 + 2)));
-                        nib.template insert<3>(dw, row_mask & (1u << (q * 4 + 3)));
-                    }
-                }
-            } else {
-                uint32_t psym[32];
-#pragma unroll
-                for (int q = 0; q < 32; q += 4) {
-                    uint32_t four[4];
-                    pat.fetch4((int)row0 + q, four);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) psym[q + r] = four[r];
-                }
-#pragma unroll
-                for (int q = 0; q < 32; ++q)
-                    if ((uint32_t)q < brows) grp.insert(psym[q], 1u << q);
-            }
-            wave_lds_fence();
+            lanes.fetch_text(txt, 0 - (int)blk);
+            lanes.build_tables(pat, blk * 32, columns ? m : 0);
 
             uint32_t carry = 0;   // of my block's addition in my last column: 0 or 1
             auto column = [&](uint32_t eq, uint32_t s) {
@@ -158,41 +77,7 @@ __global__ void __launch_bounds__(BpTraits<Sym>::kWaves * 64, BpTraits<Sym>::kMi
                     v = (uint32_t)__builtin_amdgcn_bitop3_b32((int)(uint32_t)sum, (int)v, (int)eq, 0xF4);  // a | (b & ~c)
                 }
             };
-            for (uint32_t s0 = 0; s0 < steps; s0 += 16) {
-                uint32_t tcur[kTextRegs];
-                if constexpr (kBytes) {
-                    if constexpr (kWide) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) tcur[q] = tnxt[q];
-                        txt.fix16((int)s0 - (int)blk, tshift[0], tcur);
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) tcur[q] = ByteWindow::realign(tnxt[q], tshift[q]);
-                    }
-                } else {
-#pragma unroll
-                    for (int q = 0; q < kTextRegs; ++q) tcur[q] = tnxt[q];
-                }
-                // unconditional: clamped addresses are always readable (bp_item)
-                fetch_text((int)s0 + 16 - (int)blk);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const uint32_t gs = s0 + q * 4;
-                    if (gs >= n_eff) break;  // wave-uniform: no lane has a symbol left in this group
-                    uint32_t eqs[4];
-                    if constexpr (kBytes) {
-                        eqs[0] = nib.template lookup<0>(tcur[q]);
-                        eqs[1] = nib.template lookup<1>(tcur[q]);
-                        eqs[2] = nib.template lookup<2>(tcur[q]);
-                        eqs[3] = nib.template lookup<3>(tcur[q]);
-                    } else {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) eqs[u] = grp.lookup(tcur[q * 4 + u]);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) column(eqs[u], gs + u);
-                }
-            }
+            lanes.run(txt, steps, n_eff, blk, column);
         }
 
         // the pair's LCS length: the blocks' counts, summed towards the lane of the last block (lanes past it hold 0)
@@ -214,20 +99,12 @@ __global__ void __launch_bounds__(BpTraits<Sym>::kWaves * 64, BpTraits<Sym>::kMi
     }
 }
 
-template <typename Sym, bool kWide>
-static void lcs_launch(Scope *scope, const OsaTapes &t, const LcsRun &r) {
-    constexpr int kWaves = BpTraits<Sym>::kWaves;
-    const uint64_t blocks = std::min<uint64_t>((r.item_count + kWaves - 1) / kWaves, 1u << 22);
-    hipLaunchKernelGGL((k_lcs<Sym, kWide>), dim3((uint32_t)blocks), dim3(kWaves * 64), 0, scope->stream, t, r);
-    SWH_HIP_CHECK(hipGetLastError());
-}
-
 void launch_lcs(Scope *scope, const OsaTapes &t, const LcsRun &r) {
     if (!r.item_count) return;
     StampGuard guard(scope, t.cp ? "lcs_u32" : "lcs");
-    if (t.cp) lcs_launch<uint32_t, false>(scope, t, r);
-    else if (r.wide) lcs_launch<uint8_t, true>(scope, t, r);
-    else lcs_launch<uint8_t, false>(scope, t, r);
+    if (t.cp) lane_launch<uint32_t>(scope, k_lcs<uint32_t, false>, t, r);
+    else if (r.wide) lane_launch<uint8_t>(scope, k_lcs<uint8_t, true>, t, r);
+    else lane_launch<uint8_t>(scope, k_lcs<uint8_t, false>, t, r);
 }
 
 }  // namespace swh

@@ -1,5 +1,5 @@
 // lcs.hpp -- launcher of the longest-common-subsequence / Indel kernel (lcs.hip), called by api.hip. The pairs of a launch, their
-// measurements and their work items are osa.hpp's (OsaTapes, OsaSizes, OsaItem, launch_osa_sizes), as they stand.
+// measurements and their work items are osa.hpp's (OsaTapes, OsaSizes, LaneItem, launch_osa_sizes), as they stand.
 #pragma once
 #include "osa.hpp"
 
@@ -9,7 +9,7 @@ namespace swh {
 // to `indel` -- either may be null -- at + p * stride as a u32 (pairwise), or at + (p / nb) * stride + (p % nb) * 8 as a u64
 // (cross: the pointers are where row `row0` begins, `stride` the bytes between rows).
 struct LcsRun {
-    const OsaItem *items;
+    const LaneItem *items;
     uint64_t item_count;
     char *indel, *lcs;
     uint64_t stride;

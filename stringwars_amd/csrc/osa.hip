@@ -15,48 +15,28 @@
 // bit from its neighbour: t0's bit 31 belongs to the SAME column, which the lane above runs one step later -- the timing of the
 // horizontal deltas' bit 31. A lane whose column is not active in a step advances none of them.
 //
+// The layout's shared text (tables, prefetch, super-step loop, the sizes kernel's sums and cut) is bp_lanes.hpp's.
 // Work items: k_osa_sizes measures the pairs (cells, the first pair whose shorter string is over SWH_OSA_MAX_SHORTER -- errors come
 // before any output) and cuts every run of 64 consecutive pairs greedily into items of consecutive pairs: an item takes pairs while
 // pairs x G <= 64, G the largest block count among them (lanes past a shorter string idle). The same kernels serve the pairwise
 // calls and, in slices of whole rows, the cross-products (OsaTapes). The bound only clamps the result.
 #include "osa.hpp"
-#include "bp_item.hpp"
+#include "bp_lanes.hpp"
 
 namespace swh {
 
-template <typename Off>
-__device__ __forceinline__ void osa_extent(const TapeRef &t, uint64_t i, uint64_t &start, uint32_t &len) {
-    const Off *o = (const Off *)t.offsets;
-    const Off x0 = o[i], x1 = o[i + 1];
-    start = (uint64_t)x0;
-    len = extent_length<Off>(x0, x1);
-}
-__device__ __forceinline__ void osa_extent(const TapeRef &t, uint32_t off64, uint64_t i, uint64_t &start, uint32_t &len) {
-    if (off64) osa_extent<uint64_t>(t, i, start, len);
-    else osa_extent<uint32_t>(t, i, start, len);
-}
-__device__ __forceinline__ uint32_t osa_blocks(uint32_t m) { return m ? (m + 31) >> 5 : 1u; }
-// the strings of the launch's pair p
-__device__ __forceinline__ void osa_pair(const OsaTapes &t, uint64_t p, uint64_t &ia, uint64_t &ib) {
-    if (t.nb) { const uint64_t row = p / t.nb; ia = t.row0 + row; ib = p - row * t.nb; }
-    else { ia = p; ib = p; }
-}
-
-// One thread per pair, one wave per run of 64 consecutive pairs: the sums (one atomic per workgroup and quantity), the first
-// oversize pair, and (with `items`) the run's items -- cut by the wave's first lane from the block counts the lanes left in LDS.
-__global__ void __launch_bounds__(256) k_osa_sizes(OsaTapes t, OsaSizes *sizes, OsaItem *items) {
-    __shared__ unsigned long long part[4][2];
-    __shared__ uint32_t blocks_of[4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+// One thread per pair: the sums, the first oversize pair, and (with `items`) the items of each run of 64 pairs (bp_lanes.hpp).
+__global__ void __launch_bounds__(256) k_osa_sizes(OsaTapes t, OsaSizes *sizes, LaneItem *items) {
+    __shared__ LaneSizesLds lds;
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long cells = 0, symbols = 0;
     uint32_t g = 0;   // 0: no pair here
     if (i < t.count) {
         uint64_t ia, ib, a0, b0;
         uint32_t la, lb;
-        osa_pair(t, i, ia, ib);
-        osa_extent(t.a, t.a_off64, ia, a0, la);
-        osa_extent(t.b, t.b_off64, ib, b0, lb);
+        lane_pair(t, i, ia, ib);
+        tape_extent(t.a, t.a_off64, ia, a0, la);
+        tape_extent(t.b, t.b_off64, ib, b0, lb);
         cells = (unsigned long long)la * lb;
         symbols = (unsigned long long)la + lb;
         uint32_t m = la <= lb ? la : lb;
@@ -64,83 +44,42 @@ __global__ void __launch_bounds__(256) k_osa_sizes(OsaTapes t, OsaSizes *sizes, 
             atomicMin(&sizes->first_oversize, (unsigned long long)i);
             m = SWH_OSA_MAX_SHORTER;   // (the call fails; the items only have to stay well-formed)
         }
-        g = osa_blocks(m);
+        g = lane_blocks(m);
     }
-    blocks_of[wave][lane] = g;
-    for (int s = 32; s > 0; s >>= 1) {
-        cells += __shfl_xor(cells, s);
-        symbols += __shfl_xor(symbols, s);
+    lds.blocks_of[threadIdx.x >> 6][threadIdx.x & 63] = g;
+    if (lane_sizes_sum(lds, sizes, cells, symbols) && blockIdx.x == 0) {
+        sizes->a_total = tape_total(t.a, t.a_off64);
+        sizes->b_total = tape_total(t.b, t.b_off64);
     }
-    if (lane == 0) { part[wave][0] = cells; part[wave][1] = symbols; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) { cells += part[w][0]; symbols += part[w][1]; }
-        atomicAdd(&sizes->cells, cells);
-        atomicAdd(&sizes->symbols, symbols);
-        if (blockIdx.x == 0) { sizes->a_total = tape_total(t.a, t.a_off64); sizes->b_total = tape_total(t.b, t.b_off64); }
-    }
-    if (items && lane == 0 && blocks_of[wave][0]) {
-        const uint64_t run_first = (uint64_t)blockIdx.x * blockDim.x + (uint64_t)wave * 64;
-        uint32_t in_run = 0;
-        while (in_run < 64 && blocks_of[wave][in_run]) ++in_run;
-        // the run's items are counted first, then placed with one atomic
-        uint32_t count = 0;
-        for (uint32_t first = 0; first < in_run; ++count) {
-            uint32_t G = blocks_of[wave][first], k = 1;
-            while (first + k < in_run) {
-                const uint32_t g2 = blocks_of[wave][first + k], widest = g2 > G ? g2 : G;
-                if ((k + 1) * widest > 64) break;
-                G = widest; ++k;
-            }
-            first += k;
-        }
-        OsaItem *out = items + atomicAdd(&sizes->items, (unsigned long long)count);
-        for (uint32_t first = 0; first < in_run;) {
-            uint32_t G = blocks_of[wave][first], k = 1;
-            while (first + k < in_run) {
-                const uint32_t g2 = blocks_of[wave][first + k], widest = g2 > G ? g2 : G;
-                if ((k + 1) * widest > 64) break;
-                G = widest; ++k;
-            }
-            OsaItem it;
-            it.first = run_first + first; it.pairs = k; it.blocks = G;
-            *out++ = it;
-            first += k;
-        }
-    }
+    lane_cut_run(lds, sizes, items);
 }
 
 template <typename Sym, bool kWide>
 __global__ void __launch_bounds__(BpTraits<Sym>::kWaves * 64, BpTraits<Sym>::kMinWavesPerSimd) k_osa(OsaTapes t, OsaRun run) {
-    constexpr bool kBytes = sizeof(Sym) == 1;
-    static_assert(kBytes || !kWide, "128-bit reads of the columns' string are a byte-tape variant");
+    using Lanes = BpLanes<Sym, kWide>;
     constexpr int kWaves = BpTraits<Sym>::kWaves, kEntries = BpTraits<Sym>::kEntries;
     // the wave's tables: 8 KB (bytes) or 14 KB (code points) apart, from LDS address 0 -- the layout NibbleTables / GroupTables3 need
     __shared__ __attribute__((aligned(8192))) uint32_t tables[kWaves * kEntries * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t *const table = tables + wave * kEntries * 64;
-    [[maybe_unused]] NibbleTables nib;
-    [[maybe_unused]] GroupTables3 grp;
-    if constexpr (kBytes) nib.init(table, lane);
-    else grp.init(table, lane);
+    Lanes lanes;
+    lanes.init(tables + wave * kEntries * 64, lane);
     const uint64_t a_total = tape_total(t.a, t.a_off64), b_total = tape_total(t.b, t.b_off64);
-    using Window = typename std::conditional<kBytes, ByteWindow, SymWindow32>::type;
 
     for (uint64_t item = (uint64_t)blockIdx.x * kWaves + wave; item < run.item_count; item += (uint64_t)gridDim.x * kWaves) {
-        const OsaItem it = run.items[item];
+        const LaneItem it = run.items[item];
         const uint32_t G = it.blocks;
         const uint32_t slot = (uint32_t)lane / G, blk = (uint32_t)lane - slot * G;
         const bool have = slot < it.pairs;
         const uint64_t p = it.first + (have ? slot : 0);
         uint64_t ia, ib, a0, b0;
         uint32_t la, lb;
-        osa_pair(t, p, ia, ib);
-        osa_extent(t.a, t.a_off64, ia, a0, la);
-        osa_extent(t.b, t.b_off64, ib, b0, lb);
+        lane_pair(t, p, ia, ib);
+        tape_extent(t.a, t.a_off64, ia, a0, la);
+        tape_extent(t.b, t.b_off64, ib, b0, lb);
         // rows / bits / lanes: the shorter string; columns / steps: the longer one
         const bool a_is_rows = la <= lb;
         const uint32_t m = a_is_rows ? la : lb, n = a_is_rows ? lb : la;
-        const uint32_t last = osa_blocks(m) - 1;   // the block whose lane keeps the score
+        const uint32_t last = lane_blocks(m) - 1;   // the block whose lane keeps the score
         const bool keeper = have && blk == last;
         const uint32_t columns = (have && m) ? n : 0;
 
@@ -149,70 +88,11 @@ __global__ void __launch_bounds__(BpTraits<Sym>::kWaves * 64, BpTraits<Sym>::kMi
         const uint32_t n_eff = wave_max_u32(columns ? columns + last : 0);
         if (n_eff) {   // (so both tapes hold symbols: the clamped windows below have something to read)
             const uint32_t steps = (n_eff + 15) & ~15u;
-            Window pat, txt;
+            typename Lanes::Window pat, txt;
             pat.init((const Sym *)(a_is_rows ? t.a.data : t.b.data), a_is_rows ? a0 : b0, a_is_rows ? a_total : b_total);
             txt.init((const Sym *)(a_is_rows ? t.b.data : t.a.data), a_is_rows ? b0 : a0, a_is_rows ? b_total : a_total);
-
-            // text prefetch: 16 symbols per super-step, one super-step ahead (bytes: 4 dwords; code points: 16)
-            constexpr int kTextRegs = kBytes ? 4 : 16;
-            uint32_t tnxt[kTextRegs];
-            int tshift[kBytes ? 4 : 1];
-            auto fetch_text = [&](int first) {
-                if constexpr (kBytes) {
-                    if constexpr (kWide) {
-                        tshift[0] = txt.fetch16_raw(first, tnxt);
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) tnxt[q] = txt.fetch4_raw(first + q * 4, tshift[q]);
-                    }
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 16; q += 4) {
-                        uint32_t four[4];
-                        txt.fetch4(first + q, four);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) tnxt[q + r] = four[r];
-                    }
-                }
-            };
-            fetch_text(0 - (int)blk);
-
-            // ---- the match tables of my block ----
-            const uint32_t row0 = blk * 32;
-            const uint32_t brows = columns ? (m > row0 ? (m - row0 < 32 ? m - row0 : 32) : 0) : 0;
-            const uint32_t row_mask = brows >= 32 ? 0xFFFFFFFFu : ((1u << brows) - 1u);
-#pragma unroll
-            for (int k = 0; k < kEntries; ++k) table[k * 64 + lane] = 0;
-            wave_lds_fence();
-            if constexpr (kBytes) {
-                uint32_t praw[8];
-                int pshift[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) praw[q] = pat.fetch4_raw((int)row0 + q * 4, pshift[q]);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    if (brows > (uint32_t)q * 4) {
-                        const uint32_t dw = ByteWindow::realign(praw[q], pshift[q]);
-                        nib.template insert<0>(dw, row_mask & (1u << (q * 4 + 0)));
-                        nib.template insert<1>(dw, row_mask & (1u << (q * 4 + 1)));
-                        nib.template insert<2>(dw, row_mask & (1u << (q * 4 + 2)));
-                        nib.template insert<3>(dw, row_mask & (1u << (q * 4 + 3)));
-                    }
-                }
-            } else {
-                uint32_t psym[32];
-#pragma unroll
-                for (int q = 0; q < 32; q += 4) {
-                    uint32_t four[4];
-                    pat.fetch4((int)row0 + q, four);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) psym[q + r] = four[r];
-                }
-#pragma unroll
-                for (int q = 0; q < 32; ++q)
-                    if ((uint32_t)q < brows) grp.insert(psym[q], 1u << q);
-            }
-            wave_lds_fence();
+            lanes.fetch_text(txt, 0 - (int)blk);
+            lanes.build_tables(pat, blk * 32, columns ? m : 0);
 
             // Lanes that start a pair take the boundary instead of a neighbour: a horizontal delta of +1 (the alignment is global) and
             // no transposition bit. The masks are made opaque so that the splice stays plain bitwise ops (bp_item).
@@ -248,41 +128,7 @@ __global__ void __launch_bounds__(BpTraits<Sym>::kWaves * 64, BpTraits<Sym>::kMi
                     mv = ph_s & xv;
                 }
             };
-            for (uint32_t s0 = 0; s0 < steps; s0 += 16) {
-                uint32_t tcur[kTextRegs];
-                if constexpr (kBytes) {
-                    if constexpr (kWide) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) tcur[q] = tnxt[q];
-                        txt.fix16((int)s0 - (int)blk, tshift[0], tcur);
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) tcur[q] = ByteWindow::realign(tnxt[q], tshift[q]);
-                    }
-                } else {
-#pragma unroll
-                    for (int q = 0; q < kTextRegs; ++q) tcur[q] = tnxt[q];
-                }
-                // unconditional: clamped addresses are always readable (bp_item)
-                fetch_text((int)s0 + 16 - (int)blk);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const uint32_t gs = s0 + q * 4;
-                    if (gs >= n_eff) break;  // wave-uniform: no lane has a symbol left in this group
-                    uint32_t eqs[4];
-                    if constexpr (kBytes) {
-                        eqs[0] = nib.template lookup<0>(tcur[q]);
-                        eqs[1] = nib.template lookup<1>(tcur[q]);
-                        eqs[2] = nib.template lookup<2>(tcur[q]);
-                        eqs[3] = nib.template lookup<3>(tcur[q]);
-                    } else {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) eqs[u] = grp.lookup(tcur[q * 4 + u]);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) column(eqs[u], gs + u);
-                }
-            }
+            lanes.run(txt, steps, n_eff, blk, column);
         }
 
         if (keeper) {
@@ -297,26 +143,18 @@ __global__ void __launch_bounds__(BpTraits<Sym>::kWaves * 64, BpTraits<Sym>::kMi
     }
 }
 
-void launch_osa_sizes(Scope *scope, const OsaTapes &t, OsaSizes *sizes, OsaItem *items) {
+void launch_osa_sizes(Scope *scope, const OsaTapes &t, OsaSizes *sizes, LaneItem *items) {
     StampGuard guard(scope, "osa_sizes");
     hipLaunchKernelGGL(k_osa_sizes, dim3((uint32_t)((t.count + 255) / 256)), dim3(256), 0, scope->stream, t, sizes, items);
-    SWH_HIP_CHECK(hipGetLastError());
-}
-
-template <typename Sym, bool kWide>
-static void osa_launch(Scope *scope, const OsaTapes &t, const OsaRun &r) {
-    constexpr int kWaves = BpTraits<Sym>::kWaves;
-    const uint64_t blocks = std::min<uint64_t>((r.item_count + kWaves - 1) / kWaves, 1u << 22);
-    hipLaunchKernelGGL((k_osa<Sym, kWide>), dim3((uint32_t)blocks), dim3(kWaves * 64), 0, scope->stream, t, r);
     SWH_HIP_CHECK(hipGetLastError());
 }
 
 void launch_osa(Scope *scope, const OsaTapes &t, const OsaRun &r) {
     if (!r.item_count) return;
     StampGuard guard(scope, t.cp ? "osa_u32" : "osa");
-    if (t.cp) osa_launch<uint32_t, false>(scope, t, r);
-    else if (r.wide) osa_launch<uint8_t, true>(scope, t, r);
-    else osa_launch<uint8_t, false>(scope, t, r);
+    if (t.cp) lane_launch<uint32_t>(scope, k_osa<uint32_t, false>, t, r);
+    else if (r.wide) lane_launch<uint8_t>(scope, k_osa<uint8_t, true>, t, r);
+    else lane_launch<uint8_t>(scope, k_osa<uint8_t, false>, t, r);
 }
 
 }  // namespace swh

@@ -24,20 +24,21 @@ struct OsaSizes {
     unsigned long long a_total, b_total; // symbols the two tapes (the views of them the call sees) hold
 };
 
-// A work item: `pairs` consecutive pairs from `first` on, `blocks` lanes (32-row blocks of the shorter string) each; pairs * blocks <= 64.
-struct OsaItem {
+// A work item of every lane-per-block family (bp_lanes.hpp): `pairs` consecutive pairs from `first` on, `blocks` lanes (32-row blocks of
+// the rows' string) each; pairs * blocks <= 64.
+struct LaneItem {
     uint64_t first;
     uint32_t pairs, blocks;
 };
 
 // Measures the launch's pairs into `sizes` (zeroed by the caller, first_oversize set to ~0) and, unless `items` is null, cuts them
 // into items (`items`: room for `count`).
-void launch_osa_sizes(Scope *scope, const OsaTapes &t, OsaSizes *sizes, OsaItem *items);
+void launch_osa_sizes(Scope *scope, const OsaTapes &t, OsaSizes *sizes, LaneItem *items);
 
 // Scores the items' pairs: min(d, bound + 1) of pair p goes to `out` + p * stride as a u32 (pairwise), or to
 // `out` + (p / nb) * stride + (p % nb) * 8 as a u64 (cross: `out` is where row `row0` begins, `stride` the bytes between rows).
 struct OsaRun {
-    const OsaItem *items;
+    const LaneItem *items;
     uint64_t item_count;
     char *out;
     uint64_t stride;

@@ -23,7 +23,7 @@
 //                       ordinary cross-product routes into scratch) into the row's running list. `Max` ranks by the largest score
 //                       (key (~s << 32) | j) -- the same code for a later score-maximising search; only the distance form is built.
 #include "common.hpp"
-#include "bp_window.hpp"
+#include "bp_lanes.hpp"   // the offset reader, lds_order, readlane64
 
 #include <algorithm>
 
@@ -33,26 +33,6 @@ constexpr uint32_t kTopkLongest = 32;   // longest query / candidate of the fuse
 constexpr int kTopkQueries = 16;        // queries per work item
 constexpr int kTopkWaves = 4;
 constexpr uint64_t kTopkPad = ~0ull;
-
-template <typename Off>
-__device__ __forceinline__ void topk_extent(const void *offsets, uint64_t i, uint64_t &start, uint32_t &len) {
-    const Off *o = (const Off *)offsets;
-    const Off x0 = o[i], x1 = o[i + 1];
-    start = (uint64_t)x0; len = extent_length<Off>(x0, x1);
-}
-
-// A wave's LDS operations execute in issue order: only the compiler must not move them across each other (cross.hip).
-__device__ __forceinline__ void topk_lds_order() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
-    return (uint64_t)hi << 32 | lo;
-}
 
 // Merges the keys of the `admitted` lanes into the wave's sorted list of k keys (LDS, k <= 64) and returns the new threshold.
 // Keys are distinct (candidate indices are), and no admitted key is a pad: ranks in the union are a permutation.
@@ -69,7 +49,7 @@ __device__ __forceinline__ uint64_t topk_fold(uint64_t *list, uint32_t k, uint64
 #pragma unroll
     for (uint32_t step = 64; step; step >>= 1)
         if (at + step <= k && list[at + step - 1] < key) at += step;
-    topk_lds_order();
+    lds_order();
     if ((admitted >> lane) & 1ull) {
         const uint32_t rank = at + below_key;
         if (rank < k) list[rank] = key;
@@ -78,7 +58,7 @@ __device__ __forceinline__ uint64_t topk_fold(uint64_t *list, uint32_t k, uint64
         const uint32_t rank = lane + below_own;
         if (rank < k) list[rank] = own;
     }
-    topk_lds_order();
+    lds_order();
     const uint64_t last = list[k - 1];
     return last < cap ? last : cap;
 }
@@ -103,7 +83,7 @@ __device__ __forceinline__ uint64_t topk_fold_chunk(uint64_t *list, uint32_t k, 
         below_own += v < od ? count : 0u;
         list_upto_key += v <= d ? (uint32_t)__popcll(list_level) : 0u;
     }
-    topk_lds_order();
+    lds_order();
     if (mine) {
         const uint32_t rank = list_upto_key + below_key;
         if (rank < k) list[rank] = key;
@@ -112,7 +92,7 @@ __device__ __forceinline__ uint64_t topk_fold_chunk(uint64_t *list, uint32_t k, 
         const uint32_t rank = lane + below_own;
         if (rank < k) list[rank] = own;
     }
-    topk_lds_order();
+    lds_order();
     const uint64_t last = list[k - 1];
     return last < cap ? last : cap;
 }
@@ -171,7 +151,7 @@ __global__ __launch_bounds__(kTopkWaves * 64, 3) void k_cross_topk(TopkArgs args
         const uint32_t ql = (uint32_t)lane >> 2, part = (uint32_t)lane & 3u;
         uint64_t qa0 = 0;
         uint32_t qm = 0;
-        if (ql < q_count) topk_extent<Off>(args.a.offsets, q_first + ql, qa0, qm);
+        if (ql < q_count) tape_extent<Off>(args.a.offsets, q_first + ql, qa0, qm);
         uint32_t staged[8];
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
@@ -182,7 +162,7 @@ __global__ __launch_bounds__(kTopkWaves * 64, 3) void k_cross_topk(TopkArgs args
         for (int t = 0; t < 8; ++t) (&wl.table[0][0])[lane * 8 + t] = 0;
         for (uint32_t q = 0; q < q_count; ++q)
             if ((uint32_t)lane < k) lists[q * k + lane] = kTopkPad;
-        topk_lds_order();
+        lds_order();
         if (part == 0) wl.qlen[ql] = ql < q_count ? qm : 0u;
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
@@ -193,7 +173,7 @@ __global__ __launch_bounds__(kTopkWaves * 64, 3) void k_cross_topk(TopkArgs args
             }
         }
         if (ql < q_count && qm > kTopkLongest) misfit = 1;
-        topk_lds_order();
+        lds_order();
         unsigned long long sum_m = 0;
         uint32_t item_maxa = 0;
         for (uint32_t q = 0; q < q_count; ++q) {
@@ -210,7 +190,7 @@ __global__ __launch_bounds__(kTopkWaves * 64, 3) void k_cross_topk(TopkArgs args
             const bool have = cand < nb;
             uint64_t b0 = 0;
             uint32_t n = 0;
-            if (have) topk_extent<Off>(args.b.offsets, cand, b0, n);
+            if (have) tape_extent<Off>(args.b.offsets, cand, b0, n);
             const bool fits = have && n <= kTopkLongest;
             if (have && !fits) misfit = 1;
             uint32_t tw[8];
@@ -285,7 +265,7 @@ __global__ __launch_bounds__(kTopkWaves * 64, 3) void k_cross_topk(TopkArgs args
             if (slice == 0) syms += sum_m;                             // ... and every query once
         }
         // ---- the item's lists leave: the rows themselves, or this slice's partial lists -------------------------------------------
-        topk_lds_order();
+        lds_order();
         for (uint32_t q = 0; q < q_count; ++q) {
             if ((uint32_t)lane >= k) continue;
             const uint64_t key = lists[q * k + lane];
@@ -293,7 +273,7 @@ __global__ __launch_bounds__(kTopkWaves * 64, 3) void k_cross_topk(TopkArgs args
             if (args.slices == 1) topk_emit(key, args.indices + row * k + lane, args.distances + row * k + lane);
             else args.partial[(row * args.slices + slice) * k + lane] = key;
         }
-        topk_lds_order();
+        lds_order();
     }
     // ---- summary ---------------------------------------------------------------------------------------------------------------
 #pragma unroll
@@ -326,9 +306,9 @@ __global__ __launch_bounds__(kTopkWaves * 64) void k_topk_merge(const uint64_t *
     uint64_t *list = wave_list[wave];
     for (uint64_t row = (uint64_t)blockIdx.x * kTopkWaves + wave; row < rows; row += (uint64_t)gridDim.x * kTopkWaves) {
         const uint64_t *mine = partial + row * slices * k;
-        topk_lds_order();
+        lds_order();
         if (lane < k) list[lane] = mine[lane];
-        topk_lds_order();
+        lds_order();
         uint64_t threshold = list[k - 1];
         for (uint32_t s0 = 1; s0 < slices; s0 += 8) {
             uint64_t keys[8];   // eight slices' lists requested together: one memory latency per eight folds, not per fold
@@ -368,9 +348,9 @@ __global__ __launch_bounds__(kTopkWaves * 64) void k_topk_select(TopkSelectArgs 
     const uint32_t k = args.k;
     uint64_t *list = wave_list[wave];
     for (uint64_t r = (uint64_t)blockIdx.x * kTopkWaves + wave; r < args.rows; r += (uint64_t)gridDim.x * kTopkWaves) {
-        topk_lds_order();
+        lds_order();
         if (lane < k) list[lane] = args.lists[r * k + lane];
-        topk_lds_order();
+        lds_order();
         uint64_t threshold = list[k - 1] < args.cap ? list[k - 1] : args.cap;
         const uint32_t *row = args.scores + r * args.columns;
         for (uint64_t c0 = 0; c0 < args.columns; c0 += 64) {

@@ -17,7 +17,7 @@
 //   k_within_fill              cross-product routes into scratch). Slices run in stream order, so a row's cursor meets its candidates
 //                              in ascending order.
 #include "within.hpp"
-#include "bp_window.hpp"
+#include "bp_lanes.hpp"   // the offset reader, lds_order, readlane64
 
 #include <algorithm>
 
@@ -26,26 +26,6 @@ namespace swh {
 constexpr uint32_t kWithinLongest = 32;   // longest query / candidate of the fused kernel, bytes
 constexpr int kWithinQueries = 16;        // queries per work item
 constexpr int kWithinWaves = 4;
-
-template <typename Off>
-__device__ __forceinline__ void within_extent(const void *offsets, uint64_t i, uint64_t &start, uint32_t &len) {
-    const Off *o = (const Off *)offsets;
-    const Off x0 = o[i], x1 = o[i + 1];
-    start = (uint64_t)x0; len = extent_length<Off>(x0, x1);
-}
-
-// A wave's LDS operations execute in issue order: only the compiler must not move them across each other (cross.hip).
-__device__ __forceinline__ void within_lds_order() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ uint64_t within_readlane64(uint64_t v, int lane) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
-    return (uint64_t)hi << 32 | lo;
-}
 
 struct WithinArgs {
     TapeRef a, b;              // queries, candidates: device byte tapes
@@ -96,7 +76,7 @@ __global__ __launch_bounds__(kWithinWaves * 64, 4) void k_cross_within(WithinArg
         const uint32_t ql = (uint32_t)lane >> 2, part = (uint32_t)lane & 3u;
         uint64_t qa0 = 0;
         uint32_t qm = 0;
-        if (ql < q_count) within_extent<Off>(args.a.offsets, q_first + ql, qa0, qm);
+        if (ql < q_count) tape_extent<Off>(args.a.offsets, q_first + ql, qa0, qm);
         uint32_t staged[8];
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
@@ -105,7 +85,7 @@ __global__ __launch_bounds__(kWithinWaves * 64, 4) void k_cross_within(WithinArg
         }
 #pragma unroll
         for (int t = 0; t < 8; ++t) (&wl.table[0][0])[lane * 8 + t] = 0;
-        within_lds_order();
+        lds_order();
         if (part == 0) wl.qlen[ql] = ql < q_count ? qm : 0u;
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
@@ -116,7 +96,7 @@ __global__ __launch_bounds__(kWithinWaves * 64, 4) void k_cross_within(WithinArg
             }
         }
         if (ql < q_count && qm > kWithinLongest) misfit = 1;
-        within_lds_order();
+        lds_order();
         unsigned long long sum_m = 0;
         uint32_t item_maxa = 0;
         for (uint32_t q = 0; q < q_count; ++q) {
@@ -138,7 +118,7 @@ __global__ __launch_bounds__(kWithinWaves * 64, 4) void k_cross_within(WithinArg
             const bool have = cand < nb;
             uint64_t b0 = 0;
             uint32_t n = 0;
-            if (have) within_extent<Off>(args.b.offsets, cand, b0, n);
+            if (have) tape_extent<Off>(args.b.offsets, cand, b0, n);
             const bool fits = have && n <= kWithinLongest;
             if (have && !fits) misfit = 1;
             uint32_t tw[8];
@@ -198,7 +178,7 @@ __global__ __launch_bounds__(kWithinWaves * 64, 4) void k_cross_within(WithinArg
                 if (!hits) continue;
                 const uint32_t fresh = (uint32_t)__popcll(hits);
                 if constexpr (Fill) {
-                    const uint64_t at = within_readlane64(cursor, (int)q) + (uint64_t)__popcll(hits & lanes_below);
+                    const uint64_t at = readlane64(cursor, (int)q) + (uint64_t)__popcll(hits & lanes_below);
                     if (hit && at < args.total) {   // (a total the walk outgrows: the tapes changed between the passes -- never past the arrays)
                         args.indices[at] = (uint32_t)cand;
                         args.distances[at] = d;
@@ -224,7 +204,7 @@ __global__ __launch_bounds__(kWithinWaves * 64, 4) void k_cross_within(WithinArg
             }
             if ((uint32_t)lane < q_count) args.counts[(q_first + (uint64_t)lane) * args.slices + slice] = running;
         }
-        within_lds_order();   // the next item's tables are not cleared under this item's last reads
+        lds_order();   // the next item's tables are not cleared under this item's last reads
     }
     if constexpr (Fill) return;
     // ---- summary (count pass: the call's cells and lengths are counted once) ----------------------------------------------------

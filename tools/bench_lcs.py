@@ -83,7 +83,9 @@ def main():
         lcs_timing = profiled(scope, calls["indel"], args.reps)
         osa_timing = profiled(scope, calls["osa"], args.reps)
         cells = int(lcs_timing[0]["cells"])
-        assert lcs_timing[0]["dominant_name"] == ("lcs_u32" if utf8 else "lcs") and osa_timing[0]["dominant_name"] == ("osa_u32" if utf8 else "osa")
+        # (on a million 64-byte pairs k_osa_sizes, which cuts the items of both families, outlasts k_lcs: the row says whose time it holds)
+        dominant = [lcs_timing[0]["dominant_name"], osa_timing[0]["dominant_name"]]
+        assert dominant[0] in ("lcs_u32" if utf8 else "lcs", "osa_sizes") and dominant[1] in ("osa_u32" if utf8 else "osa", "osa_sizes"), dominant
         assert osa_timing[0]["cells"] == cells
         k_lcs, k_osa = quartiles([t["dominant_ms"] for t in lcs_timing]), quartiles([t["dominant_ms"] for t in osa_timing])
         row = {"workload": name, "pairs": count * count if cross else count, "cells": cells, "symbols": "code points" if utf8 else "bytes"}
@@ -93,7 +95,7 @@ def main():
             "indel_tcups": round(cells / (row["indel_ms"]["median"] * 1e-3) / 1e12, 3),
             "indel_over_general_cost": round(row["indel_ms"]["median"] / row["general_cost_ms"]["median"], 3),
             "indel_over_pairs": round(row["indel_ms"]["median"] / row["pairs_ms"]["median"], 3),
-            "k_lcs_ms": k_lcs, "k_osa_ms": k_osa,
+            "k_lcs_ms": k_lcs, "k_osa_ms": k_osa, "dominant": dominant,
             "k_lcs_tcups": round(cells / (k_lcs["median"] * 1e-3) / 1e12, 3),
             "k_lcs_over_k_osa_per_cell": round(k_lcs["median"] / k_osa["median"], 3),
             "lcs_call_kernels_ms": round(float(np.median([t["total_ms"] for t in lcs_timing])), 4),

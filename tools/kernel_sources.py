@@ -29,11 +29,11 @@ KERNELS = {
     "align_short": ("swh::k_align_short<", ("alignshort.hip", "bp_window.hpp", "common.hpp")),
     "align_wide": ("swh::k_align_cross_wide<", ("alignshort.hip", "bp_window.hpp", "common.hpp")),
     "align_long": ("swh::k_align_cross_long<", ("alignshort.hip", "bp_window.hpp", "common.hpp")),
-    "infix": ("swh::k_infix<", ("infix.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
-    "osa": ("swh::k_osa<", ("osa.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
-    "lcs": ("swh::k_lcs<", ("lcs.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
-    "jaro": ("swh::k_jaro<unsigned char,", ("jaro.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
-    "jaro_u32": ("swh::k_jaro<unsigned int,", ("jaro.hip", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
+    "infix": ("swh::k_infix<", ("infix.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
+    "osa": ("swh::k_osa<", ("osa.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
+    "lcs": ("swh::k_lcs<", ("lcs.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
+    "jaro": ("swh::k_jaro<unsigned char,", ("jaro.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
+    "jaro_u32": ("swh::k_jaro<unsigned int,", ("jaro.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
 }
 
 
