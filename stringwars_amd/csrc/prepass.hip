@@ -1500,7 +1500,11 @@ __global__ __launch_bounds__(256) void k_utf8_finish(Utf8FinishJob job_a, Utf8Fi
     }
     const uint64_t i = (uint64_t)block * 256 + threadIdx.x;
     if (i > args.in.count) return;
-    if (tiles == 0) { args.offsets[i] = 0; return; }   // an empty tape: every string is empty
+    if (tiles == 0) {   // an empty tape: every string is empty -- unless the host only BELIEVED it empty (utf8_string_offset's check)
+        if (i == args.in.count && ((const Off *)args.in.offsets)[i] != 0) atomicMax(args.invalid, kUtf8SizesChanged);
+        args.offsets[i] = 0;
+        return;
+    }
     utf8_string_offset<Off>(args, tile_prefix, sub_prefix, i);
 }
 
