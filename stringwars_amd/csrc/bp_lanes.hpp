@@ -5,51 +5,22 @@
 // the columns' string is prefetched one super-step of 16 symbols ahead. The layout is bp_item.hpp's; these families are plan-free
 // (they cut their own items) and differ from each other in their recurrence and in what the keeper lane writes.
 //
-// Shared here: the offset reader (also align.hip's, topk.hip's and within.hip's), lane_blocks, the pair split of OsaTapes, the two
-// parts of a sizes kernel (the workgroup's sums, the cut of a wave's run of pairs into LaneItems), the item skeleton BpLanes
-// (tables, prefetch, super-step loop) and the launch of an item kernel. A family writes: which string supplies the rows, `columns`,
-// its boundary masks, its `column` recurrence, its reductions after the loop and the keeper's stores.
+// Shared here: lane_blocks, the pair split of OsaTapes, the two parts of a sizes kernel (the workgroup's sums, the cut of a wave's
+// run of pairs into LaneItems), the item skeleton BpLanes (tables, prefetch, super-step loop) and the launch of an item kernel. A
+// family writes: which string supplies the rows, `columns`, its boundary masks, its `column` recurrence, its reductions after the
+// loop and the keeper's stores.
 //
-// cross.hip keeps its own copy of the offset reader (tape_extent) and of lds_order (lds_program_order): its text is hashed into the
-// committed counter stamps of the headline's roofline (tools/kernel_sources.py), so it is left as it stands.
+// The offset reader (tape_extent), lds_order and readlane64 come from cross_words.hpp, which the word-sized cross-product kernels
+// (cross.hip, topk.hip, within.hip) include without this header's bp_item.hpp and osa.hpp.
 #pragma once
 #include <algorithm>
 #include <type_traits>
 
 #include "bp_item.hpp"
+#include "cross_words.hpp"
 #include "osa.hpp"
 
 namespace swh {
-
-// String i of a tape: where it starts and its (saturated, common.hpp) length.
-template <typename Off>
-__device__ __forceinline__ void tape_extent(const void *offsets, uint64_t i, uint64_t &start, uint32_t &len) {
-    const Off *o = (const Off *)offsets;
-    const Off x0 = o[i], x1 = o[i + 1];
-    start = (uint64_t)x0;
-    len = extent_length<Off>(x0, x1);
-}
-template <typename Off>
-__device__ __forceinline__ void tape_extent(const TapeRef &t, uint64_t i, uint64_t &start, uint32_t &len) {
-    tape_extent<Off>(t.offsets, i, start, len);
-}
-__device__ __forceinline__ void tape_extent(const TapeRef &t, uint32_t off64, uint64_t i, uint64_t &start, uint32_t &len) {
-    if (off64) tape_extent<uint64_t>(t, i, start, len);
-    else tape_extent<uint32_t>(t, i, start, len);
-}
-
-// A wave's LDS operations execute in issue order: only the compiler must not move them across each other (cross.hip).
-__device__ __forceinline__ void lds_order() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
-    return (uint64_t)hi << 32 | lo;
-}
 
 // 32-row blocks (lanes) of a string of m rows; an empty string still takes a lane
 __device__ __forceinline__ uint32_t lane_blocks(uint32_t m) { return m ? (m + 31) >> 5 : 1u; }

@@ -13,14 +13,13 @@
 //
 // Exact for queries and candidates of up to 32 bytes; a longer string raises the call summary's `violation` flag and the
 // host redoes the call on the general path (api.hip), exactly as for the other plan-free kernels.
-#include "common.hpp"
-#include "bp_window.hpp"
+#include "cross_words.hpp"   // the candidate load, the column walk and the summary tail are the fused searches' too
 
 namespace swh {
 
-constexpr uint32_t kCrossMax = 32;          // longest query / candidate in bytes
-constexpr int kCrossQueries = 16;           // queries per work item (2048 x 2048 words: 4096 items, one per wave slot)
-constexpr int kCrossWaves = 4;
+constexpr uint32_t kCrossMax = kWordLongest;   // longest query / candidate in bytes (code points: symbols)
+constexpr int kCrossQueries = kWordQueries;    // queries per work item (2048 x 2048 words: 4096 items, one per wave slot)
+constexpr int kCrossWaves = kWordWaves;
 constexpr uint32_t kCrossCompareRows = 12;  // code points: queries up to here are matched by comparison (k_cross_short_cp), longer ones through the group tables
 
 struct CrossArgs {
@@ -31,22 +30,6 @@ struct CrossArgs {
     CallSummary *summary;
 };
 
-template <typename Off>
-__device__ __forceinline__ void tape_extent(const void *offsets, uint64_t i, uint64_t &start, uint32_t &len) {
-    const Off *o = (const Off *)offsets;
-    const Off x0 = o[i], x1 = o[i + 1];
-    start = (uint64_t)x0; len = extent_length<Off>(x0, x1);
-}
-
-// Between LDS operations of ONE wave only program order has to be kept: a wave's DS instructions are queued and executed
-// in issue order, so a table update (ds_or) followed by a lookup (ds_read) of another lane's word needs no wait in
-// between -- the compiler just must not move the accesses across each other (it reasons per thread).
-__device__ __forceinline__ void lds_program_order() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-}
-
 struct CrossWaveLds {
     uint32_t table[2][32];                    // Lo[16] | Hi[16] of the current query and of the next one (built ahead)
     uint32_t qlen[kCrossQueries];
@@ -56,23 +39,19 @@ struct CrossWaveLds {
 template <typename Off>
 __global__ __launch_bounds__(kCrossWaves * 64) void k_cross_short(CrossArgs args) {
     __shared__ CrossWaveLds wave_lds[kCrossWaves];
-    __shared__ SummaryLds summary_lds;
-    __shared__ unsigned long long lcells, lsyms;
-    __shared__ uint32_t lmaxa, lmaxb, lshorts, lmisfit;
+    __shared__ WordSummary::Lds summary_lds;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     CrossWaveLds &wl = wave_lds[wave];
     if (lane < 32) { wl.table[0][lane] = 0; wl.table[1][lane] = 0; }
-    if (threadIdx.x == 0) { lcells = 0; lsyms = 0; lmaxa = 0; lmaxb = 0; lshorts = 0; lmisfit = 0; }
-    __syncthreads();
+    WordSummary sum;
+    sum.init(summary_lds);
     const Job &job = args.job;
     const uint64_t na = job.a.count, nb = job.b.count;
-    const uint8_t *a_data = (const uint8_t *)job.a.data, *b_data = (const uint8_t *)job.b.data;
+    const uint8_t *b_data = (const uint8_t *)job.b.data;
     const uint64_t b_total = (uint64_t)((const Off *)job.b.offsets)[nb];
     const uint64_t chunks = (nb + 63) / 64, qblocks = (na + kCrossQueries - 1) / kCrossQueries;
     const uint64_t items = chunks * qblocks;
     const uint64_t waves_total = (uint64_t)gridDim.x * kCrossWaves, wave_id = (uint64_t)blockIdx.x * kCrossWaves + wave;
-    unsigned long long cells = 0, syms = 0;
-    uint32_t maxa = 0, maxb = 0, shorts = 0, misfit = 0;
     const size_t elem = job.out_elem64 ? 8 : 4;
 
     for (uint64_t item = wave_id; item < items; item += waves_total) {
@@ -81,52 +60,17 @@ __global__ __launch_bounds__(kCrossWaves * 64) void k_cross_short(CrossArgs args
         const uint64_t q_first = qb * kCrossQueries, q_last = q_first + kCrossQueries < na ? q_first + kCrossQueries : na;
         const uint32_t q_count = (uint32_t)(q_last - q_first);
         // ---- every load of the item is requested here: my candidate (extent, bytes) and the item's queries ---------------
-        const uint64_t slot = chunk * 64 + (uint64_t)lane;
-        const bool have = slot < nb;
-        uint64_t cand = 0, b0 = 0;
-        uint32_t n = 0;
-        if (have) {
-            cand = slot;
-            tape_extent<Off>(job.b.offsets, cand, b0, n);
-        }
-        // queries: lane l stages bytes 8 (l % 4) .. 8 (l % 4) + 7 of query l / 4 (16 queries x 32 bytes = 64 lanes x 8 bytes)
-        const uint32_t ql = (uint32_t)lane >> 2, part = (uint32_t)lane & 3u;
-        uint64_t qa0 = 0;
-        uint32_t qm = 0;
-        if (ql < q_count) tape_extent<Off>(job.a.offsets, q_first + ql, qa0, qm);
-        uint32_t staged[8];
+        WordCandidate c;
+        c.locate<Off>(job.b, chunk * 64 + (uint64_t)lane);
+        StagedQueries<Off, uint8_t> sq;
+        sq.load(job.a, q_first, q_count, lane);
+        const uint32_t ql = sq.ql, part = sq.part, qm = sq.qm;
+        c.fetch(b_data, b_total, sum.misfit);
 #pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const uint32_t at = part * 8 + (uint32_t)t;
-            staged[t] = (at < qm && qm <= kCrossMax) ? a_data[qa0 + at] : 0u;
-        }
-        const bool fits = have && n <= kCrossMax;
-        if (have && !fits) misfit = 1;
-        uint32_t tw[8];
-        {
-            ByteWindow txt;
-            txt.init(b_data, b0, b_total);
-            if (b_total >= 16) {
-                uint32_t half[4];
-                int moved = txt.fetch16_raw(0, half);
-                txt.fix16(0, moved, half);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) tw[q] = half[q];
-                moved = txt.fetch16_raw(16, half);
-                txt.fix16(16, moved, half);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) tw[4 + q] = half[q];
-            } else {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) tw[q] = txt.fetch4(q * 4);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < 8; ++t) wl.qbytes[ql][part * 8 + t] = (uint8_t)staged[t];
+        for (int t = 0; t < 8; ++t) wl.qbytes[ql][part * 8 + t] = (uint8_t)sq.staged[t];
         if (part == 0) wl.qlen[ql] = ql < q_count ? qm : 0u;
-        lds_program_order();
-        const uint32_t n_live = fits ? n : 0;
-        const uint32_t n_max = wave_max_u32(n_live);
+        lds_order();
+        const uint32_t n_max = wave_max_u32(c.n_live);
         unsigned long long sum_m = 0;   // over the item's queries, for the work units
         uint32_t item_maxa = 0;
         // ---- the item's queries: the table of query q + 1 is built while query q's columns are walked ----------------------
@@ -143,79 +87,28 @@ __global__ __launch_bounds__(kCrossWaves * 64) void k_cross_short(CrossArgs args
         for (uint32_t q = 0; q < q_count; ++q) {
             uint32_t *table = wl.table[q & 1];
             const uint32_t m = m_next;
-            lds_program_order();                                   // table q is complete; table q - 1 (the other buffer) has been cleared
+            lds_order();                                   // table q is complete; table q - 1 (the other buffer) has been cleared
             m_next = build(q + 1, wl.table[(q + 1) & 1]);
             sum_m += m;
             item_maxa = m > item_maxa ? m : item_maxa;
-            if (m > kCrossMax) misfit = 1;
-            uint32_t pv = 0xFFFFFFFFu, mv = 0;
+            if (m > kCrossMax) sum.misfit = 1;
             if (m <= kCrossMax) {
-#pragma unroll
-                for (int w4 = 0; w4 < 8; ++w4) {
-                    if ((uint32_t)w4 * 4 >= n_max) break;
-                    const uint32_t w = tw[w4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        // Lo[c & 15] and Hi[c >> 4] as byte offsets: ((w >> 8u) & 15) << 2 and ((w >> (8u + 4)) & 15) << 2
-                        const uint32_t lo_at = (u == 0 ? (w << 2) : (w >> (8 * u - 2))) & 0x3Cu;
-                        const uint32_t hi_at = (w >> (8 * u + 2)) & 0x3Cu;
-                        const uint32_t eq = *(const uint32_t *)((const char *)table + lo_at) & *(const uint32_t *)((const char *)table + 64 + hi_at);
-                        if ((uint32_t)(w4 * 4 + u) < n_live) {
-                            const uint32_t xv = eq | mv;
-                            const uint32_t xh = (((eq & pv) + pv) ^ pv) | eq;
-                            uint32_t ph = mv | ~(xh | pv);
-                            const uint32_t mh = pv & xh;
-                            ph = (ph << 1) | 1u;
-                            pv = (mh << 1) | ~(xv | ph);
-                            mv = ph & xv;
-                        }
-                    }
-                }
-                if (fits) {
-                    const uint32_t mask = m >= 32 ? 0xFFFFFFFFu : ((1u << m) - 1u);
-                    const uint32_t d = n + __popc(pv & mask) - __popc(mv & mask);
-                    char *dst = job.out + (q_first + q) * job.row_stride + cand * elem;
+                const uint32_t d = word_distance(table, m, c.tw, c.n_live, n_max, c.n);
+                if (c.fits) {
+                    char *dst = job.out + (q_first + q) * job.row_stride + c.cand * elem;
                     store_out(dst, job.out_elem64 != 0, (int64_t)d);
                 }
             }
-            lds_program_order();   // every lane has read table q
+            lds_order();   // every lane has read table q
             if (lane < 32) table[lane] = 0;
         }
-        lds_program_order();
+        lds_order();
         if (lane < 32) wl.table[q_count & 1][lane] = 0;   // (the look-ahead build of a query past the block wrote nothing, but keep both clean)
-        lds_program_order();
-        if (have) {
-            cells += sum_m * (unsigned long long)n;
-            maxb = n > maxb ? n : maxb;
-            if (qb == 0) syms += n;                                   // every candidate once ...
-            if (fits) shorts += q_count;
-        }
-        if (lane == 0) {
-            maxa = item_maxa > maxa ? item_maxa : maxa;
-            if (chunk == 0) syms += sum_m;                             // ... and every query once (bench.rs:216-224)
-        }
+        lds_order();
+        sum.add_chunk(c.have, c.fits, c.n, sum_m, q_count, qb == 0);
+        sum.add_item(lane, item_maxa, sum_m, chunk == 0);
     }
-    // ---- summary -----------------------------------------------------------------------------------------------------------
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        cells += __shfl_xor(cells, off);
-        syms += __shfl_xor(syms, off);
-        shorts += __shfl_xor(shorts, off);
-        misfit |= __shfl_xor(misfit, off);
-        const uint32_t oa = __shfl_xor(maxa, off), ob = __shfl_xor(maxb, off);
-        maxa = oa > maxa ? oa : maxa;
-        maxb = ob > maxb ? ob : maxb;
-    }
-    if (lane == 0) {
-        atomicAdd(&lcells, cells);
-        atomicAdd(&lsyms, syms);
-        atomicAdd(&lshorts, shorts);
-        atomicMax(&lmaxa, maxa);
-        atomicMax(&lmaxb, maxb);
-        atomicOr(&lmisfit, misfit);
-    }
-    __syncthreads();
-    report_call_summary(PlanPartial{lcells, lsyms, lmaxa, lmaxb, lshorts, lmisfit}, args.partials, args.done_counter, args.summary, summary_lds);
+    sum.finish(lane, summary_lds, args.partials, args.done_counter, args.summary);
 }
 
 // ---- the same for CODE POINTS (decoded UTF-8 tapes: 32-bit symbols, 64-bit offsets): `LevenshteinDistancesUtf8` on word-sized tokens,
@@ -230,22 +123,18 @@ struct CrossCpWaveLds {
 
 __global__ __launch_bounds__(kCrossWaves * 64) void k_cross_short_cp(CrossArgs args) {
     __shared__ CrossCpWaveLds wave_lds[kCrossWaves];
-    __shared__ SummaryLds summary_lds;
-    __shared__ unsigned long long lcells, lsyms;
-    __shared__ uint32_t lmaxa, lmaxb, lshorts, lmisfit;
+    __shared__ WordSummary::Lds summary_lds;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     CrossCpWaveLds &wl = wave_lds[wave];
     if (lane < 56) { wl.table[0][lane] = 0; wl.table[1][lane] = 0; }
-    if (threadIdx.x == 0) { lcells = 0; lsyms = 0; lmaxa = 0; lmaxb = 0; lshorts = 0; lmisfit = 0; }
-    __syncthreads();
+    WordSummary sum;
+    sum.init(summary_lds);
     const Job &job = args.job;
     const uint64_t na = job.a.count, nb = job.b.count;
-    const uint32_t *a_data = (const uint32_t *)job.a.data, *b_data = (const uint32_t *)job.b.data;
+    const uint32_t *b_data = (const uint32_t *)job.b.data;
     const uint64_t chunks = (nb + 63) / 64, qblocks = (na + kCrossQueries - 1) / kCrossQueries;
     const uint64_t items = chunks * qblocks;
     const uint64_t waves_total = (uint64_t)gridDim.x * kCrossWaves, wave_id = (uint64_t)blockIdx.x * kCrossWaves + wave;
-    unsigned long long cells = 0, syms = 0;
-    uint32_t maxa = 0, maxb = 0, shorts = 0, misfit = 0;
     const size_t elem = job.out_elem64 ? 8 : 4;
     for (uint64_t item = wave_id; item < items; item += waves_total) {
         const uint64_t chunk = item / qblocks, qb = item - chunk * qblocks;
@@ -257,28 +146,20 @@ __global__ __launch_bounds__(kCrossWaves * 64) void k_cross_short_cp(CrossArgs a
         uint32_t n = 0;
         if (have) {
             cand = slot;
-            tape_extent<uint64_t>(job.b.offsets, cand, b0, n);
+            tape_extent<uint64_t>(job.b, cand, b0, n);
         }
-        // queries: lane l stages symbols 8 (l % 4) .. 8 (l % 4) + 7 of query l / 4
-        const uint32_t ql = (uint32_t)lane >> 2, part = (uint32_t)lane & 3u;
-        uint64_t qa0 = 0;
-        uint32_t qm = 0;
-        if (ql < q_count) tape_extent<uint64_t>(job.a.offsets, q_first + ql, qa0, qm);
-        uint32_t staged[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const uint32_t at = part * 8 + (uint32_t)t;
-            staged[t] = (at < qm && qm <= kCrossMax) ? a_data[qa0 + at] : 0u;
-        }
+        StagedQueries<uint64_t, uint32_t> sq;
+        sq.load(job.a, q_first, q_count, lane);
+        const uint32_t ql = sq.ql, part = sq.part, qm = sq.qm;
         const bool fits = have && n <= kCrossMax;
-        if (have && !fits) misfit = 1;
+        if (have && !fits) sum.misfit = 1;
         uint32_t tw[kCrossMax];
 #pragma unroll
         for (int t = 0; t < (int)kCrossMax; ++t) tw[t] = (fits && (uint32_t)t < n) ? b_data[b0 + (uint32_t)t] : 0u;
 #pragma unroll
-        for (int t = 0; t < 8; ++t) wl.qsyms[ql][part * 8 + t] = staged[t];
+        for (int t = 0; t < 8; ++t) wl.qsyms[ql][part * 8 + t] = sq.staged[t];
         if (part == 0) wl.qlen[ql] = ql < q_count ? qm : 0u;
-        lds_program_order();
+        lds_order();
         const uint32_t n_live = fits ? n : 0;
         const uint32_t n_max = wave_max_u32(n_live);
         unsigned long long sum_m = 0;
@@ -319,16 +200,7 @@ __global__ __launch_bounds__(kCrossWaves * 64) void k_cross_short_cp(CrossArgs a
 #pragma unroll
                 for (int t = 0; t < (int)kCrossMax; ++t) {
                     if ((uint32_t)t >= n_max) break;
-                    if ((uint32_t)t < n_live) {
-                        const uint32_t e = eq[t];
-                        const uint32_t xv = e | mv;
-                        const uint32_t xh = (((e & pv) + pv) ^ pv) | e;
-                        uint32_t ph = mv | ~(xh | pv);
-                        const uint32_t mh = pv & xh;
-                        ph = (ph << 1) | 1u;
-                        pv = (mh + mh) | ~(xv | ph);
-                        mv = ph & xv;
-                    }
+                    if ((uint32_t)t < n_live) myers_column(eq[t], pv, mv);
                 }
                 if (fits) {
                     const uint32_t mask = m >= 32 ? 0xFFFFFFFFu : ((1u << m) - 1u);
@@ -352,11 +224,11 @@ __global__ __launch_bounds__(kCrossWaves * 64) void k_cross_short_cp(CrossArgs a
         for (uint32_t q = 0; q < q_tabled; ++q) {
             uint32_t *table = wl.table[q & 1];
             const uint32_t m = m_next;
-            lds_program_order();
+            lds_order();
             m_next = build(q + 1, wl.table[(q + 1) & 1]);
             sum_m += m;
             item_maxa = m > item_maxa ? m : item_maxa;
-            if (m > kCrossMax) misfit = 1;
+            if (m > kCrossMax) sum.misfit = 1;
             uint32_t pv = 0xFFFFFFFFu, mv = 0;
             if (m <= kCrossMax) {
 #pragma unroll
@@ -366,15 +238,7 @@ __global__ __launch_bounds__(kCrossWaves * 64) void k_cross_short_cp(CrossArgs a
                     uint32_t eq = table[c & 7u] & table[8 + ((c >> 3) & 7u)] & table[16 + ((c >> 6) & 7u)];
                     eq &= table[24 + ((c >> 9) & 7u)] & table[32 + ((c >> 12) & 7u)];
                     eq &= table[40 + ((c >> 15) & 7u)] & table[48 + ((c >> 18) & 7u)];
-                    if ((uint32_t)t < n_live) {
-                        const uint32_t xv = eq | mv;
-                        const uint32_t xh = (((eq & pv) + pv) ^ pv) | eq;
-                        uint32_t ph = mv | ~(xh | pv);
-                        const uint32_t mh = pv & xh;
-                        ph = (ph << 1) | 1u;
-                        pv = (mh << 1) | ~(xv | ph);
-                        mv = ph & xv;
-                    }
+                    if ((uint32_t)t < n_live) myers_column(eq, pv, mv);
                 }
                 if (fits) {
                     const uint32_t mask = m >= 32 ? 0xFFFFFFFFu : ((1u << m) - 1u);
@@ -383,54 +247,23 @@ __global__ __launch_bounds__(kCrossWaves * 64) void k_cross_short_cp(CrossArgs a
                     store_out(dst, job.out_elem64 != 0, (int64_t)d);
                 }
             }
-            lds_program_order();
+            lds_order();
             if (lane < 56) table[lane] = 0;
         }
-        lds_program_order();
+        lds_order();
         if (q_tabled && lane < 56) wl.table[q_count & 1][lane] = 0;
-        lds_program_order();
-        if (have) {
-            cells += sum_m * (unsigned long long)n;
-            maxb = n > maxb ? n : maxb;
-            if (qb == 0) syms += n;
-            if (fits) shorts += q_count;
-        }
-        if (lane == 0) {
-            maxa = item_maxa > maxa ? item_maxa : maxa;
-            if (chunk == 0) syms += sum_m;
-        }
+        lds_order();
+        sum.add_chunk(have, fits, n, sum_m, q_count, qb == 0);
+        sum.add_item(lane, item_maxa, sum_m, chunk == 0);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        cells += __shfl_xor(cells, off);
-        syms += __shfl_xor(syms, off);
-        shorts += __shfl_xor(shorts, off);
-        misfit |= __shfl_xor(misfit, off);
-        const uint32_t oa = __shfl_xor(maxa, off), ob = __shfl_xor(maxb, off);
-        maxa = oa > maxa ? oa : maxa;
-        maxb = ob > maxb ? ob : maxb;
-    }
-    if (lane == 0) {
-        atomicAdd(&lcells, cells);
-        atomicAdd(&lsyms, syms);
-        atomicAdd(&lshorts, shorts);
-        atomicMax(&lmaxa, maxa);
-        atomicMax(&lmaxb, maxb);
-        atomicOr(&lmisfit, misfit);
-    }
-    __syncthreads();
-    report_call_summary(PlanPartial{lcells, lsyms, lmaxa, lmaxb, lshorts, lmisfit}, args.partials, args.done_counter, args.summary, summary_lds);
+    sum.finish(lane, summary_lds, args.partials, args.done_counter, args.summary);
 }
 
 void launch_cross_short(Scope *scope, const Job &job, uint32_t off64, uint32_t sym_bytes) {
     CrossArgs args{};
     args.job = job; args.off64 = off64;
     args.partials = scope->plan_partials; args.done_counter = scope->done_counter; args.summary = scope->summary_target();
-    const uint64_t items = ((job.b.count + 63) / 64) * ((job.a.count + kCrossQueries - 1) / kCrossQueries);
-    uint64_t blocks64 = (items + kCrossWaves - 1) / kCrossWaves;
-    uint32_t max_blocks = (uint32_t)scope->compute_units * 8;
-    if (max_blocks > (uint32_t)kMaxPartials) max_blocks = kMaxPartials;
-    const uint32_t blocks = blocks64 > max_blocks ? max_blocks : (uint32_t)(blocks64 ? blocks64 : 1);
+    const uint32_t blocks = word_item_blocks(scope, ((job.b.count + 63) / 64) * ((job.a.count + kCrossQueries - 1) / kCrossQueries));
     StampGuard guard(scope, sym_bytes == 4 ? "cross_short_u32" : "cross_short");
     if (sym_bytes == 4) hipLaunchKernelGGL(k_cross_short_cp, dim3(blocks), dim3(kCrossWaves * 64), 0, scope->stream, args);   // (decoded tapes: 64-bit offsets)
     else if (off64) hipLaunchKernelGGL(k_cross_short<uint64_t>, dim3(blocks), dim3(kCrossWaves * 64), 0, scope->stream, args);

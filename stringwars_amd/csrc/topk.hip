@@ -11,27 +11,22 @@
 // whatever lands at k or beyond drops out.
 //
 // Kernels:
-//   k_cross_topk<Off>   word-sized byte strings (<= 32 bytes, unit costs: the route the dense call takes to k_cross_short). The
-//                       column walk is k_cross_short's -- candidates in lanes, the query's match table once per wave in LDS -- and the
-//                       store is replaced by the selection. A work item is 16 queries x one slice of the candidates: the 16 tables
-//                       are built once per item and reused for every chunk of 64 candidates of the slice (the dense kernel's item
-//                       is one chunk, so it builds each table once per chunk). Chunks whose every lane has |m - n| >= T are skipped:
-//                       d >= |m - n| (on 2048 x 2048 random words this measured neither faster nor slower than walking them).
-//                       Each item leaves its 16 lists in the outputs (one slice) or in scratch (several).
+//   k_cross_topk<Off>   word-sized byte strings (<= 32 bytes, unit costs: the route the dense call takes to k_cross_short). The item is
+//                       cross_words.hpp's -- 16 queries x one slice of the candidates -- with the distances folded into 16 lists
+//                       instead of stored. Chunks whose every lane has |m - n| >= T are skipped: d >= |m - n| (on 2048 x 2048 random
+//                       words this measured neither faster nor slower than walking them). Each item leaves its 16 lists in the
+//                       outputs (one slice) or in scratch (several).
 //   k_topk_merge        one wave per query: the slices' partial lists folded into the final row.
 //   k_topk_select<Max>  the general path: one wave per query row folds a slice of a dense u32 distance matrix (scored by the
 //                       ordinary cross-product routes into scratch) into the row's running list. `Max` ranks by the largest score
 //                       (key (~s << 32) | j) -- the same code for a later score-maximising search; only the distance form is built.
-#include "common.hpp"
-#include "bp_lanes.hpp"   // the offset reader, lds_order, readlane64
+#include "cross_words.hpp"
 
 #include <algorithm>
 
 namespace swh {
 
-constexpr uint32_t kTopkLongest = 32;   // longest query / candidate of the fused kernel, bytes
-constexpr int kTopkQueries = 16;        // queries per work item
-constexpr int kTopkWaves = 4;
+constexpr int kTopkWaves = kWordWaves;   // (also the merge and select kernels': one wave per row)
 constexpr uint64_t kTopkPad = ~0ull;
 
 // Merges the keys of the `admitted` lanes into the wave's sorted list of k keys (LDS, k <= 64) and returns the new threshold.
@@ -103,199 +98,47 @@ __device__ __forceinline__ void topk_emit(uint64_t key, uint32_t *index, uint32_
 }
 
 struct TopkArgs {
-    TapeRef a, b;              // queries, candidates: device byte tapes
-    uint32_t k, slices;        // list length; candidate slices per query block
-    uint64_t slice_chunks;     // chunks of 64 candidates per slice
+    WordSearchArgs search;     // prune: skip a query's chunk when every lane's |m - n| bound is >= T
+    uint32_t k;                // list length
     uint64_t cap;              // admitted keys are below it: (bound + 1) << 32, or kTopkPad
-    uint32_t prune;            // skip a query's chunk when every lane's |m - n| bound is >= T
     uint64_t *partial;         // slices > 1: [query][slice][k] keys
     uint32_t *indices, *distances;   // slices == 1: the rows themselves
-    PlanPartial *partials;
-    uint32_t *done_counter;
-    CallSummary *summary;
-};
-
-struct TopkWaveLds {
-    uint32_t table[kTopkQueries][32];   // Lo[16] | Hi[16] of each query of the item
-    uint32_t qlen[kTopkQueries];
 };
 
 template <typename Off>
 __global__ __launch_bounds__(kTopkWaves * 64, 3) void k_cross_topk(TopkArgs args) {
-    __shared__ TopkWaveLds wave_lds[kTopkWaves];
+    __shared__ WordSearchLds lds;
     extern __shared__ uint64_t topk_lists[];   // [wave][query][k]
-    __shared__ SummaryLds summary_lds;
-    __shared__ unsigned long long lcells, lsyms;
-    __shared__ uint32_t lmaxa, lmaxb, lshorts, lmisfit;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    TopkWaveLds &wl = wave_lds[wave];
-    const uint32_t k = args.k;
-    uint64_t *lists = topk_lists + (size_t)wave * kTopkQueries * k;
-    if (threadIdx.x == 0) { lcells = 0; lsyms = 0; lmaxa = 0; lmaxb = 0; lshorts = 0; lmisfit = 0; }
-    __syncthreads();
-    const uint64_t na = args.a.count, nb = args.b.count;
-    const uint8_t *a_data = (const uint8_t *)args.a.data, *b_data = (const uint8_t *)args.b.data;
-    const uint64_t b_total = (uint64_t)((const Off *)args.b.offsets)[nb];
-    const uint64_t chunks = (nb + 63) / 64, qblocks = (na + kTopkQueries - 1) / kTopkQueries;
-    const uint64_t items = qblocks * args.slices;
-    const uint64_t waves_total = (uint64_t)gridDim.x * kTopkWaves, wave_id = (uint64_t)blockIdx.x * kTopkWaves + wave;
-    unsigned long long cells = 0, syms = 0;
-    uint32_t maxa = 0, maxb = 0, shorts = 0, misfit = 0;
-
-    for (uint64_t item = wave_id; item < items; item += waves_total) {
-        // neighbouring waves take neighbouring query blocks of one slice: the slice's candidates stay warm in the cache
-        const uint64_t slice = item / qblocks, qb = item - slice * qblocks;
-        const uint64_t q_first = qb * kTopkQueries, q_last = q_first + kTopkQueries < na ? q_first + kTopkQueries : na;
-        const uint32_t q_count = (uint32_t)(q_last - q_first);
-        // ---- the item's 16 match tables: lane l takes bytes 8 (l % 4) .. 8 (l % 4) + 7 of query l / 4 -------------------------
-        const uint32_t ql = (uint32_t)lane >> 2, part = (uint32_t)lane & 3u;
-        uint64_t qa0 = 0;
-        uint32_t qm = 0;
-        if (ql < q_count) tape_extent<Off>(args.a.offsets, q_first + ql, qa0, qm);
-        uint32_t staged[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const uint32_t at = part * 8 + (uint32_t)t;
-            staged[t] = (at < qm && qm <= kTopkLongest) ? a_data[qa0 + at] : 0u;
-        }
-#pragma unroll
-        for (int t = 0; t < 8; ++t) (&wl.table[0][0])[lane * 8 + t] = 0;
-        for (uint32_t q = 0; q < q_count; ++q)
-            if ((uint32_t)lane < k) lists[q * k + lane] = kTopkPad;
-        lds_order();
-        if (part == 0) wl.qlen[ql] = ql < q_count ? qm : 0u;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const uint32_t at = part * 8 + (uint32_t)t;
-            if (at < qm && qm <= kTopkLongest) {
-                atomicOr(&wl.table[ql][staged[t] & 15u], 1u << at);
-                atomicOr(&wl.table[ql][16 + (staged[t] >> 4)], 1u << at);
+    const uint32_t lane = threadIdx.x & 63, k = args.k, slices = args.search.slices;
+    uint64_t *lists = topk_lists + (size_t)(threadIdx.x >> 6) * kWordQueries * k;
+    uint64_t thresholds = args.cap, threshold = 0;   // lane q: T of query q; T of the query at hand
+    word_search_items<Off, true>(args.search, lds,
+        [&](const WordItem &item) {
+            for (uint32_t q = 0; q < item.q_count; ++q)
+                if (lane < k) lists[q * k + lane] = kTopkPad;
+            thresholds = args.cap;
+        },
+        [&](uint32_t q, uint32_t gap) { threshold = readlane64(thresholds, (int)q); return ((uint64_t)gap << 32) < threshold; },
+        [&](uint32_t q, const WordCandidate &c, uint32_t d) {
+            const uint64_t key = c.fits ? ((uint64_t)d << 32 | c.cand) : kTopkPad;
+            const uint64_t admitted = __ballot(key < threshold);
+            if (admitted) {
+                threshold = topk_fold_chunk(lists + q * k, k, key, admitted, args.cap);
+                if (lane == q) thresholds = threshold;
             }
-        }
-        if (ql < q_count && qm > kTopkLongest) misfit = 1;
-        lds_order();
-        unsigned long long sum_m = 0;
-        uint32_t item_maxa = 0;
-        for (uint32_t q = 0; q < q_count; ++q) {
-            const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)wl.qlen[q]);
-            sum_m += m;
-            item_maxa = m > item_maxa ? m : item_maxa;
-        }
-        uint64_t thresholds = args.cap;   // lane q: T of query q
-        // ---- the slice's chunks of 64 candidates --------------------------------------------------------------------------------
-        const uint64_t c_first = slice * args.slice_chunks;
-        const uint64_t c_last = c_first + args.slice_chunks < chunks ? c_first + args.slice_chunks : chunks;
-        for (uint64_t chunk = c_first; chunk < c_last; ++chunk) {
-            const uint64_t cand = chunk * 64 + (uint64_t)lane;
-            const bool have = cand < nb;
-            uint64_t b0 = 0;
-            uint32_t n = 0;
-            if (have) tape_extent<Off>(args.b.offsets, cand, b0, n);
-            const bool fits = have && n <= kTopkLongest;
-            if (have && !fits) misfit = 1;
-            uint32_t tw[8];
-            {
-                ByteWindow txt;
-                txt.init(b_data, b0, b_total);
-                if (b_total >= 16) {
-                    uint32_t half[4];
-                    int moved = txt.fetch16_raw(0, half);
-                    txt.fix16(0, moved, half);
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) tw[w] = half[w];
-                    moved = txt.fetch16_raw(16, half);
-                    txt.fix16(16, moved, half);
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) tw[4 + w] = half[w];
-                } else {
-#pragma unroll
-                    for (int w = 0; w < 8; ++w) tw[w] = txt.fetch4(w * 4);
-                }
+        },
+        // the item's lists leave: the rows themselves, or this slice's partial lists
+        [&](const WordItem &item) {
+            lds_order();
+            for (uint32_t q = 0; q < item.q_count; ++q) {
+                if (lane >= k) continue;
+                const uint64_t key = lists[q * k + lane];
+                const uint64_t row = item.q_first + q;
+                if (slices == 1) topk_emit(key, args.indices + row * k + lane, args.distances + row * k + lane);
+                else args.partial[(row * slices + item.slice) * k + lane] = key;
             }
-            const uint32_t n_live = fits ? n : 0;
-            const uint32_t n_max = wave_max_u32(n_live);
-            for (uint32_t q = 0; q < q_count; ++q) {
-                const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)wl.qlen[q]);
-                if (m > kTopkLongest) continue;
-                uint64_t threshold = readlane64(thresholds, (int)q);
-                if (args.prune) {
-                    const uint32_t gap = m > n ? m - n : n - m;
-                    if (!__ballot(fits && ((uint64_t)gap << 32) < threshold)) continue;
-                }
-                const uint32_t *table = wl.table[q];
-                uint32_t pv = 0xFFFFFFFFu, mv = 0;
-#pragma unroll
-                for (int w4 = 0; w4 < 8; ++w4) {
-                    if ((uint32_t)w4 * 4 >= n_max) break;
-                    const uint32_t w = tw[w4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const uint32_t lo_at = (u == 0 ? (w << 2) : (w >> (8 * u - 2))) & 0x3Cu;
-                        const uint32_t hi_at = (w >> (8 * u + 2)) & 0x3Cu;
-                        const uint32_t eq = *(const uint32_t *)((const char *)table + lo_at) & *(const uint32_t *)((const char *)table + 64 + hi_at);
-                        if ((uint32_t)(w4 * 4 + u) < n_live) {
-                            const uint32_t xv = eq | mv;
-                            const uint32_t xh = (((eq & pv) + pv) ^ pv) | eq;
-                            uint32_t ph = mv | ~(xh | pv);
-                            const uint32_t mh = pv & xh;
-                            ph = (ph << 1) | 1u;
-                            pv = (mh << 1) | ~(xv | ph);
-                            mv = ph & xv;
-                        }
-                    }
-                }
-                const uint32_t mask = m >= 32 ? 0xFFFFFFFFu : ((1u << m) - 1u);
-                const uint32_t d = n + __popc(pv & mask) - __popc(mv & mask);
-                const uint64_t key = fits ? ((uint64_t)d << 32 | cand) : kTopkPad;
-                const uint64_t admitted = __ballot(key < threshold);
-                if (admitted) {
-                    threshold = topk_fold_chunk(lists + q * k, k, key, admitted, args.cap);
-                    if ((uint32_t)lane == q) thresholds = threshold;
-                }
-            }
-            if (have) {
-                cells += sum_m * (unsigned long long)n;
-                maxb = n > maxb ? n : maxb;
-                if (qb == 0) syms += n;                                // every candidate once ...
-                if (fits) shorts += q_count;
-            }
-        }
-        if (lane == 0) {
-            maxa = item_maxa > maxa ? item_maxa : maxa;
-            if (slice == 0) syms += sum_m;                             // ... and every query once
-        }
-        // ---- the item's lists leave: the rows themselves, or this slice's partial lists -------------------------------------------
-        lds_order();
-        for (uint32_t q = 0; q < q_count; ++q) {
-            if ((uint32_t)lane >= k) continue;
-            const uint64_t key = lists[q * k + lane];
-            const uint64_t row = q_first + q;
-            if (args.slices == 1) topk_emit(key, args.indices + row * k + lane, args.distances + row * k + lane);
-            else args.partial[(row * args.slices + slice) * k + lane] = key;
-        }
-        lds_order();
-    }
-    // ---- summary ---------------------------------------------------------------------------------------------------------------
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        cells += __shfl_xor(cells, off);
-        syms += __shfl_xor(syms, off);
-        shorts += __shfl_xor(shorts, off);
-        misfit |= __shfl_xor(misfit, off);
-        const uint32_t oa = __shfl_xor(maxa, off), ob = __shfl_xor(maxb, off);
-        maxa = oa > maxa ? oa : maxa;
-        maxb = ob > maxb ? ob : maxb;
-    }
-    if (lane == 0) {
-        atomicAdd(&lcells, cells);
-        atomicAdd(&lsyms, syms);
-        atomicAdd(&lshorts, shorts);
-        atomicMax(&lmaxa, maxa);
-        atomicMax(&lmaxb, maxb);
-        atomicOr(&lmisfit, misfit);
-    }
-    __syncthreads();
-    report_call_summary(PlanPartial{lcells, lsyms, lmaxa, lmaxb, lshorts, lmisfit}, args.partials, args.done_counter, args.summary, summary_lds);
+            lds_order();
+        });
 }
 
 // One wave per query: the query's `slices` partial lists (each sorted, k keys) folded into its final row.
@@ -373,18 +216,13 @@ __global__ __launch_bounds__(kTopkWaves * 64) void k_topk_select(TopkSelectArgs 
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------------
-size_t topk_fused_lds(uint32_t k) { return (size_t)kTopkWaves * kTopkQueries * k * sizeof(uint64_t); }
+size_t topk_fused_lds(uint32_t k) { return (size_t)kWordWaves * kWordQueries * k * sizeof(uint64_t); }
 
 void launch_cross_topk(Scope *scope, const TopkLaunch &t) {
     TopkArgs args{};
-    args.a = t.a; args.b = t.b; args.k = t.k; args.slices = t.slices; args.slice_chunks = t.slice_chunks; args.cap = t.cap;
-    args.prune = t.prune; args.partial = t.partial; args.indices = t.indices; args.distances = t.distances;
-    args.partials = scope->plan_partials; args.done_counter = scope->done_counter; args.summary = scope->summary_target();
-    const uint64_t items = ((t.a.count + kTopkQueries - 1) / kTopkQueries) * t.slices;
-    const uint64_t blocks64 = (items + kTopkWaves - 1) / kTopkWaves;
-    uint32_t max_blocks = (uint32_t)scope->compute_units * 8;
-    if (max_blocks > (uint32_t)kMaxPartials) max_blocks = kMaxPartials;
-    const uint32_t blocks = blocks64 > max_blocks ? max_blocks : (uint32_t)(blocks64 ? blocks64 : 1);
+    args.search = {t.a, t.b, t.slices, t.prune, t.slice_chunks, scope->plan_partials, scope->done_counter, scope->summary_target()};
+    args.k = t.k; args.cap = t.cap; args.partial = t.partial; args.indices = t.indices; args.distances = t.distances;
+    const uint32_t blocks = word_item_blocks(scope, ((t.a.count + kWordQueries - 1) / kWordQueries) * t.slices);
     const size_t lds = topk_fused_lds(t.k);
     {
         StampGuard guard(scope, "cross_topk");

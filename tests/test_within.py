@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 from conftest import TEST_LIBRARY_ENV, run_in_child
-from test_topk import AB_STRINGS, CENTRE, _planted, _pool_and_words, centre_pool, gather, oracle_matrix, pooled_queries, prefix_family, staircase
+from test_topk import (AB_STRINGS, CENTRE, _planted, _pool_and_words, centre_pool, check_rows, expected_topk, gather, oracle_matrix, pooled_queries,
+                       prefix_family, staircase)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -301,6 +302,72 @@ def test_within_slice_regimes(request, sw, scope, slices):
                 assert reached == (slices if in_child else 10), (reached, timing)
     finally:
         scope.set_profiling(False)
+
+
+WORD_EDGE_LENGTHS = (0, 1, 31, 32)   # empty, one column, one short of the longest word, the longest
+WORD_EDGE_CANDIDATES = (1, 63, 64, 65, 129)
+
+
+@functools.lru_cache(maxsize=None)
+def _word_edge_case(misfit):
+    """33 queries x 129 candidates over a four-letter alphabet, every length one of WORD_EDGE_LENGTHS (`misfit`: candidate 70 has 33
+    bytes), and the oracle's matrix."""
+    import oracle
+    import stringwars_amd as sw
+    rng = np.random.default_rng(71)
+    words = [bytes(rng.choice(np.frombuffer(b"acgt", np.uint8), int(n))) for n in rng.choice(WORD_EDGE_LENGTHS, 33 + 129)]
+    if misfit:
+        words[33 + 70] = bytes(rng.choice(np.frombuffer(b"acgt", np.uint8), 33))
+    q, c = sw.Strs(words[:33]), sw.Strs(words[33:])
+    assert set(q.lengths.tolist()) == set(WORD_EDGE_LENGTHS) and int(c.lengths.max()) == (33 if misfit else 32)
+    d = oracle_matrix(sw, oracle, q, c)
+    d.setflags(write=False)
+    return q, c, d
+
+
+@pytest.mark.gpu
+def test_word_kernels_share_their_item_edges(request, sw, scope):
+    """The three word-sized cross-product kernels on the same inputs against the oracle's dense matrix: query counts around the
+    16-query block, candidate counts around the 64-candidate chunk, strings of 0, 1, 31 and 32 bytes, 32- and 64-bit offsets; then one
+    candidate of 33 bytes on raw tapes (the kernels report it and the call is redone); and the range search again on three forced
+    slices (STRINGWARS_AMD_WITHIN_SLICES=3, a child on the test library)."""
+    in_child = run_in_child(request, env=dict(TEST_LIBRARY_ENV, STRINGWARS_AMD_WITHIN_SLICES="3"), test_library=True)
+    engine = sw.LevenshteinDistances(capabilities=scope)
+    q, c, d = _word_edge_case(False)
+    scope.set_profiling(True)
+    try:
+        for w in (np.uint32, np.uint64):
+            pq, pc = sw.PreparedTape(scope, q.with_offsets(w)), sw.PreparedTape(scope, c.with_offsets(w))
+            if in_child:
+                assert os.environ["STRINGWARS_AMD_WITHIN_SLICES"] == "3" and sw.LIBRARY_PATH.endswith("libstringwars_amd_test.so")
+                for bound in (0, 2, 40):
+                    want = expected_csr(d, bound)
+                    check_csr(engine.within(pq, pc, scope, bound=bound, capacity=33 * 129), want, f"three slices {w.__name__} bound {bound}")
+                    timing = scope.last_timing()
+                    assert timing["dominant_name"] == "cross_within", timing
+                    assert _fused_slices(timing, 33, 129, int(q.lengths.sum()) + int(c.lengths.sum()), int(want[0][-1]), np.dtype(w).itemsize) == 3, timing
+                continue
+            for nq in QUERY_COUNTS:
+                for nc in WORD_EDGE_CANDIDATES:
+                    what, part = f"{w.__name__} {nq} x {nc}", d[:nq, :nc]
+                    assert (np.asarray(engine(pq[:nq], pc[:nc], scope)).astype(np.int64) == part).all(), what
+                    assert scope.last_timing()["dominant_name"] == "cross_short", (what, scope.last_timing())
+                    for bound in (0, 2, None):
+                        check_rows(engine.topk(pq[:nq], pc[:nc], scope, k=64, bound=bound), expected_topk(part, 64, bound), f"{what} top-k bound {bound}")
+                        assert "cross_topk" in scope.last_timing()["dominant_name"], (what, scope.last_timing())
+                    for bound in (0, 2, 40):
+                        check_csr(engine.within(pq[:nq], pc[:nc], scope, bound=bound), expected_csr(part, bound), f"{what} within bound {bound}")
+                        assert scope.last_timing()["dominant_name"] == "cross_within", (what, scope.last_timing())
+    finally:
+        scope.set_profiling(False)
+    if in_child:
+        return
+    q, c, d = _word_edge_case(True)
+    assert (np.asarray(engine(q, c, scope)).astype(np.int64) == d).all()
+    for bound in (0, 2, None):
+        check_rows(engine.topk(q, c, scope, k=64, bound=bound), expected_topk(d, 64, bound), f"a 33-byte candidate, top-k bound {bound}")
+    for bound in (0, 2, 40):
+        check_csr(engine.within(q, c, scope, bound=bound), expected_csr(d, bound), f"a 33-byte candidate, within bound {bound}")
 
 
 @pytest.mark.gpu
