@@ -526,6 +526,63 @@ swh_status_t swh_levenshtein_jaro_cross_prepared(swh_levenshtein_t engine, swh_s
                                                  const swh_prepared_view_t *b, size_t *matches, size_t *transpositions, size_t *prefix,
                                                  size_t row_stride_bytes, const char **error);
 
+/* ---- Score search: the k best candidates of every query by an OSA, Indel, LCS, ratio, Jaro or Jaro-Winkler score (rapidfuzz
+ *      `process.extract(query, choices, scorer=..., limit=k, score_cutoff=cutoff)`, for every query at once), unit-cost engines
+ *      only. The top-k search above is the Levenshtein form of this call; what differs is the score, a float64. ------------------
+ *      scorer                     score (float64)                                                            better is
+ *      SWH_SCORER_OSA             the OSA distance d                                                         smaller
+ *      SWH_SCORER_INDEL           the Indel distance m + n - 2 LCS                                           smaller
+ *      SWH_SCORER_LCS             the LCS length L                                                           larger
+ *      SWH_SCORER_RATIO           100.0 * (2.0 * L) / (d + 2.0 * L), d the Indel distance; 100.0 if m = n = 0   larger
+ *      SWH_SCORER_JARO            the Jaro expression above, as written                                      larger
+ *      SWH_SCORER_JARO_WINKLER    the Jaro-Winkler expression above with prefix weight p, as written         larger
+ * For every query i, the k candidates j with the best key (score(i, j), j) among those that pass the cutoff:
+ *  - best score first; equal scores -- equal as float64, nothing narrower -- in order of the SMALLER candidate index;
+ *  - a score leaves with the 64 bits that the expressions above, evaluated in IEEE double operation by operation as written, give
+ *    for the counts the pairwise and cross calls return for that pair (the query drives the Jaro matching, the candidate is
+ *    flagged; the sides are never swapped);
+ *  - `cutoff_bits` is the cutoff, a double, as its binary64 bit pattern (what memcpy of the double into a uint64_t gives): the
+ *    distance scorers admit d <= cutoff, the similarity scorers s >= cutoff, a score at the cutoff is admitted; +infinity
+ *    (distances) or 0.0 (similarities) means no cutoff; a NaN or a negative cutoff returns swh_invalid_argument_k;
+ *  - `prefix_weight_bits` is p, a double passed the same way, 0 <= p <= 0.25, else swh_invalid_argument_k; the scorers other than
+ *    SWH_SCORER_JARO_WINKLER ignore it;
+ *  - 1 <= k <= SWH_TOPK_MAX and a scorer from the table; anything else returns swh_invalid_argument_k;
+ *  - a row with fewer than k admitted candidates is padded with index 0xFFFFFFFF and a score whose 64 bits are all ones (a quiet
+ *    NaN: what memset 0xFF writes);
+ *  - candidates == NULL means queries x queries, diagonal included;
+ *  - candidates->count must be below 0xFFFFFFFF; queries->count x candidates->count has NO 2^32 limit: the pairs are scored in
+ *    slices of rows and columns, and the call's scratch memory does not grow with their number;
+ *  - `indices` is a uint32_t array and `scores` a double array (`double[queries->count * k]`), both of queries->count x k,
+ *    row-major and contiguous, each in host or device memory;
+ *  - queries->count == 0 succeeds and does nothing; candidates->count == 0 makes every row padding;
+ *  - symbols are bytes, or code points in the UTF-8 variant (invalid UTF-8 -> swh_invalid_utf8_k); the prepared variant takes
+ *    what the tapes were prepared as;
+ *  - the families' length limits hold: a pair whose SHORTER string has more than SWH_OSA_MAX_SHORTER symbols (OSA, Indel, LCS,
+ *    ratio), or either of whose strings has more than SWH_JARO_MAX_LENGTH (Jaro, Jaro-Winkler), makes the call return
+ *    swh_unsupported_length_k before any output is written; the message names such a (query, candidate) pair and both lengths;
+ *  - an engine whose costs are not (match 0, mismatch 1, open 1, extend 1) returns swh_not_implemented_k.
+ * Worked row: query MARTHA, candidates (MARHTA, DWAYNE, MARTHA, MARTHA), SWH_SCORER_JARO_WINKLER, p = 0.1, k = 3, no cutoff:
+ * indices 2, 3, 0 and scores 1.0, 1.0, 0.9611111111111111.
+ * The call is synchronous on every scope, as the other searches are. With profiling on, swh_scope_last_timing describes the whole
+ * search: `cells` = sum m n over all pairs; `dominant_name` is "extract_select/<kernel>", <kernel> the scoring kernel ("osa",
+ * "lcs", "jaro", or their "_u32" forms for code points) and `dominant_ms` its time over all slices. */
+#define SWH_SCORER_OSA 0
+#define SWH_SCORER_INDEL 1
+#define SWH_SCORER_LCS 2
+#define SWH_SCORER_RATIO 3
+#define SWH_SCORER_JARO 4
+#define SWH_SCORER_JARO_WINKLER 5
+swh_status_t swh_levenshtein_extract_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *queries,
+                                             const swh_tape_u64_t *candidates, int scorer, size_t k, uint64_t cutoff_bits,
+                                             uint64_t prefix_weight_bits, uint32_t *indices, void *scores, const char **error);
+swh_status_t swh_levenshtein_utf8_extract_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *queries,
+                                                  const swh_tape_u64_t *candidates, int scorer, size_t k, uint64_t cutoff_bits,
+                                                  uint64_t prefix_weight_bits, uint32_t *indices, void *scores,
+                                                  const char **error);
+swh_status_t swh_levenshtein_extract_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *queries,
+                                              const swh_prepared_view_t *candidates, int scorer, size_t k, uint64_t cutoff_bits,
+                                              uint64_t prefix_weight_bits, uint32_t *indices, void *scores, const char **error);
+
 /* ---- One batch over the GPUs of a multi-device scope (BASELINE config 5). --------------------------------
  * `swh_sharded_prepare_*`: HOST tapes of equal count are cut into contiguous shards balanced on the prefix sum of
  * len(a_i)*len(b_i) (DP cells, not pair counts); shard r is uploaded to and prepared on device r. The handle is the steady
@@ -632,7 +689,8 @@ const char *swh_version(void);
 /* Comma-separated capability string, e.g. "gfx950,hip,wavefront,bitparallel,banded,utf8,...";
  * "topk" when the swh_levenshtein_topk_* calls are present, "within" when the swh_levenshtein_within_* calls are, "align" when the swh_levenshtein_align_* calls are,
  * "infix" when the swh_levenshtein_infix_* calls are, "osa" when the swh_levenshtein_osa_* calls are,
- * "lcs" when the swh_levenshtein_lcs_* calls are, "jaro" when the swh_levenshtein_jaro_* calls are. */
+ * "lcs" when the swh_levenshtein_lcs_* calls are, "jaro" when the swh_levenshtein_jaro_* calls are, "extract" when the
+ * swh_levenshtein_extract_* calls are. */
 const char *swh_capabilities(void);
 
 #ifdef __cplusplus

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <fstream>
 #include <functional>
+#include <limits>
 #include <regex>
 #include <stdexcept>
 #include <string>
@@ -39,6 +40,13 @@ struct Error : std::runtime_error {
 };
 inline void check(swh_status_t status, const char *message) {
     if (status != swh_success_k) throw Error(status, message);
+}
+
+/// A double as the C ABI takes it: its binary64 bit pattern (the cutoff and the prefix weight of swh_levenshtein_extract_*).
+inline uint64_t double_bits(double value) {
+    uint64_t bits;
+    std::memcpy(&bits, &value, sizeof bits);
+    return bits;
 }
 
 /// Borrowed Arrow-style tape view, `BytesTapeView<u64>` (bench.rs:298-301); `subview` is O(1) (bench.rs:134-139).
@@ -365,6 +373,28 @@ public:
         const char *err = nullptr;
         swh_prepared_view_t q = queries.c(), c = candidates ? candidates->c() : q;
         swh_status_t status__ = swh_levenshtein_topk_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, k, bound, indices, distances, &err);
+        check(status__, err);
+    }
+    /// Score search (swh_levenshtein_extract_*): the k best candidates of every query under `scorer` (SWH_SCORER_*), `indices` /
+    /// `scores` of queries.count x k (host or device memory); rows best score first, equal doubles by the smaller index, padded with
+    /// 0xFFFFFFFF and an all-ones NaN. Distances admit d <= cutoff, similarities s >= cutoff; `no_cutoff(scorer)` admits everything.
+    /// The two doubles cross the C boundary as their bit patterns: the copy is made here.
+    static double no_cutoff(int scorer) { return scorer >= SWH_SCORER_LCS ? 0.0 : std::numeric_limits<double>::infinity(); }
+    void extract(const DeviceScope &scope, int scorer, const BytesTapeView &queries, const BytesTapeView *candidates, size_t k, uint32_t *indices,
+                 double *scores, double cutoff, double prefix_weight = 0.1) const {
+        const char *err = nullptr;
+        swh_tape_u64_t q = queries.c(), c = candidates ? candidates->c() : q;
+        auto fn = utf8_ ? swh_levenshtein_utf8_extract_u64tape : swh_levenshtein_extract_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &q, candidates ? &c : nullptr, scorer, k, double_bits(cutoff), double_bits(prefix_weight),
+                                   indices, scores, &err);
+        check(status__, err);
+    }
+    void extract(const DeviceScope &scope, int scorer, const PreparedTape &queries, const PreparedTape *candidates, size_t k, uint32_t *indices,
+                 double *scores, double cutoff, double prefix_weight = 0.1) const {
+        const char *err = nullptr;
+        swh_prepared_view_t q = queries.c(), c = candidates ? candidates->c() : q;
+        swh_status_t status__ = swh_levenshtein_extract_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, scorer, k, double_bits(cutoff),
+                                                                 double_bits(prefix_weight), indices, scores, &err);
         check(status__, err);
     }
     /// Range search (swh_levenshtein_within_*): every candidate with d <= bound of every query, as CSR -- row i at entries

@@ -57,6 +57,8 @@ INFIX_NONE = 0xFFFFFFFF    # SWH_INFIX_NONE: start / end of a pair whose best oc
 OSA_MAX_SHORTER = 2048     # SWH_OSA_MAX_SHORTER: symbols of a pair's shorter string an OSA call accepts
 LCS_MAX_SHORTER = 2048     # SWH_LCS_MAX_SHORTER: symbols of a pair's shorter string an LCS / Indel call accepts
 JARO_MAX_LENGTH = 2048     # SWH_JARO_MAX_LENGTH: symbols of either string of a pair a Jaro call accepts
+# SWH_SCORER_*: the scores a score search (swh_levenshtein_extract_*) ranks by, by name
+SCORERS = {"osa": 0, "indel": 1, "lcs": 2, "ratio": 3, "jaro": 4, "jaro_winkler": 5}
 OP_MATCH, OP_SUBST, OP_DEL, OP_INS = ord("="), ord("X"), ord("D"), ord("I")   # SWH_OP_*: the bytes of an alignment's ops
 ALGORITHM_AUTO, ALGORITHM_WAVEFRONT, ALGORITHM_BITPARALLEL, ALGORITHM_TILED = 0, 1, 2, 3
 
@@ -208,6 +210,9 @@ SIGNATURES = {
     "swh_levenshtein_jaro_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, C.c_size_t, _ERR]),
     "swh_levenshtein_utf8_jaro_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, C.c_size_t, _ERR]),
     "swh_levenshtein_jaro_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_extract_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, _P, _P, _ERR]),
+    "swh_levenshtein_utf8_extract_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, _P, _P, _ERR]),
+    "swh_levenshtein_extract_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, _P, _P, _ERR]),
     "swh_version": (C.c_char_p, []),
     "swh_capabilities": (C.c_char_p, []),
     # harness header

@@ -19,6 +19,7 @@
 #include "osa.hpp"
 #include "lcs.hpp"
 #include "jaro.hpp"
+#include "extract.hpp"
 #include <algorithm>
 #include <mutex>
 #include <utility>
@@ -1193,7 +1194,7 @@ static void free_align_scratch(const Scope *scope) {
 extern "C" {
 
 const char *swh_version(void) { return "0.1.0"; }
-const char *swh_capabilities(void) { return "gfx950,hip,wavefront,bitparallel,tiled,banded,utf8,bounded,nw-linear,nw-affine,sw-linear,sw-affine,cross,prepared,topk,within,align,infix,osa,lcs,jaro,multi-gpu-rccl"; }
+const char *swh_capabilities(void) { return "gfx950,hip,wavefront,bitparallel,tiled,banded,utf8,bounded,nw-linear,nw-affine,sw-linear,sw-affine,cross,prepared,topk,within,align,infix,osa,lcs,jaro,extract,multi-gpu-rccl"; }
 
 static swh_status_t scope_init(int device, void *stream, bool borrow, swh_scope_t *out, const char **error) {
     if (!out) return fail(error, swh_invalid_argument_k, "null scope pointer");
@@ -3063,6 +3064,220 @@ swh_status_t swh_levenshtein_utf8_jaro_cross_u64tape(swh_levenshtein_t e, swh_sc
 swh_status_t swh_levenshtein_jaro_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
                                                  size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
     return scored_prepared(kJaroFamily, e, s, a, b, true, SWH_UNBOUNDED, {matches, transpositions, prefix}, row_stride, error);
+}
+
+// ---- score search (extract.hip): the k best candidates by an OSA, Indel, LCS, ratio, Jaro or Jaro-Winkler score ------------------------
+// topk_run's general path with the three families as the scorers: query blocks x candidate slices of at most kScoredChunkPairs
+// pairs, each slice measured and cut into items by the family's sizes kernel, scored by its launcher into dense u64 counts in scratch
+// (the candidates' slice is a view of the prepared tape: pair p of the launch is (p / columns, p % columns)) and folded into the
+// block's running lists by k_extract_select, which evaluates the float64 score. The scratch is the slice's items and counts, the
+// block's lists and, for outputs in host memory, the rows: nothing grows with queries x candidates. Both length limits follow from
+// the two tapes' own lengths, so one pass over their offsets refuses the call before anything is scored or written.
+// STRINGWARS_AMD_EXTRACT_CHUNK_PAIRS (test library) lowers the slice, to put several blocks and slices into a small test.
+static uint64_t extract_chunk_pairs() {
+    const char *hook = test_hook("STRINGWARS_AMD_EXTRACT_CHUNK_PAIRS");
+    const uint64_t pairs = hook ? (uint64_t)atoll(hook) : kScoredChunkPairs;
+    return std::max<uint64_t>(1, std::min<uint64_t>(pairs, kScoredChunkPairs));
+}
+
+struct ExtractRequest {
+    int scorer;
+    uint32_t k;
+    double cutoff, prefix_weight;
+    uint32_t *indices;
+    void *scores;
+};
+
+static swh_status_t extract_run(Scope *scope, const TapePair &p, const ExtractRequest &r, const char **error) {
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t nq = p.a_count, nc = p.b_count, k = r.k;
+        if (nq == 0) return swh_success_k;
+        const size_t index_bytes = nq * k * sizeof(uint32_t), score_bytes = nq * k * sizeof(uint64_t);
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        const bool dev_i = is_device_pointer(r.indices), dev_s = is_device_pointer(r.scores);
+        if (nc == 0) {   // every row is padding
+            if (dev_i) SWH_HIP_CHECK(hipMemsetAsync(r.indices, 0xFF, index_bytes, stream)); else memset(r.indices, 0xFF, index_bytes);
+            if (dev_s) SWH_HIP_CHECK(hipMemsetAsync(r.scores, 0xFF, score_bytes, stream)); else memset(r.scores, 0xFF, score_bytes);
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            return swh_success_k;
+        }
+        const bool jaro = r.scorer >= SWH_SCORER_JARO;
+        const ScoredFamily &f = r.scorer == SWH_SCORER_OSA ? kOsaFamily : (jaro ? kJaroFamily : kLcsFamily);
+        const int counts = r.scorer == SWH_SCORER_JARO_WINKLER ? 3 : (jaro ? 2 : 1);
+        const bool cp = p.pa->utf8;
+        const uint32_t a_off64 = cp ? 1 : p.pa->off64, b_off64 = cp ? 1 : p.pb->off64;
+        const TapeRef queries = prepared_view(p.pa, cp, p.a_first, nq), candidates = prepared_view(p.pb, cp, p.b_first, nc);
+
+        // query blocks of at most 4096 rows x candidate slices, at least 64 columns wide where the slice allows it
+        const uint64_t chunk = extract_chunk_pairs();
+        const uint64_t q_step = std::min<uint64_t>(nq, std::max<uint64_t>(1, std::min<uint64_t>(4096, chunk >> 6)));
+        const uint64_t c_step = std::max<uint64_t>(1, std::min<uint64_t>(nc, chunk / q_step));
+        const uint64_t slice_pairs = q_step * c_step;
+
+        // first over-long strings | sizes | items | the slice's counts | the block's lists | rows bound for the host
+        const size_t need = pad(2 * sizeof(unsigned long long)) + pad(sizeof(OsaSizes)) + pad(slice_pairs * sizeof(LaneItem)) +
+                            counts * pad(slice_pairs * 8) + pad(q_step * k * 16) + (dev_i ? 0 : pad(index_bytes)) + (dev_s ? 0 : pad(score_bytes));
+        ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
+        Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
+        unsigned long long *first_over = sc.take<unsigned long long>(2);
+        OsaSizes *sizes = sc.take<OsaSizes>(1);
+        LaneItem *items = sc.take<LaneItem>(slice_pairs);
+        uint64_t *slice[kScoredOutputs] = {};
+        for (int o = 0; o < counts; ++o) slice[o] = sc.take<uint64_t>(slice_pairs);
+        char *lists = sc.take<char>(q_step * k * 16);
+        uint32_t *ind = dev_i ? r.indices : sc.take<uint32_t>(nq * k);
+        uint64_t *sco = dev_s ? (uint64_t *)r.scores : sc.take<uint64_t>(nq * k);
+
+        // the search as one call: with profiling on, the kernels since the last absorb() go into the sum (`scoring`: the family's kernel)
+        swh_timing_t sum{};
+        char scoring_name[40] = "";
+        auto absorb = [&](bool scoring) {
+            if (scope->profiling && scope->stamps_used) {
+                SWH_HIP_CHECK(hipStreamSynchronize(stream));
+                collect_timing(scope);
+                const swh_timing_t &t = scope->last_timing;
+                sum.total_ms += t.total_ms; sum.compute_ms += t.compute_ms; sum.kernels += t.kernels;
+                if (scoring) { sum.dominant_ms += t.dominant_ms; snprintf(scoring_name, sizeof scoring_name, "%s", t.dominant_name); }
+            }
+            scope->stamps_used = 0;
+        };
+
+        // the length limits: OSA and LCS refuse a pair whose SHORTER string is over theirs, Jaro one with either string over its own
+        SWH_HIP_CHECK(hipMemsetAsync(first_over, 0xFF, 2 * sizeof(unsigned long long), stream));
+        const uint32_t limit = jaro ? SWH_JARO_MAX_LENGTH : SWH_OSA_MAX_SHORTER;
+        launch_extract_first_over(scope, queries, a_off64, limit, first_over);
+        launch_extract_first_over(scope, candidates, b_off64, limit, first_over + 1);
+        unsigned long long over[2];
+        SWH_HIP_CHECK(hipMemcpyAsync(over, first_over, sizeof over, hipMemcpyDeviceToHost, stream));
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        absorb(false);
+        const bool a_over = over[0] != ~0ull, b_over = over[1] != ~0ull;
+        if (jaro ? (a_over || b_over) : (a_over && b_over)) {
+            const size_t i = a_over ? (size_t)over[0] : 0, j = b_over ? (size_t)over[1] : 0;
+            const uint64_t la = read_offset(queries.offsets, a_off64, i + 1, true, stream) - read_offset(queries.offsets, a_off64, i, true, stream);
+            const uint64_t lb = read_offset(candidates.offsets, b_off64, j + 1, true, stream) - read_offset(candidates.offsets, b_off64, j, true, stream);
+            return fail(error, swh_unsupported_length_k, "pair (%zu, %zu): %llu x %llu symbols, %s", i, j, (unsigned long long)la,
+                        (unsigned long long)lb, f.oversize);
+        }
+
+        // a finite cutoff of the OSA scorer is the scoring kernel's bound: what it clamps is over the cutoff anyway (the LCS kernel
+        // runs unbounded: every scorer of its family reads the LCS length)
+        const uint32_t bound = r.scorer == SWH_SCORER_OSA && r.cutoff < 4294967294.0 ? (uint32_t)r.cutoff : SWH_UNBOUNDED;
+        uint64_t cutoff_bits;
+        memcpy(&cutoff_bits, &r.cutoff, sizeof cutoff_bits);
+        uint64_t symbols = 0;
+        for (uint64_t q0 = 0; q0 < nq; q0 += q_step) {
+            const uint64_t rows = std::min<uint64_t>(q_step, nq - q0);
+            SWH_HIP_CHECK(hipMemsetAsync(lists, 0xFF, rows * k * 16, stream));   // every row is padding
+            for (uint64_t c0 = 0; c0 < nc; c0 += c_step) {
+                const uint64_t columns = std::min<uint64_t>(c_step, nc - c0);
+                OsaTapes t{};
+                t.a = prepared_view(p.pa, cp, p.a_first + q0, rows);
+                t.b = prepared_view(p.pb, cp, p.b_first + c0, columns);
+                t.a_off64 = a_off64; t.b_off64 = b_off64; t.cp = cp ? 1 : 0;
+                t.nb = columns; t.row0 = 0; t.count = rows * columns;
+                OsaSizes init{}, got{};
+                init.first_oversize = ~0ull;
+                SWH_HIP_CHECK(hipMemcpyAsync(sizes, &init, sizeof init, hipMemcpyHostToDevice, stream));
+                f.sizes(scope, t, sizes, items);
+                SWH_HIP_CHECK(hipMemcpyAsync(&got, sizes, sizeof got, hipMemcpyDeviceToHost, stream));
+                SWH_HIP_CHECK(hipStreamSynchronize(stream));
+                absorb(false);
+                if (got.first_oversize != ~0ull)   // (the memory of a prepared tape changed since the lengths were read)
+                    return fail(error, swh_unsupported_length_k, "a string of the slice at (%llu, %llu) grew over the limit: %s",
+                                (unsigned long long)q0, (unsigned long long)c0, f.oversize);
+                sum.cells += got.cells; symbols += got.symbols;
+                const bool wide = !cp && got.a_total >= 16 && got.b_total >= 16;
+                char *where[kScoredOutputs] = {};
+                if (jaro) for (int o = 0; o < counts; ++o) where[o] = (char *)slice[o];
+                else where[r.scorer == SWH_SCORER_OSA ? 0 : 1] = (char *)slice[0];   // the OSA distance; the LCS length
+                f.launch(scope, t, items, got.items, where, columns * 8, bound, wide);
+                absorb(true);
+
+                ExtractLaunch x{};
+                for (int o = 0; o < counts; ++o) x.counts[o] = slice[o];
+                x.a = queries; x.b = candidates; x.a_off64 = a_off64; x.b_off64 = b_off64;
+                x.rows = rows; x.columns = columns; x.row_first = q0; x.col_first = c0;
+                x.scorer = r.scorer; x.k = r.k; x.emit = c0 + columns == nc ? 1u : 0u;
+                x.cutoff_bits = cutoff_bits; x.prefix_weight = r.prefix_weight;
+                x.lists = lists; x.indices = ind; x.scores = sco;
+                launch_extract_select(scope, x);
+                absorb(false);
+            }
+        }
+        if (!dev_i) SWH_HIP_CHECK(hipMemcpyAsync(r.indices, ind, index_bytes, hipMemcpyDeviceToHost, stream));
+        if (!dev_s) SWH_HIP_CHECK(hipMemcpyAsync(r.scores, sco, score_bytes, hipMemcpyDeviceToHost, stream));
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        scope->summary_pending = false;
+        scope->stamps_pending = false;
+        sum.bytes = (cp ? 4 : 1) * symbols + index_bytes + score_bytes;
+        snprintf(sum.dominant_name, sizeof sum.dominant_name, "extract_select/%s", scoring_name);
+        scope->last_timing = sum;
+        if (scope->profiling) add_to_totals(scope->totals, sum);
+        return swh_success_k;
+    });
+}
+
+static swh_status_t extract_checks(swh_levenshtein_t e, swh_scope_t s, int scorer, size_t k, uint64_t cutoff_bits, uint64_t prefix_weight_bits,
+                                   size_t queries, size_t candidates, const uint32_t *indices, const void *scores, ExtractRequest &request,
+                                   const char **error) {
+    const swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    const Engine *engine = (const Engine *)e;
+    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (scorer < SWH_SCORER_OSA || scorer > SWH_SCORER_JARO_WINKLER) return fail(error, swh_invalid_argument_k, "scorer must be one of SWH_SCORER_*");
+    if (k < 1 || k > SWH_TOPK_MAX) return fail(error, swh_invalid_argument_k, "k must lie in [1, SWH_TOPK_MAX]");
+    double cutoff, prefix_weight;
+    memcpy(&cutoff, &cutoff_bits, sizeof cutoff);
+    memcpy(&prefix_weight, &prefix_weight_bits, sizeof prefix_weight);
+    if (!(cutoff >= 0.0)) return fail(error, swh_invalid_argument_k, "the cutoff must be a non-negative number (or +infinity), not NaN");
+    if (scorer == SWH_SCORER_JARO_WINKLER && !(prefix_weight >= 0.0 && prefix_weight <= 0.25))
+        return fail(error, swh_invalid_argument_k, "the prefix weight must lie in [0, 0.25]");
+    if (!engine->unit_costs)
+        return fail(error, swh_not_implemented_k, "the score search is called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)");
+    if (candidates >= 0xFFFFFFFFull) return fail(error, swh_unsupported_length_k, "2^32 - 1 candidates or more");
+    if (queries && (!indices || !scores)) return fail(error, swh_invalid_argument_k, "null output pointer");
+    request = ExtractRequest{scorer, (uint32_t)k, cutoff == 0.0 ? 0.0 : cutoff, prefix_weight, (uint32_t *)indices, (void *)scores};   // (-0.0: +0.0)
+    return swh_success_k;
+}
+
+static swh_status_t extract_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *q, const swh_tape_u64_t *c, bool utf8, int scorer,
+                                  size_t k, uint64_t cutoff_bits, uint64_t prefix_weight_bits, uint32_t *indices, void *scores, const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    if (!q) return fail(error, swh_invalid_argument_k, "null tape");
+    ExtractRequest request{};
+    status = extract_checks(e, s, scorer, k, cutoff_bits, prefix_weight_bits, q->count, (c ? c : q)->count, indices, scores, request, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    if (q->count == 0) return swh_success_k;
+    if ((status = call.prepare(q, c, utf8, true, true, error)) != swh_success_k) return status;
+    return extract_run(call.scope, call.pair, request, error);
+}
+swh_status_t swh_levenshtein_extract_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries, const swh_tape_u64_t *candidates,
+                                             int scorer, size_t k, uint64_t cutoff_bits, uint64_t prefix_weight_bits, uint32_t *indices,
+                                             void *scores, const char **error) {
+    return extract_tapes(e, s, queries, candidates, false, scorer, k, cutoff_bits, prefix_weight_bits, indices, scores, error);
+}
+swh_status_t swh_levenshtein_utf8_extract_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries,
+                                                  const swh_tape_u64_t *candidates, int scorer, size_t k, uint64_t cutoff_bits,
+                                                  uint64_t prefix_weight_bits, uint32_t *indices, void *scores, const char **error) {
+    return extract_tapes(e, s, queries, candidates, true, scorer, k, cutoff_bits, prefix_weight_bits, indices, scores, error);
+}
+swh_status_t swh_levenshtein_extract_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *queries,
+                                              const swh_prepared_view_t *candidates, int scorer, size_t k, uint64_t cutoff_bits,
+                                              uint64_t prefix_weight_bits, uint32_t *indices, void *scores, const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.views(queries, candidates, true, error)) != swh_success_k) return status;
+    ExtractRequest request{};
+    status = extract_checks(e, s, scorer, k, cutoff_bits, prefix_weight_bits, call.pair.a_count, call.pair.b_count, indices, scores, request, error);
+    if (status != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return extract_run(call.scope, call.pair, request, error);
 }
 
 }  // extern "C"

@@ -19,8 +19,10 @@
 //   k_topk_merge        one wave per query: the slices' partial lists folded into the final row.
 //   k_topk_select<Max>  the general path: one wave per query row folds a slice of a dense u32 distance matrix (scored by the
 //                       ordinary cross-product routes into scratch) into the row's running list. `Max` ranks by the largest score
-//                       (key (~s << 32) | j) -- the same code for a later score-maximising search; only the distance form is built.
+//                       (key (~s << 32) | j); only the distance form is built. (The search by a float64 score -- OSA, Indel, LCS,
+//                       ratio, Jaro, Jaro-Winkler -- is extract.hip's, with a wider key on the same fold.)
 #include "cross_words.hpp"
+#include "topk_fold.hpp"
 
 #include <algorithm>
 
@@ -29,34 +31,8 @@ namespace swh {
 constexpr int kTopkWaves = kWordWaves;   // (also the merge and select kernels': one wave per row)
 constexpr uint64_t kTopkPad = ~0ull;
 
-// Merges the keys of the `admitted` lanes into the wave's sorted list of k keys (LDS, k <= 64) and returns the new threshold.
-// Keys are distinct (candidate indices are), and no admitted key is a pad: ranks in the union are a permutation.
-__device__ __forceinline__ uint64_t topk_fold(uint64_t *list, uint32_t k, uint64_t key, uint64_t admitted, uint64_t cap) {
-    const uint32_t lane = __lane_id();
-    const uint64_t own = lane < k ? list[lane] : kTopkPad;
-    uint32_t below_key = 0, below_own = 0;
-    for (uint64_t rest = admitted; rest; rest &= rest - 1) {
-        const uint64_t other = readlane64(key, __builtin_ctzll(rest));
-        below_key += other < key ? 1u : 0u;
-        below_own += other < own ? 1u : 0u;
-    }
-    uint32_t at = 0;   // list entries below my key
-#pragma unroll
-    for (uint32_t step = 64; step; step >>= 1)
-        if (at + step <= k && list[at + step - 1] < key) at += step;
-    lds_order();
-    if ((admitted >> lane) & 1ull) {
-        const uint32_t rank = at + below_key;
-        if (rank < k) list[rank] = key;
-    }
-    if (lane < k) {
-        const uint32_t rank = lane + below_own;
-        if (rank < k) list[rank] = own;
-    }
-    lds_order();
-    const uint64_t last = list[k - 1];
-    return last < cap ? last : cap;
-}
+// (topk_fold, the merge by rank of the admitted keys into a row's sorted list, is topk_fold.hpp's: the key is its type parameter, and the
+// keys here are its uint64_t instantiation.)
 
 // The same fold for the fused kernel, where the fresh keys come from ONE chunk (candidate = chunk * 64 + lane: the key order among them
 // is (d, lane)) and every list entry from an earlier chunk of the item (a smaller candidate index than any fresh key): ranks are

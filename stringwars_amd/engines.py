@@ -27,7 +27,7 @@ __all__ = [
     "DeviceScope", "Strs", "DeviceTape", "PreparedTape", "ShardedPairs", "shard_cuts", "LevenshteinDistances", "LevenshteinDistancesUTF8",
     "NeedlemanWunschScores", "SmithWatermanScores", "edit_distance", "StringWarsError", "UNBOUNDED", "TOPK_MAX",
     "ALIGN_MAX_CELLS", "Alignments", "RangeMatches", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "OSA_MAX_SHORTER", "LCS_MAX_SHORTER",
-    "JARO_MAX_LENGTH",
+    "JARO_MAX_LENGTH", "SCORERS",
 ]
 
 StringWarsError = N.StringWarsError
@@ -39,6 +39,7 @@ INFIX_NONE = N.INFIX_NONE
 OSA_MAX_SHORTER = N.OSA_MAX_SHORTER
 LCS_MAX_SHORTER = N.LCS_MAX_SHORTER
 JARO_MAX_LENGTH = N.JARO_MAX_LENGTH
+SCORERS = tuple(N.SCORERS)   # the scorers of ``engine.extract``, by name
 
 
 def _pointer(obj) -> int:
@@ -1062,6 +1063,43 @@ class LevenshteinDistances(_Engine):
                            prefix_weight: float = 0.1):
         """The dense float64 matrix of Jaro-Winkler similarities."""
         return self._jaro_similarity(queries, candidates, scope, True, prefix_weight)
+
+    def extract(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None, *, scorer: str, k: int,
+                cutoff: Optional[float] = None, prefix_weight: float = 0.1, out=None):
+        """The ``k`` best candidates of every query under ``scorer`` (``swh_levenshtein_extract_*``): ``(indices, scores)``, each
+        ``(len(queries), k)``, uint32 and float64. ``scorer`` is one of ``SCORERS``: ``"osa"`` and ``"indel"`` are distances (smaller is
+        better, ``d <= cutoff`` is admitted), ``"lcs"``, ``"ratio"``, ``"jaro"`` and ``"jaro_winkler"`` similarities (larger is better,
+        ``s >= cutoff``); ``cutoff=None`` admits everything. Rows are ordered best score first, equal float64 scores by the smaller
+        candidate index; a row with fewer than ``k`` admitted candidates is padded with index ``0xFFFFFFFF`` and a NaN whose 64 bits
+        are all ones. A score has the bits that ``osa``, ``indel``, ``lcs``, ``ratio``, ``jaro`` and ``jaro_winkler`` (with this
+        ``prefix_weight``, in [0, 0.25]) return for that pair. ``candidates=None`` searches the queries themselves (diagonal included).
+        ``out=(indices, scores)`` fills given arrays or device tensors (contiguous, ``len(queries) * k`` entries of 4 and 8 bytes).
+        The two sides are tapes, or both ``PreparedTape``s.
+        rapidfuzz: ``process.extract(q, candidates, scorer=fuzz.ratio, limit=k, score_cutoff=cutoff)`` per query."""
+        if scope is None:
+            raise ValueError("a DeviceScope is required")
+        if scorer not in N.SCORERS:
+            raise ValueError("scorer must be one of %s" % ", ".join(N.SCORERS))
+        queries = _as_tape(queries)
+        if candidates is not None:
+            candidates = _as_tape(candidates)
+        count = len(queries)
+        if out is None:
+            indices, scores = np.empty((count, int(k)), dtype=np.uint32), np.empty((count, int(k)), dtype=np.float64)
+        else:
+            indices, scores = out
+            for array, width in ((indices, 4), (scores, 8)):
+                if isinstance(array, np.ndarray) and (array.dtype.itemsize != width or array.size != count * int(k) or not array.flags.c_contiguous):
+                    raise ValueError("out arrays must be contiguous (len(queries), k) arrays of uint32 and float64")
+                if hasattr(array, "element_size") and (array.element_size() != width or array.numel() != count * int(k) or not array.is_contiguous()):
+                    raise ValueError("out tensors must be contiguous, of len(queries) * k elements of 4 (indices) and 8 (scores) bytes")
+        if cutoff is None:
+            cutoff = 0.0 if N.SCORERS[scorer] >= N.SCORERS["lcs"] else float("inf")
+        bits = [C.c_uint64(int(np.float64(value).view(np.uint64))) for value in (cutoff, prefix_weight)]   # what memcpy of the double gives
+        err = C.c_char_p()
+        N.check(self._two_tapes(queries, candidates, scope, "extract")(N.SCORERS[scorer], int(k), bits[0], bits[1], C.c_void_p(_pointer(indices)),
+                                                                       C.c_void_p(_pointer(scores)), C.byref(err)), err)
+        return indices, scores
 
     def pairs_sharded(self, batch: "ShardedPairs", scope: DeviceScope, bound: Optional[int] = None, out=None):
         """One batch over every GPU of a multi-device scope; the distances come back gathered, in pair order."""

@@ -46,6 +46,14 @@ pub struct TimingTotals { pub total_ms: f64, pub dominant_ms: f64, pub compute_m
 pub struct ShardTiming { pub compute_ms: f64, pub gather_ms: f64, pub cells: u64, pub pairs: u64 }
 
 pub const UNBOUNDED: u32 = u32::MAX;
+/// `SWH_SCORER_*`: what a score search (`extract_into`) ranks by. The first two are distances (smaller is better), the rest similarities.
+#[repr(i32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Scorer { Osa = 0, Indel = 1, Lcs = 2, Ratio = 3, Jaro = 4, JaroWinkler = 5 }
+impl Scorer {
+    /// The cutoff that admits every candidate: +infinity for a distance, 0.0 for a similarity.
+    pub fn no_cutoff(self) -> f64 { if (self as i32) >= (Scorer::Lcs as i32) { 0.0 } else { f64::INFINITY } }
+}
 /// `SWH_ALIGN_MAX_CELLS`: len(a_i) * len(b_i) an alignment accepts per pair.
 pub const ALIGN_MAX_CELLS: u64 = 1 << 30;
 /// `SWH_INFIX_MAX_PATTERN`: symbols per pattern an infix search accepts.
@@ -146,6 +154,9 @@ extern "C" {
     fn swh_levenshtein_jaro_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, matches: *mut usize, transpositions: *mut usize, prefix: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_utf8_jaro_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, matches: *mut usize, transpositions: *mut usize, prefix: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_jaro_cross_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, matches: *mut usize, transpositions: *mut usize, prefix: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_extract_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, scorer: c_int, k: usize, cutoff_bits: u64, prefix_weight_bits: u64, indices: *mut u32, scores: *mut c_void, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_extract_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, scorer: c_int, k: usize, cutoff_bits: u64, prefix_weight_bits: u64, indices: *mut u32, scores: *mut c_void, error: Err) -> c_int;
+    fn swh_levenshtein_extract_prepared(engine: Handle, scope: Handle, queries: *const PreparedView, candidates: *const PreparedView, scorer: c_int, k: usize, cutoff_bits: u64, prefix_weight_bits: u64, indices: *mut u32, scores: *mut c_void, error: Err) -> c_int;
     fn swh_sharded_prepare_u32tape(scope: Handle, a: *const TapeU32, b: *const TapeU32, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_prepare_u64tape(scope: Handle, a: *const TapeU64, b: *const TapeU64, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_free(sharded: Handle) -> c_int;
@@ -459,6 +470,29 @@ impl LevenshteinDistances {
         check(unsafe { swh_levenshtein_topk_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64), k,
                                                     bound.unwrap_or(UNBOUNDED), indices.as_mut_ptr(), distances.as_mut_ptr(), &mut message) }, message)
     }
+    /// Score search: the `k` best candidates of every query under `scorer` (`process.extract(scorer = ..., limit = k, score_cutoff =
+    /// cutoff)` per query), `indices` / `scores` of `queries.len() * k`, rows best score first and equal scores by the smaller index,
+    /// padded with `u32::MAX` and an all-ones NaN. `cutoff`: `None` admits everything. The doubles cross as their bit patterns.
+    pub fn extract_into(&self, scope: &DeviceScope, queries: &BytesTapeView<u64>, candidates: Option<&BytesTapeView<u64>>, scorer: Scorer, k: usize,
+                        cutoff: Option<f64>, prefix_weight: f64, indices: &mut [u32], scores: &mut [f64]) -> Result<(), Error> {
+        assert!(indices.len() >= queries.len() * k && scores.len() >= queries.len() * k);
+        let tq = bytes_tape(queries);
+        let tc = candidates.map(bytes_tape);
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_extract_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64), scorer as c_int, k,
+                                                       cutoff.unwrap_or(scorer.no_cutoff()).to_bits(), prefix_weight.to_bits(), indices.as_mut_ptr(),
+                                                       scores.as_mut_ptr() as *mut c_void, &mut message) }, message)
+    }
+    pub fn extract_into_prepared(&self, scope: &DeviceScope, queries: &PreparedTape, candidates: Option<&PreparedTape>, scorer: Scorer, k: usize,
+                                 cutoff: Option<f64>, prefix_weight: f64, indices: &mut [u32], scores: &mut [f64]) -> Result<(), Error> {
+        assert!(indices.len() >= queries.len() * k && scores.len() >= queries.len() * k);
+        let vq = queries.view();
+        let vc = candidates.map(|c| c.view());
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_extract_prepared(self.handle, scope.handle, &vq, vc.as_ref().map_or(ptr::null(), |v| v as *const PreparedView), scorer as c_int, k,
+                                                        cutoff.unwrap_or(scorer.no_cutoff()).to_bits(), prefix_weight.to_bits(), indices.as_mut_ptr(),
+                                                        scores.as_mut_ptr() as *mut c_void, &mut message) }, message)
+    }
     /// Range search: every candidate within `bound` edits of every query (`process.extract(score_cutoff = bound, limit = None)` per
     /// query), as CSR: row i is `indices` / `distances` `[row_offsets[i] .. row_offsets[i + 1])`, ascending by candidate; `None` = q x q.
     /// `row_offsets` (`queries.len() + 1` entries) is always filled; the two arrays only if the total fits them. Returns the total:
@@ -688,6 +722,17 @@ impl LevenshteinDistancesUtf8 {
         let mut message = ptr::null();
         check(unsafe { swh_levenshtein_utf8_lcs_cross_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64), indel.map_or(ptr::null_mut(), |o| o.as_mut_ptr()),
                           lcs.map_or(ptr::null_mut(), |o| o.as_mut_ptr()), columns * 8, &mut message) }, message)
+    }
+    /// Score search over code points (see `LevenshteinDistances::extract_into`).
+    pub fn extract_into(&self, scope: &DeviceScope, queries: &CharsTapeView<u64>, candidates: Option<&CharsTapeView<u64>>, scorer: Scorer, k: usize,
+                        cutoff: Option<f64>, prefix_weight: f64, indices: &mut [u32], scores: &mut [f64]) -> Result<(), Error> {
+        assert!(indices.len() >= queries.len() * k && scores.len() >= queries.len() * k);
+        let tq = chars_tape(queries);
+        let tc = candidates.map(chars_tape);
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_utf8_extract_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64), scorer as c_int, k,
+                                                            cutoff.unwrap_or(scorer.no_cutoff()).to_bits(), prefix_weight.to_bits(), indices.as_mut_ptr(),
+                                                            scores.as_mut_ptr() as *mut c_void, &mut message) }, message)
     }
     /// Top-k search over code points (see `LevenshteinDistances::topk_into`).
     pub fn topk_into(&self, scope: &DeviceScope, queries: &CharsTapeView<u64>, candidates: Option<&CharsTapeView<u64>>, k: usize, bound: Option<u32>,
