@@ -1,4 +1,4 @@
-// align.hpp -- launchers of the Levenshtein alignment kernels (align.hip), called by api.hip.
+// align.hpp -- launchers of the Levenshtein alignment kernels (align.hip), called by two_tape.hip.
 // Kept apart from common.hpp, which every kernel family's profile stamp hashes (tools/kernel_sources.py).
 #pragma once
 #include "common.hpp"

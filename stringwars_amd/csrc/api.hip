@@ -1,4 +1,5 @@
-// api.hip -- the extern "C" boundary declared in include/stringwars_amd.h.
+// api.hip -- the extern "C" boundary declared in include/stringwars_amd.h: scopes, engines, prepared tapes and the engine calls
+// (pairs, cross-products). The synchronous two-tape calls (searches, alignments, infix, the scored families) are two_tape.hip.
 //
 // Host-side plumbing only: scope/engine lifetime, residency detection and staging of host tapes,
 // scratch carving, the device pre-pass, kernel dispatch and optional hipEvent timing. There is no
@@ -12,14 +13,7 @@
 #include <cstring>
 #include <new>
 
-#include "common.hpp"
-#include "within.hpp"
-#include "align.hpp"
-#include "infix.hpp"
-#include "osa.hpp"
-#include "lcs.hpp"
-#include "jaro.hpp"
-#include "extract.hpp"
+#include "api.hpp"
 #include <algorithm>
 #include <mutex>
 #include <utility>
@@ -28,7 +22,7 @@ namespace swh {
 
 // ---- error text (static storage, one slot per thread) ----------------------------------------
 static thread_local char g_error_text[512];
-__attribute__((format(printf, 3, 4))) static swh_status_t fail(const char **error, swh_status_t status, const char *fmt, ...) {
+swh_status_t fail(const char **error, swh_status_t status, const char *fmt, ...) {
     va_list args;
     va_start(args, fmt);
     vsnprintf(g_error_text, sizeof g_error_text, fmt, args);
@@ -36,7 +30,7 @@ __attribute__((format(printf, 3, 4))) static swh_status_t fail(const char **erro
     if (error) *error = g_error_text;
     return status;
 }
-static swh_status_t fail_hip(const char **error, const HipFailure &f) {
+swh_status_t fail_hip(const char **error, const HipFailure &f) {
     (void)hipGetLastError();
     return fail(error, f.code == hipErrorOutOfMemory ? swh_bad_alloc_k : swh_device_error_k, "HIP error '%s' in %s", hipGetErrorString(f.code), f.what);
 }
@@ -73,7 +67,7 @@ StampGuard::~StampGuard() {
     }
 }
 
-static void collect_timing(Scope *scope) {
+void collect_timing(Scope *scope) {
     swh_timing_t &t = scope->last_timing;
     t.total_ms = 0; t.dominant_ms = 0; t.compute_ms = 0; t.dominant_name[0] = 0; t.kernels = (uint32_t)scope->stamps_used;
     if (!scope->stamps_used) return;
@@ -114,7 +108,7 @@ static void collect_timing(Scope *scope) {
     t.compute_ms = covered;
 }
 
-static void add_to_totals(swh_timing_totals_t &totals, const swh_timing_t &call) {
+void add_to_totals(swh_timing_totals_t &totals, const swh_timing_t &call) {
     totals.total_ms += call.total_ms;
     totals.dominant_ms += call.dominant_ms;
     totals.compute_ms += call.compute_ms;
@@ -124,7 +118,7 @@ static void add_to_totals(swh_timing_totals_t &totals, const swh_timing_t &call)
 // Reads the events of the scope's last call once they are complete and adds the call to the running totals.
 // `complete`: the caller has synchronised with the scope's last call. Otherwise (the start of the next call in
 // asynchronous mode) completion is only known when profiling is on, through the call's stop events.
-static void harvest_timing(Scope *scope, bool complete) {
+void harvest_timing(Scope *scope, bool complete) {
     const bool timed = scope->profiling && scope->stamps_pending && scope->stamps_used;
     if (timed) {
         for (size_t i = 0; i < scope->stamps_used; ++i) (void)hipEventSynchronize(scope->stamps[i].stop);   // two streams: no single last event
@@ -160,17 +154,7 @@ static void harvest_timing(Scope *scope, bool complete) {
 }
 
 // ---- scratch -------------------------------------------------------------------------------------
-static size_t pad(size_t n) { return (n + 255) & ~(size_t)255; }
-struct Carver {
-    char *base; size_t used, cap;
-    template <typename T> T *take(size_t n) {
-        char *p = base ? base + used : nullptr;
-        used += pad(n * sizeof(T));
-        return (T *)p;
-    }
-};
-
-static void ensure(char *&buf, size_t &cap, size_t need) {
+void ensure(char *&buf, size_t &cap, size_t need) {
     if (need <= cap) return;
     if (buf) SWH_HIP_CHECK(hipFree(buf));
     buf = nullptr; cap = 0;
@@ -199,7 +183,7 @@ static size_t utf8_scratch_words(uint64_t bytes) {
     return (size_t)((tiles + 4) + (kUtf8Subs * tiles + 4) + 2 * (tiles + 4) + 2 * ((tiles + 1023) / 1024 + 4) + (tiles + 6));
 }
 
-static bool is_device_pointer(const void *p) {
+bool is_device_pointer(const void *p) {
     if (!p) return true;
     hipPointerAttribute_t attr;
     hipError_t err = hipPointerGetAttributes(&attr, p);
@@ -217,50 +201,18 @@ static bool is_plain_device_memory(const void *p, int device) {
     return attr.type == hipMemoryTypeDevice && attr.device == device;
 }
 
-// ---- one engine call ---------------------------------------------------------------------------
-struct HostTape { const uint8_t *data; const void *offsets; size_t count; int off64; };
-
-// swh_prepared_t: a tape made ready once -- resident on the device, measured, and (UTF-8) validated and decoded --
-// the counterpart of the `BytesTapeView` / `CharsTapeView` the reference builds ONCE outside its timed closures
-// (bench.rs:292-306) and sub-views per iteration (bench.rs:134-139).
-struct Prepared {
-    int device = 0;
-    bool utf8 = false;           // symbols are Unicode scalar values
-    bool ascii = false;          // utf8 and every code point is one byte: the byte tape is the code-point tape
-    uint32_t off64 = 0;          // width of the byte tape's offsets
-    TapeRef bytes{};             // device: u8 data, u32/u64 offsets
-    TapeRef symbols{};           // utf8: u32 code points + u64 code-point offsets; otherwise unused
-    uint64_t total_bytes = 0, total_symbols = 0;   // offsets[count]: the end of the last string (and, of the symbols, how many were decoded)
-    uint64_t first_byte = 0;     // offsets[0]: a tape may be a window of a larger buffer
-    uint32_t longest_bytes = 0, longest_symbols = 0;
-    std::vector<void *> owned;   // device buffers that go with the handle
-};
-
-struct CallSpec {
-    HostTape a, b;
-    bool cross, utf8;
-    uint32_t bound;
-    void *out; size_t out_stride, row_stride; bool out64;
-    const Prepared *pa = nullptr, *pb = nullptr;   // prepared tapes (both or neither); a.count / b.count = the views' counts
-    size_t a_first = 0, b_first = 0;
-    bool force_planned = false;                    // redo of a call whose plan-free kernel met a pair it could not score
-    uint32_t skip_upto = 0;                        // ... where that kernel HAS scored every pair of two strings of at most this many symbols
-    bool flat_staging = false;                     // redo of a raw UTF-8 call whose string-by-string staging met a string too long for it
-};
-
-// ---- prepared tapes in a call -------------------------------------------------------------------------------------------------
-static bool view_fits(const swh_prepared_view_t *view) {
+// ---- prepared tapes in a call (HostTape, Prepared, CallSpec: api.hpp) ---------------------------------------------------------
+bool view_fits(const swh_prepared_view_t *view) {
     const Prepared *p = (const Prepared *)view->tape;
     return view->first <= p->bytes.count && view->count <= p->bytes.count - view->first;
 }
-static swh_status_t check_prepared_pair(const Scope *scope, const Prepared *pa, const Prepared *pb, const char **error) {
+swh_status_t check_prepared_pair(const Scope *scope, const Prepared *pa, const Prepared *pb, const char **error) {
     if (pa->utf8 != pb->utf8) return fail(error, swh_invalid_argument_k, "one tape was prepared as UTF-8, the other as bytes");
     if (pa->device != scope->device || pb->device != scope->device)
         return fail(error, swh_invalid_argument_k, "a prepared tape lives on another device than the scope");
     return swh_success_k;
 }
-// strings [first, first + count) of a prepared tape: its code points (`code_points` on a UTF-8 tape: u64 offsets) or its bytes
-static TapeRef prepared_view(const Prepared *p, bool code_points, size_t first, size_t count) {
+TapeRef prepared_view(const Prepared *p, bool code_points, size_t first, size_t count) {
     const bool decoded = code_points && p->utf8;
     TapeRef t = decoded ? p->symbols : p->bytes;
     t.offsets = (const char *)t.offsets + first * (decoded || p->off64 ? 8 : 4);
@@ -268,7 +220,7 @@ static TapeRef prepared_view(const Prepared *p, bool code_points, size_t first, 
     return t;
 }
 
-static uint64_t read_offset(const void *offs, int off64, size_t i, bool device, hipStream_t stream) {
+uint64_t read_offset(const void *offs, int off64, size_t i, bool device, hipStream_t stream) {
     uint64_t v = 0;
     size_t w = off64 ? 8 : 4;
     if (device) {
@@ -279,8 +231,6 @@ static uint64_t read_offset(const void *offs, int off64, size_t i, bool device, 
     }
     return v;
 }
-
-static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSpec &spec, const char **error);
 
 // Does either tape hold a byte above 0x7F? Runs in front of the byte kernels when a UTF-8 call BELIEVES its raw tapes to be ASCII
 // (they were, the last time this scope staged them): sixteen bytes per thread and step, the flag in host-mapped memory.
@@ -326,9 +276,6 @@ static swh_status_t run_call(Scope *scope, const Engine *engine, const CallSpec 
     scope->last_timing = lane->last_timing;
     return status;
 }
-
-// Which kernels a unit-cost Levenshtein call runs on.
-enum Route { kRoutePlanned, kRouteTiled, kRouteDirectShort, kRouteShortTiled, kRouteCrossShort, kRouteAlignShort, kRouteAlignLong };
 
 // Strings up to this many symbols (G <= 8 blocks) are scored by the tiled kernel when their lengths are known; beyond it
 // a tile holds too few pairs per block count and the global sort of the planned path packs the waves better.
@@ -426,14 +373,8 @@ static bool bitparallel_ok(const Engine *engine) {
 }
 static uint64_t call_pairs(const CallSpec &spec) { return spec.cross ? (uint64_t)spec.a.count * spec.b.count : spec.a.count; }
 
-// What a call knows about its strings' lengths before it launches anything: a guarantee for prepared tapes, a belief from the scope's
-// previous call (the kernels verify it), or -- a Levenshtein engine forced onto the tiled kernel -- that kernel's 2048 symbols.
-struct Lengths {
-    bool known = false, guaranteed = false;
-    uint32_t la_max = 0, lb_max = 0;
-    uint64_t prepared_mean_x16 = 0;   // prepared tapes: the longer mean string of the two whole tapes, bytes x 16
-};
-static Lengths call_lengths(const Scope *scope, const Engine *engine, const CallSpec &spec, bool utf8) {
+// What a call knows about its strings' lengths before it launches anything (Lengths: api.hpp).
+Lengths call_lengths(const Scope *scope, const Engine *engine, const CallSpec &spec, bool utf8) {
     Lengths l;
     if (spec.pa) {
         l.known = l.guaranteed = true;
@@ -452,14 +393,9 @@ static Lengths call_lengths(const Scope *scope, const Engine *engine, const Call
     return l;
 }
 
-struct RouteChoice {
-    Route route = kRoutePlanned;
-    uint32_t longest = 0;      // what the plan-free kernel is launched for
-    bool align_wide = false;   // kRouteAlignShort on k_align_cross_wide (its alphabet condition is checked by the kernel)
-};
 // Which kernels a call runs on (DESIGN.md §4's route table). Calls no HIP API and changes nothing on the scope. `dev_out`: the output is
 // in device memory, where an asynchronous call cannot look at the outcome -- it only acts on lengths that are guaranteed.
-static RouteChoice pick_route(const Scope *scope, const Engine *engine, const CallSpec &spec, bool utf8, bool dev_out, const Lengths &len) {
+RouteChoice pick_route(const Scope *scope, const Engine *engine, const CallSpec &spec, bool utf8, bool dev_out, const Lengths &len) {
     RouteChoice r;
     const bool can_verify = !scope->async || !dev_out;
     const bool usable = len.known && (len.guaranteed || can_verify);
@@ -1154,7 +1090,7 @@ struct Call {
     }
 };
 
-static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSpec &first, const char **error) {
+swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSpec &first, const char **error) {
     const swh_status_t checked = check_call(scope, engine, first, error);
     if (checked != swh_success_k) return checked;
     CallSpec spec = first;
@@ -1175,11 +1111,13 @@ static swh_status_t run_call_on(Scope *scope, const Engine *engine, const CallSp
 
 using namespace swh;
 
-// Alignment scratch (align.hip) of every scope that ran an alignment: stored delta vectors, op slots, scans. Kept here rather than in
-// Scope so that common.hpp -- which every kernel family's profile stamp hashes -- stays as it is; freed with the scope.
-struct AlignScratch { char *buf = nullptr; size_t bytes = 0; };
+// The alignment scratch of every scope that used one (AlignScratch: api.hpp), freed with the scope.
 static std::mutex g_align_scratch_lock;
 static std::unordered_map<const Scope *, AlignScratch> g_align_scratch;
+AlignScratch *swh::call_scratch(const Scope *scope) {
+    std::lock_guard<std::mutex> hold(g_align_scratch_lock);
+    return &g_align_scratch[scope];
+}
 static void free_align_scratch(const Scope *scope) {
     std::lock_guard<std::mutex> hold(g_align_scratch_lock);
     auto it = g_align_scratch.find(scope);
@@ -1458,15 +1396,17 @@ swh_status_t swh_copy_to_host(swh_scope_t handle, void *dst, const void *src, si
     return swh_success_k;
 }
 
-// ---- prepared tapes ----------------------------------------------------------------------------------
-static void free_prepared(Prepared *p) {
+}  // extern "C"
+
+// ---- prepared tapes (shared with two_tape.hip: outside the C block) -----------------------------------
+void swh::free_prepared(Prepared *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
     for (void *buffer : p->owned) (void)hipFree(buffer);
     delete p;
 }
 
-static swh_status_t prepare_tape(Scope *scope, const HostTape &tape, bool utf8, swh_prepared_t *out, const char **error) {
+swh_status_t swh::prepare_tape(Scope *scope, const HostTape &tape, bool utf8, swh_prepared_t *out, const char **error) {
     if (!scope || !out) return fail(error, swh_invalid_argument_k, "null argument");
     *out = nullptr;
     if (scope->pipelined) return fail(error, swh_invalid_argument_k, "prepare tapes before switching the scope to pipelined mode");
@@ -1571,6 +1511,7 @@ static swh_status_t prepare_tape(Scope *scope, const HostTape &tape, bool utf8, 
     }
 }
 
+extern "C" {
 // ---- engines --------------------------------------------------------------------------------------
 static swh_status_t upload_matrix(Engine *engine, const int8_t *matrix, const char **error) {
     hipError_t err = hipMalloc((void **)&engine->matrix_dev, 65536);
@@ -1736,8 +1677,6 @@ swh_status_t swh_sw_init_classes(swh_scope_t handle, const uint8_t *byte_to_clas
 swh_status_t swh_sw_free(swh_sw_t handle) { return swh_levenshtein_free((swh_levenshtein_t)handle); }
 
 // ---- calls -----------------------------------------------------------------------------------------
-#define SWH_TAPE(t, w) HostTape{(t)->data, (const void *)(t)->offsets, (t)->count, (w)}
-
 static swh_status_t lev_pairs(swh_levenshtein_t e, swh_scope_t s, HostTape a, HostTape b, bool utf8, uint32_t bound,
                               uint32_t *out, size_t stride, const char **error) {
     if (e && ((Engine *)e)->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
@@ -1903,1381 +1842,3 @@ swh_status_t swh_sw_cross_prepared(swh_sw_t e, swh_scope_t s, const swh_prepared
 
 }  // extern "C"
 
-// ---- the synchronous two-tape calls: one front end ------------------------------------------------------------------------------------
-// Top-k and range searches, alignments, infix search and the scored families (OSA, LCS, Jaro) are synchronous on every scope:
-// outstanding asynchronous / pipelined work is joined first, and the call runs on the scope itself (not on a pipeline lane) with the
-// asynchronous mode held off until it returns. Every export runs its own null tests and argument checks in its own order -- which
-// refusal wins is its contract (DESIGN.md lists where the calls differ on purpose) -- and between them resolves its two sides here,
-// into the TapePair its *_run takes.
-struct TapePair {
-    const Prepared *pa = nullptr, *pb = nullptr;   // null where a raw call prepared nothing: every *_run returns before it looks at them
-    size_t a_first = 0, a_count = 0, b_first = 0, b_count = 0;
-};
-struct PreparedOwner {
-    Prepared *p = nullptr;
-    ~PreparedOwner() { free_prepared(p); }
-};
-static swh_status_t join_outstanding(Scope *scope, const char **error) {
-    if (!scope->async && !scope->pipelined) return swh_success_k;
-    return swh_scope_synchronize((swh_scope_t)scope, error);
-}
-
-struct HoldSynchronous {
-    Scope *scope = nullptr;
-    bool async = false, pipelined = false;
-    void hold(Scope *s) { scope = s; async = s->async; pipelined = s->pipelined; s->async = false; s->pipelined = false; }
-    ~HoldSynchronous() {
-        if (scope) { scope->async = async; scope->pipelined = pipelined; }
-    }
-};
-struct TwoTapeCall {
-    HoldSynchronous mode;             // declared first, so the scope's mode comes back last: after what the call prepared is freed
-    Scope *scope = nullptr;           // set once the call has begun
-    PreparedOwner owned_a, owned_b;   // what a raw call prepared: it lives as long as the call
-    TapePair pair;
-
-    // joins what is outstanding and holds the scope synchronous until the call returns
-    swh_status_t begin(swh_scope_t s, const char **error) {
-        const swh_status_t status = join_outstanding((Scope *)s, error);
-        if (status != swh_success_k) return status;
-        scope = (Scope *)s;
-        mode.hold(scope);
-        return swh_success_k;
-    }
-    // Raw tapes, after begin(): the sides named are made resident and measured for the call (prepare_tape: device tapes in place, host
-    // tapes uploaded; UTF-8 validated and decoded), so the route is chosen on lengths that are known, not believed. Without `b` the
-    // second side is the first. A call without pairs names no side: its pair keeps the counts and null tapes.
-    swh_status_t prepare(const swh_tape_u64_t *a, const swh_tape_u64_t *b, bool utf8, bool prepare_a, bool prepare_b, const char **error) {
-        pair = TapePair{nullptr, nullptr, 0, a->count, 0, (b ? b : a)->count};
-        swh_status_t status = swh_success_k;
-        if (prepare_a && (status = prepare_tape(scope, SWH_TAPE(a, 1), utf8, (swh_prepared_t *)&owned_a.p, error)) != swh_success_k) return status;
-        if (b && prepare_b && (status = prepare_tape(scope, SWH_TAPE(b, 1), utf8, (swh_prepared_t *)&owned_b.p, error)) != swh_success_k) return status;
-        pair.pa = owned_a.p; pair.pb = b ? owned_b.p : owned_a.p;
-        return swh_success_k;
-    }
-    // Prepared views, before the call's own checks: the null tests and the bounds of both. A missing b is a (the self-search, the
-    // self-product) where `b_optional`.
-    swh_status_t views(const swh_prepared_view_t *a, const swh_prepared_view_t *b, bool b_optional, const char **error) {
-        if (!a || !a->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
-        const swh_prepared_view_t *bb = (b && b->tape) ? b : (b_optional ? a : nullptr);
-        if (!bb) return fail(error, swh_invalid_argument_k, "null prepared view");
-        if (!view_fits(a) || !view_fits(bb)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
-        pair = TapePair{(const Prepared *)a->tape, (const Prepared *)bb->tape, a->first, a->count, bb->first, bb->count};
-        return swh_success_k;
-    }
-    // ... and after them: the two tapes go together and live on the scope's device, and the call begins
-    swh_status_t begin_on_views(swh_scope_t s, const char **error) {
-        const swh_status_t status = check_prepared_pair((Scope *)s, pair.pa, pair.pb, error);
-        return status != swh_success_k ? status : begin(s, error);
-    }
-};
-
-// What every *_run is wrapped in: the previous call's timing is harvested and this call's begins empty; a HIP or allocation failure
-// anywhere in `body` becomes the call's status.
-template <typename Body> static swh_status_t synchronous_run(Scope *scope, const char **error, Body body) {
-    harvest_timing(scope, false);
-    scope->stamps_used = 0;
-    scope->last_timing = swh_timing_t{};
-    try {
-        return body();
-    } catch (const HipFailure &f) {
-        return fail_hip(error, f);
-    } catch (const std::bad_alloc &) {
-        return fail(error, swh_bad_alloc_k, "host allocation failed");
-    }
-}
-
-// ---- the search planner: what top-k and the range search decide alike ---------------------------------------------------------------
-// Both searches run word-sized byte strings on unit costs through a fused kernel of their own (k_cross_topk, k_cross_within): the
-// searches a dense cross-product of the same views would run on k_cross_short (pick_route for prepared tapes). Everything else takes
-// the general path: the candidates in slices, each slice scored by the ordinary cross-product routes into a u32 matrix in scratch
-// (with the caller's bound, so long strings may take the banded kernel) and handed to the search's own kernels. What differs between
-// the two comes in as a value or a callback.
-// `force_select`: the search's STRINGWARS_AMD_*_ROUTE=select hook; `dev_out`: its results go to device memory
-static bool search_is_fused(const Scope *scope, const Engine *engine, const TapePair &p, uint32_t bound, bool force_select, bool dev_out) {
-    const bool utf8 = p.pa->utf8 && !(p.pa->ascii && p.pb->ascii && p.pa->off64 == p.pb->off64);
-    CallSpec whole{};   // the dense cross-product of the two views, as run_call_on would route it
-    whole.a.count = p.a_count; whole.b.count = p.b_count; whole.cross = true; whole.bound = bound; whole.pa = p.pa; whole.pb = p.pb;
-    return !force_select && !utf8 && engine->algorithm == swh_algorithm_auto_k && p.pa->off64 == p.pb->off64 &&
-           pick_route(scope, engine, whole, false, dev_out, call_lengths(scope, engine, whole, false)).route == kRouteCrossShort;
-}
-
-// The fused kernels' candidate slices per block of 16 queries: enough for ~32 items per compute unit (a few rounds of its 12 wave
-// slots: 65 536 x 1 M words ran top-k at 4.6 TCUPS with 16, 5.9 with 32), while what the search keeps per (row, slice) --
-// `row_slice_bytes` -- stays under 256 MB; at most one per chunk of 64 candidates. `forced`: a test hook's count, 0 without one.
-struct SearchSlices { uint64_t slices, slice_chunks; };
-static SearchSlices search_slices(uint64_t nq, uint64_t nc, uint64_t compute_units, uint64_t row_slice_bytes, uint64_t forced) {
-    const uint64_t qblocks = (nq + 15) / 16, chunks = (nc + 63) / 64;
-    const uint64_t target = compute_units * 32;
-    uint64_t slices = std::min<uint64_t>(std::max<uint64_t>((target + qblocks - 1) / qblocks, 1), chunks);
-    slices = std::max<uint64_t>(1, std::min<uint64_t>(slices, ((uint64_t)256 << 20) / (nq * row_slice_bytes)));
-    if (forced) slices = std::min<uint64_t>(forced, chunks);
-    const uint64_t slice_chunks = (chunks + slices - 1) / slices;
-    return SearchSlices{(chunks + slice_chunks - 1) / slice_chunks, slice_chunks};
-}
-
-// The general path: query blocks of at most 2^18 rows x candidate slices of at most 2^26 pairs (a 256 MB u32 matrix), and the search
-// reported as one call whose name says which path ran and which kernel scored the pairs.
-struct SearchSweep {
-    Scope *scope; const Engine *engine; const TapePair &pair; uint32_t bound;
-    uint64_t q_step, c_step;
-    swh_timing_totals_t totals_before;
-    swh_timing_t sum{};
-    char scoring_name[64] = "";
-
-    SearchSweep(Scope *s, const Engine *e, const TapePair &p, uint32_t bound_)
-        : scope(s), engine(e), pair(p), bound(bound_), q_step(std::min<uint64_t>(p.a_count, (uint64_t)1 << 18)),
-          c_step(std::max<uint64_t>(1, std::min<uint64_t>(p.b_count, ((uint64_t)1 << 26) / q_step))), totals_before(s->totals) {}
-
-    // One walk over the blocks. rows_begin(q0, rows) opens every block of queries, before its first slice is scored; each slice is then
-    // scored into `matrix` (q_step * c_step entries) and handed to block(q0, rows, c0, columns, last_slice) with the stamps reset.
-    // `counted`: the walk's cells and bytes go into the sum (a second walk of the same pairs: not again).
-    template <typename Rows, typename Block>
-    swh_status_t walk(uint32_t *matrix, bool counted, const char **error, Rows rows_begin, Block block) {
-        const uint64_t nq = pair.a_count, nc = pair.b_count;
-        for (uint64_t q0 = 0; q0 < nq; q0 += q_step) {
-            const uint64_t rows = std::min<uint64_t>(q_step, nq - q0);
-            rows_begin(q0, rows);
-            for (uint64_t c0 = 0; c0 < nc; c0 += c_step) {
-                const uint64_t columns = std::min<uint64_t>(c_step, nc - c0);
-                CallSpec spec{};
-                spec.a = HostTape{nullptr, nullptr, (size_t)rows, 0};
-                spec.b = HostTape{nullptr, nullptr, (size_t)columns, 0};
-                spec.cross = true; spec.utf8 = pair.pa->utf8; spec.bound = bound;
-                spec.out = matrix; spec.out_stride = 4; spec.row_stride = columns * 4; spec.out64 = false;
-                spec.pa = pair.pa; spec.pb = pair.pb; spec.a_first = pair.a_first + q0; spec.b_first = pair.b_first + c0;
-                const swh_status_t status = run_call_on(scope, engine, spec, error);
-                if (status != swh_success_k) return status;
-                const swh_timing_t &dp = scope->last_timing;
-                if (counted) { sum.cells += dp.cells; sum.bytes += dp.bytes; }
-                sum.total_ms += dp.total_ms; sum.compute_ms += dp.compute_ms; sum.kernels += dp.kernels;
-                if (dp.dominant_ms > sum.dominant_ms) { sum.dominant_ms = dp.dominant_ms; snprintf(scoring_name, sizeof scoring_name, "%s", dp.dominant_name); }
-                scope->stamps_used = 0;
-                scope->stamps_pending = false;
-                block(q0, rows, c0, columns, c0 + columns == nc);
-            }
-        }
-        return swh_success_k;
-    }
-    // with profiling on, the time of the `launched` kernels of the search's own since the last scoring call
-    void time_own_kernels(uint32_t launched) {
-        if (!scope->profiling) return;
-        SWH_HIP_CHECK(hipStreamSynchronize(scope->stream));
-        collect_timing(scope);
-        sum.total_ms += scope->last_timing.total_ms; sum.compute_ms += scope->last_timing.compute_ms; sum.kernels += launched;
-        scope->stamps_used = 0;
-    }
-    // the search as one call, "<search>_select/<scoring kernel>", once in the scope's totals
-    void close(const char *search) {
-        scope->summary_pending = false;
-        scope->stamps_pending = false;
-        snprintf(sum.dominant_name, sizeof sum.dominant_name, "%s_select/%s", search, scoring_name);
-        scope->last_timing = sum;
-        if (scope->profiling) {
-            scope->totals = totals_before;
-            add_to_totals(scope->totals, sum);
-        }
-    }
-};
-
-extern "C" {
-// ---- top-k search (topk.hip) ----------------------------------------------------------------------------------------------------------
-// The fused kernel keeps a list of k per (row, slice) and merges them; the general path folds each scored slice into the running
-// lists with k_topk_select.
-// STRINGWARS_AMD_TOPK_PRUNE=0 (test library): the fused kernel walks every chunk, also those the length bound rules out (the comparison knob)
-static uint32_t topk_prune() {
-    static const uint32_t on = [] { const char *e = test_hook("STRINGWARS_AMD_TOPK_PRUNE"); return !e || atoi(e) != 0 ? 1u : 0u; }();
-    return on;
-}
-// STRINGWARS_AMD_TOPK_ROUTE=select (test library): every search on the general path
-static bool topk_force_select() {
-    static const bool on = [] { const char *e = test_hook("STRINGWARS_AMD_TOPK_ROUTE"); return e && !strcmp(e, "select"); }();
-    return on;
-}
-
-static swh_status_t topk_run(Scope *scope, const Engine *engine, const TapePair &p, uint32_t k32, uint32_t bound, uint32_t *indices,
-                             uint32_t *distances, const char **error) {
-    return synchronous_run(scope, error, [&]() -> swh_status_t {
-        const uint64_t nq = p.a_count, nc = p.b_count, k = k32;
-        if (nq == 0) return swh_success_k;
-        const uint64_t cap = bound == SWH_UNBOUNDED ? ~0ull : ((uint64_t)bound + 1) << 32;
-        const size_t out_bytes = nq * k * sizeof(uint32_t);
-        SWH_HIP_CHECK(hipSetDevice(scope->device));
-        hipStream_t stream = scope->stream;
-        const bool dev_i = is_device_pointer(indices), dev_d = is_device_pointer(distances);
-        if (nc == 0) {   // every row is padding
-            if (dev_i) SWH_HIP_CHECK(hipMemsetAsync(indices, 0xFF, out_bytes, stream)); else memset(indices, 0xFF, out_bytes);
-            if (dev_d) SWH_HIP_CHECK(hipMemsetAsync(distances, 0xFF, out_bytes, stream)); else memset(distances, 0xFF, out_bytes);
-            SWH_HIP_CHECK(hipStreamSynchronize(stream));
-            return swh_success_k;
-        }
-        const size_t ow = p.pa->off64 ? 8 : 4;
-        auto finish_outputs = [&](uint32_t *ind, uint32_t *dist) {
-            if (!dev_i) SWH_HIP_CHECK(hipMemcpyAsync(indices, ind, out_bytes, hipMemcpyDeviceToHost, stream));
-            if (!dev_d) SWH_HIP_CHECK(hipMemcpyAsync(distances, dist, out_bytes, hipMemcpyDeviceToHost, stream));
-            SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        };
-
-        if (search_is_fused(scope, engine, p, bound, topk_force_select(), dev_i)) {
-            // ---- fused: a partial list of k (index, distance) words per (row, slice) ------------------------------------------------------
-            const SearchSlices cut = search_slices(nq, nc, scope->compute_units, k * 8, 0);
-            const uint64_t slices = cut.slices;
-            const size_t need = (slices > 1 ? pad(nq * slices * k * 8) : 0) + (dev_i ? 0 : pad(out_bytes)) + (dev_d ? 0 : pad(out_bytes));
-            ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
-            Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
-            TopkLaunch t{};
-            t.a = prepared_view(p.pa, false, p.a_first, nq); t.b = prepared_view(p.pb, false, p.b_first, nc);
-            t.off64 = p.pa->off64; t.k = (uint32_t)k; t.slices = (uint32_t)slices; t.prune = topk_prune();
-            t.slice_chunks = cut.slice_chunks; t.cap = cap;
-            t.partial = slices > 1 ? sc.take<uint64_t>(nq * slices * k) : nullptr;
-            t.indices = dev_i ? indices : sc.take<uint32_t>(nq * k);
-            t.distances = dev_d ? distances : sc.take<uint32_t>(nq * k);
-            scope->summary_slot = 0;
-            launch_cross_topk(scope, t);
-            finish_outputs(t.indices, t.distances);
-            const CallSummary sm = scope->summary_host[0];
-            if (!sm.violation) {
-                if (scope->profiling && scope->stamps_used) {
-                    collect_timing(scope);
-                    add_to_totals(scope->totals, scope->last_timing);
-                }
-                scope->last_timing.cells = sm.cells;
-                scope->last_timing.bytes = p.pa->total_bytes + p.pb->total_bytes + (nq + nc) * ow + 2 * out_bytes;
-                return swh_success_k;
-            }
-            // a string longer than the kernel takes (the memory of a prepared tape changed since it was measured): the general path
-            scope->stamps_used = 0;
-            scope->last_timing = swh_timing_t{};
-        }
-
-        // ---- general path: each slice folded into the block's running lists ---------------------------------------------------------------
-        SearchSweep sweep(scope, engine, p, bound);
-        const size_t need = pad(sweep.q_step * sweep.c_step * 4) + pad(sweep.q_step * k * 8) + (dev_i ? 0 : pad(out_bytes)) + (dev_d ? 0 : pad(out_bytes));
-        ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
-        Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
-        uint32_t *matrix = sc.take<uint32_t>(sweep.q_step * sweep.c_step);
-        uint64_t *lists = sc.take<uint64_t>(sweep.q_step * k);
-        uint32_t *ind = dev_i ? indices : sc.take<uint32_t>(nq * k);
-        uint32_t *dist = dev_d ? distances : sc.take<uint32_t>(nq * k);
-        auto pad_lists = [&](uint64_t, uint64_t rows) { SWH_HIP_CHECK(hipMemsetAsync(lists, 0xFF, rows * k * 8, stream)); };   // every row is padding
-        const swh_status_t status = sweep.walk(matrix, true, error, pad_lists, [&](uint64_t q0, uint64_t rows, uint64_t c0, uint64_t columns, bool last_slice) {
-            launch_topk_select(scope, matrix, rows, columns, q0, c0, (uint32_t)k, cap, lists, last_slice, ind, dist);
-            sweep.time_own_kernels(1);
-        });
-        if (status != swh_success_k) return status;
-        finish_outputs(ind, dist);
-        sweep.close("topk");
-        return swh_success_k;
-    });
-}
-
-static swh_status_t topk_checks(swh_levenshtein_t e, swh_scope_t s, size_t k, size_t queries, size_t candidates, const uint32_t *indices,
-                                const uint32_t *distances, const char **error) {
-    if (!s || !e) return fail(error, swh_invalid_argument_k, "null scope or engine");
-    if (((Engine *)e)->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
-    if (k < 1 || k > SWH_TOPK_MAX) return fail(error, swh_invalid_argument_k, "k must lie in [1, SWH_TOPK_MAX]");
-    if (candidates >= 0xFFFFFFFFull) return fail(error, swh_unsupported_length_k, "2^32 - 1 candidates or more");
-    if (queries && (!indices || !distances)) return fail(error, swh_invalid_argument_k, "null output pointer");
-    return swh_success_k;
-}
-
-static swh_status_t topk_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *q, const swh_tape_u64_t *c, bool utf8, size_t k,
-                               uint32_t bound, uint32_t *indices, uint32_t *distances, const char **error) {
-    if (!q) return fail(error, swh_invalid_argument_k, "null tape");
-    swh_status_t status = topk_checks(e, s, k, q->count, (c ? c : q)->count, indices, distances, error);
-    if (status != swh_success_k) return status;
-    TwoTapeCall call;
-    if ((status = call.begin(s, error)) != swh_success_k) return status;
-    if (q->count == 0) return swh_success_k;
-    if ((status = call.prepare(q, c, utf8, true, true, error)) != swh_success_k) return status;
-    return topk_run(call.scope, (Engine *)e, call.pair, (uint32_t)k, bound, indices, distances, error);
-}
-swh_status_t swh_levenshtein_topk_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries, const swh_tape_u64_t *candidates,
-                                          size_t k, uint32_t bound, uint32_t *indices, uint32_t *distances, const char **error) {
-    return topk_tapes(e, s, queries, candidates, false, k, bound, indices, distances, error);
-}
-swh_status_t swh_levenshtein_utf8_topk_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries,
-                                               const swh_tape_u64_t *candidates, size_t k, uint32_t bound, uint32_t *indices,
-                                               uint32_t *distances, const char **error) {
-    return topk_tapes(e, s, queries, candidates, true, k, bound, indices, distances, error);
-}
-swh_status_t swh_levenshtein_topk_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *queries,
-                                           const swh_prepared_view_t *candidates, size_t k, uint32_t bound, uint32_t *indices,
-                                           uint32_t *distances, const char **error) {
-    TwoTapeCall call;
-    swh_status_t status = call.views(queries, candidates, true, error);
-    if (status != swh_success_k) return status;
-    if ((status = topk_checks(e, s, k, call.pair.a_count, call.pair.b_count, indices, distances, error)) != swh_success_k) return status;
-    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
-    return topk_run(call.scope, (Engine *)e, call.pair, (uint32_t)k, bound, indices, distances, error);
-}
-
-// ---- range search (within.hip) ---------------------------------------------------------------------------------------------------------
-// Every candidate within `bound` of every query, as CSR, on the search planner's routes. Both count first, scan the counts into the row
-// offsets on the device, read the total (8 bytes) and fill only if the caller's arrays hold it.
-// STRINGWARS_AMD_WITHIN_PRUNE=0 (test library): the fused kernel walks every chunk, also those the length gap rules out
-static uint32_t within_prune() {
-    static const uint32_t on = [] { const char *e = test_hook("STRINGWARS_AMD_WITHIN_PRUNE"); return !e || atoi(e) != 0 ? 1u : 0u; }();
-    return on;
-}
-// STRINGWARS_AMD_WITHIN_ROUTE=select (test library): every search on the general path
-static bool within_force_select() {
-    static const bool on = [] { const char *e = test_hook("STRINGWARS_AMD_WITHIN_ROUTE"); return e && !strcmp(e, "select"); }();
-    return on;
-}
-// STRINGWARS_AMD_WITHIN_SLICES=n (test library): the fused kernel's candidate slices per query block (at most one per chunk)
-static uint64_t within_slices_hook() {
-    static const uint64_t n = [] { const char *e = test_hook("STRINGWARS_AMD_WITHIN_SLICES"); return e && atoll(e) > 0 ? (uint64_t)atoll(e) : 0; }();
-    return n;
-}
-
-struct WithinOutputs {
-    size_t *row_offsets;
-    uint32_t *indices, *distances;
-    size_t capacity;
-};
-
-static swh_status_t within_run(Scope *scope, const Engine *engine, const TapePair &p, uint32_t bound, const WithinOutputs &r, const char **error) {
-    static_assert(sizeof(size_t) == sizeof(uint64_t), "row offsets are scanned as 64-bit words");
-    return synchronous_run(scope, error, [&]() -> swh_status_t {
-        const uint64_t nq = p.a_count, nc = p.b_count;
-        SWH_HIP_CHECK(hipSetDevice(scope->device));
-        hipStream_t stream = scope->stream;
-        const bool dev_o = is_device_pointer(r.row_offsets), dev_i = is_device_pointer(r.indices), dev_d = is_device_pointer(r.distances);
-        if (nq == 0 || nc == 0) {   // no row, or every row empty
-            const size_t bytes = (nq + 1) * sizeof(size_t);
-            if (dev_o) {
-                SWH_HIP_CHECK(hipMemsetAsync(r.row_offsets, 0, bytes, stream));
-                SWH_HIP_CHECK(hipStreamSynchronize(stream));
-            } else {
-                memset(r.row_offsets, 0, bytes);
-            }
-            return swh_success_k;
-        }
-        const size_t ow = p.pa->off64 ? 8 : 4;
-        // the offsets are complete on the device: the total decides the fill, the rest goes to a host caller
-        auto read_total = [&](const uint64_t *offs) {
-            uint64_t total = 0;
-            SWH_HIP_CHECK(hipMemcpyAsync(&total, offs + nq, sizeof total, hipMemcpyDeviceToHost, stream));
-            SWH_HIP_CHECK(hipStreamSynchronize(stream));
-            return total;
-        };
-        auto finish_offsets = [&](const uint64_t *offs) {
-            if (!dev_o) SWH_HIP_CHECK(hipMemcpyAsync(r.row_offsets, offs, (nq + 1) * sizeof(size_t), hipMemcpyDeviceToHost, stream));
-        };
-        // where the fill pass writes: the caller's device arrays, or staging for its host arrays
-        uint32_t *ind = nullptr, *dist = nullptr;
-        auto stage_outputs = [&](uint64_t total) {
-            const size_t need = (dev_i ? 0 : pad(total * 4)) + (dev_d ? 0 : pad(total * 4));
-            ensure(scope->within_out, scope->within_out_bytes, need);
-            Carver oc{scope->within_out, 0, scope->within_out_bytes};
-            ind = dev_i ? r.indices : oc.take<uint32_t>(total);
-            dist = dev_d ? r.distances : oc.take<uint32_t>(total);
-        };
-        auto finish_outputs = [&](uint64_t total) {
-            if (!dev_i) SWH_HIP_CHECK(hipMemcpyAsync(r.indices, ind, total * 4, hipMemcpyDeviceToHost, stream));
-            if (!dev_d) SWH_HIP_CHECK(hipMemcpyAsync(r.distances, dist, total * 4, hipMemcpyDeviceToHost, stream));
-        };
-
-        if (search_is_fused(scope, engine, p, bound, within_force_select(), dev_i)) {
-            // ---- fused: a count (4 bytes) and a start (8) per (row, slice) ----------------------------------------------------------------
-            const SearchSlices cut = search_slices(nq, nc, scope->compute_units, 12, within_slices_hook());
-            const uint64_t slices = cut.slices;
-            const uint64_t n_counts = nq * slices, tiles = (n_counts + kWithinScanTile - 1) / kWithinScanTile;
-            const size_t need = pad(n_counts * 4) + pad(n_counts * 8) + pad(tiles * 8) + (dev_o ? 0 : pad((nq + 1) * 8));
-            ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
-            Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
-            WithinLaunch w{};
-            w.a = prepared_view(p.pa, false, p.a_first, nq); w.b = prepared_view(p.pb, false, p.b_first, nc);
-            w.off64 = p.pa->off64; w.slices = (uint32_t)slices; w.bound = bound; w.prune = within_prune(); w.slice_chunks = cut.slice_chunks;
-            w.counts = sc.take<uint32_t>(n_counts);
-            uint64_t *starts = sc.take<uint64_t>(n_counts), *block_sums = sc.take<uint64_t>(tiles);
-            uint64_t *offs = dev_o ? (uint64_t *)r.row_offsets : sc.take<uint64_t>(nq + 1);
-            w.starts = starts;
-            scope->summary_slot = 0;
-            launch_cross_within(scope, w, false);
-            launch_within_offsets(scope, w.counts, nq, (uint32_t)slices, block_sums, starts, offs);
-            const uint64_t total = read_total(offs);
-            const CallSummary sm = scope->summary_host[0];
-            if (!sm.violation) {
-                finish_offsets(offs);
-                if (total && total <= r.capacity) {
-                    stage_outputs(total);
-                    w.total = total; w.indices = ind; w.distances = dist;
-                    launch_cross_within(scope, w, true);
-                    finish_outputs(total);
-                }
-                SWH_HIP_CHECK(hipStreamSynchronize(stream));
-                if (scope->profiling && scope->stamps_used) {
-                    collect_timing(scope);
-                    // the search is named after its walk, also where a tiny call's scan takes longer: the longer of the two passes
-                    swh_timing_t &t = scope->last_timing;
-                    t.dominant_ms = 0;
-                    for (size_t i = 0; i < scope->stamps_used; ++i) {
-                        float ms = 0;
-                        if (!strcmp(scope->stamps[i].name, "cross_within")) (void)hipEventElapsedTime(&ms, scope->stamps[i].start, scope->stamps[i].stop);
-                        if (ms > t.dominant_ms) t.dominant_ms = ms;
-                    }
-                    snprintf(t.dominant_name, sizeof t.dominant_name, "cross_within");
-                    add_to_totals(scope->totals, scope->last_timing);
-                }
-                scope->last_timing.cells = sm.cells;
-                // the tapes, a count and a start per (row, slice), the row offsets and the hits
-                scope->last_timing.bytes = p.pa->total_bytes + p.pb->total_bytes + (nq + nc) * ow + n_counts * 12 + (nq + 1) * 8 +
-                                           (total <= r.capacity ? total * 8 : 0);
-                return swh_success_k;
-            }
-            // a string longer than the kernel takes (the memory of a prepared tape changed since it was measured): the general path
-            scope->stamps_used = 0;
-            scope->last_timing = swh_timing_t{};
-        }
-
-        // ---- general path: every block scored twice, once to count and once to fill -------------------------------------------------------
-        SearchSweep sweep(scope, engine, p, bound);
-        const uint64_t tiles = (nq + kWithinScanTile - 1) / kWithinScanTile;
-        const size_t need = pad(sweep.q_step * sweep.c_step * 4) + pad(nq * 4) + pad(nq * 8) + pad(tiles * 8) + (dev_o ? 0 : pad((nq + 1) * 8));
-        ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
-        Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
-        uint32_t *matrix = sc.take<uint32_t>(sweep.q_step * sweep.c_step);
-        uint32_t *counts = sc.take<uint32_t>(nq);
-        uint64_t *cursors = sc.take<uint64_t>(nq), *block_sums = sc.take<uint64_t>(tiles);
-        uint64_t *offs = dev_o ? (uint64_t *)r.row_offsets : sc.take<uint64_t>(nq + 1);
-        SWH_HIP_CHECK(hipMemsetAsync(counts, 0, nq * 4, stream));
-        auto no_rows_begin = [](uint64_t, uint64_t) {};   // (counts and cursors span all queries: nothing to open per block)
-        swh_status_t status = sweep.walk(matrix, true, error, no_rows_begin, [&](uint64_t q0, uint64_t rows, uint64_t, uint64_t columns, bool) {
-            launch_within_count(scope, matrix, rows, columns, bound, counts + q0);
-            sweep.time_own_kernels(1);
-        });
-        if (status != swh_success_k) return status;
-        launch_within_offsets(scope, counts, nq, 1, block_sums, cursors, offs);
-        sweep.time_own_kernels(2);
-        const uint64_t total = read_total(offs);
-        finish_offsets(offs);
-        if (total && total <= r.capacity) {
-            stage_outputs(total);
-            status = sweep.walk(matrix, false, error, no_rows_begin, [&](uint64_t q0, uint64_t rows, uint64_t c0, uint64_t columns, bool) {
-                launch_within_fill(scope, matrix, rows, columns, c0, bound, cursors + q0, total, ind, dist);
-                sweep.time_own_kernels(1);
-            });
-            if (status != swh_success_k) return status;
-            finish_outputs(total);
-        }
-        SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        sweep.close("within");
-        return swh_success_k;
-    });
-}
-
-static swh_status_t within_checks(swh_levenshtein_t e, swh_scope_t s, size_t candidates, uint32_t bound, const size_t *row_offsets,
-                                  const uint32_t *indices, const uint32_t *distances, size_t capacity, const char **error) {
-    if (!s || !e) return fail(error, swh_invalid_argument_k, "null scope or engine");
-    if (((Engine *)e)->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
-    if (bound == SWH_UNBOUNDED) return fail(error, swh_invalid_argument_k, "a range search needs a bound: without one it is the dense cross-product");
-    if (candidates >= 0xFFFFFFFFull) return fail(error, swh_unsupported_length_k, "2^32 - 1 candidates or more");
-    if (!row_offsets) return fail(error, swh_invalid_argument_k, "null row_offsets");
-    if (!indices != !distances) return fail(error, swh_invalid_argument_k, "indices and distances must both be given, or neither");
-    if (!indices && capacity) return fail(error, swh_invalid_argument_k, "a capacity without arrays: the counting call passes NULL, NULL, 0");
-    return swh_success_k;
-}
-
-static swh_status_t within_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *q, const swh_tape_u64_t *c, bool utf8, uint32_t bound,
-                                 const WithinOutputs &outs, const char **error) {
-    if (!q) return fail(error, swh_invalid_argument_k, "null tape");
-    const size_t candidates = (c ? c : q)->count;
-    swh_status_t status = within_checks(e, s, candidates, bound, outs.row_offsets, outs.indices, outs.distances, outs.capacity, error);
-    if (status != swh_success_k) return status;
-    TwoTapeCall call;
-    if ((status = call.begin(s, error)) != swh_success_k) return status;
-    // (a search without queries prepares nothing, one without candidates the queries alone: the offsets are still written)
-    if ((status = call.prepare(q, c, utf8, q->count != 0, q->count && candidates, error)) != swh_success_k) return status;
-    return within_run(call.scope, (Engine *)e, call.pair, bound, outs, error);
-}
-swh_status_t swh_levenshtein_within_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries, const swh_tape_u64_t *candidates,
-                                            uint32_t bound, size_t *row_offsets, uint32_t *indices, uint32_t *distances, size_t capacity,
-                                            const char **error) {
-    return within_tapes(e, s, queries, candidates, false, bound, WithinOutputs{row_offsets, indices, distances, capacity}, error);
-}
-swh_status_t swh_levenshtein_utf8_within_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries,
-                                                 const swh_tape_u64_t *candidates, uint32_t bound, size_t *row_offsets, uint32_t *indices,
-                                                 uint32_t *distances, size_t capacity, const char **error) {
-    return within_tapes(e, s, queries, candidates, true, bound, WithinOutputs{row_offsets, indices, distances, capacity}, error);
-}
-swh_status_t swh_levenshtein_within_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *queries,
-                                             const swh_prepared_view_t *candidates, uint32_t bound, size_t *row_offsets, uint32_t *indices,
-                                             uint32_t *distances, size_t capacity, const char **error) {
-    TwoTapeCall call;
-    swh_status_t status = call.views(queries, candidates, true, error);
-    if (status != swh_success_k) return status;
-    if ((status = within_checks(e, s, call.pair.b_count, bound, row_offsets, indices, distances, capacity, error)) != swh_success_k) return status;
-    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
-    return within_run(call.scope, (Engine *)e, call.pair, bound, WithinOutputs{row_offsets, indices, distances, capacity}, error);
-}
-
-// ---- alignments (align.hip) ----------------------------------------------------------------------------------------------------------
-// k_align_sizes measures the batch (stored bytes, symbols, cells, the first pair over SWH_ALIGN_MAX_CELLS) and the stored bytes and slot
-// sizes are scanned on the device; one read-back of the measurements decides the errors and the chunks, before any output is written.
-// Then per chunk of consecutive pairs the forward pass + walk (k_align), the counts scanned into the offsets, and k_align_emit places
-// the ops -- no host round trip between the forward pass and the outputs.
-// A chunk holds enough pairs to fill the device -- kAlignFillWaves waves per compute unit, a lane per pair -- and, beyond that, as many
-// as keep its stored delta vectors near 128 MiB, where the walk still reads the forward pass's stores from the Infinity Cache. Long
-// pairs therefore give up the residency rather than the parallelism (1 K protein pairs of 4 K symbols store 6 GB: one chunk).
-// STRINGWARS_AMD_ALIGN_CHUNK_KB=n (test library) sets the byte target and drops the fill minimum, to put many chunks in a small test.
-constexpr uint64_t kAlignFillWaves = 8;
-static const char *align_chunk_hook() {
-    static const char *e = test_hook("STRINGWARS_AMD_ALIGN_CHUNK_KB");
-    return e;
-}
-static uint64_t align_chunk_pairs(const Scope *scope, uint64_t count, uint64_t store_total) {
-    const char *hook = align_chunk_hook();
-    const uint64_t target = hook ? (uint64_t)atol(hook) << 10 : (uint64_t)128 << 20;
-    const uint64_t fill = hook ? 1 : (uint64_t)scope->compute_units * kAlignFillWaves * 64;
-    const uint64_t mean = std::max<uint64_t>(1, store_total / std::max<uint64_t>(count, 1));
-    uint64_t pairs = std::max<uint64_t>(fill, target / mean);
-    // no chunk asks for more than half the device memory that is free
-    size_t free_bytes = 0, total_bytes = 0;
-    if (hipMemGetInfo(&free_bytes, &total_bytes) == hipSuccess && free_bytes)
-        pairs = std::min<uint64_t>(pairs, std::max<uint64_t>(1, (uint64_t)(free_bytes / 2) / mean));
-    return std::max<uint64_t>(1, std::min<uint64_t>(pairs, count));
-}
-
-struct AlignOutputs {
-    uint32_t *distances;
-    uint64_t *offsets;
-    uint8_t *ops;
-    size_t capacity;
-};
-
-static swh_status_t align_run(Scope *scope, const TapePair &p, uint32_t bound, const AlignOutputs &r, const char **error) {
-    return synchronous_run(scope, error, [&]() -> swh_status_t {
-        const uint64_t count = p.a_count;
-        SWH_HIP_CHECK(hipSetDevice(scope->device));
-        hipStream_t stream = scope->stream;
-        const bool dev_d = is_device_pointer(r.distances), dev_o = is_device_pointer(r.offsets), dev_ops = is_device_pointer(r.ops);
-        if (count == 0) {
-            const uint64_t zero = 0;
-            if (dev_o) SWH_HIP_CHECK(hipMemcpyAsync(r.offsets, &zero, sizeof zero, hipMemcpyHostToDevice, stream)); else r.offsets[0] = 0;
-            SWH_HIP_CHECK(hipStreamSynchronize(stream));
-            return swh_success_k;
-        }
-        const bool cp = p.pa->utf8;
-        AlignTapes t{};
-        t.a = prepared_view(p.pa, cp, p.a_first, count);
-        t.b = prepared_view(p.pb, cp, p.b_first, count);
-        t.a_off64 = cp ? 1 : p.pa->off64;
-        t.b_off64 = cp ? 1 : p.pb->off64;
-        t.cp = cp ? 1 : 0;
-        t.count = count;
-
-        AlignScratch *sc_entry;
-        {
-            std::lock_guard<std::mutex> hold(g_align_scratch_lock);
-            sc_entry = &g_align_scratch[scope];
-        }
-        // fixed part: sizes | store_base | slot_base | counts | offsets | distances | scan partials
-        const size_t partial_words = align_scan_partials(count);
-        const size_t fixed = pad(sizeof(AlignSizes)) + 2 * pad((count + 1) * 8) + pad(count * 4) + (dev_o ? 0 : pad((count + 1) * 8)) +
-                             (dev_d ? 0 : pad(count * 4)) + pad(partial_words * 8);
-        ensure(sc_entry->buf, sc_entry->bytes, fixed);
-        Carver sc{sc_entry->buf, 0, sc_entry->bytes};
-        AlignSizes *sizes = sc.take<AlignSizes>(1);
-        uint64_t *store_base = sc.take<uint64_t>(count + 1), *slot_base = sc.take<uint64_t>(count + 1);
-        uint32_t *counts = sc.take<uint32_t>(count);
-        uint64_t *offsets = dev_o ? r.offsets : sc.take<uint64_t>(count + 1);
-        uint32_t *distances = dev_d ? r.distances : sc.take<uint32_t>(count);
-        uint64_t *partials = sc.take<uint64_t>(partial_words);
-
-        AlignSizes init{};
-        init.first_oversize = ~0ull;
-        SWH_HIP_CHECK(hipMemcpyAsync(sizes, &init, sizeof init, hipMemcpyHostToDevice, stream));
-        launch_align_sizes(scope, t, store_base, slot_base, sizes);
-        launch_align_scan(scope, store_base, count, partials);
-        launch_align_scan(scope, slot_base, count, partials);
-        AlignSizes got{};
-        SWH_HIP_CHECK(hipMemcpyAsync(&got, sizes, sizeof got, hipMemcpyDeviceToHost, stream));
-        SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        if (got.first_oversize != ~0ull) {
-            const size_t i = (size_t)got.first_oversize;
-            const uint64_t la = read_offset(t.a.offsets, t.a_off64, i + 1, true, stream) - read_offset(t.a.offsets, t.a_off64, i, true, stream);
-            const uint64_t lb = read_offset(t.b.offsets, t.b_off64, i + 1, true, stream) - read_offset(t.b.offsets, t.b_off64, i, true, stream);
-            scope->stamps_used = 0;
-            return fail(error, swh_unsupported_length_k, "pair %zu: %llu x %llu symbols exceeds SWH_ALIGN_MAX_CELLS (2^30 cells per pair)", i,
-                        (unsigned long long)la, (unsigned long long)lb);
-        }
-        if (r.capacity < got.symbols) {
-            scope->stamps_used = 0;
-            return fail(error, swh_invalid_argument_k, "ops_capacity %zu is below the %llu symbols of the two tapes", r.capacity,
-                        (unsigned long long)got.symbols);
-        }
-
-        // chunks of consecutive pairs; where they start in the storage space is read back (one strided copy) to size the largest
-        const uint64_t per_chunk = align_chunk_pairs(scope, count, got.store_total);
-        const uint64_t chunks = (count + per_chunk - 1) / per_chunk;
-        std::vector<uint64_t> starts(chunks + 1, 0);
-        if (chunks > 1) {
-            SWH_HIP_CHECK(hipMemcpy2DAsync(starts.data(), 8, store_base, per_chunk * 8, 8, chunks, hipMemcpyDeviceToHost, stream));
-            SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        }
-        starts[chunks] = got.store_total;
-        uint64_t widest = 0;
-        for (uint64_t q = 0; q < chunks; ++q) widest = std::max<uint64_t>(widest, starts[q + 1] - starts[q]);
-        // variable part: the op slots (whole batch) | staged ops for host outputs | the widest chunk of stored delta vectors
-        const size_t store_bytes = (size_t)widest;
-        const size_t need = fixed + pad(got.symbols + 16) + (dev_ops ? 0 : pad(got.symbols + 16)) + pad(store_bytes + 16);
-        if (need > sc_entry->bytes) {
-            // keep what the fixed part already holds: the measurements and scans live there
-            char *grown = nullptr;
-            const size_t want = need + need / 4 + (1 << 20);
-            SWH_HIP_CHECK(hipMalloc((void **)&grown, want));
-            SWH_HIP_CHECK(hipMemcpyAsync(grown, sc_entry->buf, fixed, hipMemcpyDeviceToDevice, stream));
-            SWH_HIP_CHECK(hipStreamSynchronize(stream));
-            SWH_HIP_CHECK(hipFree(sc_entry->buf));
-            sc_entry->buf = grown;
-            sc_entry->bytes = want;
-            sc = Carver{grown, 0, want};
-            sizes = sc.take<AlignSizes>(1);
-            store_base = sc.take<uint64_t>(count + 1); slot_base = sc.take<uint64_t>(count + 1);
-            counts = sc.take<uint32_t>(count);
-            offsets = dev_o ? r.offsets : sc.take<uint64_t>(count + 1);
-            distances = dev_d ? r.distances : sc.take<uint32_t>(count);
-            partials = sc.take<uint64_t>(partial_words);
-        }
-        uint8_t *slots = sc.take<uint8_t>(got.symbols + 16);
-        uint8_t *ops = dev_ops ? r.ops : sc.take<uint8_t>(got.symbols + 16);
-        char *store = sc.take<char>(store_bytes + 16);
-
-        AlignChunk c{};
-        c.store_base = store_base; c.slot_base = slot_base; c.store = store; c.slots = slots;
-        c.counts = counts; c.distances = distances; c.bound = bound;
-        for (uint64_t q = 0; q < chunks; ++q) {
-            c.pair_first = q * per_chunk;
-            c.pair_end = std::min<uint64_t>(count, (q + 1) * per_chunk);
-            c.store_first = starts[q];
-            launch_align_chunk(scope, t, c);
-        }
-        launch_align_scan_counts(scope, counts, offsets, count, partials);
-        launch_align_emit(scope, count, slot_base, counts, offsets, slots, ops);
-        if (!dev_d) SWH_HIP_CHECK(hipMemcpyAsync(r.distances, distances, count * 4, hipMemcpyDeviceToHost, stream));
-        if (!dev_o) SWH_HIP_CHECK(hipMemcpyAsync(r.offsets, offsets, (count + 1) * 8, hipMemcpyDeviceToHost, stream));
-        if (!dev_ops) {
-            uint64_t total_ops = 0;
-            SWH_HIP_CHECK(hipMemcpyAsync(&total_ops, offsets + count, 8, hipMemcpyDeviceToHost, stream));
-            SWH_HIP_CHECK(hipStreamSynchronize(stream));
-            if (total_ops) SWH_HIP_CHECK(hipMemcpyAsync(r.ops, ops, total_ops, hipMemcpyDeviceToHost, stream));
-        }
-        SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        if (scope->profiling && scope->stamps_used) {
-            collect_timing(scope);
-            add_to_totals(scope->totals, scope->last_timing);
-        }
-        scope->stamps_used = 0;
-        scope->last_timing.cells = got.cells;
-        scope->last_timing.bytes = (cp ? 4 : 1) * got.symbols + 2 * (count + 1) * 8 + count * 4 + got.symbols;
-        return swh_success_k;
-    });
-}
-
-static swh_status_t align_checks(swh_levenshtein_t e, swh_scope_t s, size_t a_count, size_t b_count, const uint32_t *distances,
-                                 const uint64_t *offsets, const uint8_t *ops, const char **error) {
-    if (!s || !e) return fail(error, swh_invalid_argument_k, "null scope or engine");
-    const Engine *engine = (const Engine *)e;
-    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
-    if (!engine->unit_costs) return fail(error, swh_not_implemented_k, "alignments need unit costs (match 0, mismatch 1, open 1, extend 1)");
-    if (a_count != b_count) return fail(error, swh_invalid_argument_k, "a and b must hold the same number of strings");
-    if (!offsets || (a_count && (!distances || !ops))) return fail(error, swh_invalid_argument_k, "null output pointer");
-    return swh_success_k;
-}
-
-static swh_status_t align_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, bool utf8, uint32_t bound,
-                                const AlignOutputs &outs, const char **error) {
-    if (!a || !b) return fail(error, swh_invalid_argument_k, "null tape");
-    swh_status_t status = align_checks(e, s, a->count, b->count, outs.distances, outs.offsets, outs.ops, error);
-    if (status != swh_success_k) return status;
-    TwoTapeCall call;
-    if ((status = call.begin(s, error)) != swh_success_k) return status;
-    const bool pairs = a->count != 0;
-    if ((status = call.prepare(a, b, utf8, pairs, pairs, error)) != swh_success_k) return status;
-    return align_run(call.scope, call.pair, bound, outs, error);
-}
-swh_status_t swh_levenshtein_align_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,
-                                           uint32_t *distances, size_t *ops_offsets, char *ops, size_t ops_capacity, const char **error) {
-    return align_tapes(e, s, a, b, false, bound, AlignOutputs{distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity}, error);
-}
-swh_status_t swh_levenshtein_utf8_align_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                                uint32_t bound, uint32_t *distances, size_t *ops_offsets, char *ops, size_t ops_capacity,
-                                                const char **error) {
-    return align_tapes(e, s, a, b, true, bound, AlignOutputs{distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity}, error);
-}
-swh_status_t swh_levenshtein_align_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
-                                            uint32_t bound, uint32_t *distances, size_t *ops_offsets, char *ops, size_t ops_capacity,
-                                            const char **error) {
-    const AlignOutputs outs{distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity};
-    TwoTapeCall call;
-    swh_status_t status = call.views(a, b, false, error);
-    if (status != swh_success_k) return status;
-    if ((status = align_checks(e, s, call.pair.a_count, call.pair.b_count, outs.distances, outs.offsets, outs.ops, error)) != swh_success_k) return status;
-    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
-    return align_run(call.scope, call.pair, bound, outs, error);
-}
-
-// ---- infix search (infix.hip) ---------------------------------------------------------------------------------------------------------
-// k_infix_sizes measures the batch (cells, the first pattern over SWH_INFIX_MAX_PATTERN) and cuts it into work items; one read-back of
-// the measurements decides the errors before any output is written. Then the forward pass (distance and end of every pair) and the
-// start pass (the starts, the bound) over the same items, and the copy-out of outputs that live on the host. The scratch -- the item
-// list and, for host outputs, the three result arrays -- is the scope's alignment scratch: both calls are synchronous.
-struct InfixOutputs { uint32_t *distances, *starts, *ends; };
-
-static swh_status_t infix_run(Scope *scope, const TapePair &p, uint32_t bound, const InfixOutputs &r, const char **error) {
-    return synchronous_run(scope, error, [&]() -> swh_status_t {
-        const uint64_t count = p.a_count;
-        if (count == 0) return swh_success_k;
-        SWH_HIP_CHECK(hipSetDevice(scope->device));
-        hipStream_t stream = scope->stream;
-        const bool dev_d = is_device_pointer(r.distances), dev_s = is_device_pointer(r.starts), dev_e = is_device_pointer(r.ends);
-        const bool cp = p.pa->utf8;
-        InfixTapes t{};
-        t.patterns = prepared_view(p.pa, cp, p.a_first, count);
-        t.texts = prepared_view(p.pb, cp, p.b_first, count);
-        t.p_off64 = cp ? 1 : p.pa->off64;
-        t.t_off64 = cp ? 1 : p.pb->off64;
-        t.cp = cp ? 1 : 0;
-        t.count = count;
-
-        AlignScratch *sc_entry;
-        {
-            std::lock_guard<std::mutex> hold(g_align_scratch_lock);
-            sc_entry = &g_align_scratch[scope];
-        }
-        // sizes | items | distances | starts | ends (the last three only where the caller's array lives on the host)
-        const size_t need = pad(sizeof(InfixSizes)) + pad(count * sizeof(LaneItem)) + ((dev_d ? 0 : 1) + (dev_s ? 0 : 1) + (dev_e ? 0 : 1)) * pad(count * 4);
-        ensure(sc_entry->buf, sc_entry->bytes, need);
-        Carver sc{sc_entry->buf, 0, sc_entry->bytes};
-        InfixSizes *sizes = sc.take<InfixSizes>(1);
-        LaneItem *items = sc.take<LaneItem>(count);
-        uint32_t *distances = dev_d ? r.distances : sc.take<uint32_t>(count);
-        uint32_t *starts = dev_s ? r.starts : sc.take<uint32_t>(count);
-        uint32_t *ends = dev_e ? r.ends : sc.take<uint32_t>(count);
-
-        InfixSizes init{};
-        init.first_oversize = ~0ull;
-        SWH_HIP_CHECK(hipMemcpyAsync(sizes, &init, sizeof init, hipMemcpyHostToDevice, stream));
-        launch_infix_sizes(scope, t, sizes, items);
-        InfixSizes got{};
-        SWH_HIP_CHECK(hipMemcpyAsync(&got, sizes, sizeof got, hipMemcpyDeviceToHost, stream));
-        SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        if (got.first_oversize != ~0ull) {
-            const size_t i = (size_t)got.first_oversize;
-            const uint64_t m = read_offset(t.patterns.offsets, t.p_off64, i + 1, true, stream) - read_offset(t.patterns.offsets, t.p_off64, i, true, stream);
-            scope->stamps_used = 0;
-            return fail(error, swh_unsupported_length_k, "pair %zu: a pattern of %llu symbols exceeds SWH_INFIX_MAX_PATTERN (2048)", i,
-                        (unsigned long long)m);
-        }
-
-        InfixRun run{};
-        run.items = items; run.item_count = got.items;
-        run.distances = distances; run.starts = starts; run.ends = ends;
-        run.bound = bound;
-        run.wide_text = !cp && got.text_symbols >= 16;
-        launch_infix_forward(scope, t, run);
-        launch_infix_starts(scope, t, run);
-        if (!dev_d) SWH_HIP_CHECK(hipMemcpyAsync(r.distances, distances, count * 4, hipMemcpyDeviceToHost, stream));
-        if (!dev_s) SWH_HIP_CHECK(hipMemcpyAsync(r.starts, starts, count * 4, hipMemcpyDeviceToHost, stream));
-        if (!dev_e) SWH_HIP_CHECK(hipMemcpyAsync(r.ends, ends, count * 4, hipMemcpyDeviceToHost, stream));
-        SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        if (scope->profiling && scope->stamps_used) {
-            collect_timing(scope);
-            add_to_totals(scope->totals, scope->last_timing);
-        }
-        scope->stamps_used = 0;
-        scope->last_timing.cells = got.cells;
-        scope->last_timing.bytes = (cp ? 4 : 1) * got.symbols + 2 * (count + 1) * 8 + 3 * count * 4;
-        return swh_success_k;
-    });
-}
-
-// no scope or engine can exist without a device: a call that gets a null handle says so where there is none, as scope creation does
-// (infix search and the scored families ask; top-k, within and align answer "null scope or engine" without the probe)
-static swh_status_t probe_null_handles(swh_levenshtein_t e, swh_scope_t s, const char **error) {
-    if (s && e) return swh_success_k;
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0) {
-        (void)hipGetLastError();
-        return fail(error, swh_no_device_k, "no HIP device visible (this backend has no CPU path)");
-    }
-    return fail(error, swh_invalid_argument_k, "null scope or engine");
-}
-static swh_status_t infix_checks(swh_levenshtein_t e, swh_scope_t s, size_t p_count, size_t t_count, const uint32_t *distances,
-                                 const uint32_t *starts, const uint32_t *ends, const char **error) {
-    const Engine *engine = (const Engine *)e;
-    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
-    if (!engine->unit_costs) return fail(error, swh_not_implemented_k, "infix search needs unit costs (match 0, mismatch 1, open 1, extend 1)");
-    if (p_count != t_count) return fail(error, swh_invalid_argument_k, "patterns and texts must hold the same number of strings");
-    if (p_count && (!distances || !starts || !ends)) return fail(error, swh_invalid_argument_k, "null output pointer");
-    return swh_success_k;
-}
-
-static swh_status_t infix_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts, bool utf8,
-                                uint32_t bound, const InfixOutputs &outs, const char **error) {
-    swh_status_t status = probe_null_handles(e, s, error);
-    if (status != swh_success_k) return status;
-    if (!patterns || !texts) return fail(error, swh_invalid_argument_k, "null tape");
-    status = infix_checks(e, s, patterns->count, texts->count, outs.distances, outs.starts, outs.ends, error);
-    if (status != swh_success_k) return status;
-    TwoTapeCall call;
-    if ((status = call.begin(s, error)) != swh_success_k) return status;
-    const bool pairs = patterns->count != 0;
-    if ((status = call.prepare(patterns, texts, utf8, pairs, pairs, error)) != swh_success_k) return status;
-    return infix_run(call.scope, call.pair, bound, outs, error);
-}
-swh_status_t swh_levenshtein_infix_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts,
-                                           uint32_t bound, uint32_t *distances, uint32_t *starts, uint32_t *ends, const char **error) {
-    return infix_tapes(e, s, patterns, texts, false, bound, InfixOutputs{distances, starts, ends}, error);
-}
-swh_status_t swh_levenshtein_utf8_infix_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts,
-                                                uint32_t bound, uint32_t *distances, uint32_t *starts, uint32_t *ends, const char **error) {
-    return infix_tapes(e, s, patterns, texts, true, bound, InfixOutputs{distances, starts, ends}, error);
-}
-swh_status_t swh_levenshtein_infix_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *patterns,
-                                            const swh_prepared_view_t *texts, uint32_t bound, uint32_t *distances, uint32_t *starts,
-                                            uint32_t *ends, const char **error) {
-    swh_status_t status = probe_null_handles(e, s, error);
-    if (status != swh_success_k) return status;
-    TwoTapeCall call;
-    if ((status = call.views(patterns, texts, false, error)) != swh_success_k) return status;
-    if ((status = infix_checks(e, s, call.pair.a_count, call.pair.b_count, distances, starts, ends, error)) != swh_success_k) return status;
-    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
-    return infix_run(call.scope, call.pair, bound, InfixOutputs{distances, starts, ends}, error);
-}
-
-// ---- OSA distances, LCS lengths / Indel distances, Jaro counts (osa.hip, lcs.hip, jaro.hip): one planner --------------------------------
-// The three families score pairs on the same phases. A sizes kernel measures the pairs (cells, symbols, the first pair over the
-// family's length limit) and cuts them into work items; one read-back of the measurements decides the errors before any output is
-// written; the family's kernel scores the items and writes whichever of its outputs the caller asked for. A pairwise call is one such
-// round. A cross-product maps pair p to (p / nb, p % nb) and runs in slices of whole rows of about kScoredChunkPairs pairs -- the item
-// list and, per output that lives on the host, the staged slice are all the scratch there is, whatever the matrix size; with more
-// than one slice the whole matrix is measured first (no items), so that a refusal still comes before the first row is written. The
-// family's test hook (test library) lowers the slice, to put many of them in a small test. The scratch is the scope's alignment
-// scratch: the calls are synchronous, and they learn nothing into the scope.
-// What a family brings is its ScoredFamily: the two launchers, its words, and the few argument rules that differ.
-//  - OSA: k_osa_sizes cuts the items by the blocks of a pair's shorter string, which holds at most SWH_OSA_MAX_SHORTER symbols; one output.
-//  - LCS / Indel: OSA's sizes kernel and limit as they stand (SWH_LCS_MAX_SHORTER); two outputs, indel and lcs.
-//  - Jaro: k_jaro_sizes cuts the items by the blocks of b, and neither string holds more than SWH_JARO_MAX_LENGTH symbols; three
-//    outputs, matches, transpositions and prefix, and the only family that holds strides to multiples of the element.
-constexpr uint64_t kScoredChunkPairs = (uint64_t)1 << 21;
-constexpr int kScoredOutputs = 3;
-
-struct ScoredFamily {
-    int outputs;   // of kScoredOutputs
-    void (*sizes)(Scope *scope, const OsaTapes &t, OsaSizes *sizes, LaneItem *items);
-    // scores the items into where[0 .. outputs), null where an output is not written by this launch, all at `stride`
-    void (*launch)(Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride,
-                   uint32_t bound, bool wide);
-    const char *chunk_hook;      // the test hook that lowers the slice
-    const char *oversize;        // how the refusal of a pair over the length limit ends
-    const char *unit_costs;      // the refusal of a general-cost engine
-    const char *null_outputs;    // the refusal of a call that wants no output ...
-    bool null_outputs_on_empty;  // ... which a call without pairs meets too
-    bool element_strides;        // strides are multiples of the element (4 bytes pairwise, 8 cross), not merely large enough
-};
-
-static const ScoredFamily kOsaFamily = {
-    1, launch_osa_sizes,
-    [](Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
-       bool wide) {
-        OsaRun run{};
-        run.items = items; run.item_count = item_count;
-        run.out = where[0];
-        run.stride = stride; run.bound = bound; run.wide = wide;
-        launch_osa(scope, t, run);
-    },
-    "STRINGWARS_AMD_OSA_CHUNK_PAIRS", "the shorter string exceeds SWH_OSA_MAX_SHORTER (2048)",
-    "OSA distances need unit costs (match 0, mismatch 1, open 1, extend 1)", "null output pointer", false, false};
-static const ScoredFamily kLcsFamily = {
-    2, launch_osa_sizes,
-    [](Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
-       bool wide) {
-        LcsRun run{};
-        run.items = items; run.item_count = item_count;
-        run.indel = where[0]; run.lcs = where[1];
-        run.stride = stride; run.bound = bound; run.wide = wide;
-        launch_lcs(scope, t, run);
-    },
-    "STRINGWARS_AMD_LCS_CHUNK_PAIRS", "the shorter string exceeds SWH_LCS_MAX_SHORTER (2048)",
-    "LCS lengths and Indel distances are called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)",
-    "null output pointers: one of indel and lcs is needed", true, false};
-static const ScoredFamily kJaroFamily = {
-    3, launch_jaro_sizes,
-    [](Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t,
-       bool wide) {
-        JaroRun run{};
-        run.items = items; run.item_count = item_count;
-        run.matches = where[0]; run.transpositions = where[1]; run.prefix = where[2];
-        run.stride = stride; run.wide = wide;
-        launch_jaro(scope, t, run);
-    },
-    "STRINGWARS_AMD_JARO_CHUNK_PAIRS", "a string exceeds SWH_JARO_MAX_LENGTH (2048)",
-    "Jaro and Jaro-Winkler counts are called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)",
-    "null output pointers: one of matches, transpositions and prefix is needed", true, true};
-
-static uint64_t scored_chunk_pairs(const ScoredFamily &f) {
-    const char *hook = test_hook(f.chunk_hook);
-    const uint64_t pairs = hook ? (uint64_t)atoll(hook) : kScoredChunkPairs;
-    return std::max<uint64_t>(1, std::min<uint64_t>(pairs, kScoredChunkPairs));
-}
-
-struct ScoredRequest {
-    bool cross;
-    uint32_t bound;
-    void *outs[kScoredOutputs];   // the family's outputs in the order of its exports: any may be null, those past its count are
-    size_t stride;                // bytes between consecutive results (pairs) or rows (cross), of every output
-};
-
-static swh_status_t scored_run(Scope *scope, const ScoredFamily &f, const TapePair &p, const ScoredRequest &r, const char **error) {
-    return synchronous_run(scope, error, [&]() -> swh_status_t {
-        const uint64_t na = p.a_count, nb = p.b_count;
-        if (na == 0 || nb == 0) return swh_success_k;
-        if (r.cross && na > ((uint64_t)1 << 40) / nb) return fail(error, swh_unsupported_length_k, "more than 2^40 pairs in one call");
-        const uint64_t total = r.cross ? na * nb : na;
-        SWH_HIP_CHECK(hipSetDevice(scope->device));
-        hipStream_t stream = scope->stream;
-        bool stage[kScoredOutputs];
-        size_t staged_count = 0, wanted = 0;
-        for (int k = 0; k < f.outputs; ++k) {
-            stage[k] = r.outs[k] && !is_device_pointer(r.outs[k]);
-            staged_count += stage[k] ? 1 : 0;
-            wanted += r.outs[k] ? 1 : 0;
-        }
-        const bool cp = p.pa->utf8;
-        OsaTapes t{};
-        t.a = prepared_view(p.pa, cp, p.a_first, na);
-        t.b = prepared_view(p.pb, cp, p.b_first, nb);
-        t.a_off64 = cp ? 1 : p.pa->off64;
-        t.b_off64 = cp ? 1 : p.pb->off64;
-        t.cp = cp ? 1 : 0;
-        t.nb = r.cross ? nb : 0;
-
-        // slices: all pairs of a pairwise call; whole rows of a cross-product
-        const uint64_t rows_per_slice = r.cross ? std::max<uint64_t>(1, scored_chunk_pairs(f) / nb) : na;
-        const uint64_t slices = (na + rows_per_slice - 1) / rows_per_slice;
-        const uint64_t slice_pairs = r.cross ? std::min<uint64_t>(rows_per_slice, na) * nb : na;
-        const size_t width = r.cross ? 8 : 4;
-
-        AlignScratch *sc_entry;
-        {
-            std::lock_guard<std::mutex> hold(g_align_scratch_lock);
-            sc_entry = &g_align_scratch[scope];
-        }
-        // sizes | items | the slice's results (one array per output that lives on the host)
-        const size_t need = pad(sizeof(OsaSizes)) + pad(slice_pairs * sizeof(LaneItem)) + staged_count * pad(slice_pairs * width);
-        ensure(sc_entry->buf, sc_entry->bytes, need);
-        Carver sc{sc_entry->buf, 0, sc_entry->bytes};
-        OsaSizes *sizes = sc.take<OsaSizes>(1);
-        LaneItem *items = sc.take<LaneItem>(slice_pairs);
-        char *staged[kScoredOutputs];
-        for (int k = 0; k < f.outputs; ++k) staged[k] = stage[k] ? sc.take<char>(slice_pairs * width) : nullptr;
-
-        // measures pairs [row0 .. row0 + rows) x nb (or all pairs of a pairwise call) and, with `cut`, cuts them into `items`
-        auto measure = [&](uint64_t row0, uint64_t pairs, bool cut) {
-            OsaSizes init{};
-            init.first_oversize = ~0ull;
-            SWH_HIP_CHECK(hipMemcpyAsync(sizes, &init, sizeof init, hipMemcpyHostToDevice, stream));
-            t.row0 = row0; t.count = pairs;
-            f.sizes(scope, t, sizes, cut ? items : nullptr);
-            OsaSizes got{};
-            SWH_HIP_CHECK(hipMemcpyAsync(&got, sizes, sizeof got, hipMemcpyDeviceToHost, stream));
-            SWH_HIP_CHECK(hipStreamSynchronize(stream));
-            return got;
-        };
-        const OsaSizes whole = measure(0, total, slices == 1);
-        if (whole.first_oversize != ~0ull) {
-            const size_t i = (size_t)(r.cross ? whole.first_oversize / nb : whole.first_oversize);
-            const size_t j = (size_t)(r.cross ? whole.first_oversize % nb : whole.first_oversize);
-            const uint64_t la = read_offset(t.a.offsets, t.a_off64, i + 1, true, stream) - read_offset(t.a.offsets, t.a_off64, i, true, stream);
-            const uint64_t lb = read_offset(t.b.offsets, t.b_off64, j + 1, true, stream) - read_offset(t.b.offsets, t.b_off64, j, true, stream);
-            scope->stamps_used = 0;
-            if (r.cross)
-                return fail(error, swh_unsupported_length_k, "pair (%zu, %zu): %llu x %llu symbols, %s", i, j, (unsigned long long)la,
-                            (unsigned long long)lb, f.oversize);
-            return fail(error, swh_unsupported_length_k, "pair %zu: %llu x %llu symbols, %s", i, (unsigned long long)la, (unsigned long long)lb,
-                        f.oversize);
-        }
-
-        const bool wide = !cp && whole.a_total >= 16 && whole.b_total >= 16;
-        // the kernel writes its outputs at one stride: the caller's for those written in place, the packed one for those that are
-        // staged; a call with outputs of both kinds runs the slice once per kind
-        for (uint64_t q = 0; q < slices; ++q) {
-            const uint64_t row0 = q * rows_per_slice, rows = std::min<uint64_t>(rows_per_slice, na - row0);
-            const uint64_t pairs = r.cross ? rows * nb : na;
-            const uint64_t item_count = slices == 1 ? whole.items : measure(row0, pairs, true).items;
-            t.row0 = row0; t.count = pairs;
-            for (int packed = 0; packed < 2; ++packed) {
-                char *where[kScoredOutputs] = {};
-                bool any = false;
-                for (int k = 0; k < f.outputs; ++k) {
-                    if (!r.outs[k] || stage[k] != (packed == 1)) continue;
-                    where[k] = packed ? staged[k] : (char *)r.outs[k] + (r.cross ? row0 * r.stride : 0);
-                    any = true;
-                }
-                if (any) f.launch(scope, t, items, item_count, where, packed ? (r.cross ? nb * 8 : 4) : r.stride, r.bound, wide);
-            }
-            for (int k = 0; k < f.outputs; ++k) {
-                if (!stage[k]) continue;
-                if (r.cross)
-                    SWH_HIP_CHECK(hipMemcpy2DAsync((char *)r.outs[k] + row0 * r.stride, r.stride, staged[k], nb * 8, nb * 8, rows, hipMemcpyDeviceToHost, stream));
-                else if (r.stride == 4)
-                    SWH_HIP_CHECK(hipMemcpyAsync(r.outs[k], staged[k], pairs * 4, hipMemcpyDeviceToHost, stream));
-                else
-                    SWH_HIP_CHECK(hipMemcpy2DAsync(r.outs[k], r.stride, staged[k], 4, 4, pairs, hipMemcpyDeviceToHost, stream));
-            }
-            if (staged_count) SWH_HIP_CHECK(hipStreamSynchronize(stream));   // the next slice reuses the staging
-        }
-        SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        if (scope->profiling && scope->stamps_used) {
-            collect_timing(scope);
-            add_to_totals(scope->totals, scope->last_timing);
-        }
-        scope->stamps_used = 0;
-        scope->last_timing.cells = whole.cells;
-        scope->last_timing.bytes = (cp ? 4 : 1) * whole.symbols + (na + nb + 2) * 8 + total * width * wanted;
-        return swh_success_k;
-    });
-}
-
-// the argument rules; a stride of 0 becomes the packed one
-static swh_status_t scored_checks(const ScoredFamily &f, swh_levenshtein_t e, size_t a_count, size_t b_count, bool cross,
-                                  void *const (&outs)[kScoredOutputs], size_t &stride, const char **error) {
-    const Engine *engine = (const Engine *)e;
-    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
-    if (!engine->unit_costs) return fail(error, swh_not_implemented_k, "%s", f.unit_costs);
-    if (!cross && a_count != b_count) return fail(error, swh_invalid_argument_k, "a and b must hold the same number of strings");
-    bool wanted = false;
-    for (int k = 0; k < f.outputs; ++k) wanted = wanted || outs[k];
-    if (!wanted && (f.null_outputs_on_empty || (a_count && b_count))) return fail(error, swh_invalid_argument_k, "%s", f.null_outputs);
-    if (cross) {
-        if (!stride) stride = b_count * 8;
-        if (f.element_strides && stride % 8) return fail(error, swh_invalid_argument_k, "row_stride_bytes must be 0 or a multiple of 8");
-        if (stride < b_count * 8) return fail(error, swh_invalid_argument_k, "row_stride_bytes too small");
-    } else {
-        if (!stride) stride = 4;
-        if (f.element_strides && stride % 4) return fail(error, swh_invalid_argument_k, "out_stride_bytes must be 0 or a multiple of 4");
-        if (stride < 4) return fail(error, swh_invalid_argument_k, "out_stride_bytes must be >= 4");
-    }
-    return swh_success_k;
-}
-
-static swh_status_t scored_tapes(const ScoredFamily &f, swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                 bool utf8, bool cross, uint32_t bound, void *const (&outs)[kScoredOutputs], size_t stride, const char **error) {
-    swh_status_t status = probe_null_handles(e, s, error);
-    if (status != swh_success_k) return status;
-    if (!a || (!b && !cross)) return fail(error, swh_invalid_argument_k, "null tape");
-    const size_t b_count = (b ? b : a)->count;   // a cross-product without b: the self-product
-    status = scored_checks(f, e, a->count, b_count, cross, outs, stride, error);
-    if (status != swh_success_k) return status;
-    TwoTapeCall call;
-    if ((status = call.begin(s, error)) != swh_success_k) return status;
-    const bool pairs = a->count && b_count;
-    if ((status = call.prepare(a, b, utf8, pairs, pairs, error)) != swh_success_k) return status;
-    return scored_run(call.scope, f, call.pair, ScoredRequest{cross, bound, {outs[0], outs[1], outs[2]}, stride}, error);
-}
-static swh_status_t scored_prepared(const ScoredFamily &f, swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a,
-                                    const swh_prepared_view_t *b, bool cross, uint32_t bound, void *const (&outs)[kScoredOutputs], size_t stride,
-                                    const char **error) {
-    swh_status_t status = probe_null_handles(e, s, error);
-    if (status != swh_success_k) return status;
-    TwoTapeCall call;
-    if ((status = call.views(a, b, cross, error)) != swh_success_k) return status;
-    if ((status = scored_checks(f, e, call.pair.a_count, call.pair.b_count, cross, outs, stride, error)) != swh_success_k) return status;
-    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
-    return scored_run(call.scope, f, call.pair, ScoredRequest{cross, bound, {outs[0], outs[1], outs[2]}, stride}, error);
-}
-
-swh_status_t swh_levenshtein_osa_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,
-                                               uint32_t *out, size_t stride, const char **error) {
-    return scored_tapes(kOsaFamily, e, s, a, b, false, false, bound, {out}, stride, error);
-}
-swh_status_t swh_levenshtein_utf8_osa_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                                    uint32_t bound, uint32_t *out, size_t stride, const char **error) {
-    return scored_tapes(kOsaFamily, e, s, a, b, true, false, bound, {out}, stride, error);
-}
-swh_status_t swh_levenshtein_osa_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
-                                                uint32_t bound, uint32_t *out, size_t stride, const char **error) {
-    return scored_prepared(kOsaFamily, e, s, a, b, false, bound, {out}, stride, error);
-}
-swh_status_t swh_levenshtein_osa_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, size_t *out,
-                                               size_t row_stride, const char **error) {
-    return scored_tapes(kOsaFamily, e, s, a, b, false, true, SWH_UNBOUNDED, {out}, row_stride, error);
-}
-swh_status_t swh_levenshtein_utf8_osa_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                                    size_t *out, size_t row_stride, const char **error) {
-    return scored_tapes(kOsaFamily, e, s, a, b, true, true, SWH_UNBOUNDED, {out}, row_stride, error);
-}
-swh_status_t swh_levenshtein_osa_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
-                                                size_t *out, size_t row_stride, const char **error) {
-    return scored_prepared(kOsaFamily, e, s, a, b, true, SWH_UNBOUNDED, {out}, row_stride, error);
-}
-
-swh_status_t swh_levenshtein_lcs_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,
-                                               uint32_t *indel, uint32_t *lcs, size_t stride, const char **error) {
-    return scored_tapes(kLcsFamily, e, s, a, b, false, false, bound, {indel, lcs}, stride, error);
-}
-swh_status_t swh_levenshtein_utf8_lcs_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                                    uint32_t bound, uint32_t *indel, uint32_t *lcs, size_t stride, const char **error) {
-    return scored_tapes(kLcsFamily, e, s, a, b, true, false, bound, {indel, lcs}, stride, error);
-}
-swh_status_t swh_levenshtein_lcs_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
-                                                uint32_t bound, uint32_t *indel, uint32_t *lcs, size_t stride, const char **error) {
-    return scored_prepared(kLcsFamily, e, s, a, b, false, bound, {indel, lcs}, stride, error);
-}
-swh_status_t swh_levenshtein_lcs_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, size_t *indel,
-                                               size_t *lcs, size_t row_stride, const char **error) {
-    return scored_tapes(kLcsFamily, e, s, a, b, false, true, SWH_UNBOUNDED, {indel, lcs}, row_stride, error);
-}
-swh_status_t swh_levenshtein_utf8_lcs_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                                    size_t *indel, size_t *lcs, size_t row_stride, const char **error) {
-    return scored_tapes(kLcsFamily, e, s, a, b, true, true, SWH_UNBOUNDED, {indel, lcs}, row_stride, error);
-}
-swh_status_t swh_levenshtein_lcs_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
-                                                size_t *indel, size_t *lcs, size_t row_stride, const char **error) {
-    return scored_prepared(kLcsFamily, e, s, a, b, true, SWH_UNBOUNDED, {indel, lcs}, row_stride, error);
-}
-
-// (the Jaro kernel takes no bound)
-swh_status_t swh_levenshtein_jaro_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                                uint32_t *matches, uint32_t *transpositions, uint32_t *prefix, size_t stride, const char **error) {
-    return scored_tapes(kJaroFamily, e, s, a, b, false, false, SWH_UNBOUNDED, {matches, transpositions, prefix}, stride, error);
-}
-swh_status_t swh_levenshtein_utf8_jaro_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                                     uint32_t *matches, uint32_t *transpositions, uint32_t *prefix, size_t stride, const char **error) {
-    return scored_tapes(kJaroFamily, e, s, a, b, true, false, SWH_UNBOUNDED, {matches, transpositions, prefix}, stride, error);
-}
-swh_status_t swh_levenshtein_jaro_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
-                                                 uint32_t *matches, uint32_t *transpositions, uint32_t *prefix, size_t stride, const char **error) {
-    return scored_prepared(kJaroFamily, e, s, a, b, false, SWH_UNBOUNDED, {matches, transpositions, prefix}, stride, error);
-}
-swh_status_t swh_levenshtein_jaro_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                                size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
-    return scored_tapes(kJaroFamily, e, s, a, b, false, true, SWH_UNBOUNDED, {matches, transpositions, prefix}, row_stride, error);
-}
-swh_status_t swh_levenshtein_utf8_jaro_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
-                                                     size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
-    return scored_tapes(kJaroFamily, e, s, a, b, true, true, SWH_UNBOUNDED, {matches, transpositions, prefix}, row_stride, error);
-}
-swh_status_t swh_levenshtein_jaro_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
-                                                 size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
-    return scored_prepared(kJaroFamily, e, s, a, b, true, SWH_UNBOUNDED, {matches, transpositions, prefix}, row_stride, error);
-}
-
-// ---- score search (extract.hip): the k best candidates by an OSA, Indel, LCS, ratio, Jaro or Jaro-Winkler score ------------------------
-// topk_run's general path with the three families as the scorers: query blocks x candidate slices of at most kScoredChunkPairs
-// pairs, each slice measured and cut into items by the family's sizes kernel, scored by its launcher into dense u64 counts in scratch
-// (the candidates' slice is a view of the prepared tape: pair p of the launch is (p / columns, p % columns)) and folded into the
-// block's running lists by k_extract_select, which evaluates the float64 score. The scratch is the slice's items and counts, the
-// block's lists and, for outputs in host memory, the rows: nothing grows with queries x candidates. Both length limits follow from
-// the two tapes' own lengths, so one pass over their offsets refuses the call before anything is scored or written.
-// STRINGWARS_AMD_EXTRACT_CHUNK_PAIRS (test library) lowers the slice, to put several blocks and slices into a small test.
-static uint64_t extract_chunk_pairs() {
-    const char *hook = test_hook("STRINGWARS_AMD_EXTRACT_CHUNK_PAIRS");
-    const uint64_t pairs = hook ? (uint64_t)atoll(hook) : kScoredChunkPairs;
-    return std::max<uint64_t>(1, std::min<uint64_t>(pairs, kScoredChunkPairs));
-}
-
-struct ExtractRequest {
-    int scorer;
-    uint32_t k;
-    double cutoff, prefix_weight;
-    uint32_t *indices;
-    void *scores;
-};
-
-static swh_status_t extract_run(Scope *scope, const TapePair &p, const ExtractRequest &r, const char **error) {
-    return synchronous_run(scope, error, [&]() -> swh_status_t {
-        const uint64_t nq = p.a_count, nc = p.b_count, k = r.k;
-        if (nq == 0) return swh_success_k;
-        const size_t index_bytes = nq * k * sizeof(uint32_t), score_bytes = nq * k * sizeof(uint64_t);
-        SWH_HIP_CHECK(hipSetDevice(scope->device));
-        hipStream_t stream = scope->stream;
-        const bool dev_i = is_device_pointer(r.indices), dev_s = is_device_pointer(r.scores);
-        if (nc == 0) {   // every row is padding
-            if (dev_i) SWH_HIP_CHECK(hipMemsetAsync(r.indices, 0xFF, index_bytes, stream)); else memset(r.indices, 0xFF, index_bytes);
-            if (dev_s) SWH_HIP_CHECK(hipMemsetAsync(r.scores, 0xFF, score_bytes, stream)); else memset(r.scores, 0xFF, score_bytes);
-            SWH_HIP_CHECK(hipStreamSynchronize(stream));
-            return swh_success_k;
-        }
-        const bool jaro = r.scorer >= SWH_SCORER_JARO;
-        const ScoredFamily &f = r.scorer == SWH_SCORER_OSA ? kOsaFamily : (jaro ? kJaroFamily : kLcsFamily);
-        const int counts = r.scorer == SWH_SCORER_JARO_WINKLER ? 3 : (jaro ? 2 : 1);
-        const bool cp = p.pa->utf8;
-        const uint32_t a_off64 = cp ? 1 : p.pa->off64, b_off64 = cp ? 1 : p.pb->off64;
-        const TapeRef queries = prepared_view(p.pa, cp, p.a_first, nq), candidates = prepared_view(p.pb, cp, p.b_first, nc);
-
-        // query blocks of at most 4096 rows x candidate slices, at least 64 columns wide where the slice allows it
-        const uint64_t chunk = extract_chunk_pairs();
-        const uint64_t q_step = std::min<uint64_t>(nq, std::max<uint64_t>(1, std::min<uint64_t>(4096, chunk >> 6)));
-        const uint64_t c_step = std::max<uint64_t>(1, std::min<uint64_t>(nc, chunk / q_step));
-        const uint64_t slice_pairs = q_step * c_step;
-
-        // first over-long strings | sizes | items | the slice's counts | the block's lists | rows bound for the host
-        const size_t need = pad(2 * sizeof(unsigned long long)) + pad(sizeof(OsaSizes)) + pad(slice_pairs * sizeof(LaneItem)) +
-                            counts * pad(slice_pairs * 8) + pad(q_step * k * 16) + (dev_i ? 0 : pad(index_bytes)) + (dev_s ? 0 : pad(score_bytes));
-        ensure(scope->topk_scratch, scope->topk_scratch_bytes, need);
-        Carver sc{scope->topk_scratch, 0, scope->topk_scratch_bytes};
-        unsigned long long *first_over = sc.take<unsigned long long>(2);
-        OsaSizes *sizes = sc.take<OsaSizes>(1);
-        LaneItem *items = sc.take<LaneItem>(slice_pairs);
-        uint64_t *slice[kScoredOutputs] = {};
-        for (int o = 0; o < counts; ++o) slice[o] = sc.take<uint64_t>(slice_pairs);
-        char *lists = sc.take<char>(q_step * k * 16);
-        uint32_t *ind = dev_i ? r.indices : sc.take<uint32_t>(nq * k);
-        uint64_t *sco = dev_s ? (uint64_t *)r.scores : sc.take<uint64_t>(nq * k);
-
-        // the search as one call: with profiling on, the kernels since the last absorb() go into the sum (`scoring`: the family's kernel)
-        swh_timing_t sum{};
-        char scoring_name[40] = "";
-        auto absorb = [&](bool scoring) {
-            if (scope->profiling && scope->stamps_used) {
-                SWH_HIP_CHECK(hipStreamSynchronize(stream));
-                collect_timing(scope);
-                const swh_timing_t &t = scope->last_timing;
-                sum.total_ms += t.total_ms; sum.compute_ms += t.compute_ms; sum.kernels += t.kernels;
-                if (scoring) { sum.dominant_ms += t.dominant_ms; snprintf(scoring_name, sizeof scoring_name, "%s", t.dominant_name); }
-            }
-            scope->stamps_used = 0;
-        };
-
-        // the length limits: OSA and LCS refuse a pair whose SHORTER string is over theirs, Jaro one with either string over its own
-        SWH_HIP_CHECK(hipMemsetAsync(first_over, 0xFF, 2 * sizeof(unsigned long long), stream));
-        const uint32_t limit = jaro ? SWH_JARO_MAX_LENGTH : SWH_OSA_MAX_SHORTER;
-        launch_extract_first_over(scope, queries, a_off64, limit, first_over);
-        launch_extract_first_over(scope, candidates, b_off64, limit, first_over + 1);
-        unsigned long long over[2];
-        SWH_HIP_CHECK(hipMemcpyAsync(over, first_over, sizeof over, hipMemcpyDeviceToHost, stream));
-        SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        absorb(false);
-        const bool a_over = over[0] != ~0ull, b_over = over[1] != ~0ull;
-        if (jaro ? (a_over || b_over) : (a_over && b_over)) {
-            const size_t i = a_over ? (size_t)over[0] : 0, j = b_over ? (size_t)over[1] : 0;
-            const uint64_t la = read_offset(queries.offsets, a_off64, i + 1, true, stream) - read_offset(queries.offsets, a_off64, i, true, stream);
-            const uint64_t lb = read_offset(candidates.offsets, b_off64, j + 1, true, stream) - read_offset(candidates.offsets, b_off64, j, true, stream);
-            return fail(error, swh_unsupported_length_k, "pair (%zu, %zu): %llu x %llu symbols, %s", i, j, (unsigned long long)la,
-                        (unsigned long long)lb, f.oversize);
-        }
-
-        // a finite cutoff of the OSA scorer is the scoring kernel's bound: what it clamps is over the cutoff anyway (the LCS kernel
-        // runs unbounded: every scorer of its family reads the LCS length)
-        const uint32_t bound = r.scorer == SWH_SCORER_OSA && r.cutoff < 4294967294.0 ? (uint32_t)r.cutoff : SWH_UNBOUNDED;
-        uint64_t cutoff_bits;
-        memcpy(&cutoff_bits, &r.cutoff, sizeof cutoff_bits);
-        uint64_t symbols = 0;
-        for (uint64_t q0 = 0; q0 < nq; q0 += q_step) {
-            const uint64_t rows = std::min<uint64_t>(q_step, nq - q0);
-            SWH_HIP_CHECK(hipMemsetAsync(lists, 0xFF, rows * k * 16, stream));   // every row is padding
-            for (uint64_t c0 = 0; c0 < nc; c0 += c_step) {
-                const uint64_t columns = std::min<uint64_t>(c_step, nc - c0);
-                OsaTapes t{};
-                t.a = prepared_view(p.pa, cp, p.a_first + q0, rows);
-                t.b = prepared_view(p.pb, cp, p.b_first + c0, columns);
-                t.a_off64 = a_off64; t.b_off64 = b_off64; t.cp = cp ? 1 : 0;
-                t.nb = columns; t.row0 = 0; t.count = rows * columns;
-                OsaSizes init{}, got{};
-                init.first_oversize = ~0ull;
-                SWH_HIP_CHECK(hipMemcpyAsync(sizes, &init, sizeof init, hipMemcpyHostToDevice, stream));
-                f.sizes(scope, t, sizes, items);
-                SWH_HIP_CHECK(hipMemcpyAsync(&got, sizes, sizeof got, hipMemcpyDeviceToHost, stream));
-                SWH_HIP_CHECK(hipStreamSynchronize(stream));
-                absorb(false);
-                if (got.first_oversize != ~0ull)   // (the memory of a prepared tape changed since the lengths were read)
-                    return fail(error, swh_unsupported_length_k, "a string of the slice at (%llu, %llu) grew over the limit: %s",
-                                (unsigned long long)q0, (unsigned long long)c0, f.oversize);
-                sum.cells += got.cells; symbols += got.symbols;
-                const bool wide = !cp && got.a_total >= 16 && got.b_total >= 16;
-                char *where[kScoredOutputs] = {};
-                if (jaro) for (int o = 0; o < counts; ++o) where[o] = (char *)slice[o];
-                else where[r.scorer == SWH_SCORER_OSA ? 0 : 1] = (char *)slice[0];   // the OSA distance; the LCS length
-                f.launch(scope, t, items, got.items, where, columns * 8, bound, wide);
-                absorb(true);
-
-                ExtractLaunch x{};
-                for (int o = 0; o < counts; ++o) x.counts[o] = slice[o];
-                x.a = queries; x.b = candidates; x.a_off64 = a_off64; x.b_off64 = b_off64;
-                x.rows = rows; x.columns = columns; x.row_first = q0; x.col_first = c0;
-                x.scorer = r.scorer; x.k = r.k; x.emit = c0 + columns == nc ? 1u : 0u;
-                x.cutoff_bits = cutoff_bits; x.prefix_weight = r.prefix_weight;
-                x.lists = lists; x.indices = ind; x.scores = sco;
-                launch_extract_select(scope, x);
-                absorb(false);
-            }
-        }
-        if (!dev_i) SWH_HIP_CHECK(hipMemcpyAsync(r.indices, ind, index_bytes, hipMemcpyDeviceToHost, stream));
-        if (!dev_s) SWH_HIP_CHECK(hipMemcpyAsync(r.scores, sco, score_bytes, hipMemcpyDeviceToHost, stream));
-        SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        scope->summary_pending = false;
-        scope->stamps_pending = false;
-        sum.bytes = (cp ? 4 : 1) * symbols + index_bytes + score_bytes;
-        snprintf(sum.dominant_name, sizeof sum.dominant_name, "extract_select/%s", scoring_name);
-        scope->last_timing = sum;
-        if (scope->profiling) add_to_totals(scope->totals, sum);
-        return swh_success_k;
-    });
-}
-
-static swh_status_t extract_checks(swh_levenshtein_t e, swh_scope_t s, int scorer, size_t k, uint64_t cutoff_bits, uint64_t prefix_weight_bits,
-                                   size_t queries, size_t candidates, const uint32_t *indices, const void *scores, ExtractRequest &request,
-                                   const char **error) {
-    const swh_status_t status = probe_null_handles(e, s, error);
-    if (status != swh_success_k) return status;
-    const Engine *engine = (const Engine *)e;
-    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
-    if (scorer < SWH_SCORER_OSA || scorer > SWH_SCORER_JARO_WINKLER) return fail(error, swh_invalid_argument_k, "scorer must be one of SWH_SCORER_*");
-    if (k < 1 || k > SWH_TOPK_MAX) return fail(error, swh_invalid_argument_k, "k must lie in [1, SWH_TOPK_MAX]");
-    double cutoff, prefix_weight;
-    memcpy(&cutoff, &cutoff_bits, sizeof cutoff);
-    memcpy(&prefix_weight, &prefix_weight_bits, sizeof prefix_weight);
-    if (!(cutoff >= 0.0)) return fail(error, swh_invalid_argument_k, "the cutoff must be a non-negative number (or +infinity), not NaN");
-    if (scorer == SWH_SCORER_JARO_WINKLER && !(prefix_weight >= 0.0 && prefix_weight <= 0.25))
-        return fail(error, swh_invalid_argument_k, "the prefix weight must lie in [0, 0.25]");
-    if (!engine->unit_costs)
-        return fail(error, swh_not_implemented_k, "the score search is called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)");
-    if (candidates >= 0xFFFFFFFFull) return fail(error, swh_unsupported_length_k, "2^32 - 1 candidates or more");
-    if (queries && (!indices || !scores)) return fail(error, swh_invalid_argument_k, "null output pointer");
-    request = ExtractRequest{scorer, (uint32_t)k, cutoff == 0.0 ? 0.0 : cutoff, prefix_weight, (uint32_t *)indices, (void *)scores};   // (-0.0: +0.0)
-    return swh_success_k;
-}
-
-static swh_status_t extract_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *q, const swh_tape_u64_t *c, bool utf8, int scorer,
-                                  size_t k, uint64_t cutoff_bits, uint64_t prefix_weight_bits, uint32_t *indices, void *scores, const char **error) {
-    swh_status_t status = probe_null_handles(e, s, error);
-    if (status != swh_success_k) return status;
-    if (!q) return fail(error, swh_invalid_argument_k, "null tape");
-    ExtractRequest request{};
-    status = extract_checks(e, s, scorer, k, cutoff_bits, prefix_weight_bits, q->count, (c ? c : q)->count, indices, scores, request, error);
-    if (status != swh_success_k) return status;
-    TwoTapeCall call;
-    if ((status = call.begin(s, error)) != swh_success_k) return status;
-    if (q->count == 0) return swh_success_k;
-    if ((status = call.prepare(q, c, utf8, true, true, error)) != swh_success_k) return status;
-    return extract_run(call.scope, call.pair, request, error);
-}
-swh_status_t swh_levenshtein_extract_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries, const swh_tape_u64_t *candidates,
-                                             int scorer, size_t k, uint64_t cutoff_bits, uint64_t prefix_weight_bits, uint32_t *indices,
-                                             void *scores, const char **error) {
-    return extract_tapes(e, s, queries, candidates, false, scorer, k, cutoff_bits, prefix_weight_bits, indices, scores, error);
-}
-swh_status_t swh_levenshtein_utf8_extract_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries,
-                                                  const swh_tape_u64_t *candidates, int scorer, size_t k, uint64_t cutoff_bits,
-                                                  uint64_t prefix_weight_bits, uint32_t *indices, void *scores, const char **error) {
-    return extract_tapes(e, s, queries, candidates, true, scorer, k, cutoff_bits, prefix_weight_bits, indices, scores, error);
-}
-swh_status_t swh_levenshtein_extract_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *queries,
-                                              const swh_prepared_view_t *candidates, int scorer, size_t k, uint64_t cutoff_bits,
-                                              uint64_t prefix_weight_bits, uint32_t *indices, void *scores, const char **error) {
-    swh_status_t status = probe_null_handles(e, s, error);
-    if (status != swh_success_k) return status;
-    TwoTapeCall call;
-    if ((status = call.views(queries, candidates, true, error)) != swh_success_k) return status;
-    ExtractRequest request{};
-    status = extract_checks(e, s, scorer, k, cutoff_bits, prefix_weight_bits, call.pair.a_count, call.pair.b_count, indices, scores, request, error);
-    if (status != swh_success_k) return status;
-    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
-    return extract_run(call.scope, call.pair, request, error);
-}
-
-}  // extern "C"

@@ -1,4 +1,4 @@
-// extract.hpp -- launchers of the score search's own kernels (extract.hip), called by api.hip: swh_levenshtein_extract_* keeps the k
+// extract.hpp -- launchers of the score search's own kernels (extract.hip), called by two_tape.hip: swh_levenshtein_extract_* keeps the k
 // best candidates of every query under an OSA, Indel, LCS, ratio, Jaro or Jaro-Winkler score. The pairs are scored by the families'
 // own launchers (osa.hpp, lcs.hpp, jaro.hpp) into a slice of counts; what lives here ranks them.
 #pragma once

@@ -1,4 +1,4 @@
-// infix.hpp -- launchers of the Levenshtein infix-search kernels (infix.hip), called by api.hip.
+// infix.hpp -- launchers of the Levenshtein infix-search kernels (infix.hip), called by two_tape.hip.
 // Kept apart from common.hpp, which every kernel family's profile stamp hashes (tools/kernel_sources.py).
 #pragma once
 #include "osa.hpp"   // LaneItem: the work items of the two passes

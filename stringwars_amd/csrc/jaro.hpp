@@ -1,4 +1,4 @@
-// jaro.hpp -- launchers of the Jaro / Jaro-Winkler kernels (jaro.hip), called by api.hip. The pairs of a launch and the shapes of
+// jaro.hpp -- launchers of the Jaro / Jaro-Winkler kernels (jaro.hip), called by two_tape.hip. The pairs of a launch and the shapes of
 // their measurements and work items are osa.hpp's (OsaTapes, OsaSizes, LaneItem), as they stand; the items are cut by jaro.hip's own
 // k_jaro_sizes, because here the blocks follow b (never the shorter string) and both lengths are limited.
 #pragma once

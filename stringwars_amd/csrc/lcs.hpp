@@ -1,4 +1,4 @@
-// lcs.hpp -- launcher of the longest-common-subsequence / Indel kernel (lcs.hip), called by api.hip. The pairs of a launch, their
+// lcs.hpp -- launcher of the longest-common-subsequence / Indel kernel (lcs.hip), called by two_tape.hip. The pairs of a launch, their
 // measurements and their work items are osa.hpp's (OsaTapes, OsaSizes, LaneItem, launch_osa_sizes), as they stand.
 #pragma once
 #include "osa.hpp"

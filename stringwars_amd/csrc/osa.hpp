@@ -1,4 +1,4 @@
-// osa.hpp -- launchers of the optimal-string-alignment (restricted Damerau-Levenshtein) kernels (osa.hip), called by api.hip.
+// osa.hpp -- launchers of the optimal-string-alignment (restricted Damerau-Levenshtein) kernels (osa.hip), called by two_tape.hip.
 // Kept apart from common.hpp, which every kernel family's profile stamp hashes (tools/kernel_sources.py).
 #pragma once
 #include "common.hpp"

@@ -1,0 +1,1341 @@
+// two_tape.hip -- the synchronous two-tape calls of include/stringwars_amd.h: top-k, range and score searches, alignments, infix
+// search and the scored families (OSA, LCS / Indel, Jaro). Host code only: the kernels are the families' own files, the engine-call
+// path the searches score their slices on is api.hip (api.hpp: what the two files share).
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+#include "api.hpp"
+#include "within.hpp"
+#include "align.hpp"
+#include "infix.hpp"
+#include "osa.hpp"
+#include "lcs.hpp"
+#include "jaro.hpp"
+#include "extract.hpp"
+
+using namespace swh;
+
+// ---- the synchronous two-tape calls: one front end ------------------------------------------------------------------------------------
+// Top-k and range searches, alignments, infix search and the scored families (OSA, LCS, Jaro) are synchronous on every scope:
+// outstanding asynchronous / pipelined work is joined first, and the call runs on the scope itself (not on a pipeline lane) with the
+// asynchronous mode held off until it returns. Every export runs its own null tests and argument checks in its own order -- which
+// refusal wins is its contract (DESIGN.md lists where the calls differ on purpose) -- and between them resolves its two sides here,
+// into the TapePair its *_run takes.
+struct TapePair {
+    const Prepared *pa = nullptr, *pb = nullptr;   // null where a raw call prepared nothing: every *_run returns before it looks at them
+    size_t a_first = 0, a_count = 0, b_first = 0, b_count = 0;
+};
+struct PreparedOwner {
+    Prepared *p = nullptr;
+    ~PreparedOwner() { free_prepared(p); }
+};
+static swh_status_t join_outstanding(Scope *scope, const char **error) {
+    if (!scope->async && !scope->pipelined) return swh_success_k;
+    return swh_scope_synchronize((swh_scope_t)scope, error);
+}
+
+struct HoldSynchronous {
+    Scope *scope = nullptr;
+    bool async = false, pipelined = false;
+    void hold(Scope *s) { scope = s; async = s->async; pipelined = s->pipelined; s->async = false; s->pipelined = false; }
+    ~HoldSynchronous() {
+        if (scope) { scope->async = async; scope->pipelined = pipelined; }
+    }
+};
+struct TwoTapeCall {
+    HoldSynchronous mode;             // declared first, so the scope's mode comes back last: after what the call prepared is freed
+    Scope *scope = nullptr;           // set once the call has begun
+    PreparedOwner owned_a, owned_b;   // what a raw call prepared: it lives as long as the call
+    TapePair pair;
+
+    // joins what is outstanding and holds the scope synchronous until the call returns
+    swh_status_t begin(swh_scope_t s, const char **error) {
+        const swh_status_t status = join_outstanding((Scope *)s, error);
+        if (status != swh_success_k) return status;
+        scope = (Scope *)s;
+        mode.hold(scope);
+        return swh_success_k;
+    }
+    // Raw tapes, after begin(): the sides named are made resident and measured for the call (prepare_tape: device tapes in place, host
+    // tapes uploaded; UTF-8 validated and decoded), so the route is chosen on lengths that are known, not believed. Without `b` the
+    // second side is the first. A call without pairs names no side: its pair keeps the counts and null tapes.
+    swh_status_t prepare(const swh_tape_u64_t *a, const swh_tape_u64_t *b, bool utf8, bool prepare_a, bool prepare_b, const char **error) {
+        pair = TapePair{nullptr, nullptr, 0, a->count, 0, (b ? b : a)->count};
+        swh_status_t status = swh_success_k;
+        if (prepare_a && (status = prepare_tape(scope, SWH_TAPE(a, 1), utf8, (swh_prepared_t *)&owned_a.p, error)) != swh_success_k) return status;
+        if (b && prepare_b && (status = prepare_tape(scope, SWH_TAPE(b, 1), utf8, (swh_prepared_t *)&owned_b.p, error)) != swh_success_k) return status;
+        pair.pa = owned_a.p; pair.pb = b ? owned_b.p : owned_a.p;
+        return swh_success_k;
+    }
+    // Prepared views, before the call's own checks: the null tests and the bounds of both. A missing b is a (the self-search, the
+    // self-product) where `b_optional`.
+    swh_status_t views(const swh_prepared_view_t *a, const swh_prepared_view_t *b, bool b_optional, const char **error) {
+        if (!a || !a->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
+        const swh_prepared_view_t *bb = (b && b->tape) ? b : (b_optional ? a : nullptr);
+        if (!bb) return fail(error, swh_invalid_argument_k, "null prepared view");
+        if (!view_fits(a) || !view_fits(bb)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
+        pair = TapePair{(const Prepared *)a->tape, (const Prepared *)bb->tape, a->first, a->count, bb->first, bb->count};
+        return swh_success_k;
+    }
+    // ... and after them: the two tapes go together and live on the scope's device, and the call begins
+    swh_status_t begin_on_views(swh_scope_t s, const char **error) {
+        const swh_status_t status = check_prepared_pair((Scope *)s, pair.pa, pair.pb, error);
+        return status != swh_success_k ? status : begin(s, error);
+    }
+};
+
+// What every *_run is wrapped in: the previous call's timing is harvested and this call's begins empty; a HIP or allocation failure
+// anywhere in `body` becomes the call's status.
+template <typename Body> static swh_status_t synchronous_run(Scope *scope, const char **error, Body body) {
+    harvest_timing(scope, false);
+    scope->stamps_used = 0;
+    scope->last_timing = swh_timing_t{};
+    try {
+        return body();
+    } catch (const HipFailure &f) {
+        return fail_hip(error, f);
+    } catch (const std::bad_alloc &) {
+        return fail(error, swh_bad_alloc_k, "host allocation failed");
+    }
+}
+
+// ---- the phases the *_run bodies share ------------------------------------------------------------------------------------------------
+// An output of the caller's that may live on the host. The kernels write a device array: the caller's own in place (a null output
+// counts as one: nothing is staged for it), or staging in the call's scratch, which copy_back() sends on -- asynchronously: the call
+// waits once, for all its outputs. Contiguous outputs only (scored_run copies its strided ones itself).
+template <typename T> struct Staged {
+    T *out; bool on_device;
+    T *dev = nullptr;   // what to launch on, once placed
+    explicit Staged(T *caller) : out(caller), on_device(is_device_pointer(caller)) {}
+    size_t need(size_t n) const { return on_device ? 0 : pad(n * sizeof(T)); }   // of the scratch
+    T *place(Carver &sc, size_t n) { return dev = on_device ? out : sc.take<T>(n); }
+    void copy_back(hipStream_t stream, size_t n) const {
+        if (!on_device) SWH_HIP_CHECK(hipMemcpyAsync(out, dev, n * sizeof(T), hipMemcpyDeviceToHost, stream));
+    }
+    void fill_padding(hipStream_t stream, size_t n) const {   // "every row is padding": all 0xFF, where the caller's array is
+        if (on_device) SWH_HIP_CHECK(hipMemsetAsync(out, 0xFF, n * sizeof(T), stream)); else memset(out, 0xFF, n * sizeof(T));
+    }
+};
+// a scratch buffer grown to `need` bytes, ready to be carved
+static Carver carve(char *&buf, size_t &cap, size_t need) {
+    ensure(buf, cap, need);
+    return Carver{buf, 0, cap};
+}
+
+// Measure, then decide: the family's Sizes struct starts on the device with no string over the limit, `launch` enqueues the sizes
+// kernel (and what is scanned with it), and one read-back and wait bring the measurements to the host, before any output is written.
+template <typename Sizes, typename Launch> static Sizes measure(Scope *scope, Sizes *device_sizes, Launch launch) {
+    Sizes init{}, got{};
+    init.first_oversize = ~0ull;
+    SWH_HIP_CHECK(hipMemcpyAsync(device_sizes, &init, sizeof init, hipMemcpyHostToDevice, scope->stream));
+    launch();
+    SWH_HIP_CHECK(hipMemcpyAsync(&got, device_sizes, sizeof got, hipMemcpyDeviceToHost, scope->stream));
+    SWH_HIP_CHECK(hipStreamSynchronize(scope->stream));
+    return got;
+}
+
+// One side of a launch on prepared tapes as the lane-per-block and alignment kernels read it: strings [first, first + count) as code
+// points (`cp`: u64 offsets) or as bytes at the tape's own offset width, which goes to `off64`.
+static TapeRef tape_side(const Prepared *p, bool cp, size_t first, size_t count, uint32_t &off64) {
+    off64 = cp ? 1u : p->off64;
+    return prepared_view(p, cp, first, count);
+}
+// the symbols of string i of a device tape, for an error text (two reads and waits: refusals only)
+static uint64_t string_symbols(const TapeRef &tape, uint32_t off64, size_t i, hipStream_t stream) {
+    return read_offset(tape.offsets, (int)off64, i + 1, true, stream) - read_offset(tape.offsets, (int)off64, i, true, stream);
+}
+
+// The common end of a call whose kernels have completed on the scope's stream: with profiling on they are the call's timing, once in
+// the totals. (SearchSweep::close, extract_run and within's fused path end in their own ways.)
+static void close_call(Scope *scope, uint64_t cells, uint64_t bytes) {
+    if (scope->profiling && scope->stamps_used) { collect_timing(scope); add_to_totals(scope->totals, scope->last_timing); }
+    scope->stamps_used = 0;
+    scope->last_timing.cells = cells; scope->last_timing.bytes = bytes;
+}
+
+// ---- the search planner: what top-k and the range search decide alike ---------------------------------------------------------------
+// Both searches run word-sized byte strings on unit costs through a fused kernel of their own (k_cross_topk, k_cross_within): the
+// searches a dense cross-product of the same views would run on k_cross_short (pick_route for prepared tapes). Everything else takes
+// the general path: the candidates in slices, each slice scored by the ordinary cross-product routes into a u32 matrix in scratch
+// (with the caller's bound, so long strings may take the banded kernel) and handed to the search's own kernels. What differs between
+// the two comes in as a value or a callback.
+// `force_select`: the search's STRINGWARS_AMD_*_ROUTE=select hook; `dev_out`: its results go to device memory
+static bool search_is_fused(const Scope *scope, const Engine *engine, const TapePair &p, uint32_t bound, bool force_select, bool dev_out) {
+    const bool utf8 = p.pa->utf8 && !(p.pa->ascii && p.pb->ascii && p.pa->off64 == p.pb->off64);
+    CallSpec whole{};   // the dense cross-product of the two views, as run_call_on would route it
+    whole.a.count = p.a_count; whole.b.count = p.b_count; whole.cross = true; whole.bound = bound; whole.pa = p.pa; whole.pb = p.pb;
+    return !force_select && !utf8 && engine->algorithm == swh_algorithm_auto_k && p.pa->off64 == p.pb->off64 &&
+           pick_route(scope, engine, whole, false, dev_out, call_lengths(scope, engine, whole, false)).route == kRouteCrossShort;
+}
+
+// The fused kernels' candidate slices per block of 16 queries: enough for ~32 items per compute unit (a few rounds of its 12 wave
+// slots: 65 536 x 1 M words ran top-k at 4.6 TCUPS with 16, 5.9 with 32), while what the search keeps per (row, slice) --
+// `row_slice_bytes` -- stays under 256 MB; at most one per chunk of 64 candidates. `forced`: a test hook's count, 0 without one.
+struct SearchSlices { uint64_t slices, slice_chunks; };
+static SearchSlices search_slices(uint64_t nq, uint64_t nc, uint64_t compute_units, uint64_t row_slice_bytes, uint64_t forced) {
+    const uint64_t qblocks = (nq + 15) / 16, chunks = (nc + 63) / 64;
+    const uint64_t target = compute_units * 32;
+    uint64_t slices = std::min<uint64_t>(std::max<uint64_t>((target + qblocks - 1) / qblocks, 1), chunks);
+    slices = std::max<uint64_t>(1, std::min<uint64_t>(slices, ((uint64_t)256 << 20) / (nq * row_slice_bytes)));
+    if (forced) slices = std::min<uint64_t>(forced, chunks);
+    const uint64_t slice_chunks = (chunks + slices - 1) / slices;
+    return SearchSlices{(chunks + slice_chunks - 1) / slice_chunks, slice_chunks};
+}
+
+// The general path: query blocks of at most 2^18 rows x candidate slices of at most 2^26 pairs (a 256 MB u32 matrix), and the search
+// reported as one call whose name says which path ran and which kernel scored the pairs.
+struct SearchSweep {
+    Scope *scope; const Engine *engine; const TapePair &pair; uint32_t bound;
+    uint64_t q_step, c_step;
+    swh_timing_totals_t totals_before;
+    swh_timing_t sum{};
+    char scoring_name[64] = "";
+
+    SearchSweep(Scope *s, const Engine *e, const TapePair &p, uint32_t bound_)
+        : scope(s), engine(e), pair(p), bound(bound_), q_step(std::min<uint64_t>(p.a_count, (uint64_t)1 << 18)),
+          c_step(std::max<uint64_t>(1, std::min<uint64_t>(p.b_count, ((uint64_t)1 << 26) / q_step))), totals_before(s->totals) {}
+
+    // One walk over the blocks. rows_begin(q0, rows) opens every block of queries, before its first slice is scored; each slice is then
+    // scored into `matrix` (q_step * c_step entries) and handed to block(q0, rows, c0, columns, last_slice) with the stamps reset.
+    // `counted`: the walk's cells and bytes go into the sum (a second walk of the same pairs: not again).
+    template <typename Rows, typename Block>
+    swh_status_t walk(uint32_t *matrix, bool counted, const char **error, Rows rows_begin, Block block) {
+        const uint64_t nq = pair.a_count, nc = pair.b_count;
+        for (uint64_t q0 = 0; q0 < nq; q0 += q_step) {
+            const uint64_t rows = std::min<uint64_t>(q_step, nq - q0);
+            rows_begin(q0, rows);
+            for (uint64_t c0 = 0; c0 < nc; c0 += c_step) {
+                const uint64_t columns = std::min<uint64_t>(c_step, nc - c0);
+                CallSpec spec{};
+                spec.a = HostTape{nullptr, nullptr, (size_t)rows, 0};
+                spec.b = HostTape{nullptr, nullptr, (size_t)columns, 0};
+                spec.cross = true; spec.utf8 = pair.pa->utf8; spec.bound = bound;
+                spec.out = matrix; spec.out_stride = 4; spec.row_stride = columns * 4; spec.out64 = false;
+                spec.pa = pair.pa; spec.pb = pair.pb; spec.a_first = pair.a_first + q0; spec.b_first = pair.b_first + c0;
+                const swh_status_t status = run_call_on(scope, engine, spec, error);
+                if (status != swh_success_k) return status;
+                const swh_timing_t &dp = scope->last_timing;
+                if (counted) { sum.cells += dp.cells; sum.bytes += dp.bytes; }
+                sum.total_ms += dp.total_ms; sum.compute_ms += dp.compute_ms; sum.kernels += dp.kernels;
+                if (dp.dominant_ms > sum.dominant_ms) { sum.dominant_ms = dp.dominant_ms; snprintf(scoring_name, sizeof scoring_name, "%s", dp.dominant_name); }
+                scope->stamps_used = 0;
+                scope->stamps_pending = false;
+                block(q0, rows, c0, columns, c0 + columns == nc);
+            }
+        }
+        return swh_success_k;
+    }
+    // with profiling on, the time of the `launched` kernels of the search's own since the last scoring call
+    void time_own_kernels(uint32_t launched) {
+        if (!scope->profiling) return;
+        SWH_HIP_CHECK(hipStreamSynchronize(scope->stream));
+        collect_timing(scope);
+        sum.total_ms += scope->last_timing.total_ms; sum.compute_ms += scope->last_timing.compute_ms; sum.kernels += launched;
+        scope->stamps_used = 0;
+    }
+    // the search as one call, "<search>_select/<scoring kernel>", once in the scope's totals
+    void close(const char *search) {
+        scope->summary_pending = false;
+        scope->stamps_pending = false;
+        snprintf(sum.dominant_name, sizeof sum.dominant_name, "%s_select/%s", search, scoring_name);
+        scope->last_timing = sum;
+        if (scope->profiling) {
+            scope->totals = totals_before;
+            add_to_totals(scope->totals, sum);
+        }
+    }
+};
+
+extern "C" {
+// ---- top-k search (topk.hip) ----------------------------------------------------------------------------------------------------------
+// The fused kernel keeps a list of k per (row, slice) and merges them; the general path folds each scored slice into the running
+// lists with k_topk_select.
+// STRINGWARS_AMD_TOPK_PRUNE=0 (test library): the fused kernel walks every chunk, also those the length bound rules out (the comparison knob)
+static uint32_t topk_prune() {
+    static const uint32_t on = [] { const char *e = test_hook("STRINGWARS_AMD_TOPK_PRUNE"); return !e || atoi(e) != 0 ? 1u : 0u; }();
+    return on;
+}
+// STRINGWARS_AMD_TOPK_ROUTE=select (test library): every search on the general path
+static bool topk_force_select() {
+    static const bool on = [] { const char *e = test_hook("STRINGWARS_AMD_TOPK_ROUTE"); return e && !strcmp(e, "select"); }();
+    return on;
+}
+
+static swh_status_t topk_run(Scope *scope, const Engine *engine, const TapePair &p, uint32_t k32, uint32_t bound, uint32_t *indices,
+                             uint32_t *distances, const char **error) {
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t nq = p.a_count, nc = p.b_count, k = k32;
+        if (nq == 0) return swh_success_k;
+        const uint64_t cap = bound == SWH_UNBOUNDED ? ~0ull : ((uint64_t)bound + 1) << 32;
+        const size_t out_bytes = nq * k * sizeof(uint32_t);
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        Staged<uint32_t> ind(indices), dist(distances);
+        if (nc == 0) {   // every row is padding
+            ind.fill_padding(stream, nq * k); dist.fill_padding(stream, nq * k);
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            return swh_success_k;
+        }
+        const size_t ow = p.pa->off64 ? 8 : 4;
+        auto finish_outputs = [&] {
+            ind.copy_back(stream, nq * k); dist.copy_back(stream, nq * k);
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        };
+
+        if (search_is_fused(scope, engine, p, bound, topk_force_select(), ind.on_device)) {
+            // ---- fused: a partial list of k (index, distance) words per (row, slice) ------------------------------------------------------
+            const SearchSlices cut = search_slices(nq, nc, scope->compute_units, k * 8, 0);
+            const uint64_t slices = cut.slices;
+            const size_t need = (slices > 1 ? pad(nq * slices * k * 8) : 0) + ind.need(nq * k) + dist.need(nq * k);
+            Carver sc = carve(scope->topk_scratch, scope->topk_scratch_bytes, need);
+            TopkLaunch t{};
+            t.a = prepared_view(p.pa, false, p.a_first, nq); t.b = prepared_view(p.pb, false, p.b_first, nc);
+            t.off64 = p.pa->off64; t.k = (uint32_t)k; t.slices = (uint32_t)slices; t.prune = topk_prune();
+            t.slice_chunks = cut.slice_chunks; t.cap = cap;
+            t.partial = slices > 1 ? sc.take<uint64_t>(nq * slices * k) : nullptr;
+            t.indices = ind.place(sc, nq * k);
+            t.distances = dist.place(sc, nq * k);
+            scope->summary_slot = 0;
+            launch_cross_topk(scope, t);
+            finish_outputs();
+            const CallSummary sm = scope->summary_host[0];
+            if (!sm.violation) {
+                close_call(scope, sm.cells, p.pa->total_bytes + p.pb->total_bytes + (nq + nc) * ow + 2 * out_bytes);
+                return swh_success_k;
+            }
+            // a string longer than the kernel takes (the memory of a prepared tape changed since it was measured): the general path
+            scope->stamps_used = 0;
+            scope->last_timing = swh_timing_t{};
+        }
+
+        // ---- general path: each slice folded into the block's running lists ---------------------------------------------------------------
+        SearchSweep sweep(scope, engine, p, bound);
+        const size_t need = pad(sweep.q_step * sweep.c_step * 4) + pad(sweep.q_step * k * 8) + ind.need(nq * k) + dist.need(nq * k);
+        Carver sc = carve(scope->topk_scratch, scope->topk_scratch_bytes, need);
+        uint32_t *matrix = sc.take<uint32_t>(sweep.q_step * sweep.c_step);
+        uint64_t *lists = sc.take<uint64_t>(sweep.q_step * k);
+        ind.place(sc, nq * k); dist.place(sc, nq * k);
+        auto pad_lists = [&](uint64_t, uint64_t rows) { SWH_HIP_CHECK(hipMemsetAsync(lists, 0xFF, rows * k * 8, stream)); };   // every row is padding
+        const swh_status_t status = sweep.walk(matrix, true, error, pad_lists, [&](uint64_t q0, uint64_t rows, uint64_t c0, uint64_t columns, bool last_slice) {
+            launch_topk_select(scope, matrix, rows, columns, q0, c0, (uint32_t)k, cap, lists, last_slice, ind.dev, dist.dev);
+            sweep.time_own_kernels(1);
+        });
+        if (status != swh_success_k) return status;
+        finish_outputs();
+        sweep.close("topk");
+        return swh_success_k;
+    });
+}
+
+static swh_status_t topk_checks(swh_levenshtein_t e, swh_scope_t s, size_t k, size_t queries, size_t candidates, const uint32_t *indices,
+                                const uint32_t *distances, const char **error) {
+    if (!s || !e) return fail(error, swh_invalid_argument_k, "null scope or engine");
+    if (((Engine *)e)->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (k < 1 || k > SWH_TOPK_MAX) return fail(error, swh_invalid_argument_k, "k must lie in [1, SWH_TOPK_MAX]");
+    if (candidates >= 0xFFFFFFFFull) return fail(error, swh_unsupported_length_k, "2^32 - 1 candidates or more");
+    if (queries && (!indices || !distances)) return fail(error, swh_invalid_argument_k, "null output pointer");
+    return swh_success_k;
+}
+
+static swh_status_t topk_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *q, const swh_tape_u64_t *c, bool utf8, size_t k,
+                               uint32_t bound, uint32_t *indices, uint32_t *distances, const char **error) {
+    if (!q) return fail(error, swh_invalid_argument_k, "null tape");
+    swh_status_t status = topk_checks(e, s, k, q->count, (c ? c : q)->count, indices, distances, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    if (q->count == 0) return swh_success_k;
+    if ((status = call.prepare(q, c, utf8, true, true, error)) != swh_success_k) return status;
+    return topk_run(call.scope, (Engine *)e, call.pair, (uint32_t)k, bound, indices, distances, error);
+}
+swh_status_t swh_levenshtein_topk_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries, const swh_tape_u64_t *candidates,
+                                          size_t k, uint32_t bound, uint32_t *indices, uint32_t *distances, const char **error) {
+    return topk_tapes(e, s, queries, candidates, false, k, bound, indices, distances, error);
+}
+swh_status_t swh_levenshtein_utf8_topk_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries,
+                                               const swh_tape_u64_t *candidates, size_t k, uint32_t bound, uint32_t *indices,
+                                               uint32_t *distances, const char **error) {
+    return topk_tapes(e, s, queries, candidates, true, k, bound, indices, distances, error);
+}
+swh_status_t swh_levenshtein_topk_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *queries,
+                                           const swh_prepared_view_t *candidates, size_t k, uint32_t bound, uint32_t *indices,
+                                           uint32_t *distances, const char **error) {
+    TwoTapeCall call;
+    swh_status_t status = call.views(queries, candidates, true, error);
+    if (status != swh_success_k) return status;
+    if ((status = topk_checks(e, s, k, call.pair.a_count, call.pair.b_count, indices, distances, error)) != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return topk_run(call.scope, (Engine *)e, call.pair, (uint32_t)k, bound, indices, distances, error);
+}
+
+// ---- range search (within.hip) ---------------------------------------------------------------------------------------------------------
+// Every candidate within `bound` of every query, as CSR, on the search planner's routes. Both count first, scan the counts into the row
+// offsets on the device, read the total (8 bytes) and fill only if the caller's arrays hold it.
+// STRINGWARS_AMD_WITHIN_PRUNE=0 (test library): the fused kernel walks every chunk, also those the length gap rules out
+static uint32_t within_prune() {
+    static const uint32_t on = [] { const char *e = test_hook("STRINGWARS_AMD_WITHIN_PRUNE"); return !e || atoi(e) != 0 ? 1u : 0u; }();
+    return on;
+}
+// STRINGWARS_AMD_WITHIN_ROUTE=select (test library): every search on the general path
+static bool within_force_select() {
+    static const bool on = [] { const char *e = test_hook("STRINGWARS_AMD_WITHIN_ROUTE"); return e && !strcmp(e, "select"); }();
+    return on;
+}
+// STRINGWARS_AMD_WITHIN_SLICES=n (test library): the fused kernel's candidate slices per query block (at most one per chunk)
+static uint64_t within_slices_hook() {
+    static const uint64_t n = [] { const char *e = test_hook("STRINGWARS_AMD_WITHIN_SLICES"); return e && atoll(e) > 0 ? (uint64_t)atoll(e) : 0; }();
+    return n;
+}
+
+struct WithinOutputs {
+    size_t *row_offsets;
+    uint32_t *indices, *distances;
+    size_t capacity;
+};
+
+static swh_status_t within_run(Scope *scope, const Engine *engine, const TapePair &p, uint32_t bound, const WithinOutputs &r, const char **error) {
+    static_assert(sizeof(size_t) == sizeof(uint64_t), "row offsets are scanned as 64-bit words");
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t nq = p.a_count, nc = p.b_count;
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        Staged<uint64_t> offs((uint64_t *)r.row_offsets);
+        Staged<uint32_t> ind(r.indices), dist(r.distances);   // (both null in a counting call: nothing is staged, nothing filled)
+        if (nq == 0 || nc == 0) {   // no row, or every row empty
+            const size_t bytes = (nq + 1) * sizeof(size_t);
+            if (offs.on_device) {
+                SWH_HIP_CHECK(hipMemsetAsync(r.row_offsets, 0, bytes, stream));
+                SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            } else {
+                memset(r.row_offsets, 0, bytes);
+            }
+            return swh_success_k;
+        }
+        const size_t ow = p.pa->off64 ? 8 : 4;
+        // Once the offsets are complete on the device their last word, the total (one read and wait), decides the fill, and the rest
+        // goes to a host caller. Where the fill pass writes: the caller's device arrays, or staging for its host arrays.
+        auto stage_outputs = [&](uint64_t total) {
+            Carver oc = carve(scope->within_out, scope->within_out_bytes, ind.need(total) + dist.need(total));
+            ind.place(oc, total); dist.place(oc, total);
+        };
+
+        if (search_is_fused(scope, engine, p, bound, within_force_select(), ind.on_device)) {
+            // ---- fused: a count (4 bytes) and a start (8) per (row, slice) ----------------------------------------------------------------
+            const SearchSlices cut = search_slices(nq, nc, scope->compute_units, 12, within_slices_hook());
+            const uint64_t slices = cut.slices;
+            const uint64_t n_counts = nq * slices, tiles = (n_counts + kWithinScanTile - 1) / kWithinScanTile;
+            const size_t need = pad(n_counts * 4) + pad(n_counts * 8) + pad(tiles * 8) + offs.need(nq + 1);
+            Carver sc = carve(scope->topk_scratch, scope->topk_scratch_bytes, need);
+            WithinLaunch w{};
+            w.a = prepared_view(p.pa, false, p.a_first, nq); w.b = prepared_view(p.pb, false, p.b_first, nc);
+            w.off64 = p.pa->off64; w.slices = (uint32_t)slices; w.bound = bound; w.prune = within_prune(); w.slice_chunks = cut.slice_chunks;
+            w.counts = sc.take<uint32_t>(n_counts);
+            uint64_t *starts = sc.take<uint64_t>(n_counts), *block_sums = sc.take<uint64_t>(tiles);
+            offs.place(sc, nq + 1);
+            w.starts = starts;
+            scope->summary_slot = 0;
+            launch_cross_within(scope, w, false);
+            launch_within_offsets(scope, w.counts, nq, (uint32_t)slices, block_sums, starts, offs.dev);
+            const uint64_t total = read_offset(offs.dev, 1, nq, true, stream);
+            const CallSummary sm = scope->summary_host[0];
+            if (!sm.violation) {
+                offs.copy_back(stream, nq + 1);
+                if (total && total <= r.capacity) {
+                    stage_outputs(total);
+                    w.total = total; w.indices = ind.dev; w.distances = dist.dev;
+                    launch_cross_within(scope, w, true);
+                    ind.copy_back(stream, total); dist.copy_back(stream, total);
+                }
+                SWH_HIP_CHECK(hipStreamSynchronize(stream));
+                if (scope->profiling && scope->stamps_used) {
+                    collect_timing(scope);
+                    // the search is named after its walk, also where a tiny call's scan takes longer: the longer of the two passes
+                    swh_timing_t &t = scope->last_timing;
+                    t.dominant_ms = 0;
+                    for (size_t i = 0; i < scope->stamps_used; ++i) {
+                        float ms = 0;
+                        if (!strcmp(scope->stamps[i].name, "cross_within")) (void)hipEventElapsedTime(&ms, scope->stamps[i].start, scope->stamps[i].stop);
+                        if (ms > t.dominant_ms) t.dominant_ms = ms;
+                    }
+                    snprintf(t.dominant_name, sizeof t.dominant_name, "cross_within");
+                    add_to_totals(scope->totals, scope->last_timing);
+                }
+                scope->last_timing.cells = sm.cells;
+                // the tapes, a count and a start per (row, slice), the row offsets and the hits
+                scope->last_timing.bytes = p.pa->total_bytes + p.pb->total_bytes + (nq + nc) * ow + n_counts * 12 + (nq + 1) * 8 +
+                                           (total <= r.capacity ? total * 8 : 0);
+                return swh_success_k;
+            }
+            // a string longer than the kernel takes (the memory of a prepared tape changed since it was measured): the general path
+            scope->stamps_used = 0;
+            scope->last_timing = swh_timing_t{};
+        }
+
+        // ---- general path: every block scored twice, once to count and once to fill -------------------------------------------------------
+        SearchSweep sweep(scope, engine, p, bound);
+        const uint64_t tiles = (nq + kWithinScanTile - 1) / kWithinScanTile;
+        const size_t need = pad(sweep.q_step * sweep.c_step * 4) + pad(nq * 4) + pad(nq * 8) + pad(tiles * 8) + offs.need(nq + 1);
+        Carver sc = carve(scope->topk_scratch, scope->topk_scratch_bytes, need);
+        uint32_t *matrix = sc.take<uint32_t>(sweep.q_step * sweep.c_step);
+        uint32_t *counts = sc.take<uint32_t>(nq);
+        uint64_t *cursors = sc.take<uint64_t>(nq), *block_sums = sc.take<uint64_t>(tiles);
+        offs.place(sc, nq + 1);
+        SWH_HIP_CHECK(hipMemsetAsync(counts, 0, nq * 4, stream));
+        auto no_rows_begin = [](uint64_t, uint64_t) {};   // (counts and cursors span all queries: nothing to open per block)
+        swh_status_t status = sweep.walk(matrix, true, error, no_rows_begin, [&](uint64_t q0, uint64_t rows, uint64_t, uint64_t columns, bool) {
+            launch_within_count(scope, matrix, rows, columns, bound, counts + q0);
+            sweep.time_own_kernels(1);
+        });
+        if (status != swh_success_k) return status;
+        launch_within_offsets(scope, counts, nq, 1, block_sums, cursors, offs.dev);
+        sweep.time_own_kernels(2);
+        const uint64_t total = read_offset(offs.dev, 1, nq, true, stream);
+        offs.copy_back(stream, nq + 1);
+        if (total && total <= r.capacity) {
+            stage_outputs(total);
+            status = sweep.walk(matrix, false, error, no_rows_begin, [&](uint64_t q0, uint64_t rows, uint64_t c0, uint64_t columns, bool) {
+                launch_within_fill(scope, matrix, rows, columns, c0, bound, cursors + q0, total, ind.dev, dist.dev);
+                sweep.time_own_kernels(1);
+            });
+            if (status != swh_success_k) return status;
+            ind.copy_back(stream, total); dist.copy_back(stream, total);
+        }
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        sweep.close("within");
+        return swh_success_k;
+    });
+}
+
+static swh_status_t within_checks(swh_levenshtein_t e, swh_scope_t s, size_t candidates, uint32_t bound, const size_t *row_offsets,
+                                  const uint32_t *indices, const uint32_t *distances, size_t capacity, const char **error) {
+    if (!s || !e) return fail(error, swh_invalid_argument_k, "null scope or engine");
+    if (((Engine *)e)->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (bound == SWH_UNBOUNDED) return fail(error, swh_invalid_argument_k, "a range search needs a bound: without one it is the dense cross-product");
+    if (candidates >= 0xFFFFFFFFull) return fail(error, swh_unsupported_length_k, "2^32 - 1 candidates or more");
+    if (!row_offsets) return fail(error, swh_invalid_argument_k, "null row_offsets");
+    if (!indices != !distances) return fail(error, swh_invalid_argument_k, "indices and distances must both be given, or neither");
+    if (!indices && capacity) return fail(error, swh_invalid_argument_k, "a capacity without arrays: the counting call passes NULL, NULL, 0");
+    return swh_success_k;
+}
+
+static swh_status_t within_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *q, const swh_tape_u64_t *c, bool utf8, uint32_t bound,
+                                 const WithinOutputs &outs, const char **error) {
+    if (!q) return fail(error, swh_invalid_argument_k, "null tape");
+    const size_t candidates = (c ? c : q)->count;
+    swh_status_t status = within_checks(e, s, candidates, bound, outs.row_offsets, outs.indices, outs.distances, outs.capacity, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    // (a search without queries prepares nothing, one without candidates the queries alone: the offsets are still written)
+    if ((status = call.prepare(q, c, utf8, q->count != 0, q->count && candidates, error)) != swh_success_k) return status;
+    return within_run(call.scope, (Engine *)e, call.pair, bound, outs, error);
+}
+swh_status_t swh_levenshtein_within_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries, const swh_tape_u64_t *candidates,
+                                            uint32_t bound, size_t *row_offsets, uint32_t *indices, uint32_t *distances, size_t capacity,
+                                            const char **error) {
+    return within_tapes(e, s, queries, candidates, false, bound, WithinOutputs{row_offsets, indices, distances, capacity}, error);
+}
+swh_status_t swh_levenshtein_utf8_within_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries,
+                                                 const swh_tape_u64_t *candidates, uint32_t bound, size_t *row_offsets, uint32_t *indices,
+                                                 uint32_t *distances, size_t capacity, const char **error) {
+    return within_tapes(e, s, queries, candidates, true, bound, WithinOutputs{row_offsets, indices, distances, capacity}, error);
+}
+swh_status_t swh_levenshtein_within_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *queries,
+                                             const swh_prepared_view_t *candidates, uint32_t bound, size_t *row_offsets, uint32_t *indices,
+                                             uint32_t *distances, size_t capacity, const char **error) {
+    TwoTapeCall call;
+    swh_status_t status = call.views(queries, candidates, true, error);
+    if (status != swh_success_k) return status;
+    if ((status = within_checks(e, s, call.pair.b_count, bound, row_offsets, indices, distances, capacity, error)) != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return within_run(call.scope, (Engine *)e, call.pair, bound, WithinOutputs{row_offsets, indices, distances, capacity}, error);
+}
+
+// ---- alignments (align.hip) ----------------------------------------------------------------------------------------------------------
+// k_align_sizes measures the batch (stored bytes, symbols, cells, the first pair over SWH_ALIGN_MAX_CELLS) and the stored bytes and slot
+// sizes are scanned on the device; one read-back of the measurements decides the errors and the chunks, before any output is written.
+// Then per chunk of consecutive pairs the forward pass + walk (k_align), the counts scanned into the offsets, and k_align_emit places
+// the ops -- no host round trip between the forward pass and the outputs.
+// A chunk holds enough pairs to fill the device -- kAlignFillWaves waves per compute unit, a lane per pair -- and, beyond that, as many
+// as keep its stored delta vectors near 128 MiB, where the walk still reads the forward pass's stores from the Infinity Cache. Long
+// pairs therefore give up the residency rather than the parallelism (1 K protein pairs of 4 K symbols store 6 GB: one chunk).
+// STRINGWARS_AMD_ALIGN_CHUNK_KB=n (test library) sets the byte target and drops the fill minimum, to put many chunks in a small test.
+constexpr uint64_t kAlignFillWaves = 8;
+static const char *align_chunk_hook() {
+    static const char *e = test_hook("STRINGWARS_AMD_ALIGN_CHUNK_KB");
+    return e;
+}
+static uint64_t align_chunk_pairs(const Scope *scope, uint64_t count, uint64_t store_total) {
+    const char *hook = align_chunk_hook();
+    const uint64_t target = hook ? (uint64_t)atol(hook) << 10 : (uint64_t)128 << 20;
+    const uint64_t fill = hook ? 1 : (uint64_t)scope->compute_units * kAlignFillWaves * 64;
+    const uint64_t mean = std::max<uint64_t>(1, store_total / std::max<uint64_t>(count, 1));
+    uint64_t pairs = std::max<uint64_t>(fill, target / mean);
+    // no chunk asks for more than half the device memory that is free
+    size_t free_bytes = 0, total_bytes = 0;
+    if (hipMemGetInfo(&free_bytes, &total_bytes) == hipSuccess && free_bytes)
+        pairs = std::min<uint64_t>(pairs, std::max<uint64_t>(1, (uint64_t)(free_bytes / 2) / mean));
+    return std::max<uint64_t>(1, std::min<uint64_t>(pairs, count));
+}
+
+struct AlignOutputs {
+    uint32_t *distances;
+    uint64_t *offsets;
+    uint8_t *ops;
+    size_t capacity;
+};
+
+static swh_status_t align_run(Scope *scope, const TapePair &p, uint32_t bound, const AlignOutputs &r, const char **error) {
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t count = p.a_count;
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        Staged<uint32_t> distances(r.distances); Staged<uint64_t> offsets(r.offsets); Staged<uint8_t> ops(r.ops);
+        if (count == 0) {
+            const uint64_t zero = 0;
+            if (offsets.on_device) SWH_HIP_CHECK(hipMemcpyAsync(r.offsets, &zero, sizeof zero, hipMemcpyHostToDevice, stream)); else r.offsets[0] = 0;
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            return swh_success_k;
+        }
+        const bool cp = p.pa->utf8;
+        AlignTapes t{};
+        t.a = tape_side(p.pa, cp, p.a_first, count, t.a_off64);
+        t.b = tape_side(p.pb, cp, p.b_first, count, t.b_off64);
+        t.cp = cp ? 1 : 0;
+        t.count = count;
+
+        AlignScratch *sc_entry = call_scratch(scope);
+        // fixed part: sizes | store_base | slot_base | counts | offsets | distances | scan partials
+        const size_t partial_words = align_scan_partials(count);
+        const size_t fixed = pad(sizeof(AlignSizes)) + 2 * pad((count + 1) * 8) + pad(count * 4) + offsets.need(count + 1) + distances.need(count) +
+                             pad(partial_words * 8);
+        ensure(sc_entry->buf, sc_entry->bytes, fixed);
+        Carver sc{};
+        AlignSizes *sizes;
+        uint64_t *store_base, *slot_base, *partials;
+        uint32_t *counts;
+        auto carve_fixed = [&] {   // (again after the scratch has been regrown)
+            sc = Carver{sc_entry->buf, 0, sc_entry->bytes};
+            sizes = sc.take<AlignSizes>(1);
+            store_base = sc.take<uint64_t>(count + 1); slot_base = sc.take<uint64_t>(count + 1);
+            counts = sc.take<uint32_t>(count);
+            offsets.place(sc, count + 1); distances.place(sc, count);
+            partials = sc.take<uint64_t>(partial_words);
+        };
+        carve_fixed();
+
+        const AlignSizes got = measure(scope, sizes, [&] {
+            launch_align_sizes(scope, t, store_base, slot_base, sizes);
+            launch_align_scan(scope, store_base, count, partials);
+            launch_align_scan(scope, slot_base, count, partials);
+        });
+        if (got.first_oversize != ~0ull) {
+            const size_t i = (size_t)got.first_oversize;
+            const uint64_t la = string_symbols(t.a, t.a_off64, i, stream), lb = string_symbols(t.b, t.b_off64, i, stream);
+            scope->stamps_used = 0;
+            return fail(error, swh_unsupported_length_k, "pair %zu: %llu x %llu symbols exceeds SWH_ALIGN_MAX_CELLS (2^30 cells per pair)", i,
+                        (unsigned long long)la, (unsigned long long)lb);
+        }
+        if (r.capacity < got.symbols) {
+            scope->stamps_used = 0;
+            return fail(error, swh_invalid_argument_k, "ops_capacity %zu is below the %llu symbols of the two tapes", r.capacity,
+                        (unsigned long long)got.symbols);
+        }
+
+        // chunks of consecutive pairs; where they start in the storage space is read back (one strided copy) to size the largest
+        const uint64_t per_chunk = align_chunk_pairs(scope, count, got.store_total);
+        const uint64_t chunks = (count + per_chunk - 1) / per_chunk;
+        std::vector<uint64_t> starts(chunks + 1, 0);
+        if (chunks > 1) {
+            SWH_HIP_CHECK(hipMemcpy2DAsync(starts.data(), 8, store_base, per_chunk * 8, 8, chunks, hipMemcpyDeviceToHost, stream));
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        }
+        starts[chunks] = got.store_total;
+        uint64_t widest = 0;
+        for (uint64_t q = 0; q < chunks; ++q) widest = std::max<uint64_t>(widest, starts[q + 1] - starts[q]);
+        // variable part: the op slots (whole batch) | staged ops for host outputs | the widest chunk of stored delta vectors
+        const size_t store_bytes = (size_t)widest;
+        const size_t need = fixed + pad(got.symbols + 16) + ops.need(got.symbols + 16) + pad(store_bytes + 16);
+        if (need > sc_entry->bytes) {
+            // keep what the fixed part already holds: the measurements and scans live there
+            char *grown = nullptr;
+            const size_t want = need + need / 4 + (1 << 20);
+            SWH_HIP_CHECK(hipMalloc((void **)&grown, want));
+            SWH_HIP_CHECK(hipMemcpyAsync(grown, sc_entry->buf, fixed, hipMemcpyDeviceToDevice, stream));
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            SWH_HIP_CHECK(hipFree(sc_entry->buf));
+            sc_entry->buf = grown;
+            sc_entry->bytes = want;
+            carve_fixed();
+        }
+        uint8_t *slots = sc.take<uint8_t>(got.symbols + 16);
+        ops.place(sc, got.symbols + 16);
+        char *store = sc.take<char>(store_bytes + 16);
+
+        AlignChunk c{};
+        c.store_base = store_base; c.slot_base = slot_base; c.store = store; c.slots = slots;
+        c.counts = counts; c.distances = distances.dev; c.bound = bound;
+        for (uint64_t q = 0; q < chunks; ++q) {
+            c.pair_first = q * per_chunk;
+            c.pair_end = std::min<uint64_t>(count, (q + 1) * per_chunk);
+            c.store_first = starts[q];
+            launch_align_chunk(scope, t, c);
+        }
+        launch_align_scan_counts(scope, counts, offsets.dev, count, partials);
+        launch_align_emit(scope, count, slot_base, counts, offsets.dev, slots, ops.dev);
+        distances.copy_back(stream, count); offsets.copy_back(stream, count + 1);
+        if (!ops.on_device) {   // only the ops there are, not the capacity: their number is read first
+            const uint64_t total_ops = read_offset(offsets.dev, 1, count, true, stream);
+            if (total_ops) ops.copy_back(stream, total_ops);
+        }
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        close_call(scope, got.cells, (cp ? 4 : 1) * got.symbols + 2 * (count + 1) * 8 + count * 4 + got.symbols);
+        return swh_success_k;
+    });
+}
+
+static swh_status_t align_checks(swh_levenshtein_t e, swh_scope_t s, size_t a_count, size_t b_count, const uint32_t *distances,
+                                 const uint64_t *offsets, const uint8_t *ops, const char **error) {
+    if (!s || !e) return fail(error, swh_invalid_argument_k, "null scope or engine");
+    const Engine *engine = (const Engine *)e;
+    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (!engine->unit_costs) return fail(error, swh_not_implemented_k, "alignments need unit costs (match 0, mismatch 1, open 1, extend 1)");
+    if (a_count != b_count) return fail(error, swh_invalid_argument_k, "a and b must hold the same number of strings");
+    if (!offsets || (a_count && (!distances || !ops))) return fail(error, swh_invalid_argument_k, "null output pointer");
+    return swh_success_k;
+}
+
+static swh_status_t align_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, bool utf8, uint32_t bound,
+                                const AlignOutputs &outs, const char **error) {
+    if (!a || !b) return fail(error, swh_invalid_argument_k, "null tape");
+    swh_status_t status = align_checks(e, s, a->count, b->count, outs.distances, outs.offsets, outs.ops, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    const bool pairs = a->count != 0;
+    if ((status = call.prepare(a, b, utf8, pairs, pairs, error)) != swh_success_k) return status;
+    return align_run(call.scope, call.pair, bound, outs, error);
+}
+swh_status_t swh_levenshtein_align_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,
+                                           uint32_t *distances, size_t *ops_offsets, char *ops, size_t ops_capacity, const char **error) {
+    return align_tapes(e, s, a, b, false, bound, AlignOutputs{distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity}, error);
+}
+swh_status_t swh_levenshtein_utf8_align_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                uint32_t bound, uint32_t *distances, size_t *ops_offsets, char *ops, size_t ops_capacity,
+                                                const char **error) {
+    return align_tapes(e, s, a, b, true, bound, AlignOutputs{distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity}, error);
+}
+swh_status_t swh_levenshtein_align_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                            uint32_t bound, uint32_t *distances, size_t *ops_offsets, char *ops, size_t ops_capacity,
+                                            const char **error) {
+    const AlignOutputs outs{distances, (uint64_t *)ops_offsets, (uint8_t *)ops, ops_capacity};
+    TwoTapeCall call;
+    swh_status_t status = call.views(a, b, false, error);
+    if (status != swh_success_k) return status;
+    if ((status = align_checks(e, s, call.pair.a_count, call.pair.b_count, outs.distances, outs.offsets, outs.ops, error)) != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return align_run(call.scope, call.pair, bound, outs, error);
+}
+
+// ---- infix search (infix.hip) ---------------------------------------------------------------------------------------------------------
+// k_infix_sizes measures the batch (cells, the first pattern over SWH_INFIX_MAX_PATTERN) and cuts it into work items; one read-back of
+// the measurements decides the errors before any output is written. Then the forward pass (distance and end of every pair) and the
+// start pass (the starts, the bound) over the same items, and the copy-out of outputs that live on the host. The scratch -- the item
+// list and, for host outputs, the three result arrays -- is the scope's alignment scratch: both calls are synchronous.
+struct InfixOutputs { uint32_t *distances, *starts, *ends; };
+
+static swh_status_t infix_run(Scope *scope, const TapePair &p, uint32_t bound, const InfixOutputs &r, const char **error) {
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t count = p.a_count;
+        if (count == 0) return swh_success_k;
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        Staged<uint32_t> distances(r.distances), starts(r.starts), ends(r.ends);
+        const bool cp = p.pa->utf8;
+        InfixTapes t{};
+        t.patterns = tape_side(p.pa, cp, p.a_first, count, t.p_off64);
+        t.texts = tape_side(p.pb, cp, p.b_first, count, t.t_off64);
+        t.cp = cp ? 1 : 0;
+        t.count = count;
+
+        AlignScratch *sc_entry = call_scratch(scope);
+        // sizes | items | distances | starts | ends (the last three only where the caller's array lives on the host)
+        const size_t need = pad(sizeof(InfixSizes)) + pad(count * sizeof(LaneItem)) + distances.need(count) + starts.need(count) + ends.need(count);
+        Carver sc = carve(sc_entry->buf, sc_entry->bytes, need);
+        InfixSizes *sizes = sc.take<InfixSizes>(1);
+        LaneItem *items = sc.take<LaneItem>(count);
+        distances.place(sc, count); starts.place(sc, count); ends.place(sc, count);
+
+        const InfixSizes got = measure(scope, sizes, [&] { launch_infix_sizes(scope, t, sizes, items); });
+        if (got.first_oversize != ~0ull) {
+            const size_t i = (size_t)got.first_oversize;
+            const uint64_t m = string_symbols(t.patterns, t.p_off64, i, stream);
+            scope->stamps_used = 0;
+            return fail(error, swh_unsupported_length_k, "pair %zu: a pattern of %llu symbols exceeds SWH_INFIX_MAX_PATTERN (2048)", i,
+                        (unsigned long long)m);
+        }
+
+        InfixRun run{};
+        run.items = items; run.item_count = got.items;
+        run.distances = distances.dev; run.starts = starts.dev; run.ends = ends.dev;
+        run.bound = bound;
+        run.wide_text = !cp && got.text_symbols >= 16;
+        launch_infix_forward(scope, t, run);
+        launch_infix_starts(scope, t, run);
+        distances.copy_back(stream, count); starts.copy_back(stream, count); ends.copy_back(stream, count);
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        close_call(scope, got.cells, (cp ? 4 : 1) * got.symbols + 2 * (count + 1) * 8 + 3 * count * 4);
+        return swh_success_k;
+    });
+}
+
+// no scope or engine can exist without a device: a call that gets a null handle says so where there is none, as scope creation does
+// (infix search and the scored families ask; top-k, within and align answer "null scope or engine" without the probe)
+static swh_status_t probe_null_handles(swh_levenshtein_t e, swh_scope_t s, const char **error) {
+    if (s && e) return swh_success_k;
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0) {
+        (void)hipGetLastError();
+        return fail(error, swh_no_device_k, "no HIP device visible (this backend has no CPU path)");
+    }
+    return fail(error, swh_invalid_argument_k, "null scope or engine");
+}
+static swh_status_t infix_checks(swh_levenshtein_t e, swh_scope_t s, size_t p_count, size_t t_count, const uint32_t *distances,
+                                 const uint32_t *starts, const uint32_t *ends, const char **error) {
+    const Engine *engine = (const Engine *)e;
+    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (!engine->unit_costs) return fail(error, swh_not_implemented_k, "infix search needs unit costs (match 0, mismatch 1, open 1, extend 1)");
+    if (p_count != t_count) return fail(error, swh_invalid_argument_k, "patterns and texts must hold the same number of strings");
+    if (p_count && (!distances || !starts || !ends)) return fail(error, swh_invalid_argument_k, "null output pointer");
+    return swh_success_k;
+}
+
+static swh_status_t infix_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts, bool utf8,
+                                uint32_t bound, const InfixOutputs &outs, const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    if (!patterns || !texts) return fail(error, swh_invalid_argument_k, "null tape");
+    status = infix_checks(e, s, patterns->count, texts->count, outs.distances, outs.starts, outs.ends, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    const bool pairs = patterns->count != 0;
+    if ((status = call.prepare(patterns, texts, utf8, pairs, pairs, error)) != swh_success_k) return status;
+    return infix_run(call.scope, call.pair, bound, outs, error);
+}
+swh_status_t swh_levenshtein_infix_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts,
+                                           uint32_t bound, uint32_t *distances, uint32_t *starts, uint32_t *ends, const char **error) {
+    return infix_tapes(e, s, patterns, texts, false, bound, InfixOutputs{distances, starts, ends}, error);
+}
+swh_status_t swh_levenshtein_utf8_infix_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts,
+                                                uint32_t bound, uint32_t *distances, uint32_t *starts, uint32_t *ends, const char **error) {
+    return infix_tapes(e, s, patterns, texts, true, bound, InfixOutputs{distances, starts, ends}, error);
+}
+swh_status_t swh_levenshtein_infix_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *patterns,
+                                            const swh_prepared_view_t *texts, uint32_t bound, uint32_t *distances, uint32_t *starts,
+                                            uint32_t *ends, const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.views(patterns, texts, false, error)) != swh_success_k) return status;
+    if ((status = infix_checks(e, s, call.pair.a_count, call.pair.b_count, distances, starts, ends, error)) != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return infix_run(call.scope, call.pair, bound, InfixOutputs{distances, starts, ends}, error);
+}
+
+// ---- OSA distances, LCS lengths / Indel distances, Jaro counts (osa.hip, lcs.hip, jaro.hip): one planner --------------------------------
+// The three families score pairs on the same phases. A sizes kernel measures the pairs (cells, symbols, the first pair over the
+// family's length limit) and cuts them into work items; one read-back of the measurements decides the errors before any output is
+// written; the family's kernel scores the items and writes whichever of its outputs the caller asked for. A pairwise call is one such
+// round. A cross-product maps pair p to (p / nb, p % nb) and runs in slices of whole rows of about kScoredChunkPairs pairs -- the item
+// list and, per output that lives on the host, the staged slice are all the scratch there is, whatever the matrix size; with more
+// than one slice the whole matrix is measured first (no items), so that a refusal still comes before the first row is written. The
+// family's test hook (test library) lowers the slice, to put many of them in a small test. The scratch is the scope's alignment
+// scratch: the calls are synchronous, and they learn nothing into the scope.
+// What a family brings is its ScoredFamily: the two launchers, its words, and the few argument rules that differ.
+//  - OSA: k_osa_sizes cuts the items by the blocks of a pair's shorter string, which holds at most SWH_OSA_MAX_SHORTER symbols; one output.
+//  - LCS / Indel: OSA's sizes kernel and limit as they stand (SWH_LCS_MAX_SHORTER); two outputs, indel and lcs.
+//  - Jaro: k_jaro_sizes cuts the items by the blocks of b, and neither string holds more than SWH_JARO_MAX_LENGTH symbols; three
+//    outputs, matches, transpositions and prefix, and the only family that holds strides to multiples of the element.
+constexpr uint64_t kScoredChunkPairs = (uint64_t)1 << 21;
+constexpr int kScoredOutputs = 3;
+
+struct ScoredFamily {
+    int outputs;   // of kScoredOutputs
+    void (*sizes)(Scope *scope, const OsaTapes &t, OsaSizes *sizes, LaneItem *items);
+    // scores the items into where[0 .. outputs), null where an output is not written by this launch, all at `stride`
+    void (*launch)(Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride,
+                   uint32_t bound, bool wide);
+    const char *chunk_hook;      // the test hook that lowers the slice
+    const char *oversize;        // how the refusal of a pair over the length limit ends
+    const char *unit_costs;      // the refusal of a general-cost engine
+    const char *null_outputs;    // the refusal of a call that wants no output ...
+    bool null_outputs_on_empty;  // ... which a call without pairs meets too
+    bool element_strides;        // strides are multiples of the element (4 bytes pairwise, 8 cross), not merely large enough
+};
+
+static const ScoredFamily kOsaFamily = {
+    1, launch_osa_sizes,
+    [](Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
+       bool wide) {
+        OsaRun run{};
+        run.items = items; run.item_count = item_count;
+        run.out = where[0];
+        run.stride = stride; run.bound = bound; run.wide = wide;
+        launch_osa(scope, t, run);
+    },
+    "STRINGWARS_AMD_OSA_CHUNK_PAIRS", "the shorter string exceeds SWH_OSA_MAX_SHORTER (2048)",
+    "OSA distances need unit costs (match 0, mismatch 1, open 1, extend 1)", "null output pointer", false, false};
+static const ScoredFamily kLcsFamily = {
+    2, launch_osa_sizes,
+    [](Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
+       bool wide) {
+        LcsRun run{};
+        run.items = items; run.item_count = item_count;
+        run.indel = where[0]; run.lcs = where[1];
+        run.stride = stride; run.bound = bound; run.wide = wide;
+        launch_lcs(scope, t, run);
+    },
+    "STRINGWARS_AMD_LCS_CHUNK_PAIRS", "the shorter string exceeds SWH_LCS_MAX_SHORTER (2048)",
+    "LCS lengths and Indel distances are called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)",
+    "null output pointers: one of indel and lcs is needed", true, false};
+static const ScoredFamily kJaroFamily = {
+    3, launch_jaro_sizes,
+    [](Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t,
+       bool wide) {
+        JaroRun run{};
+        run.items = items; run.item_count = item_count;
+        run.matches = where[0]; run.transpositions = where[1]; run.prefix = where[2];
+        run.stride = stride; run.wide = wide;
+        launch_jaro(scope, t, run);
+    },
+    "STRINGWARS_AMD_JARO_CHUNK_PAIRS", "a string exceeds SWH_JARO_MAX_LENGTH (2048)",
+    "Jaro and Jaro-Winkler counts are called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)",
+    "null output pointers: one of matches, transpositions and prefix is needed", true, true};
+
+static uint64_t scored_chunk_pairs(const char *chunk_hook) {
+    const char *hook = test_hook(chunk_hook);
+    const uint64_t pairs = hook ? (uint64_t)atoll(hook) : kScoredChunkPairs;
+    return std::max<uint64_t>(1, std::min<uint64_t>(pairs, kScoredChunkPairs));
+}
+
+struct ScoredRequest {
+    bool cross;
+    uint32_t bound;
+    void *outs[kScoredOutputs];   // the family's outputs in the order of its exports: any may be null, those past its count are
+    size_t stride;                // bytes between consecutive results (pairs) or rows (cross), of every output
+};
+
+// The pieces of a scored launch, which the score search (extract_run) scores its slices on too.
+// Strings [a_first, a_first + na) x [b_first, b_first + nb) of the call's two views: pair p is (p / nb, p % nb) of a cross-product,
+// (p, p) of a pairwise call.
+static OsaTapes scored_view(const TapePair &p, size_t a_first, size_t na, size_t b_first, size_t nb, bool cross) {
+    const bool cp = p.pa->utf8;
+    OsaTapes t{};
+    t.a = tape_side(p.pa, cp, p.a_first + a_first, na, t.a_off64);
+    t.b = tape_side(p.pb, cp, p.b_first + b_first, nb, t.b_off64);
+    t.cp = cp ? 1 : 0;
+    t.nb = cross ? nb : 0;
+    return t;
+}
+// makes `pairs` pairs from row `row0` on the view's launch, measures them and, with `items`, cuts them into items
+static OsaSizes scored_measure(Scope *scope, const ScoredFamily &f, OsaTapes &t, uint64_t row0, uint64_t pairs, OsaSizes *sizes, LaneItem *items) {
+    t.row0 = row0; t.count = pairs;
+    return measure(scope, sizes, [&] { f.sizes(scope, t, sizes, items); });
+}
+// both byte tapes hold at least 16 bytes: the kernels read the columns' string with 128-bit loads
+static bool scored_wide(const OsaTapes &t, const OsaSizes &got) { return !t.cp && got.a_total >= 16 && got.b_total >= 16; }
+// the refusal of pair (i, j) of the view, whose strings are over the family's length limit
+static swh_status_t scored_oversize(const ScoredFamily &f, const OsaTapes &t, size_t i, size_t j, bool cross, hipStream_t stream, const char **error) {
+    const uint64_t la = string_symbols(t.a, t.a_off64, i, stream), lb = string_symbols(t.b, t.b_off64, j, stream);
+    if (cross)
+        return fail(error, swh_unsupported_length_k, "pair (%zu, %zu): %llu x %llu symbols, %s", i, j, (unsigned long long)la,
+                    (unsigned long long)lb, f.oversize);
+    return fail(error, swh_unsupported_length_k, "pair %zu: %llu x %llu symbols, %s", i, (unsigned long long)la, (unsigned long long)lb, f.oversize);
+}
+
+static swh_status_t scored_run(Scope *scope, const ScoredFamily &f, const TapePair &p, const ScoredRequest &r, const char **error) {
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t na = p.a_count, nb = p.b_count;
+        if (na == 0 || nb == 0) return swh_success_k;
+        if (r.cross && na > ((uint64_t)1 << 40) / nb) return fail(error, swh_unsupported_length_k, "more than 2^40 pairs in one call");
+        const uint64_t total = r.cross ? na * nb : na;
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        // (an output the caller does not want is null, as are those past the family's count: not staged, not written)
+        Staged<char> outs[kScoredOutputs] = {Staged<char>((char *)r.outs[0]), Staged<char>((char *)r.outs[1]), Staged<char>((char *)r.outs[2])};
+        size_t staged_count = 0, wanted = 0;
+        for (int k = 0; k < f.outputs; ++k) { staged_count += outs[k].on_device ? 0 : 1; wanted += r.outs[k] ? 1 : 0; }
+        OsaTapes t = scored_view(p, 0, na, 0, nb, r.cross);
+
+        // slices: all pairs of a pairwise call; whole rows of a cross-product
+        const uint64_t rows_per_slice = r.cross ? std::max<uint64_t>(1, scored_chunk_pairs(f.chunk_hook) / nb) : na;
+        const uint64_t slices = (na + rows_per_slice - 1) / rows_per_slice;
+        const uint64_t slice_pairs = r.cross ? std::min<uint64_t>(rows_per_slice, na) * nb : na;
+        const size_t width = r.cross ? 8 : 4;
+
+        AlignScratch *sc_entry = call_scratch(scope);
+        // sizes | items | the slice's results (one array per output that lives on the host)
+        const size_t need = pad(sizeof(OsaSizes)) + pad(slice_pairs * sizeof(LaneItem)) + staged_count * pad(slice_pairs * width);
+        Carver sc = carve(sc_entry->buf, sc_entry->bytes, need);
+        OsaSizes *sizes = sc.take<OsaSizes>(1);
+        LaneItem *items = sc.take<LaneItem>(slice_pairs);
+        for (int k = 0; k < f.outputs; ++k) outs[k].place(sc, slice_pairs * width);
+
+        // with more than one slice the whole matrix is measured first (no items): a refusal comes before the first row is written
+        const OsaSizes whole = scored_measure(scope, f, t, 0, total, sizes, slices == 1 ? items : nullptr);
+        if (whole.first_oversize != ~0ull) {
+            scope->stamps_used = 0;
+            const size_t first = (size_t)whole.first_oversize;
+            return scored_oversize(f, t, r.cross ? first / nb : first, r.cross ? first % nb : first, r.cross, stream, error);
+        }
+
+        const bool wide = scored_wide(t, whole);
+        // the kernel writes its outputs at one stride: the caller's for those written in place, the packed one for those that are
+        // staged; a call with outputs of both kinds runs the slice once per kind
+        for (uint64_t q = 0; q < slices; ++q) {
+            const uint64_t row0 = q * rows_per_slice, rows = std::min<uint64_t>(rows_per_slice, na - row0);
+            const uint64_t pairs = r.cross ? rows * nb : na;
+            const uint64_t item_count = slices == 1 ? whole.items : scored_measure(scope, f, t, row0, pairs, sizes, items).items;
+            for (int packed = 0; packed < 2; ++packed) {
+                char *where[kScoredOutputs] = {};
+                bool any = false;
+                for (int k = 0; k < f.outputs; ++k) {
+                    if (!r.outs[k] || outs[k].on_device == (packed == 1)) continue;
+                    where[k] = packed ? outs[k].dev : outs[k].out + (r.cross ? row0 * r.stride : 0);
+                    any = true;
+                }
+                if (any) f.launch(scope, t, items, item_count, where, packed ? (r.cross ? nb * 8 : 4) : r.stride, r.bound, wide);
+            }
+            for (int k = 0; k < f.outputs; ++k) {   // at the caller's stride: Staged::copy_back is for contiguous outputs
+                if (outs[k].on_device) continue;
+                if (r.cross)
+                    SWH_HIP_CHECK(hipMemcpy2DAsync(outs[k].out + row0 * r.stride, r.stride, outs[k].dev, nb * 8, nb * 8, rows, hipMemcpyDeviceToHost, stream));
+                else if (r.stride == 4)
+                    outs[k].copy_back(stream, pairs * 4);
+                else
+                    SWH_HIP_CHECK(hipMemcpy2DAsync(outs[k].out, r.stride, outs[k].dev, 4, 4, pairs, hipMemcpyDeviceToHost, stream));
+            }
+            if (staged_count) SWH_HIP_CHECK(hipStreamSynchronize(stream));   // the next slice reuses the staging
+        }
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        close_call(scope, whole.cells, (t.cp ? 4 : 1) * whole.symbols + (na + nb + 2) * 8 + total * width * wanted);
+        return swh_success_k;
+    });
+}
+
+// the argument rules; a stride of 0 becomes the packed one
+static swh_status_t scored_checks(const ScoredFamily &f, swh_levenshtein_t e, size_t a_count, size_t b_count, bool cross,
+                                  void *const (&outs)[kScoredOutputs], size_t &stride, const char **error) {
+    const Engine *engine = (const Engine *)e;
+    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (!engine->unit_costs) return fail(error, swh_not_implemented_k, "%s", f.unit_costs);
+    if (!cross && a_count != b_count) return fail(error, swh_invalid_argument_k, "a and b must hold the same number of strings");
+    bool wanted = false;
+    for (int k = 0; k < f.outputs; ++k) wanted = wanted || outs[k];
+    if (!wanted && (f.null_outputs_on_empty || (a_count && b_count))) return fail(error, swh_invalid_argument_k, "%s", f.null_outputs);
+    if (cross) {
+        if (!stride) stride = b_count * 8;
+        if (f.element_strides && stride % 8) return fail(error, swh_invalid_argument_k, "row_stride_bytes must be 0 or a multiple of 8");
+        if (stride < b_count * 8) return fail(error, swh_invalid_argument_k, "row_stride_bytes too small");
+    } else {
+        if (!stride) stride = 4;
+        if (f.element_strides && stride % 4) return fail(error, swh_invalid_argument_k, "out_stride_bytes must be 0 or a multiple of 4");
+        if (stride < 4) return fail(error, swh_invalid_argument_k, "out_stride_bytes must be >= 4");
+    }
+    return swh_success_k;
+}
+
+static swh_status_t scored_tapes(const ScoredFamily &f, swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                 bool utf8, bool cross, uint32_t bound, void *const (&outs)[kScoredOutputs], size_t stride, const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    if (!a || (!b && !cross)) return fail(error, swh_invalid_argument_k, "null tape");
+    const size_t b_count = (b ? b : a)->count;   // a cross-product without b: the self-product
+    status = scored_checks(f, e, a->count, b_count, cross, outs, stride, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    const bool pairs = a->count && b_count;
+    if ((status = call.prepare(a, b, utf8, pairs, pairs, error)) != swh_success_k) return status;
+    return scored_run(call.scope, f, call.pair, ScoredRequest{cross, bound, {outs[0], outs[1], outs[2]}, stride}, error);
+}
+static swh_status_t scored_prepared(const ScoredFamily &f, swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a,
+                                    const swh_prepared_view_t *b, bool cross, uint32_t bound, void *const (&outs)[kScoredOutputs], size_t stride,
+                                    const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.views(a, b, cross, error)) != swh_success_k) return status;
+    if ((status = scored_checks(f, e, call.pair.a_count, call.pair.b_count, cross, outs, stride, error)) != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return scored_run(call.scope, f, call.pair, ScoredRequest{cross, bound, {outs[0], outs[1], outs[2]}, stride}, error);
+}
+
+swh_status_t swh_levenshtein_osa_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,
+                                               uint32_t *out, size_t stride, const char **error) {
+    return scored_tapes(kOsaFamily, e, s, a, b, false, false, bound, {out}, stride, error);
+}
+swh_status_t swh_levenshtein_utf8_osa_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                    uint32_t bound, uint32_t *out, size_t stride, const char **error) {
+    return scored_tapes(kOsaFamily, e, s, a, b, true, false, bound, {out}, stride, error);
+}
+swh_status_t swh_levenshtein_osa_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                uint32_t bound, uint32_t *out, size_t stride, const char **error) {
+    return scored_prepared(kOsaFamily, e, s, a, b, false, bound, {out}, stride, error);
+}
+swh_status_t swh_levenshtein_osa_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, size_t *out,
+                                               size_t row_stride, const char **error) {
+    return scored_tapes(kOsaFamily, e, s, a, b, false, true, SWH_UNBOUNDED, {out}, row_stride, error);
+}
+swh_status_t swh_levenshtein_utf8_osa_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                    size_t *out, size_t row_stride, const char **error) {
+    return scored_tapes(kOsaFamily, e, s, a, b, true, true, SWH_UNBOUNDED, {out}, row_stride, error);
+}
+swh_status_t swh_levenshtein_osa_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                size_t *out, size_t row_stride, const char **error) {
+    return scored_prepared(kOsaFamily, e, s, a, b, true, SWH_UNBOUNDED, {out}, row_stride, error);
+}
+
+swh_status_t swh_levenshtein_lcs_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,
+                                               uint32_t *indel, uint32_t *lcs, size_t stride, const char **error) {
+    return scored_tapes(kLcsFamily, e, s, a, b, false, false, bound, {indel, lcs}, stride, error);
+}
+swh_status_t swh_levenshtein_utf8_lcs_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                    uint32_t bound, uint32_t *indel, uint32_t *lcs, size_t stride, const char **error) {
+    return scored_tapes(kLcsFamily, e, s, a, b, true, false, bound, {indel, lcs}, stride, error);
+}
+swh_status_t swh_levenshtein_lcs_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                uint32_t bound, uint32_t *indel, uint32_t *lcs, size_t stride, const char **error) {
+    return scored_prepared(kLcsFamily, e, s, a, b, false, bound, {indel, lcs}, stride, error);
+}
+swh_status_t swh_levenshtein_lcs_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, size_t *indel,
+                                               size_t *lcs, size_t row_stride, const char **error) {
+    return scored_tapes(kLcsFamily, e, s, a, b, false, true, SWH_UNBOUNDED, {indel, lcs}, row_stride, error);
+}
+swh_status_t swh_levenshtein_utf8_lcs_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                    size_t *indel, size_t *lcs, size_t row_stride, const char **error) {
+    return scored_tapes(kLcsFamily, e, s, a, b, true, true, SWH_UNBOUNDED, {indel, lcs}, row_stride, error);
+}
+swh_status_t swh_levenshtein_lcs_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                size_t *indel, size_t *lcs, size_t row_stride, const char **error) {
+    return scored_prepared(kLcsFamily, e, s, a, b, true, SWH_UNBOUNDED, {indel, lcs}, row_stride, error);
+}
+
+// (the Jaro kernel takes no bound)
+swh_status_t swh_levenshtein_jaro_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                uint32_t *matches, uint32_t *transpositions, uint32_t *prefix, size_t stride, const char **error) {
+    return scored_tapes(kJaroFamily, e, s, a, b, false, false, SWH_UNBOUNDED, {matches, transpositions, prefix}, stride, error);
+}
+swh_status_t swh_levenshtein_utf8_jaro_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                     uint32_t *matches, uint32_t *transpositions, uint32_t *prefix, size_t stride, const char **error) {
+    return scored_tapes(kJaroFamily, e, s, a, b, true, false, SWH_UNBOUNDED, {matches, transpositions, prefix}, stride, error);
+}
+swh_status_t swh_levenshtein_jaro_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                 uint32_t *matches, uint32_t *transpositions, uint32_t *prefix, size_t stride, const char **error) {
+    return scored_prepared(kJaroFamily, e, s, a, b, false, SWH_UNBOUNDED, {matches, transpositions, prefix}, stride, error);
+}
+swh_status_t swh_levenshtein_jaro_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
+    return scored_tapes(kJaroFamily, e, s, a, b, false, true, SWH_UNBOUNDED, {matches, transpositions, prefix}, row_stride, error);
+}
+swh_status_t swh_levenshtein_utf8_jaro_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                     size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
+    return scored_tapes(kJaroFamily, e, s, a, b, true, true, SWH_UNBOUNDED, {matches, transpositions, prefix}, row_stride, error);
+}
+swh_status_t swh_levenshtein_jaro_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                 size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
+    return scored_prepared(kJaroFamily, e, s, a, b, true, SWH_UNBOUNDED, {matches, transpositions, prefix}, row_stride, error);
+}
+
+// ---- score search (extract.hip): the k best candidates by an OSA, Indel, LCS, ratio, Jaro or Jaro-Winkler score ------------------------
+// topk_run's general path with the three families as the scorers: query blocks x candidate slices of at most kScoredChunkPairs
+// pairs, each slice measured and cut into items (scored_measure) and scored by the family's launcher into dense u64 counts in scratch
+// (the candidates' slice is a view of the prepared tape: pair p of the launch is (p / columns, p % columns)) and folded into the
+// block's running lists by k_extract_select, which evaluates the float64 score. The scratch is the slice's items and counts, the
+// block's lists and, for outputs in host memory, the rows: nothing grows with queries x candidates. Both length limits follow from
+// the two tapes' own lengths, so one pass over their offsets refuses the call before anything is scored or written.
+// STRINGWARS_AMD_EXTRACT_CHUNK_PAIRS (test library) lowers the slice, to put several blocks and slices into a small test.
+struct ExtractRequest {
+    int scorer;
+    uint32_t k;
+    double cutoff, prefix_weight;
+    uint32_t *indices;
+    void *scores;
+};
+
+static swh_status_t extract_run(Scope *scope, const TapePair &p, const ExtractRequest &r, const char **error) {
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t nq = p.a_count, nc = p.b_count, k = r.k;
+        if (nq == 0) return swh_success_k;
+        const size_t index_bytes = nq * k * sizeof(uint32_t), score_bytes = nq * k * sizeof(uint64_t);
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        Staged<uint32_t> ind(r.indices); Staged<uint64_t> sco((uint64_t *)r.scores);
+        if (nc == 0) {   // every row is padding
+            ind.fill_padding(stream, nq * k); sco.fill_padding(stream, nq * k);
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            return swh_success_k;
+        }
+        const bool jaro = r.scorer >= SWH_SCORER_JARO;
+        const ScoredFamily &f = r.scorer == SWH_SCORER_OSA ? kOsaFamily : (jaro ? kJaroFamily : kLcsFamily);
+        const int counts = r.scorer == SWH_SCORER_JARO_WINKLER ? 3 : (jaro ? 2 : 1);
+        const OsaTapes whole = scored_view(p, 0, nq, 0, nc, true);   // its two sides: the queries, the candidates
+
+        // query blocks of at most 4096 rows x candidate slices, at least 64 columns wide where the slice allows it
+        const uint64_t chunk = scored_chunk_pairs("STRINGWARS_AMD_EXTRACT_CHUNK_PAIRS");
+        const uint64_t q_step = std::min<uint64_t>(nq, std::max<uint64_t>(1, std::min<uint64_t>(4096, chunk >> 6)));
+        const uint64_t c_step = std::max<uint64_t>(1, std::min<uint64_t>(nc, chunk / q_step));
+        const uint64_t slice_pairs = q_step * c_step;
+
+        // first over-long strings | sizes | items | the slice's counts | the block's lists | rows bound for the host
+        const size_t need = pad(2 * sizeof(unsigned long long)) + pad(sizeof(OsaSizes)) + pad(slice_pairs * sizeof(LaneItem)) +
+                            counts * pad(slice_pairs * 8) + pad(q_step * k * 16) + ind.need(nq * k) + sco.need(nq * k);
+        Carver sc = carve(scope->topk_scratch, scope->topk_scratch_bytes, need);
+        unsigned long long *first_over = sc.take<unsigned long long>(2);
+        OsaSizes *sizes = sc.take<OsaSizes>(1);
+        LaneItem *items = sc.take<LaneItem>(slice_pairs);
+        uint64_t *slice[kScoredOutputs] = {};
+        for (int o = 0; o < counts; ++o) slice[o] = sc.take<uint64_t>(slice_pairs);
+        char *lists = sc.take<char>(q_step * k * 16);
+        ind.place(sc, nq * k); sco.place(sc, nq * k);
+
+        // the search as one call: with profiling on, the kernels since the last absorb() go into the sum (`scoring`: the family's kernel)
+        swh_timing_t sum{};
+        char scoring_name[40] = "";
+        auto absorb = [&](bool scoring) {
+            if (scope->profiling && scope->stamps_used) {
+                SWH_HIP_CHECK(hipStreamSynchronize(stream));
+                collect_timing(scope);
+                const swh_timing_t &t = scope->last_timing;
+                sum.total_ms += t.total_ms; sum.compute_ms += t.compute_ms; sum.kernels += t.kernels;
+                if (scoring) { sum.dominant_ms += t.dominant_ms; snprintf(scoring_name, sizeof scoring_name, "%s", t.dominant_name); }
+            }
+            scope->stamps_used = 0;
+        };
+
+        // the length limits: OSA and LCS refuse a pair whose SHORTER string is over theirs, Jaro one with either string over its own
+        SWH_HIP_CHECK(hipMemsetAsync(first_over, 0xFF, 2 * sizeof(unsigned long long), stream));
+        const uint32_t limit = jaro ? SWH_JARO_MAX_LENGTH : SWH_OSA_MAX_SHORTER;
+        launch_extract_first_over(scope, whole.a, whole.a_off64, limit, first_over);
+        launch_extract_first_over(scope, whole.b, whole.b_off64, limit, first_over + 1);
+        unsigned long long over[2];
+        SWH_HIP_CHECK(hipMemcpyAsync(over, first_over, sizeof over, hipMemcpyDeviceToHost, stream));
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        absorb(false);
+        const bool a_over = over[0] != ~0ull, b_over = over[1] != ~0ull;
+        if (jaro ? (a_over || b_over) : (a_over && b_over))
+            return scored_oversize(f, whole, a_over ? (size_t)over[0] : 0, b_over ? (size_t)over[1] : 0, true, stream, error);
+
+        // a finite cutoff of the OSA scorer is the scoring kernel's bound: what it clamps is over the cutoff anyway (the LCS kernel
+        // runs unbounded: every scorer of its family reads the LCS length)
+        const uint32_t bound = r.scorer == SWH_SCORER_OSA && r.cutoff < 4294967294.0 ? (uint32_t)r.cutoff : SWH_UNBOUNDED;
+        uint64_t cutoff_bits;
+        memcpy(&cutoff_bits, &r.cutoff, sizeof cutoff_bits);
+        uint64_t symbols = 0;
+        for (uint64_t q0 = 0; q0 < nq; q0 += q_step) {
+            const uint64_t rows = std::min<uint64_t>(q_step, nq - q0);
+            SWH_HIP_CHECK(hipMemsetAsync(lists, 0xFF, rows * k * 16, stream));   // every row is padding
+            for (uint64_t c0 = 0; c0 < nc; c0 += c_step) {
+                const uint64_t columns = std::min<uint64_t>(c_step, nc - c0);
+                OsaTapes t = scored_view(p, q0, rows, c0, columns, true);
+                const OsaSizes got = scored_measure(scope, f, t, 0, rows * columns, sizes, items);
+                absorb(false);
+                if (got.first_oversize != ~0ull)   // (the memory of a prepared tape changed since the lengths were read)
+                    return fail(error, swh_unsupported_length_k, "a string of the slice at (%llu, %llu) grew over the limit: %s",
+                                (unsigned long long)q0, (unsigned long long)c0, f.oversize);
+                sum.cells += got.cells; symbols += got.symbols;
+                char *where[kScoredOutputs] = {};
+                if (jaro) for (int o = 0; o < counts; ++o) where[o] = (char *)slice[o];
+                else where[r.scorer == SWH_SCORER_OSA ? 0 : 1] = (char *)slice[0];   // the OSA distance; the LCS length
+                f.launch(scope, t, items, got.items, where, columns * 8, bound, scored_wide(t, got));
+                absorb(true);
+
+                ExtractLaunch x{};
+                for (int o = 0; o < counts; ++o) x.counts[o] = slice[o];
+                x.a = whole.a; x.b = whole.b; x.a_off64 = whole.a_off64; x.b_off64 = whole.b_off64;
+                x.rows = rows; x.columns = columns; x.row_first = q0; x.col_first = c0;
+                x.scorer = r.scorer; x.k = r.k; x.emit = c0 + columns == nc ? 1u : 0u;
+                x.cutoff_bits = cutoff_bits; x.prefix_weight = r.prefix_weight;
+                x.lists = lists; x.indices = ind.dev; x.scores = sco.dev;
+                launch_extract_select(scope, x);
+                absorb(false);
+            }
+        }
+        ind.copy_back(stream, nq * k); sco.copy_back(stream, nq * k);
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        scope->summary_pending = false;
+        scope->stamps_pending = false;
+        sum.bytes = (whole.cp ? 4 : 1) * symbols + index_bytes + score_bytes;
+        snprintf(sum.dominant_name, sizeof sum.dominant_name, "extract_select/%s", scoring_name);
+        scope->last_timing = sum;
+        if (scope->profiling) add_to_totals(scope->totals, sum);
+        return swh_success_k;
+    });
+}
+
+static swh_status_t extract_checks(swh_levenshtein_t e, swh_scope_t s, int scorer, size_t k, uint64_t cutoff_bits, uint64_t prefix_weight_bits,
+                                   size_t queries, size_t candidates, const uint32_t *indices, const void *scores, ExtractRequest &request,
+                                   const char **error) {
+    const swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    const Engine *engine = (const Engine *)e;
+    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (scorer < SWH_SCORER_OSA || scorer > SWH_SCORER_JARO_WINKLER) return fail(error, swh_invalid_argument_k, "scorer must be one of SWH_SCORER_*");
+    if (k < 1 || k > SWH_TOPK_MAX) return fail(error, swh_invalid_argument_k, "k must lie in [1, SWH_TOPK_MAX]");
+    double cutoff, prefix_weight;
+    memcpy(&cutoff, &cutoff_bits, sizeof cutoff);
+    memcpy(&prefix_weight, &prefix_weight_bits, sizeof prefix_weight);
+    if (!(cutoff >= 0.0)) return fail(error, swh_invalid_argument_k, "the cutoff must be a non-negative number (or +infinity), not NaN");
+    if (scorer == SWH_SCORER_JARO_WINKLER && !(prefix_weight >= 0.0 && prefix_weight <= 0.25))
+        return fail(error, swh_invalid_argument_k, "the prefix weight must lie in [0, 0.25]");
+    if (!engine->unit_costs)
+        return fail(error, swh_not_implemented_k, "the score search is called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)");
+    if (candidates >= 0xFFFFFFFFull) return fail(error, swh_unsupported_length_k, "2^32 - 1 candidates or more");
+    if (queries && (!indices || !scores)) return fail(error, swh_invalid_argument_k, "null output pointer");
+    request = ExtractRequest{scorer, (uint32_t)k, cutoff == 0.0 ? 0.0 : cutoff, prefix_weight, (uint32_t *)indices, (void *)scores};   // (-0.0: +0.0)
+    return swh_success_k;
+}
+
+static swh_status_t extract_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *q, const swh_tape_u64_t *c, bool utf8, int scorer,
+                                  size_t k, uint64_t cutoff_bits, uint64_t prefix_weight_bits, uint32_t *indices, void *scores, const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    if (!q) return fail(error, swh_invalid_argument_k, "null tape");
+    ExtractRequest request{};
+    status = extract_checks(e, s, scorer, k, cutoff_bits, prefix_weight_bits, q->count, (c ? c : q)->count, indices, scores, request, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    if (q->count == 0) return swh_success_k;
+    if ((status = call.prepare(q, c, utf8, true, true, error)) != swh_success_k) return status;
+    return extract_run(call.scope, call.pair, request, error);
+}
+swh_status_t swh_levenshtein_extract_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries, const swh_tape_u64_t *candidates,
+                                             int scorer, size_t k, uint64_t cutoff_bits, uint64_t prefix_weight_bits, uint32_t *indices,
+                                             void *scores, const char **error) {
+    return extract_tapes(e, s, queries, candidates, false, scorer, k, cutoff_bits, prefix_weight_bits, indices, scores, error);
+}
+swh_status_t swh_levenshtein_utf8_extract_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries,
+                                                  const swh_tape_u64_t *candidates, int scorer, size_t k, uint64_t cutoff_bits,
+                                                  uint64_t prefix_weight_bits, uint32_t *indices, void *scores, const char **error) {
+    return extract_tapes(e, s, queries, candidates, true, scorer, k, cutoff_bits, prefix_weight_bits, indices, scores, error);
+}
+swh_status_t swh_levenshtein_extract_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *queries,
+                                              const swh_prepared_view_t *candidates, int scorer, size_t k, uint64_t cutoff_bits,
+                                              uint64_t prefix_weight_bits, uint32_t *indices, void *scores, const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.views(queries, candidates, true, error)) != swh_success_k) return status;
+    ExtractRequest request{};
+    status = extract_checks(e, s, scorer, k, cutoff_bits, prefix_weight_bits, call.pair.a_count, call.pair.b_count, indices, scores, request, error);
+    if (status != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return extract_run(call.scope, call.pair, request, error);
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// within.hpp -- launchers of the Levenshtein range search (within.hip), called from api.hip.
+// within.hpp -- launchers of the Levenshtein range search (within.hip), called from two_tape.hip.
 #pragma once
 #include "common.hpp"
 

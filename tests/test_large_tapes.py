@@ -33,7 +33,7 @@ offsets only, so their u32 tapes run prepared (`raw32=False`); align, infix, OSA
 in the Python wrapper before they call, so for them a raw form would be the prepared one again and only those run (`raw=False`); the
 code-point engine runs at two bases, and raw with one far tape only (device memory, below).
 
-Device memory, by arithmetic from api.hip (no test may need more than 24 GiB):
+Device memory, by arithmetic from api.hip and, for the searches, two_tape.hip (no test may need more than 24 GiB):
   * the two buffers: 2 x (2^32 + 2^21 + 16) B = 8.004 GiB, allocated once per module and freed at its teardown;
   * byte calls add the regions' small copies, offsets, results and the searches' matrices (24 x 400 x 4 B): under 0.1 GiB -> 8.1 GiB;
   * a prepared UTF-8 tape owns (total + 4) x 4 B of symbols = 4.008 GiB at total = 2^30 + S/2, 8 B per string of offsets, and while it

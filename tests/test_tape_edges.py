@@ -14,7 +14,7 @@ Every comparison is exact, against the references of test_osa.py, test_lcs.py, t
 is computed once (`expected` remembers it) and shared by the tests. The one CPU test runs the generators alone and asserts what the
 sweeps are meant to contain.
 
-OSA, LCS and Jaro share their host path (api.hip: scored_run and its front ends); section f holds each of them to its own argument
+OSA, LCS and Jaro share their host path (two_tape.hip: scored_run and its front ends); section f holds each of them to its own argument
 rules and error texts at the C ABI, from one table."""
 import ctypes as C
 import functools
