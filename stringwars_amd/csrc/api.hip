@@ -875,6 +875,8 @@ struct Call {
             k.boundary = (int32_t *)scope->boundary;
             launch_align_long(scope, k, longest);
         }
+        else if (prepared && !utf8 && !spec.cross && spec.pa->side && spec.pb->side)   // byte views of two prepared tapes with side arrays
+            launch_bitparallel_tiled_side(scope, k, pairs, longest, spec.pa->side + 2 * spec.a_first, spec.pb->side + 2 * spec.b_first);
         else launch_bitparallel_tiled(scope, k, pairs, longest);
         if (invalid_dev) SWH_HIP_CHECK(hipMemcpyAsync(invalid_host, invalid_dev, 4 * (kUtf8AsciiWord + 2), hipMemcpyDeviceToHost, stream));
         copy_results_back();
@@ -1399,6 +1401,35 @@ swh_status_t swh_copy_to_host(swh_scope_t handle, void *dst, const void *src, si
 }  // extern "C"
 
 // ---- prepared tapes (shared with two_tape.hip: outside the C block) -----------------------------------
+// The side arrays of a byte tape with 32-bit offsets (Prepared::side): string i's first sixteen bytes into side[2 i], its last sixteen
+// into side[2 i + 1]. A window that lies inside the tape is one 16-byte load; one that crosses either end of it is put together byte by
+// byte, positions outside [0, total) as zero (so are all of them where a tape's offsets point outside it: nothing is read there).
+__global__ __launch_bounds__(256) void k_tape_side(const uint8_t *data, const uint32_t *offsets, uint64_t count, uint64_t total, uint4 *side) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const int64_t first[2] = {(int64_t)offsets[i], (int64_t)offsets[i + 1] - 16};
+#pragma unroll
+    for (int w = 0; w < 2; ++w) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (first[w] >= 0 && (uint64_t)first[w] + 16 <= total) {
+            __builtin_memcpy(&v, data + first[w], 16);
+        } else {
+            uint8_t bytes[16];
+            for (int j = 0; j < 16; ++j) {
+                const int64_t at = first[w] + j;
+                bytes[j] = at >= 0 && (uint64_t)at < total ? data[at] : (uint8_t)0;
+            }
+            __builtin_memcpy(&v, bytes, 16);
+        }
+        side[2 * i + w] = v;
+    }
+}
+// STRINGWARS_AMD_SIDE (test library): 1 builds the side arrays for a byte tape of any size, 0 never builds them (A/B runs); else -1
+static int side_hook() {
+    static const int choice = [] { const char *e = test_hook("STRINGWARS_AMD_SIDE"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
+    return choice;
+}
+
 void swh::free_prepared(Prepared *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
@@ -1500,6 +1531,28 @@ swh_status_t swh::prepare_tape(Scope *scope, const HostTape &tape, bool utf8, sw
         // (offsets that do not ascend are the caller's error and every kernel's reads stay clamped into the tape regardless; the mean only
         // sizes short.hip's chunks, so all it needs from such a tape is a difference that does not wrap)
         p->first_byte = std::min(first_byte, p->total_bytes);
+        // Side arrays, where the kernel that plans from them can be chosen for a call on this tape: byte symbols (a UTF-8 tape: pure
+        // ASCII), 32-bit offsets, strings the tiled route takes, and enough of them for launch_bitparallel_tiled's sixteen-wave
+        // workgroup. 32 bytes per string of device memory.
+        const int side_choice = side_hook();
+        const bool side_fits = (!utf8 || p->ascii) && !p->off64 && tape.count > 0;
+        if (side_fits && side_choice != 0 &&
+            (side_choice == 1 || (p->longest_bytes <= tiled_longest_limit() && tape.count >= (uint64_t)scope->compute_units * 2048))) {
+            // The arrays are an extra: where the device has no room for them the tape is prepared without them and its calls plan from
+            // the tapes' own windows, as they do for every tape that does not qualify.
+            void *side = nullptr;
+            if (hipMalloc(&side, tape.count * 2 * sizeof(uint4)) == hipSuccess) {
+                p->owned.push_back(side);
+                hipLaunchKernelGGL(k_tape_side, dim3((uint32_t)((tape.count + 255) / 256)), dim3(256), 0, stream, (const uint8_t *)p->bytes.data,
+                                   (const uint32_t *)p->bytes.offsets, (uint64_t)tape.count, p->total_bytes, (uint4 *)side);
+                SWH_HIP_CHECK(hipGetLastError());
+                // (a handle may be used from another scope's stream on this device, so the arrays are complete before it is handed out)
+                SWH_HIP_CHECK(hipStreamSynchronize(stream));
+                p->side = (const uint4 *)side;
+            } else {
+                (void)hipGetLastError();   // the refused allocation is no error of this call
+            }
+        }
         *out = (swh_prepared_t)p;
         return swh_success_k;
     } catch (const HipFailure &f) {
@@ -1787,6 +1840,17 @@ swh_status_t swh_prepared_info(swh_prepared_t handle, swh_prepared_info_t *info)
     info->ascii = p->ascii ? 1 : 0;
     return swh_success_k;
 }
+#ifdef SWH_TEST_HOOKS
+// Test library only: the side arrays of a prepared tape's first `strings` strings (32 bytes each) copied to the host. Returns how many
+// strings were copied: 0 where the tape has no side arrays.
+size_t swh_debug_prepared_side(swh_prepared_t handle, void *out, size_t strings) {
+    const Prepared *p = (const Prepared *)handle;
+    if (!p || !p->side || !out) return 0;
+    strings = std::min<size_t>(strings, (size_t)p->bytes.count);
+    if (hipSetDevice(p->device) != hipSuccess || hipMemcpy(out, p->side, strings * 32, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    return strings;
+}
+#endif
 swh_status_t swh_prepared_free(swh_prepared_t handle) {
     free_prepared((Prepared *)handle);
     return swh_success_k;

@@ -47,8 +47,15 @@ struct Prepared {
     uint64_t total_bytes = 0, total_symbols = 0;   // offsets[count]: the end of the last string (and, of the symbols, how many were decoded)
     uint64_t first_byte = 0;     // offsets[0]: a tape may be a window of a larger buffer
     uint32_t longest_bytes = 0, longest_symbols = 0;
+    // Side arrays of a byte tape (or null): per string two entries -- its first sixteen bytes [start, start + 16) and its last sixteen
+    // [end - 16, end), positions outside the tape's bytes [0, total_bytes) as zero, the neighbouring strings' bytes included. What the
+    // tiled kernel's planning needs of the strings, laid out so that it finds it by string number (tiled.hip: kSide). Only built where
+    // that kernel can be chosen: prepare_tape has the conditions.
+    const uint4 *side = nullptr;
     std::vector<void *> owned;   // device buffers that go with the handle
 };
+// (declared here, not in common.hpp, which every kernel family's profile stamp hashes)
+void launch_bitparallel_tiled_side(Scope *scope, const KernelArgs &args, uint64_t pairs, uint32_t longest_text, const uint4 *side_a, const uint4 *side_b);
 swh_status_t prepare_tape(Scope *scope, const HostTape &tape, bool utf8, swh_prepared_t *out, const char **error);
 void free_prepared(Prepared *p);
 

@@ -18,9 +18,11 @@
 // `violation` flag (host-mapped memory) and is left alone: the host only picks this kernel when tape statistics or the
 // previous call say no such pair exists, checks the flag after the call and falls back to the planned path if it is
 // set (api.hip).
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 
+#include "api.hpp"   // launch_bitparallel_tiled_side
 #include "bp_item.hpp"
 
 namespace swh {
@@ -81,14 +83,21 @@ template <typename Sym, int kWaves> constexpr size_t tiled_lds_bytes() {
     return (size_t)kWaves * (bp_table_words<Sym>() + 64) * 4 + sizeof(TileLds<tile_max(kWaves)>);
 }
 
-#ifdef SWH_TILE_PROFILE
-// Diagnostic build only (make EXTRA=-DSWH_TILE_PROFILE): wave cycles per phase of k_bitparallel_tiled, summed over waves.
-__device__ unsigned long long g_tile_phase[8];
+#if defined(SWH_TILE_PROFILE) || defined(SWH_TILE_SPANS)
+// Diagnostic builds only. make EXTRA=-DSWH_TILE_SPANS: four time stamps per workgroup of k_bitparallel_tiled, taken by its first thread
+// (tools/tile_spans.py) -- close to the shipped kernel's time. EXTRA=-DSWH_TILE_PROFILE: those, and wave cycles per phase summed over
+// the waves (tools/tile_phases.py), which make the kernel several times slower.
 __device__ unsigned long long g_tile_span[2048][4];   // per workgroup: start, end of planning, end of items, end (100 MHz clock)
 extern "C" void swh_debug_tile_spans(unsigned long long *out) {
     (void)hipDeviceSynchronize();
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tile_span), sizeof(unsigned long long) * 2048 * 4);
 }
+#define TILE_SPAN(slot) do { if (threadIdx.x == 0) g_tile_span[blockIdx.x][slot] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#else
+#define TILE_SPAN(slot) do {} while (0)
+#endif
+#ifdef SWH_TILE_PROFILE
+__device__ unsigned long long g_tile_phase[8];
 extern "C" void swh_debug_tile_phases(unsigned long long *out) {
     unsigned long long zero[8] = {};
     (void)hipDeviceSynchronize();
@@ -98,6 +107,12 @@ extern "C" void swh_debug_tile_phases(unsigned long long *out) {
 #define TILE_STAMP(slot) do { const unsigned long long now__ = __builtin_readcyclecounter(); phase_acc[slot] += now__ - phase_t; phase_t = now__; } while (0)
 #else
 #define TILE_STAMP(slot) do {} while (0)
+#endif
+
+#ifdef SWH_TEST_HOOKS
+// Test library only: how often this process chose k_bitparallel_tiled_side, so that a test sees which kernel its call ran on.
+static std::atomic<unsigned long long> g_tiled_side_launches{0};
+extern "C" unsigned long long swh_debug_tiled_side_launches() { return g_tiled_side_launches.load(); }
 #endif
 
 struct TiledArgs {
@@ -110,11 +125,17 @@ struct TiledArgs {
     PlanPartial *partials;  // per-workgroup work-unit sums (cells, symbols, maxima, "met a pair that does not fit")
     uint32_t *done_counter;
     CallSummary *summary;   // host-mapped: the last workgroup reports (common.hpp: report_call_summary)
+    const uint4 *side_a, *side_b;   // kSide: per string its first and its last sixteen bytes (api.hip: k_tape_side), already moved to the views' first strings
 };
 
 // kPlain: the launch's shape is known when the kernel is compiled -- 32-bit offsets, pairwise, unbounded (what launch_tiled_sym sends
 // there) -- so the per-pair tests of offset width, cross-product split and bound fold away.
-template <typename Sym, int kWaves, bool kWide, bool kPlain = false>
+// kSide (only with kPlain, on wide byte tapes): both tapes are prepared ones that carry side arrays, and step B takes a pair's windows from
+// them -- entries 2 p and 2 p + 1 of either array, addressed by the pair's index like its offsets, so that nothing step B loads depends
+// on anything it loaded before: everything a thread needs is requested at the very top of the tile, above the table clear and step A's
+// barrier. Positions of a window that lie outside the tape read as zero there; only positions inside BOTH strings count (the clamps
+// to min(la, lb)), so no pair needs the `inside` exception.
+template <typename Sym, int kWaves, bool kWide, bool kPlain = false, bool kSide = false>
 __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, const uint64_t a_total, const uint64_t b_total) {
     constexpr int kThreads = kWaves * 64, kTableWords = bp_table_words<Sym>();
     // pairs per thread and tile, rounded UP: ten-wave workgroups (code points) have 640 threads, and 1024 / 640 = 1 left the
@@ -133,20 +154,53 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
     }
     const KernelArgs &args = *shaped_or_sent;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    static_assert(!kSide || (kPlain && kWide && sizeof(Sym) == 1), "side arrays: the headline shape only");
     BpWave<Sym> wv;
-    wv.init((uint32_t *)smem + (size_t)wave * kTableWords, (uint32_t *)smem + (size_t)kWaves * kTableWords + wave * 64, lane,
-            a_total, b_total);
+    const auto init_tables = [&] {
+        wv.init((uint32_t *)smem + (size_t)wave * kTableWords, (uint32_t *)smem + (size_t)kWaves * kTableWords + wave * 64, lane,
+                a_total, b_total);
+    };
+    if constexpr (!kSide) init_tables();   // (kSide: under the first tile's loads)
     TileLds<kTileMax> &tl = *(TileLds<kTileMax> *)(smem + (size_t)kWaves * (kTableWords + 64) * 4);
     unsigned long long cells = 0, syms = 0;
     uint32_t maxa = 0, maxb = 0, shorts = 0, misfit = 0;
 #ifdef SWH_TILE_PROFILE
     unsigned long long phase_acc[4] = {0, 0, 0, 0}, phase_t = __builtin_readcyclecounter(), items_done = 0;
-    if (threadIdx.x == 0) g_tile_span[blockIdx.x][0] = __builtin_amdgcn_s_memrealtime();
 #endif
+    TILE_SPAN(0);
 
     for (uint32_t tile = blockIdx.x; tile < targs.tiles; tile += gridDim.x) {
         const uint64_t base = (uint64_t)tile * targs.tile;
         const uint32_t count = (uint32_t)(args.job.pairs - base < targs.tile ? args.job.pairs - base : targs.tile);
+        // (two pairs per thread at a time: a pair's four 16-byte windows are 16 registers while they are in flight)
+#ifndef SWH_TILE_BATCH
+#define SWH_TILE_BATCH 2
+#endif
+        constexpr int kBatch = kPer < SWH_TILE_BATCH ? kPer : SWH_TILE_BATCH;
+        static_assert(kPer % kBatch == 0, "pairs per thread come in whole batches");
+        // (kSide) what step B reads of a batch -- four offsets and four windows per pair, all of them addressed by the pair's index -- is
+        // requested here, before anything else, for the first batch, and for the next one as soon as a batch's windows have been used
+        // (all four pairs' windows at once made the kernel spill, as they did on the other path)
+        constexpr int kBatchSide = kSide ? kBatch : 1;
+        [[maybe_unused]] uint32_t side_off[kBatchSide][4];
+        [[maybe_unused]] uint4 side_win[kBatchSide][4];
+        [[maybe_unused]] const auto request_side = [&](int kb) {
+            // (the tile's own bases, wave-uniform, and 32-bit indices into the tile: no address takes a register pair)
+            const uint32_t *oa = (const uint32_t *)args.job.a.offsets + base, *ob = (const uint32_t *)args.job.b.offsets + base;
+            const uint4 *sa = targs.side_a + 2 * base, *sb = targs.side_b + 2 * base;
+#pragma unroll
+            for (int j = 0; j < kBatchSide; ++j) {
+                const uint32_t idx = (uint32_t)(kb + j) * kThreads + threadIdx.x, at = idx < count ? idx : count - 1;
+                const uint32_t *xa = (const uint32_t *)((const char *)oa + at * 4u), *xb = (const uint32_t *)((const char *)ob + at * 4u);
+                const uint4 *wa = (const uint4 *)((const char *)sa + at * 32u), *wb = (const uint4 *)((const char *)sb + at * 32u);
+                side_off[j][0] = xa[0]; side_off[j][1] = xa[1]; side_off[j][2] = xb[0]; side_off[j][3] = xb[1];
+                side_win[j][0] = wa[0]; side_win[j][1] = wa[1]; side_win[j][2] = wb[0]; side_win[j][3] = wb[1];
+            }
+        };
+        if constexpr (kSide) {
+            request_side(0);
+            if (tile == blockIdx.x) init_tables();
+        }
         // ---- A: clear the counters ------------------------------------------------------------------------------
         __builtin_amdgcn_s_setprio(3);   // planning is a chain of round trips and barriers: it goes first, the work items of other workgroups fill the gaps
         for (int i = threadIdx.x; i < kTileBins / 2; i += kThreads) tl.bins[i] = 0;
@@ -159,23 +213,22 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
         // pair. What a pair shares at both ends is cut off before it is classified (the first thing rapidfuzz's Levenshtein
         // does, too): up to kAffixCap symbols each, kept in the upper bits of the pair's entry in the tile's index list.
         uint32_t cls[kPer], txt[kPer], rank[kPer], affix[kPer];
-        [[maybe_unused]] unsigned long long lo_a = ~0ull, hi_a = 0, lo_b = ~0ull, hi_b = 0;   // where my pairs' strings lie (whole strings, affixes included)
-        // (two pairs per thread at a time: a pair's four 16-byte windows are 16 registers while they are in flight)
-#ifndef SWH_TILE_BATCH
-#define SWH_TILE_BATCH 2
-#endif
-        constexpr int kBatch = kPer < SWH_TILE_BATCH ? kPer : SWH_TILE_BATCH;
-        static_assert(kPer % kBatch == 0, "pairs per thread come in whole batches");
+        using Ext = std::conditional_t<kSide, uint32_t, unsigned long long>;   // (kSide's offsets are 32-bit ones: half the registers)
+        [[maybe_unused]] Ext lo_a = (Ext)~0ull, hi_a = 0, lo_b = (Ext)~0ull, hi_b = 0;   // where my pairs' strings lie (whole strings, affixes included)
 #pragma unroll
         for (int kb = 0; kb < kPer; kb += kBatch) {
-        uint64_t a0s[kBatch], b0s[kBatch];
+        std::conditional_t<kSide, uint32_t, uint64_t> a0s[kBatch], b0s[kBatch];
         uint32_t las[kBatch], lbs[kBatch];
 #pragma unroll
         for (int j = 0; j < kBatch; ++j) {
             const int k = kb + j;
             const uint64_t p = base + (uint32_t)k * kThreads + threadIdx.x;
             const uint64_t pc = p < args.job.pairs ? p : args.job.pairs - 1;
-            if (args.off64) pair_extent<uint64_t, true>(args.job, pc, a0s[j], las[j], b0s[j], lbs[j]);
+            if constexpr (kSide) {
+                a0s[j] = side_off[j][0]; las[j] = side_off[j][1] - side_off[j][0];
+                b0s[j] = side_off[j][2]; lbs[j] = side_off[j][3] - side_off[j][2];
+            }
+            else if (args.off64) pair_extent<uint64_t, true>(args.job, pc, a0s[j], las[j], b0s[j], lbs[j]);
             else pair_extent<uint32_t, true>(args.job, pc, a0s[j], las[j], b0s[j], lbs[j]);
             affix[k] = 0;
         }
@@ -185,6 +238,11 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
                 bool inside[kBatch];
 #pragma unroll
                 for (int j = 0; j < kBatch; ++j) {
+                    if constexpr (kSide) {
+                        inside[j] = true;
+                        ha[j] = side_win[j][0]; ta[j] = side_win[j][1]; hb[j] = side_win[j][2]; tb[j] = side_win[j][3];
+                        continue;
+                    }
                     // windows that would leave the tapes (the first / last strings) are read at the tapes' start and not used
                     const uint64_t ea = a0s[j] + las[j], eb = b0s[j] + lbs[j];
                     inside[j] = a0s[j] + 16 <= a_total && b0s[j] + 16 <= b_total && ea >= 16 && eb >= 16;
@@ -208,6 +266,9 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
                     affix[kb + j] = inside[j] ? pre | (suf << 6) : 0u;
                 }
             }
+        }
+        if constexpr (kSide) {
+            if (kb + kBatch < kPer) request_side(kb + kBatch);   // under this batch's class counters
         }
 #pragma unroll
         for (int j = 0; j < kBatch; ++j) {
@@ -265,8 +326,8 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
                 }
             }
             if (lane == 0) {
-                atomicMin(&tl.span.lo_a, lo_a); atomicMax(&tl.span.hi_a, hi_a);
-                atomicMin(&tl.span.lo_b, lo_b); atomicMax(&tl.span.hi_b, hi_b);
+                atomicMin(&tl.span.lo_a, (unsigned long long)lo_a); atomicMax(&tl.span.hi_a, (unsigned long long)hi_a);
+                atomicMin(&tl.span.lo_b, (unsigned long long)lo_b); atomicMax(&tl.span.hi_b, (unsigned long long)hi_b);
             }
         }
         __syncthreads();
@@ -385,9 +446,7 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
         }
         __syncthreads();
         TILE_STAMP(0);   // planning the tile
-#ifdef SWH_TILE_PROFILE
-        if (threadIdx.x == 0) g_tile_span[blockIdx.x][1] = __builtin_amdgcn_s_memrealtime();
-#endif
+        TILE_SPAN(1);
         // The key counters have done their work: keep the 64 class starts (class_thr is free since step D), then the
         // 4 KB they occupied stage the tile's distances -- one coalesced sweep at the end instead of 4-byte stores
         // scattered over the tile's window (which reached HBM as one 32-byte sector each: 6x the result bytes).
@@ -453,17 +512,15 @@ __device__ __forceinline__ void tiled_run(const TiledArgs &targs, char *smem, co
         TILE_STAMP(1);   // work items
         __syncthreads();
         TILE_STAMP(2);   // waiting for the workgroup's other waves
-#ifdef SWH_TILE_PROFILE
-        if (threadIdx.x == 0) g_tile_span[blockIdx.x][2] = __builtin_amdgcn_s_memrealtime();
-#endif
+        TILE_SPAN(2);
         for (uint32_t i = threadIdx.x; i < count; i += kThreads) {
             const uint32_t d = staged[i];
             if (d != 0xFFFFu) store_result(args.job, base + i, (int64_t)d);
         }
         __syncthreads();   // the next tile rewrites the lists
     }
+    TILE_SPAN(3);
 #ifdef SWH_TILE_PROFILE
-    if (threadIdx.x == 0) g_tile_span[blockIdx.x][3] = __builtin_amdgcn_s_memrealtime();
     if (lane == 0) {
         for (int q = 0; q < 3; ++q) atomicAdd(&g_tile_phase[q], phase_acc[q]);
         atomicAdd(&g_tile_phase[3], 1ull);
@@ -513,6 +570,18 @@ __global__ __launch_bounds__(kWaves * 64, BpTraits<Sym>::kMinWavesPerSimd) void 
     }
 }
 
+// The plain-shape kernel on two prepared tapes with side arrays (tiled_run: kSide). A kernel of its own name rather than one more
+// parameter of the template above, which would rename every instantiation in the profiles and the resource table. Tapes shorter than a
+// window cut no affixes and so read no side arrays.
+template <int kWaves>
+__global__ __launch_bounds__(kWaves * 64, BpTraits<uint8_t>::kMinWavesPerSimd) void k_bitparallel_tiled_side(TiledArgs targs) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const KernelArgs &args = targs.k;
+    const uint64_t a_total = tape_total<uint32_t>(args.job.a), b_total = tape_total<uint32_t>(args.job.b);
+    if (a_total >= 16 && b_total >= 16) tiled_run<uint8_t, kWaves, true, true, true>(targs, smem, a_total, b_total);
+    else tiled_run<uint8_t, kWaves, false, true>(targs, smem, a_total, b_total);
+}
+
 // Tile size: every workgroup slot should get the same number of tiles (1, 2, ...), tiles stay <= kTileMax pairs, and a
 // batch too small to give every slot a useful tile uses fewer workgroups instead of smaller tiles.
 TilePlan plan_tiles(uint64_t pairs, uint32_t slots, uint32_t longest_text, uint32_t kTileMax) {
@@ -534,7 +603,7 @@ TilePlan plan_tiles(uint64_t pairs, uint32_t slots, uint32_t longest_text, uint3
 }
 
 template <typename Sym, int kWaves>
-static void launch_tiled_sym(Scope *scope, const KernelArgs &args, uint64_t pairs, uint32_t longest_text) {
+static void launch_tiled_sym(Scope *scope, const KernelArgs &args, uint64_t pairs, uint32_t longest_text, const uint4 *side_a, const uint4 *side_b) {
     constexpr size_t lds = tiled_lds_bytes<Sym, kWaves>();
     uint32_t slots = (uint32_t)scope->compute_units * (uint32_t)((160 * 1024) / lds);
     if (slots > (uint32_t)kMaxPartials) slots = kMaxPartials;
@@ -553,7 +622,17 @@ static void launch_tiled_sym(Scope *scope, const KernelArgs &args, uint64_t pair
     // the headline shape (bytes, sixteen waves, 32-bit offsets, pairwise, unbounded) has a kernel of its own
     void (*kernel)(TiledArgs) = k_bitparallel_tiled<Sym, kWaves>;
     if constexpr (sizeof(Sym) == 1 && kWaves == 16) {
-        if (!args.off64 && !args.job.cross && args.job.bound == 0xFFFFFFFFu) kernel = k_bitparallel_tiled<Sym, kWaves, true>;
+        if (!args.off64 && !args.job.cross && args.job.bound == 0xFFFFFFFFu) {
+            kernel = k_bitparallel_tiled<Sym, kWaves, true>;
+            // ... which plans its tiles from the side arrays of two prepared tapes (not where the affixes stay uncut: they are all it reads there)
+            if (side_a && side_b && t.cut_affixes) {
+                kernel = k_bitparallel_tiled_side<kWaves>;
+                t.side_a = side_a; t.side_b = side_b;
+#ifdef SWH_TEST_HOOKS
+                ++g_tiled_side_launches;
+#endif
+            }
+        }
     }
     opt_in_dynamic_lds(scope, (const void *)kernel, lds);
     static const bool debug = test_hook("STRINGWARS_AMD_DEBUG") != nullptr;
@@ -569,23 +648,29 @@ static void launch_tiled_sym(Scope *scope, const KernelArgs &args, uint64_t pair
 }
 
 void launch_bitparallel_tiled(Scope *scope, const KernelArgs &args, uint64_t pairs, uint32_t longest_text) {
+    launch_bitparallel_tiled_side(scope, args, pairs, longest_text, nullptr, nullptr);
+}
+
+// side_a / side_b: the side arrays of two prepared byte tapes (api.hpp: Prepared::side) at the views' first strings, or null. Only the
+// headline shape's kernel reads them; every other launch goes as if they were not there.
+void launch_bitparallel_tiled_side(Scope *scope, const KernelArgs &args, uint64_t pairs, uint32_t longest_text, const uint4 *side_a, const uint4 *side_b) {
     static const int forced = [] { const char *e = test_hook("STRINGWARS_AMD_TILED_WAVES"); return e ? atoi(e) : 0; }();   // comparison knob: 4; code points also 8
     if (args.sym_bytes == 4) {   // code points: 14.25 KB of tables per wave -- one workgroup of ten waves fills a CU next to the tile's lists
                                  // (latency-bound like the planned kernel: 8 -> 10 waves is 8 % on token-sized strings; STRINGWARS_AMD_TILED_WAVES=8 / =4:
                                  // eight waves; two-wave workgroups, five per CU)
-        if (forced == 4) launch_tiled_sym<uint32_t, BpTraits<uint32_t>::kWaves>(scope, args, pairs, longest_text);
-        else if (forced == 8) launch_tiled_sym<uint32_t, 8>(scope, args, pairs, longest_text);
-        else launch_tiled_sym<uint32_t, 10>(scope, args, pairs, longest_text);
+        if (forced == 4) launch_tiled_sym<uint32_t, BpTraits<uint32_t>::kWaves>(scope, args, pairs, longest_text, side_a, side_b);
+        else if (forced == 8) launch_tiled_sym<uint32_t, 8>(scope, args, pairs, longest_text, side_a, side_b);
+        else launch_tiled_sym<uint32_t, 10>(scope, args, pairs, longest_text, side_a, side_b);
     }
-    else if (forced == 4) launch_tiled_sym<uint8_t, 4>(scope, args, pairs, longest_text);
-    else if (forced == 8) launch_tiled_sym<uint8_t, 8>(scope, args, pairs, longest_text);
+    else if (forced == 4) launch_tiled_sym<uint8_t, 4>(scope, args, pairs, longest_text, side_a, side_b);
+    else if (forced == 8) launch_tiled_sym<uint8_t, 8>(scope, args, pairs, longest_text, side_a, side_b);
     // a batch that fills the device: ONE sixteen-wave workgroup per compute unit, one tile of up to 4096 pairs each. Two eight-wave
     // workgroups share a CU unevenly -- the arbiter favours the older one, it finishes at ~half time and the younger runs the rest
     // of its tile at two waves per SIMD (tools/tile_spans.py) --; sixteen waves on one ticket finish together.
     // (Not in asynchronous scopes: two pipelined launches share the device best as eight-wave workgroups side by side on a CU -- 32.8
     // TCUPS over pipelined steps against 31.2 -- where a 160 KB workgroup keeps the other launch off its CU.)
-    else if (forced == 16 || (!forced && !scope->async && pairs >= (uint64_t)scope->compute_units * 2048)) launch_tiled_sym<uint8_t, 16>(scope, args, pairs, longest_text);
-    else launch_tiled_sym<uint8_t, 8>(scope, args, pairs, longest_text);
+    else if (forced == 16 || (!forced && !scope->async && pairs >= (uint64_t)scope->compute_units * 2048)) launch_tiled_sym<uint8_t, 16>(scope, args, pairs, longest_text, side_a, side_b);
+    else launch_tiled_sym<uint8_t, 8>(scope, args, pairs, longest_text, side_a, side_b);
 }
 
 }  // namespace swh

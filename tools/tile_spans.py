@@ -1,4 +1,5 @@
-"""Diagnostic: when the workgroups of k_bitparallel_tiled start and finish (library built with EXTRA=-DSWH_TILE_PROFILE)."""
+"""Diagnostic: when the workgroups of k_bitparallel_tiled start and finish (library built with EXTRA=-DSWH_TILE_SPANS: the stamps alone, close
+to the shipped kernel; or with EXTRA=-DSWH_TILE_PROFILE)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
