@@ -333,7 +333,7 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
         uint32_t mh_in = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mh, 0x138, 0xf, 0xf, true);
         ph_in = (uint32_t)__builtin_amdgcn_bitop3_b32((int)ph_in, (int)keep_mask, (int)first_ph, 0xEA);  // (a & b) | c
         mh_in = mh_in & keep_mask;
-        if (s - blk < n) {
+        auto step = [&] {
             uint32_t xv = eq | mv;
             eq |= mh_in >> 31;
             uint32_t xh = (((eq & pv) + pv) ^ pv) | eq;
@@ -343,12 +343,18 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
             uint32_t mh_s = __builtin_amdgcn_alignbit(mh, mh_in, 31);  // (mh << 1) | hin(-1)
             pv = mh_s | ~(xv | ph_s);
             mv = ph_s & xv;
+        };
+        // (bytes) "some lane is in range" is the expected case: with that said, and with no wait or read inside the masked block
+        // (see `columns`), the compiler leaves out the s_cbranch_execz that would jump over the block for a wave with no lane in
+        // range -- sixteen VALU instructions run with an empty mask are cheaper than a branch in every column of every wave
+        if constexpr (kBytes) {
+            if (__builtin_expect(s - blk < n, 1)) step();
+        } else {
+            if (s - blk < n) step();
         }
     };
-    auto columns = [&](auto ng_tag) {
-    [[maybe_unused]] constexpr int NG = decltype(ng_tag)::value;
-    for (uint32_t s0 = 0; s0 < steps; s0 += 16) {
-        uint32_t tcur[kTextRegs];
+    // the text words of the super-step that starts at column s0, out of what fetch_text left in tnxt
+    auto take_text = [&](uint32_t (&tcur)[kTextRegs], [[maybe_unused]] uint32_t s0) {
         if constexpr (kInterior) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) tcur[q] = tnxt[q];
@@ -365,6 +371,55 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
 #pragma unroll
             for (int q = 0; q < kTextRegs; ++q) tcur[q] = tnxt[q];
         }
+    };
+    auto columns = [&](auto ng_tag) {
+    [[maybe_unused]] constexpr int NG = decltype(ng_tag)::value;
+    if constexpr (kBytes) {
+        // The eight table reads of a group of four columns are issued one group ahead, above the group before it, and their
+        // pairs are ANDed at the top of their own group: a read has four columns to come back in. They are unconditional and
+        // stand outside the columns' range tests (any text word forms addresses inside the wave's own table; words past n_eff
+        // or outside the string are read and never used), and `read_pinned` keeps the compiler from sinking them back.
+        uint32_t tcur[4], raw[8];
+        auto issue = [&](uint32_t w) {
+            raw[0] = nib.template read_lo<0>(w); raw[1] = nib.template read_hi<0>(w);
+            raw[2] = nib.template read_lo<1>(w); raw[3] = nib.template read_hi<1>(w);
+            raw[4] = nib.template read_lo<2>(w); raw[5] = nib.template read_hi<2>(w);
+            raw[6] = nib.template read_lo<3>(w); raw[7] = nib.template read_hi<3>(w);
+        };
+        take_text(tcur, 0);
+        issue(tcur[0]);
+        for (uint32_t s0 = 0; s0 < steps; s0 += 16) {
+            // unconditional: clamped addresses are always readable, and a branch around the loads would make the
+            // compiler wait for them right there (their registers merge with the skipped path's)
+            fetch_text(kInterior ? (int)s0 + 16 : (int)s0 + 16 - (int)blk);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t gs = s0 + q * 4;
+                // wave-uniform: no lane has a symbol left in this group, nor in a later one (steps is n_eff rounded up to 16);
+                // leaving both loops here keeps the reads in flight out of the loops' carried registers
+                if (gs >= n_eff) return;
+                uint32_t eqs[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) eqs[u] = raw[2 * u] & raw[2 * u + 1];
+                // The four ANDs stay here, above the columns' range tests: left alone the compiler sinks each into its column's masked
+                // block and waits for its pair there (two s_waitcnt per column, sixteen raw words live). With the wait up here a
+                // column's block holds nothing but its sixteen VALU instructions, and `column` can drop the skip branch around it.
+                asm volatile("" : "+v"(eqs[0]), "+v"(eqs[1]), "+v"(eqs[2]), "+v"(eqs[3]));
+                if (q < 3) {
+                    issue(tcur[q + 1]);
+                } else {
+                    // group 0 of the next super-step: its word is in the load requested twelve columns ago
+                    take_text(tcur, s0 + 16);
+                    issue(tcur[0]);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) column(eqs[u], gs + u);
+            }
+        }
+    } else {
+    for (uint32_t s0 = 0; s0 < steps; s0 += 16) {
+        uint32_t tcur[kTextRegs];
+        take_text(tcur, s0);
         // unconditional: clamped addresses are always readable, and a branch around the loads would make the
         // compiler wait for them right there (their registers merge with the skipped path's)
         fetch_text(kInterior ? (int)s0 + 16 : (int)s0 + 16 - (int)blk);
@@ -373,18 +428,12 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
             const uint32_t gs = s0 + q * 4;
             if (gs >= n_eff) break;  // wave-uniform: no lane has a symbol left in this group
             uint32_t eqs[4];
-            if constexpr (kBytes) {
-                eqs[0] = nib.template lookup<0>(tcur[q]);
-                eqs[1] = nib.template lookup<1>(tcur[q]);
-                eqs[2] = nib.template lookup<2>(tcur[q]);
-                eqs[3] = nib.template lookup<3>(tcur[q]);
-            } else {
 #pragma unroll
-                for (int u = 0; u < 4; ++u) eqs[u] = grp.template lookup_n<NG>(tcur[q * 4 + u]);
-            }
+            for (int u = 0; u < 4; ++u) eqs[u] = grp.template lookup_n<NG>(tcur[q * 4 + u]);
 #pragma unroll
             for (int u = 0; u < 4; ++u) column(eqs[u], gs + u);
         }
+    }
     }
     };
     if constexpr (kBytes) columns(std::integral_constant<int, 7>{});

@@ -103,6 +103,15 @@ struct NibbleTables {
     template <int U> __device__ __forceinline__ uint32_t lookup(uint32_t x) const {
         return *(const lds_u32 *)(uintptr_t)lo_addr<U>(x) & *(const lds_u32 *)(uintptr_t)(hi_addr<U>(x) + 4096);
     }
+    // The two halves of a lookup as reads that stay where they are written. A relaxed atomic load of wavefront scope is a plain
+    // ds_read_b32 and gets no wait of its own, and the compiler keeps counting it in lgkmcnt and waits where the value is first
+    // used; but it is an ordered access, so neither the sinking passes move it into the block of its only use nor the scheduler
+    // past another memory access (bp_item.hpp issues a group's reads four columns above their ANDs).
+    static __device__ __forceinline__ uint32_t read_pinned(uint32_t addr) {
+        return __hip_atomic_load((lds_u32 *)(uintptr_t)addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+    template <int U> __device__ __forceinline__ uint32_t read_lo(uint32_t x) const { return read_pinned(lo_addr<U>(x)); }
+    template <int U> __device__ __forceinline__ uint32_t read_hi(uint32_t x) const { return read_pinned(hi_addr<U>(x) + 4096); }
     template <int U> __device__ __forceinline__ void insert(uint32_t x, uint32_t bit) const {
         __hip_atomic_fetch_or((lds_u32 *)(uintptr_t)lo_addr<U>(x), bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __hip_atomic_fetch_or((lds_u32 *)(uintptr_t)(hi_addr<U>(x) + 4096), bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
