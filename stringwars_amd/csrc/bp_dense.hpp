@@ -217,14 +217,16 @@ __device__ __forceinline__ bool bp_item_dense(const KernelArgs &args, BpWave<uin
     auto column = [&](uint32_t eq, uint32_t s) {   // bp_item.hpp's
         uint32_t ph_in = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ph, 0x138, 0xf, 0xf, true);
         uint32_t mh_in = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mh, 0x138, 0xf, 0xf, true);
-        ph_in = (uint32_t)__builtin_amdgcn_bitop3_b32((int)ph_in, (int)keep_mask, (int)first_ph, 0xEA);
-        mh_in = mh_in & keep_mask;
+        ph_in |= first_ph;    // only bit 31 of either word is defined, and read
+        mh_in &= keep_mask;
+        asm volatile("" : "+v"(ph_in), "+v"(mh_in));
         if (s - blk < n) {
             uint32_t xv = eq | mv;
             eq |= mh_in >> 31;
-            uint32_t xh = (((eq & pv) + pv) ^ pv) | eq;
-            ph = mv | ~(xh | pv);
-            mh = pv & xh;
+            const uint32_t sum = (eq & pv) + pv;
+            const uint32_t xh_pv = (uint32_t)__builtin_amdgcn_bitop3_b32((int)sum, (int)pv, (int)eq, 0xFE);   // xh | pv = sum | pv | eq
+            ph = (uint32_t)__builtin_amdgcn_bitop3_b32((int)mv, (int)xh_pv, (int)pv, 0xF1);                 // mv | ~(xh | pv)
+            mh = pv & ((sum ^ pv) | eq);
             uint32_t ph_s = __builtin_amdgcn_alignbit(ph, ph_in, 31);
             uint32_t mh_s = __builtin_amdgcn_alignbit(mh, mh_in, 31);
             pv = mh_s | ~(xv | ph_s);

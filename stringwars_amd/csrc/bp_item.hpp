@@ -318,27 +318,44 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
     const uint32_t n_eff = wave_max_u32(have ? n + G - 1 : 0);
     const uint32_t steps = (n_eff + 15) & ~15u;
 
-    // Lanes that start a pair take the DP boundary (+1 horizontal delta) instead of a neighbour. The masks are
-    // made opaque so that the splice stays two plain bitwise ops (v_bitop3 / v_and issue in ~2.7 cycles); knowing
-    // where they come from, the compiler turns it into two v_cndmask_e64 (4.4 cycles each and an SGPR-pair read).
+    // Lanes that start a pair take the DP boundary (+1 horizontal delta) instead of a neighbour. A column reads nothing but
+    // BIT 31 of the two words it takes over (v_alignbit(x, *_in, 31) and mh_in >> 31), so only that bit of ph_in and mh_in is
+    // defined: ph_in = dpp(ph) | first_ph (a first block keeps the low bits of the pair in front of it, never read) and
+    // mh_in = dpp(mh) & keep_mask.
+    // One bitwise op on a DPP move is one VOP2 with the DPP modifier. The masks are made opaque so that the two stay bitwise
+    // ops; knowing where they come from, the compiler turns them into v_cndmask_e64 (4.4 cycles each and an SGPR-pair read).
     const bool first_blk = blk == 0;
     uint32_t keep_mask = first_blk ? 0u : 0xFFFFFFFFu, first_ph = first_blk ? 0x80000000u : 0u;
     asm volatile("" : "+v"(keep_mask), "+v"(first_ph));
     uint32_t pv = 0xFFFFFFFFu, mv = 0, ph = 0, mh = 0;
     // One DP column of this lane's block. (A variant without the per-lane range test for groups in which every lane
     // works was measured: fewer VALU instructions, slower kernel -- the test rides on the scalar unit for free.)
-    auto column = [&](uint32_t eq, uint32_t s) {
+    // The match vector of a byte column is Eq = lo & hi, the words of the two nibble tables (bp_window.hpp); it is never formed:
+    // the AND rides in the two ops that consume it. A code-point column brings its looked-up Eq as `lo`.
+    auto column = [&](uint32_t lo, [[maybe_unused]] uint32_t hi, uint32_t s) {
         // bound_ctrl: lane 0 (no source lane) reads 0, so no `old` register has to be re-materialised per step
         uint32_t ph_in = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ph, 0x138, 0xf, 0xf, true);
         uint32_t mh_in = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mh, 0x138, 0xf, 0xf, true);
-        ph_in = (uint32_t)__builtin_amdgcn_bitop3_b32((int)ph_in, (int)keep_mask, (int)first_ph, 0xEA);  // (a & b) | c
-        mh_in = mh_in & keep_mask;
+        ph_in |= first_ph;
+        mh_in &= keep_mask;
+        // each pair folds into one DPP VOP2 (v_or_b32_dpp, v_and_b32_dpp); pinned here, above the range test, because inside the
+        // masked block the source lanes of a DPP read may be switched off
+        asm volatile("" : "+v"(ph_in), "+v"(mh_in));
         auto step = [&] {
-            uint32_t xv = eq | mv;
-            eq |= mh_in >> 31;
-            uint32_t xh = (((eq & pv) + pv) ^ pv) | eq;
-            ph = mv | ~(xh | pv);
-            mh = pv & xh;
+            const uint32_t hin = mh_in >> 31;
+            uint32_t xv, eq;   // Eq | mv; Eq | hin(-1)
+            if constexpr (kBytes) {
+                xv = (uint32_t)__builtin_amdgcn_bitop3_b32((int)lo, (int)hi, (int)mv, 0xEA);   // (a & b) | c
+                eq = (uint32_t)__builtin_amdgcn_bitop3_b32((int)lo, (int)hi, (int)hin, 0xEA);
+            } else {
+                xv = lo | mv;
+                eq = lo | hin;
+            }
+            const uint32_t sum = (eq & pv) + pv;
+            // xh = (sum ^ pv) | eq is formed only inside mh: xh | pv = sum | pv | eq, so ph = mv | ~(xh | pv) is two v_bitop3
+            const uint32_t xh_pv = (uint32_t)__builtin_amdgcn_bitop3_b32((int)sum, (int)pv, (int)eq, 0xFE);   // a | b | c
+            ph = (uint32_t)__builtin_amdgcn_bitop3_b32((int)mv, (int)xh_pv, (int)pv, 0xF1);                 // a | ~(b | c)
+            mh = pv & ((sum ^ pv) | eq);
             uint32_t ph_s = __builtin_amdgcn_alignbit(ph, ph_in, 31);  // (ph << 1) | hin(+1)
             uint32_t mh_s = __builtin_amdgcn_alignbit(mh, mh_in, 31);  // (mh << 1) | hin(-1)
             pv = mh_s | ~(xv | ph_s);
@@ -346,7 +363,7 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
         };
         // (bytes) "some lane is in range" is the expected case: with that said, and with no wait or read inside the masked block
         // (see `columns`), the compiler leaves out the s_cbranch_execz that would jump over the block for a wave with no lane in
-        // range -- sixteen VALU instructions run with an empty mask are cheaper than a branch in every column of every wave
+        // range -- twelve VALU instructions run with an empty mask are cheaper than a branch in every column of every wave
         if constexpr (kBytes) {
             if (__builtin_expect(s - blk < n, 1)) step();
         } else {
@@ -375,8 +392,8 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
     auto columns = [&](auto ng_tag) {
     [[maybe_unused]] constexpr int NG = decltype(ng_tag)::value;
     if constexpr (kBytes) {
-        // The eight table reads of a group of four columns are issued one group ahead, above the group before it, and their
-        // pairs are ANDed at the top of their own group: a read has four columns to come back in. They are unconditional and
+        // The eight table reads of a group of four columns are issued one group ahead, above the group before it, and are
+        // waited for at the top of their own group: a read has four columns to come back in. They are unconditional and
         // stand outside the columns' range tests (any text word forms addresses inside the wave's own table; words past n_eff
         // or outside the string are read and never used), and `read_pinned` keeps the compiler from sinking them back.
         uint32_t tcur[4], raw[8];
@@ -398,13 +415,14 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
                 // wave-uniform: no lane has a symbol left in this group, nor in a later one (steps is n_eff rounded up to 16);
                 // leaving both loops here keeps the reads in flight out of the loops' carried registers
                 if (gs >= n_eff) return;
-                uint32_t eqs[4];
+                // The group's eight words are anchored here, above the columns' range tests: left alone the compiler waits for each pair
+                // inside its column's masked block (two s_waitcnt per column). With the one wait up here a column's block holds nothing
+                // but its twelve VALU instructions, and `column` can drop the skip branch around it. (Sixteen raw words are live
+                // across a group: these and the next group's, in flight.)
+                uint32_t cur[8];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) eqs[u] = raw[2 * u] & raw[2 * u + 1];
-                // The four ANDs stay here, above the columns' range tests: left alone the compiler sinks each into its column's masked
-                // block and waits for its pair there (two s_waitcnt per column, sixteen raw words live). With the wait up here a
-                // column's block holds nothing but its sixteen VALU instructions, and `column` can drop the skip branch around it.
-                asm volatile("" : "+v"(eqs[0]), "+v"(eqs[1]), "+v"(eqs[2]), "+v"(eqs[3]));
+                for (int u = 0; u < 8; ++u) cur[u] = raw[u];
+                asm volatile("" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur[4]), "+v"(cur[5]), "+v"(cur[6]), "+v"(cur[7]));
                 if (q < 3) {
                     issue(tcur[q + 1]);
                 } else {
@@ -413,7 +431,7 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
                     issue(tcur[0]);
                 }
 #pragma unroll
-                for (int u = 0; u < 4; ++u) column(eqs[u], gs + u);
+                for (int u = 0; u < 4; ++u) column(cur[2 * u], cur[2 * u + 1], gs + u);
             }
         }
     } else {
@@ -431,7 +449,7 @@ __device__ __forceinline__ void bp_item(const KernelArgs &args, BpWave<Sym> &wv,
 #pragma unroll
             for (int u = 0; u < 4; ++u) eqs[u] = grp.template lookup_n<NG>(tcur[q * 4 + u]);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) column(eqs[u], gs + u);
+            for (int u = 0; u < 4; ++u) column(eqs[u], 0u, gs + u);
         }
     }
     }
