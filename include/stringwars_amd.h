@@ -583,6 +583,59 @@ swh_status_t swh_levenshtein_extract_prepared(swh_levenshtein_t engine, swh_scop
                                               const swh_prepared_view_t *candidates, int scorer, size_t k, uint64_t cutoff_bits,
                                               uint64_t prefix_weight_bits, uint32_t *indices, void *scores, const char **error);
 
+/* ---- Score range search: EVERY candidate whose score passes the cutoff, as CSR (rapidfuzz `process.extract(query, choices,
+ *      scorer=..., score_cutoff=cutoff, limit=None)` / `process.cdist(..., score_cutoff=cutoff)`, for every query at once),
+ *      unit-cost engines only. The call takes its scores and its admission rule from the score search above and its result shape
+ *      and counting protocol from the range search (swh_levenshtein_within_*). -------------------------------------------------
+ * Scores and admission, as in swh_levenshtein_extract_*:
+ *  - `scorer` is one of SWH_SCORER_*; a score leaves with exactly the 64 bits the score search gives for that pair -- the bits of
+ *    the table's expressions, evaluated in IEEE double operation by operation as written, on the counts the pairwise and cross
+ *    calls return (the query drives the Jaro matching, the candidate is flagged; the sides are never swapped);
+ *  - `cutoff_bits` is the cutoff, a double, as its binary64 bit pattern: the distance scorers admit d <= cutoff, the similarity
+ *    scorers s >= cutoff, a score at the cutoff is admitted -- any cutoff admits the same pairs here and in the score search;
+ *  - a NaN or a negative cutoff returns swh_invalid_argument_k; so does +infinity with a distance scorer (that is the dense
+ *    cross-product, as the range search refuses SWH_UNBOUNDED). Any finite cutoff is accepted: a similarity cutoff of 0.0 returns
+ *    every pair;
+ *  - `prefix_weight_bits` is p, a double passed the same way, 0 <= p <= 0.25, else swh_invalid_argument_k; the scorers other than
+ *    SWH_SCORER_JARO_WINKLER ignore it;
+ *  - the families' length limits hold as in the score search (swh_unsupported_length_k, the message names a pair and both
+ *    lengths), and an engine whose costs are not (match 0, mismatch 1, open 1, extend 1) returns swh_not_implemented_k: both
+ *    before any output is written.
+ * Result and counting protocol, as in swh_levenshtein_within_*:
+ *  - row i holds every candidate j that passes the cutoff, in ASCENDING j, at entries [row_offsets[i], row_offsets[i + 1]) of
+ *    `indices` (uint32_t) and `scores` (double: `double[capacity]`); the output is bit-for-bit deterministic;
+ *  - `row_offsets` has queries->count + 1 entries, row_offsets[0] = 0, and is ALWAYS written in full, with the true counts.
+ *    `indices` and `scores` (`capacity` entries each) are written only if row_offsets[count] <= capacity; otherwise they are left
+ *    untouched and the call still returns swh_success_k -- the caller compares row_offsets[count] with `capacity`.
+ *    indices == NULL && scores == NULL && capacity == 0 is the counting call. One of the two arrays NULL and the other not, both
+ *    NULL with a capacity, or a NULL `row_offsets`, is swh_invalid_argument_k and nothing is written;
+ *  - candidates == NULL means queries x queries, diagonal and both orientations included;
+ *  - candidates->count must be below 0xFFFFFFFF; queries->count x candidates->count has NO 2^32 limit and the hit total is a size_t;
+ *    queries->count == 0 writes row_offsets[0] = 0 only; candidates->count == 0 makes every row empty;
+ *  - each of the three outputs may be host or device memory, independently;
+ *  - symbols are bytes, or code points in the UTF-8 variant (invalid UTF-8 -> swh_invalid_utf8_k); the prepared variant takes
+ *    what the tapes were prepared as.
+ * Worked row: query MARTHA, candidates (MARHTA, DWAYNE, MARTHA, MARTHA), SWH_SCORER_JARO_WINKLER, p = 0.1: cutoff 0.97 gives
+ * indices 2, 3 and scores 1.0, 1.0; cutoff 0.9611111111111111 gives indices 0, 2, 3 and scores 0.9611111111111111, 1.0, 1.0.
+ * The call is synchronous on every scope. The pairs are walked twice -- counted, then, if the arrays hold them, stored -- and BOTH
+ * walks score them: nothing is kept between the walks but a count per query, so a filled call costs about twice the scoring of
+ * the score search on the same shape, a counting call about once. The scratch memory does not grow with queries x candidates.
+ * With profiling on, swh_scope_last_timing describes the whole search: `cells` = sum m n over all pairs, counted once although the
+ * pairs of a filled call are walked twice; `dominant_name` is "extract_within/<kernel>", <kernel> the scoring kernel ("osa",
+ * "lcs", "jaro", or their "_u32" forms for code points) and `dominant_ms` its time over all slices of both walks. */
+swh_status_t swh_levenshtein_extract_within_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *queries,
+                                                    const swh_tape_u64_t *candidates, int scorer, uint64_t cutoff_bits,
+                                                    uint64_t prefix_weight_bits, size_t *row_offsets, uint32_t *indices,
+                                                    void *scores, size_t capacity, const char **error);
+swh_status_t swh_levenshtein_utf8_extract_within_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *queries,
+                                                         const swh_tape_u64_t *candidates, int scorer, uint64_t cutoff_bits,
+                                                         uint64_t prefix_weight_bits, size_t *row_offsets, uint32_t *indices,
+                                                         void *scores, size_t capacity, const char **error);
+swh_status_t swh_levenshtein_extract_within_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *queries,
+                                                     const swh_prepared_view_t *candidates, int scorer, uint64_t cutoff_bits,
+                                                     uint64_t prefix_weight_bits, size_t *row_offsets, uint32_t *indices,
+                                                     void *scores, size_t capacity, const char **error);
+
 /* ---- One batch over the GPUs of a multi-device scope (BASELINE config 5). --------------------------------
  * `swh_sharded_prepare_*`: HOST tapes of equal count are cut into contiguous shards balanced on the prefix sum of
  * len(a_i)*len(b_i) (DP cells, not pair counts); shard r is uploaded to and prepared on device r. The handle is the steady
@@ -690,7 +743,7 @@ const char *swh_version(void);
  * "topk" when the swh_levenshtein_topk_* calls are present, "within" when the swh_levenshtein_within_* calls are, "align" when the swh_levenshtein_align_* calls are,
  * "infix" when the swh_levenshtein_infix_* calls are, "osa" when the swh_levenshtein_osa_* calls are,
  * "lcs" when the swh_levenshtein_lcs_* calls are, "jaro" when the swh_levenshtein_jaro_* calls are, "extract" when the
- * swh_levenshtein_extract_* calls are. */
+ * swh_levenshtein_extract_* calls are, "extract_within" when the swh_levenshtein_extract_within_* calls are. */
 const char *swh_capabilities(void);
 
 #ifdef __cplusplus

@@ -417,6 +417,29 @@ public:
                                                                 distances, capacity, &err);
         check(status__, err);
     }
+    /// Score range search (swh_levenshtein_extract_within_*): every candidate of every query whose score under `scorer` passes the cutoff
+    /// (distances d <= cutoff, similarities s >= cutoff; a distance needs a finite cutoff), as CSR -- row i at entries
+    /// [row_offsets[i], row_offsets[i + 1]) of `indices` / `scores`, ascending by candidate, the scores with the bits `extract` gives.
+    /// `row_offsets` (queries.count + 1, host or device) is always written; the arrays (`capacity` entries each, host or device) only
+    /// if the total fits: a caller compares row_offsets[count] with `capacity` and calls again with larger arrays. nullptr, nullptr, 0
+    /// is the counting call. A filled call scores the pairs twice (count, then fill).
+    void extract_within(const DeviceScope &scope, int scorer, const BytesTapeView &queries, const BytesTapeView *candidates, double cutoff,
+                        size_t *row_offsets, uint32_t *indices, double *scores, size_t capacity, double prefix_weight = 0.1) const {
+        const char *err = nullptr;
+        swh_tape_u64_t q = queries.c(), c = candidates ? candidates->c() : q;
+        auto fn = utf8_ ? swh_levenshtein_utf8_extract_within_u64tape : swh_levenshtein_extract_within_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &q, candidates ? &c : nullptr, scorer, double_bits(cutoff), double_bits(prefix_weight),
+                                   row_offsets, indices, scores, capacity, &err);
+        check(status__, err);
+    }
+    void extract_within(const DeviceScope &scope, int scorer, const PreparedTape &queries, const PreparedTape *candidates, double cutoff,
+                        size_t *row_offsets, uint32_t *indices, double *scores, size_t capacity, double prefix_weight = 0.1) const {
+        const char *err = nullptr;
+        swh_prepared_view_t q = queries.c(), c = candidates ? candidates->c() : q;
+        swh_status_t status__ = swh_levenshtein_extract_within_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, scorer, double_bits(cutoff),
+                                                                        double_bits(prefix_weight), row_offsets, indices, scores, capacity, &err);
+        check(status__, err);
+    }
     /// `compute_into` over every GPU of a multi-device scope: each device fills its rows of the matrix.
     void compute_into(const DeviceScope &scope, const ShardedCross &product, size_t *matrix, size_t row_stride_bytes = 0) const {
         const char *err = nullptr;

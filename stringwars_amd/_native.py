@@ -213,6 +213,9 @@ SIGNATURES = {
     "swh_levenshtein_extract_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, _P, _P, _ERR]),
     "swh_levenshtein_utf8_extract_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, _P, _P, _ERR]),
     "swh_levenshtein_extract_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, _P, _P, _ERR]),
+    "swh_levenshtein_extract_within_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_utf8_extract_within_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_extract_within_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P, C.c_size_t, _ERR]),
     "swh_version": (C.c_char_p, []),
     "swh_capabilities": (C.c_char_p, []),
     # harness header

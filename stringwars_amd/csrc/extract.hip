@@ -4,7 +4,8 @@
 // The pairs are scored by the families' own kernels (osa.hip, lcs.hip, jaro.hip) into a slice of integer counts in scratch; the
 // kernel here is the fold, topk.hip's k_topk_select with two differences.
 //  - The score is a float64 that the host expressions (engines.py's _ratio, _jaro and _winkler, the header's formulas) define as a
-//    chain of single IEEE operations on the counts and the two symbol lengths. extract_score performs the same chain: f64 division
+//    chain of single IEEE operations on the counts and the two symbol lengths. extract_score (extract.hpp: the one function this
+//    search and extract_within.hip's both call) performs the same chain: f64 division
 //    is expanded to the correctly rounded v_div_scale / v_div_fmas / v_div_fixup sequence, and contraction is switched off for the
 //    whole evaluation -- contracted, `jaro + l * p * (1.0 - jaro)` becomes a fused multiply-add that drops the product's rounding
 //    and differs from the host in the last bit. So a score leaves with the 64 bits the host computes from the dense calls' counts.
@@ -21,41 +22,6 @@
 #include <algorithm>
 
 namespace swh {
-
-constexpr int kExtractWaves = 4;
-constexpr int kExtractBatch = 4;   // chunks of 64 columns whose loads are in flight together
-
-template <int Scorer> constexpr bool kLargerIsBetter = Scorer >= SWH_SCORER_LCS;
-
-// The score of one pair from its counts (ExtractLaunch::counts) and the symbol lengths m (query) and n (candidate), operation by
-// operation as the host writes it.
-template <int Scorer>
-__device__ __forceinline__ double extract_score(uint64_t c0, uint64_t c1, uint64_t c2, uint32_t m, uint32_t n, double prefix_weight) {
-#pragma clang fp contract(off)
-    if constexpr (Scorer == SWH_SCORER_OSA) {
-        return (double)c0;
-    } else if constexpr (Scorer == SWH_SCORER_INDEL) {
-        return (double)((uint64_t)m + n - 2 * c0);
-    } else if constexpr (Scorer == SWH_SCORER_LCS) {
-        return (double)c0;
-    } else if constexpr (Scorer == SWH_SCORER_RATIO) {
-        const double twice = 2.0 * (double)c0;
-        const double total = (double)((uint64_t)m + n - 2 * c0) + twice;
-        return total > 0 ? 100.0 * twice / total : 100.0;
-    } else {
-        double jaro;
-        if (c0 > 0) {
-            const double M = (double)c0, t = (double)c1;
-            jaro = (M / (double)m + M / (double)n + (M - t) / M) / 3.0;
-        } else {
-            jaro = (m == 0 && n == 0) ? 1.0 : 0.0;
-        }
-        if constexpr (Scorer == SWH_SCORER_JARO_WINKLER) {
-            if (jaro > 0.7) jaro = jaro + (double)c2 * prefix_weight * (1.0 - jaro);
-        }
-        return jaro;
-    }
-}
 
 template <int Scorer>
 __global__ __launch_bounds__(kExtractWaves * 64) void k_extract_select(ExtractLaunch x) {

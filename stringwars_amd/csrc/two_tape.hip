@@ -1,7 +1,8 @@
-// two_tape.hip -- the synchronous two-tape calls of include/stringwars_amd.h: top-k, range and score searches, alignments, infix
-// search and the scored families (OSA, LCS / Indel, Jaro). Host code only: the kernels are the families' own files, the engine-call
-// path the searches score their slices on is api.hip (api.hpp: what the two files share).
+// two_tape.hip -- the synchronous two-tape calls of include/stringwars_amd.h: top-k, range, score and score range searches,
+// alignments, infix search and the scored families (OSA, LCS / Indel, Jaro). Host code only: the kernels are the families' own files,
+// the engine-call path the searches score their slices on is api.hip (api.hpp: what the two files share).
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -115,6 +116,10 @@ template <typename T> struct Staged {
     void copy_back(hipStream_t stream, size_t n) const {
         if (!on_device) SWH_HIP_CHECK(hipMemcpyAsync(out, dev, n * sizeof(T), hipMemcpyDeviceToHost, stream));
     }
+    void fill_zero(hipStream_t stream, size_t n) const {      // "no row, or every row empty", where the caller's array is; waits
+        if (on_device) { SWH_HIP_CHECK(hipMemsetAsync(out, 0, n * sizeof(T), stream)); SWH_HIP_CHECK(hipStreamSynchronize(stream)); }
+        else memset(out, 0, n * sizeof(T));
+    }
     void fill_padding(hipStream_t stream, size_t n) const {   // "every row is padding": all 0xFF, where the caller's array is
         if (on_device) SWH_HIP_CHECK(hipMemsetAsync(out, 0xFF, n * sizeof(T), stream)); else memset(out, 0xFF, n * sizeof(T));
     }
@@ -149,7 +154,7 @@ static uint64_t string_symbols(const TapeRef &tape, uint32_t off64, size_t i, hi
 }
 
 // The common end of a call whose kernels have completed on the scope's stream: with profiling on they are the call's timing, once in
-// the totals. (SearchSweep::close, extract_run and within's fused path end in their own ways.)
+// the totals. (SearchSweep::close, ExtractSweep::close and within's fused path end in their own ways.)
 static void close_call(Scope *scope, uint64_t cells, uint64_t bytes) {
     if (scope->profiling && scope->stamps_used) { collect_timing(scope); add_to_totals(scope->totals, scope->last_timing); }
     scope->stamps_used = 0;
@@ -405,13 +410,7 @@ static swh_status_t within_run(Scope *scope, const Engine *engine, const TapePai
         Staged<uint64_t> offs((uint64_t *)r.row_offsets);
         Staged<uint32_t> ind(r.indices), dist(r.distances);   // (both null in a counting call: nothing is staged, nothing filled)
         if (nq == 0 || nc == 0) {   // no row, or every row empty
-            const size_t bytes = (nq + 1) * sizeof(size_t);
-            if (offs.on_device) {
-                SWH_HIP_CHECK(hipMemsetAsync(r.row_offsets, 0, bytes, stream));
-                SWH_HIP_CHECK(hipStreamSynchronize(stream));
-            } else {
-                memset(r.row_offsets, 0, bytes);
-            }
+            offs.fill_zero(stream, nq + 1);
             return swh_success_k;
         }
         const size_t ow = p.pa->off64 ? 8 : 4;
@@ -1167,6 +1166,122 @@ struct ExtractRequest {
     void *scores;
 };
 
+// What the two score searches (extract_run, extract_within_run) do alike: the family and its counts, the blocks and slices, the
+// length pre-pass, and the walk that measures and scores every slice before the search's own kernel gets it. The search as one call:
+// with profiling on, the kernels of every slice go into `sum`, the family's kernel as the dominant one.
+extern "C++" {   // (its walk is a template)
+struct ExtractSweep {
+    Scope *scope; const TapePair &p; int scorer; double cutoff, prefix_weight;
+    bool jaro; const ScoredFamily &f; int counts;
+    OsaTapes whole;   // its two sides: the queries, the candidates
+    uint64_t q_step, c_step, slice_pairs;
+    unsigned long long *first_over = nullptr;
+    OsaSizes *sizes = nullptr;
+    LaneItem *items = nullptr;
+    uint64_t *slice[kScoredOutputs] = {};
+    swh_timing_t sum{};
+    char scoring_name[40] = "";
+    uint64_t symbols = 0;
+
+    ExtractSweep(Scope *s, const TapePair &pair, int scorer_, double cutoff_, double prefix_weight_)
+        : scope(s), p(pair), scorer(scorer_), cutoff(cutoff_), prefix_weight(prefix_weight_), jaro(scorer_ >= SWH_SCORER_JARO),
+          f(scorer_ == SWH_SCORER_OSA ? kOsaFamily : (scorer_ >= SWH_SCORER_JARO ? kJaroFamily : kLcsFamily)),
+          counts(scorer_ == SWH_SCORER_JARO_WINKLER ? 3 : (scorer_ >= SWH_SCORER_JARO ? 2 : 1)),
+          whole(scored_view(pair, 0, pair.a_count, 0, pair.b_count, true)) {
+        // query blocks of at most 4096 rows x candidate slices, at least 64 columns wide where the slice allows it
+        const uint64_t nq = pair.a_count, nc = pair.b_count;
+        const uint64_t chunk = scored_chunk_pairs("STRINGWARS_AMD_EXTRACT_CHUNK_PAIRS");
+        q_step = std::min<uint64_t>(nq, std::max<uint64_t>(1, std::min<uint64_t>(4096, chunk >> 6)));
+        c_step = std::max<uint64_t>(1, std::min<uint64_t>(nc, chunk / q_step));
+        slice_pairs = q_step * c_step;
+    }
+    // first over-long strings | sizes | items | the slice's counts
+    size_t need() const {
+        return pad(2 * sizeof(unsigned long long)) + pad(sizeof(OsaSizes)) + pad(slice_pairs * sizeof(LaneItem)) + counts * pad(slice_pairs * 8);
+    }
+    void take(Carver &sc) {
+        first_over = sc.take<unsigned long long>(2);
+        sizes = sc.take<OsaSizes>(1);
+        items = sc.take<LaneItem>(slice_pairs);
+        for (int o = 0; o < counts; ++o) slice[o] = sc.take<uint64_t>(slice_pairs);
+    }
+    // the kernels since the last absorb() go into the sum (`scoring`: the family's kernel)
+    void absorb(bool scoring) {
+        if (scope->profiling && scope->stamps_used) {
+            SWH_HIP_CHECK(hipStreamSynchronize(scope->stream));
+            collect_timing(scope);
+            const swh_timing_t &t = scope->last_timing;
+            sum.total_ms += t.total_ms; sum.compute_ms += t.compute_ms; sum.kernels += t.kernels;
+            if (scoring) { sum.dominant_ms += t.dominant_ms; snprintf(scoring_name, sizeof scoring_name, "%s", t.dominant_name); }
+        }
+        scope->stamps_used = 0;
+    }
+    // The length limits: OSA and LCS refuse a pair whose SHORTER string is over theirs, Jaro one with either string over its own.
+    // Both follow from the two tapes' own lengths, so one pass over their offsets refuses the call before anything is scored or written.
+    swh_status_t lengths(const char **error) {
+        hipStream_t stream = scope->stream;
+        SWH_HIP_CHECK(hipMemsetAsync(first_over, 0xFF, 2 * sizeof(unsigned long long), stream));
+        const uint32_t limit = jaro ? SWH_JARO_MAX_LENGTH : SWH_OSA_MAX_SHORTER;
+        launch_extract_first_over(scope, whole.a, whole.a_off64, limit, first_over);
+        launch_extract_first_over(scope, whole.b, whole.b_off64, limit, first_over + 1);
+        unsigned long long over[2];
+        SWH_HIP_CHECK(hipMemcpyAsync(over, first_over, sizeof over, hipMemcpyDeviceToHost, stream));
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        absorb(false);
+        const bool a_over = over[0] != ~0ull, b_over = over[1] != ~0ull;
+        if (jaro ? (a_over || b_over) : (a_over && b_over))
+            return scored_oversize(f, whole, a_over ? (size_t)over[0] : 0, b_over ? (size_t)over[1] : 0, true, stream, error);
+        return swh_success_k;
+    }
+    // One walk over the blocks and slices. rows_begin(rows) opens every block of queries; each slice is measured, cut into items and
+    // scored into the count arrays, and each(slice, last_slice) launches the search's own kernel on it.
+    // `counted`: the walk's cells and symbols go into the sums (a second walk of the same pairs: not again).
+    template <typename Rows, typename Each> swh_status_t walk(bool counted, const char **error, Rows rows_begin, Each each) {
+        const uint64_t nq = p.a_count, nc = p.b_count;
+        // a finite cutoff of the OSA scorer is the scoring kernel's bound: what it clamps is over the cutoff anyway (the LCS kernel
+        // runs unbounded: every scorer of its family reads the LCS length)
+        const uint32_t bound = scorer == SWH_SCORER_OSA && cutoff < 4294967294.0 ? (uint32_t)cutoff : SWH_UNBOUNDED;
+        ExtractSlice x{};
+        for (int o = 0; o < counts; ++o) x.counts[o] = slice[o];
+        x.a = whole.a; x.b = whole.b; x.a_off64 = whole.a_off64; x.b_off64 = whole.b_off64;
+        x.scorer = scorer; x.prefix_weight = prefix_weight;
+        memcpy(&x.cutoff_bits, &cutoff, sizeof x.cutoff_bits);
+        for (uint64_t q0 = 0; q0 < nq; q0 += q_step) {
+            const uint64_t rows = std::min<uint64_t>(q_step, nq - q0);
+            rows_begin(rows);
+            for (uint64_t c0 = 0; c0 < nc; c0 += c_step) {
+                const uint64_t columns = std::min<uint64_t>(c_step, nc - c0);
+                OsaTapes t = scored_view(p, q0, rows, c0, columns, true);
+                const OsaSizes got = scored_measure(scope, f, t, 0, rows * columns, sizes, items);
+                absorb(false);
+                if (got.first_oversize != ~0ull)   // (the memory of a prepared tape changed since the lengths were read)
+                    return fail(error, swh_unsupported_length_k, "a string of the slice at (%llu, %llu) grew over the limit: %s",
+                                (unsigned long long)q0, (unsigned long long)c0, f.oversize);
+                if (counted) { sum.cells += got.cells; symbols += got.symbols; }
+                char *where[kScoredOutputs] = {};
+                if (jaro) for (int o = 0; o < counts; ++o) where[o] = (char *)slice[o];
+                else where[scorer == SWH_SCORER_OSA ? 0 : 1] = (char *)slice[0];   // the OSA distance; the LCS length
+                f.launch(scope, t, items, got.items, where, columns * 8, bound, scored_wide(t, got));
+                absorb(true);
+                x.rows = rows; x.columns = columns; x.row_first = q0; x.col_first = c0;
+                each(x, c0 + columns == nc);
+                absorb(false);
+            }
+        }
+        return swh_success_k;
+    }
+    // the search as one call, "<search>/<scoring kernel>", once in the scope's totals; `out_bytes`: what it wrote for the caller
+    void close(const char *search, uint64_t out_bytes) {
+        scope->summary_pending = false;
+        scope->stamps_pending = false;
+        sum.bytes = (whole.cp ? 4 : 1) * symbols + out_bytes;
+        snprintf(sum.dominant_name, sizeof sum.dominant_name, "%s/%s", search, scoring_name);
+        scope->last_timing = sum;
+        if (scope->profiling) add_to_totals(scope->totals, sum);
+    }
+};
+}  // extern "C++"
+
 static swh_status_t extract_run(Scope *scope, const TapePair &p, const ExtractRequest &r, const char **error) {
     return synchronous_run(scope, error, [&]() -> swh_status_t {
         const uint64_t nq = p.a_count, nc = p.b_count, k = r.k;
@@ -1180,123 +1295,67 @@ static swh_status_t extract_run(Scope *scope, const TapePair &p, const ExtractRe
             SWH_HIP_CHECK(hipStreamSynchronize(stream));
             return swh_success_k;
         }
-        const bool jaro = r.scorer >= SWH_SCORER_JARO;
-        const ScoredFamily &f = r.scorer == SWH_SCORER_OSA ? kOsaFamily : (jaro ? kJaroFamily : kLcsFamily);
-        const int counts = r.scorer == SWH_SCORER_JARO_WINKLER ? 3 : (jaro ? 2 : 1);
-        const OsaTapes whole = scored_view(p, 0, nq, 0, nc, true);   // its two sides: the queries, the candidates
+        ExtractSweep sweep(scope, p, r.scorer, r.cutoff, r.prefix_weight);
 
-        // query blocks of at most 4096 rows x candidate slices, at least 64 columns wide where the slice allows it
-        const uint64_t chunk = scored_chunk_pairs("STRINGWARS_AMD_EXTRACT_CHUNK_PAIRS");
-        const uint64_t q_step = std::min<uint64_t>(nq, std::max<uint64_t>(1, std::min<uint64_t>(4096, chunk >> 6)));
-        const uint64_t c_step = std::max<uint64_t>(1, std::min<uint64_t>(nc, chunk / q_step));
-        const uint64_t slice_pairs = q_step * c_step;
-
-        // first over-long strings | sizes | items | the slice's counts | the block's lists | rows bound for the host
-        const size_t need = pad(2 * sizeof(unsigned long long)) + pad(sizeof(OsaSizes)) + pad(slice_pairs * sizeof(LaneItem)) +
-                            counts * pad(slice_pairs * 8) + pad(q_step * k * 16) + ind.need(nq * k) + sco.need(nq * k);
+        // the sweep's part | the block's lists | rows bound for the host
+        const size_t need = sweep.need() + pad(sweep.q_step * k * 16) + ind.need(nq * k) + sco.need(nq * k);
         Carver sc = carve(scope->topk_scratch, scope->topk_scratch_bytes, need);
-        unsigned long long *first_over = sc.take<unsigned long long>(2);
-        OsaSizes *sizes = sc.take<OsaSizes>(1);
-        LaneItem *items = sc.take<LaneItem>(slice_pairs);
-        uint64_t *slice[kScoredOutputs] = {};
-        for (int o = 0; o < counts; ++o) slice[o] = sc.take<uint64_t>(slice_pairs);
-        char *lists = sc.take<char>(q_step * k * 16);
+        sweep.take(sc);
+        char *lists = sc.take<char>(sweep.q_step * k * 16);
         ind.place(sc, nq * k); sco.place(sc, nq * k);
 
-        // the search as one call: with profiling on, the kernels since the last absorb() go into the sum (`scoring`: the family's kernel)
-        swh_timing_t sum{};
-        char scoring_name[40] = "";
-        auto absorb = [&](bool scoring) {
-            if (scope->profiling && scope->stamps_used) {
-                SWH_HIP_CHECK(hipStreamSynchronize(stream));
-                collect_timing(scope);
-                const swh_timing_t &t = scope->last_timing;
-                sum.total_ms += t.total_ms; sum.compute_ms += t.compute_ms; sum.kernels += t.kernels;
-                if (scoring) { sum.dominant_ms += t.dominant_ms; snprintf(scoring_name, sizeof scoring_name, "%s", t.dominant_name); }
-            }
-            scope->stamps_used = 0;
-        };
-
-        // the length limits: OSA and LCS refuse a pair whose SHORTER string is over theirs, Jaro one with either string over its own
-        SWH_HIP_CHECK(hipMemsetAsync(first_over, 0xFF, 2 * sizeof(unsigned long long), stream));
-        const uint32_t limit = jaro ? SWH_JARO_MAX_LENGTH : SWH_OSA_MAX_SHORTER;
-        launch_extract_first_over(scope, whole.a, whole.a_off64, limit, first_over);
-        launch_extract_first_over(scope, whole.b, whole.b_off64, limit, first_over + 1);
-        unsigned long long over[2];
-        SWH_HIP_CHECK(hipMemcpyAsync(over, first_over, sizeof over, hipMemcpyDeviceToHost, stream));
-        SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        absorb(false);
-        const bool a_over = over[0] != ~0ull, b_over = over[1] != ~0ull;
-        if (jaro ? (a_over || b_over) : (a_over && b_over))
-            return scored_oversize(f, whole, a_over ? (size_t)over[0] : 0, b_over ? (size_t)over[1] : 0, true, stream, error);
-
-        // a finite cutoff of the OSA scorer is the scoring kernel's bound: what it clamps is over the cutoff anyway (the LCS kernel
-        // runs unbounded: every scorer of its family reads the LCS length)
-        const uint32_t bound = r.scorer == SWH_SCORER_OSA && r.cutoff < 4294967294.0 ? (uint32_t)r.cutoff : SWH_UNBOUNDED;
-        uint64_t cutoff_bits;
-        memcpy(&cutoff_bits, &r.cutoff, sizeof cutoff_bits);
-        uint64_t symbols = 0;
-        for (uint64_t q0 = 0; q0 < nq; q0 += q_step) {
-            const uint64_t rows = std::min<uint64_t>(q_step, nq - q0);
-            SWH_HIP_CHECK(hipMemsetAsync(lists, 0xFF, rows * k * 16, stream));   // every row is padding
-            for (uint64_t c0 = 0; c0 < nc; c0 += c_step) {
-                const uint64_t columns = std::min<uint64_t>(c_step, nc - c0);
-                OsaTapes t = scored_view(p, q0, rows, c0, columns, true);
-                const OsaSizes got = scored_measure(scope, f, t, 0, rows * columns, sizes, items);
-                absorb(false);
-                if (got.first_oversize != ~0ull)   // (the memory of a prepared tape changed since the lengths were read)
-                    return fail(error, swh_unsupported_length_k, "a string of the slice at (%llu, %llu) grew over the limit: %s",
-                                (unsigned long long)q0, (unsigned long long)c0, f.oversize);
-                sum.cells += got.cells; symbols += got.symbols;
-                char *where[kScoredOutputs] = {};
-                if (jaro) for (int o = 0; o < counts; ++o) where[o] = (char *)slice[o];
-                else where[r.scorer == SWH_SCORER_OSA ? 0 : 1] = (char *)slice[0];   // the OSA distance; the LCS length
-                f.launch(scope, t, items, got.items, where, columns * 8, bound, scored_wide(t, got));
-                absorb(true);
-
+        swh_status_t status = sweep.lengths(error);
+        if (status != swh_success_k) return status;
+        status = sweep.walk(true, error,
+            [&](uint64_t rows) { SWH_HIP_CHECK(hipMemsetAsync(lists, 0xFF, rows * k * 16, stream)); },   // every row is padding
+            [&](const ExtractSlice &slice, bool last_slice) {
                 ExtractLaunch x{};
-                for (int o = 0; o < counts; ++o) x.counts[o] = slice[o];
-                x.a = whole.a; x.b = whole.b; x.a_off64 = whole.a_off64; x.b_off64 = whole.b_off64;
-                x.rows = rows; x.columns = columns; x.row_first = q0; x.col_first = c0;
-                x.scorer = r.scorer; x.k = r.k; x.emit = c0 + columns == nc ? 1u : 0u;
-                x.cutoff_bits = cutoff_bits; x.prefix_weight = r.prefix_weight;
+                static_cast<ExtractSlice &>(x) = slice;
+                x.k = r.k; x.emit = last_slice ? 1u : 0u;
                 x.lists = lists; x.indices = ind.dev; x.scores = sco.dev;
                 launch_extract_select(scope, x);
-                absorb(false);
-            }
-        }
+            });
+        if (status != swh_success_k) return status;
         ind.copy_back(stream, nq * k); sco.copy_back(stream, nq * k);
         SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        scope->summary_pending = false;
-        scope->stamps_pending = false;
-        sum.bytes = (whole.cp ? 4 : 1) * symbols + index_bytes + score_bytes;
-        snprintf(sum.dominant_name, sizeof sum.dominant_name, "extract_select/%s", scoring_name);
-        scope->last_timing = sum;
-        if (scope->profiling) add_to_totals(scope->totals, sum);
+        sweep.close("extract_select", index_bytes + score_bytes);
         return swh_success_k;
     });
 }
 
-static swh_status_t extract_checks(swh_levenshtein_t e, swh_scope_t s, int scorer, size_t k, uint64_t cutoff_bits, uint64_t prefix_weight_bits,
-                                   size_t queries, size_t candidates, const uint32_t *indices, const void *scores, ExtractRequest &request,
-                                   const char **error) {
+// the checks both score searches make, in extract's order: the handles, the engine's kind and the scorer ...
+static swh_status_t extract_scorer_checks(swh_levenshtein_t e, swh_scope_t s, int scorer, const char **error) {
     const swh_status_t status = probe_null_handles(e, s, error);
     if (status != swh_success_k) return status;
-    const Engine *engine = (const Engine *)e;
-    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (((const Engine *)e)->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
     if (scorer < SWH_SCORER_OSA || scorer > SWH_SCORER_JARO_WINKLER) return fail(error, swh_invalid_argument_k, "scorer must be one of SWH_SCORER_*");
-    if (k < 1 || k > SWH_TOPK_MAX) return fail(error, swh_invalid_argument_k, "k must lie in [1, SWH_TOPK_MAX]");
-    double cutoff, prefix_weight;
+    return swh_success_k;
+}
+// ... and the cutoff (which comes back with -0.0 made +0.0), the prefix weight, the costs and the number of candidates
+static swh_status_t extract_value_checks(swh_levenshtein_t e, int scorer, uint64_t cutoff_bits, uint64_t prefix_weight_bits, size_t candidates,
+                                         double &cutoff, double &prefix_weight, const char **error) {
     memcpy(&cutoff, &cutoff_bits, sizeof cutoff);
     memcpy(&prefix_weight, &prefix_weight_bits, sizeof prefix_weight);
     if (!(cutoff >= 0.0)) return fail(error, swh_invalid_argument_k, "the cutoff must be a non-negative number (or +infinity), not NaN");
     if (scorer == SWH_SCORER_JARO_WINKLER && !(prefix_weight >= 0.0 && prefix_weight <= 0.25))
         return fail(error, swh_invalid_argument_k, "the prefix weight must lie in [0, 0.25]");
-    if (!engine->unit_costs)
+    if (!((const Engine *)e)->unit_costs)
         return fail(error, swh_not_implemented_k, "the score search is called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)");
     if (candidates >= 0xFFFFFFFFull) return fail(error, swh_unsupported_length_k, "2^32 - 1 candidates or more");
+    if (cutoff == 0.0) cutoff = 0.0;   // (-0.0: +0.0)
+    return swh_success_k;
+}
+
+static swh_status_t extract_checks(swh_levenshtein_t e, swh_scope_t s, int scorer, size_t k, uint64_t cutoff_bits, uint64_t prefix_weight_bits,
+                                   size_t queries, size_t candidates, const uint32_t *indices, const void *scores, ExtractRequest &request,
+                                   const char **error) {
+    swh_status_t status = extract_scorer_checks(e, s, scorer, error);
+    if (status != swh_success_k) return status;
+    if (k < 1 || k > SWH_TOPK_MAX) return fail(error, swh_invalid_argument_k, "k must lie in [1, SWH_TOPK_MAX]");
+    double cutoff, prefix_weight;
+    if ((status = extract_value_checks(e, scorer, cutoff_bits, prefix_weight_bits, candidates, cutoff, prefix_weight, error)) != swh_success_k) return status;
     if (queries && (!indices || !scores)) return fail(error, swh_invalid_argument_k, "null output pointer");
-    request = ExtractRequest{scorer, (uint32_t)k, cutoff == 0.0 ? 0.0 : cutoff, prefix_weight, (uint32_t *)indices, (void *)scores};   // (-0.0: +0.0)
+    request = ExtractRequest{scorer, (uint32_t)k, cutoff, prefix_weight, (uint32_t *)indices, (void *)scores};
     return swh_success_k;
 }
 
@@ -1336,6 +1395,133 @@ swh_status_t swh_levenshtein_extract_prepared(swh_levenshtein_t e, swh_scope_t s
     if (status != swh_success_k) return status;
     if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
     return extract_run(call.scope, call.pair, request, error);
+}
+
+// ---- score range search (extract_within.hip): every candidate whose score passes the cutoff, as CSR ---------------------------------------
+// extract_run's sweep with within_run's protocol. Both walks score the pairs -- as the range search's general path does: nothing is
+// kept between them but a count per query (4 bytes) that the scan turns into a cursor (8) and the row offsets. The count walk adds
+// every slice's hits to the counts, the host reads the total (8 bytes), and only if the caller's arrays hold it the fill walk stores
+// the hits at the cursors. The scratch is the sweep's, the counts and cursors, the scan's block sums and staging for host outputs
+// (the hits' in scope->within_out, sized once the total is known): nothing grows with queries x candidates.
+struct ExtractWithinRequest {
+    int scorer;
+    double cutoff, prefix_weight;
+    size_t *row_offsets;
+    uint32_t *indices;
+    void *scores;
+    size_t capacity;
+};
+
+static swh_status_t extract_within_run(Scope *scope, const TapePair &p, const ExtractWithinRequest &r, const char **error) {
+    static_assert(sizeof(size_t) == sizeof(uint64_t), "row offsets are scanned as 64-bit words");
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t nq = p.a_count, nc = p.b_count;
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        Staged<uint64_t> offs((uint64_t *)r.row_offsets);
+        Staged<uint32_t> ind(r.indices); Staged<uint64_t> sco((uint64_t *)r.scores);   // (both null in a counting call: nothing is staged, nothing filled)
+        if (nq == 0 || nc == 0) {   // no row, or every row empty
+            offs.fill_zero(stream, nq + 1);
+            return swh_success_k;
+        }
+        ExtractSweep sweep(scope, p, r.scorer, r.cutoff, r.prefix_weight);
+        const uint64_t tiles = (nq + kWithinScanTile - 1) / kWithinScanTile;
+        // the sweep's part | a count and a cursor per query | the scan's block sums | row offsets bound for the host
+        const size_t need = sweep.need() + pad(nq * 4) + pad(nq * 8) + pad(tiles * 8) + offs.need(nq + 1);
+        Carver sc = carve(scope->topk_scratch, scope->topk_scratch_bytes, need);
+        sweep.take(sc);
+        uint32_t *hits = sc.take<uint32_t>(nq);
+        uint64_t *cursors = sc.take<uint64_t>(nq), *block_sums = sc.take<uint64_t>(tiles);
+        offs.place(sc, nq + 1);
+
+        swh_status_t status = sweep.lengths(error);
+        if (status != swh_success_k) return status;
+        ExtractWithinLaunch x{};
+        x.hits = hits; x.cursors = cursors;
+        auto no_rows_begin = [](uint64_t) {};   // (counts and cursors span all queries: nothing to open per block)
+        auto launch = [&](bool fill) {
+            return [&x, scope, fill](const ExtractSlice &slice, bool) {
+                static_cast<ExtractSlice &>(x) = slice;
+                launch_extract_within(scope, x, fill);
+            };
+        };
+        SWH_HIP_CHECK(hipMemsetAsync(hits, 0, nq * 4, stream));
+        if ((status = sweep.walk(true, error, no_rows_begin, launch(false))) != swh_success_k) return status;
+        launch_within_offsets(scope, hits, nq, 1, block_sums, cursors, offs.dev);
+        sweep.absorb(false);
+        // the offsets are complete on the device: their last word, the total (one read and wait), decides the fill
+        const uint64_t total = read_offset(offs.dev, 1, nq, true, stream);
+        offs.copy_back(stream, nq + 1);
+        const bool filled = total && total <= r.capacity;
+        if (filled) {
+            // where the fill walk writes: the caller's device arrays, or staging for its host arrays
+            Carver oc = carve(scope->within_out, scope->within_out_bytes, ind.need(total) + sco.need(total));
+            x.indices = ind.place(oc, total); x.scores = sco.place(oc, total); x.total = total;
+            if ((status = sweep.walk(false, error, no_rows_begin, launch(true))) != swh_success_k) return status;
+            ind.copy_back(stream, total); sco.copy_back(stream, total);
+        }
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        sweep.close("extract_within", (nq + 1) * 8 + (filled ? total * 12 : 0));
+        return swh_success_k;
+    });
+}
+
+static swh_status_t extract_within_checks(swh_levenshtein_t e, swh_scope_t s, int scorer, uint64_t cutoff_bits, uint64_t prefix_weight_bits,
+                                          size_t candidates, size_t *row_offsets, uint32_t *indices, void *scores, size_t capacity,
+                                          ExtractWithinRequest &request, const char **error) {
+    swh_status_t status = extract_scorer_checks(e, s, scorer, error);
+    if (status != swh_success_k) return status;
+    double cutoff, prefix_weight;
+    if ((status = extract_value_checks(e, scorer, cutoff_bits, prefix_weight_bits, candidates, cutoff, prefix_weight, error)) != swh_success_k) return status;
+    if (scorer < SWH_SCORER_LCS && std::isinf(cutoff))
+        return fail(error, swh_invalid_argument_k, "a range search by a distance needs a finite cutoff: without one it is the dense cross-product");
+    if (!row_offsets) return fail(error, swh_invalid_argument_k, "null row_offsets");
+    if (!indices != !scores) return fail(error, swh_invalid_argument_k, "indices and scores must both be given, or neither");
+    if (!indices && capacity) return fail(error, swh_invalid_argument_k, "a capacity without arrays: the counting call passes NULL, NULL, 0");
+    request = ExtractWithinRequest{scorer, cutoff, prefix_weight, row_offsets, indices, scores, capacity};
+    return swh_success_k;
+}
+
+static swh_status_t extract_within_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *q, const swh_tape_u64_t *c, bool utf8, int scorer,
+                                         uint64_t cutoff_bits, uint64_t prefix_weight_bits, size_t *row_offsets, uint32_t *indices, void *scores,
+                                         size_t capacity, const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    if (!q) return fail(error, swh_invalid_argument_k, "null tape");
+    const size_t candidates = (c ? c : q)->count;
+    ExtractWithinRequest request{};
+    status = extract_within_checks(e, s, scorer, cutoff_bits, prefix_weight_bits, candidates, row_offsets, indices, scores, capacity, request, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    // (a search without queries prepares nothing, one without candidates the queries alone: the offsets are still written)
+    if ((status = call.prepare(q, c, utf8, q->count != 0, q->count && candidates, error)) != swh_success_k) return status;
+    return extract_within_run(call.scope, call.pair, request, error);
+}
+swh_status_t swh_levenshtein_extract_within_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries,
+                                                    const swh_tape_u64_t *candidates, int scorer, uint64_t cutoff_bits, uint64_t prefix_weight_bits,
+                                                    size_t *row_offsets, uint32_t *indices, void *scores, size_t capacity, const char **error) {
+    return extract_within_tapes(e, s, queries, candidates, false, scorer, cutoff_bits, prefix_weight_bits, row_offsets, indices, scores, capacity, error);
+}
+swh_status_t swh_levenshtein_utf8_extract_within_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *queries,
+                                                         const swh_tape_u64_t *candidates, int scorer, uint64_t cutoff_bits,
+                                                         uint64_t prefix_weight_bits, size_t *row_offsets, uint32_t *indices, void *scores,
+                                                         size_t capacity, const char **error) {
+    return extract_within_tapes(e, s, queries, candidates, true, scorer, cutoff_bits, prefix_weight_bits, row_offsets, indices, scores, capacity, error);
+}
+swh_status_t swh_levenshtein_extract_within_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *queries,
+                                                     const swh_prepared_view_t *candidates, int scorer, uint64_t cutoff_bits,
+                                                     uint64_t prefix_weight_bits, size_t *row_offsets, uint32_t *indices, void *scores,
+                                                     size_t capacity, const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.views(queries, candidates, true, error)) != swh_success_k) return status;
+    ExtractWithinRequest request{};
+    status = extract_within_checks(e, s, scorer, cutoff_bits, prefix_weight_bits, call.pair.b_count, row_offsets, indices, scores, capacity, request, error);
+    if (status != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return extract_within_run(call.scope, call.pair, request, error);
 }
 
 }  // extern "C"

@@ -26,7 +26,7 @@ from . import _native as N
 __all__ = [
     "DeviceScope", "Strs", "DeviceTape", "PreparedTape", "ShardedPairs", "shard_cuts", "LevenshteinDistances", "LevenshteinDistancesUTF8",
     "NeedlemanWunschScores", "SmithWatermanScores", "edit_distance", "StringWarsError", "UNBOUNDED", "TOPK_MAX",
-    "ALIGN_MAX_CELLS", "Alignments", "RangeMatches", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "OSA_MAX_SHORTER", "LCS_MAX_SHORTER",
+    "ALIGN_MAX_CELLS", "Alignments", "RangeMatches", "ScoreMatches", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "OSA_MAX_SHORTER", "LCS_MAX_SHORTER",
     "JARO_MAX_LENGTH", "SCORERS",
 ]
 
@@ -461,6 +461,55 @@ class RangeMatches:
         return i, j, d
 
 
+class ScoreMatches:
+    """The result of ``LevenshteinDistances.extract_within``: for every query the candidates whose score passes the cutoff, as CSR.
+
+    Row ``i`` is ``indices[offsets[i]:offsets[i + 1]]`` with the float64 scores in ``scores`` at the same places, ascending by
+    candidate index (callers who want them by score sort a row, or use ``extract``). ``offsets`` is uint64 with one entry more than
+    there are queries. Arrays that live on the device (``out=`` tensors) are brought to the host when a row or the pairs are asked for.
+    The result of a counting call (``out=(offsets, None, None)``) has ``offsets`` and ``counts`` only: ``indices`` and ``scores`` are None."""
+
+    def __init__(self, offsets, indices, scores):
+        self.offsets, self.indices, self.scores = offsets, indices, scores
+        if len(offsets) < 1 or (indices is None) != (scores is None) or (indices is not None and len(indices) != len(scores)):
+            raise ValueError("offsets needs at least one entry, indices and scores the same length (or both None: counted, not filled)")
+
+    _host = staticmethod(RangeMatches._host)
+
+    def __len__(self) -> int:
+        """The number of queries (rows)."""
+        return len(self.offsets) - 1
+
+    @property
+    def counts(self) -> np.ndarray:
+        """Hits per query."""
+        return np.diff(self._host(self.offsets, np.uint64)).astype(np.uint64)
+
+    def row(self, i: int):
+        """``(indices, scores)`` of query ``i``."""
+        if not -len(self) <= i < len(self):
+            raise IndexError("query index out of range")
+        i %= len(self)
+        if self.indices is None:
+            raise ValueError("a counting call holds no rows")
+        offsets = self._host(self.offsets, np.uint64)
+        first, last = int(offsets[i]), int(offsets[i + 1])
+        return self._host(self.indices, np.uint32)[first:last], self._host(self.scores, np.float64)[first:last]
+
+    def pairs(self, upper: bool = False):
+        """Flat ``(i, j, score)`` arrays of every hit, in row order. ``upper=True`` keeps ``i < j``: each unordered pair of a
+        self-search once and no string with itself, which is what deduplication wants."""
+        if self.indices is None:
+            raise ValueError("a counting call holds no pairs")
+        total = int(self._host(self.offsets, np.uint64)[-1])
+        i = np.repeat(np.arange(len(self), dtype=np.uint64), self.counts.astype(np.int64))
+        j, score = self._host(self.indices, np.uint32)[:total], self._host(self.scores, np.float64)[:total]
+        if upper:
+            keep = i < j
+            return i[keep], j[keep], score[keep]
+        return i, j, score
+
+
 class Alignments:
     """The result of ``LevenshteinDistances.align``: a tape of edit operations, one string of op bytes per pair.
 
@@ -803,6 +852,42 @@ class LevenshteinDistances(_Engine):
                                                                     C.c_void_p(_pointer(distances)), C.byref(err)), err)
         return indices, distances
 
+    @staticmethod
+    def _csr_search(call, count, others, out, capacity, value_dtype, result):
+        """The capacity protocol of the two range searches (``within``, ``extract_within``). ``call(offsets, indices, values, room)``
+        runs the search and returns the hit total; ``values`` are the distances (uint32) or the scores (float64). With ``out`` the
+        given arrays or tensors are checked and filled (too small: the offsets are written, then ``ValueError``); without, the first
+        call has room for ``capacity`` hits and a second is made with the exact size only if they did not fit."""
+        value_width = np.dtype(value_dtype).itemsize
+        if out is not None:
+            offsets, indices, values = out
+            room = 0 if indices is None else int(indices.numel() if hasattr(indices, "numel") else indices.size)
+            for array, width, entries in ((offsets, 8, count + 1), (indices, 4, room), (values, value_width, room)):
+                if array is None:
+                    continue
+                size = int(array.numel() if hasattr(array, "numel") else array.size)
+                itemsize = array.element_size() if hasattr(array, "element_size") else array.dtype.itemsize
+                contiguous = array.is_contiguous() if hasattr(array, "is_contiguous") else array.flags.c_contiguous
+                if itemsize != width or size != entries or not contiguous:
+                    raise ValueError("out needs len(queries) + 1 64-bit offsets, and contiguous 32-bit indices and %d-bit values of one size"
+                                     % (8 * value_width))
+            if (indices is None) != (values is None):
+                raise ValueError("out needs both arrays, or None for both (the counting call)")
+            total = call(offsets, indices, values, room)
+            if indices is None:
+                return result(offsets, None, None)
+            if total > room:
+                raise ValueError("out holds %d hits, the search found %d (the offsets are written)" % (room, total))
+            return result(offsets, indices[:total], values[:total])
+        room = max(1024, 4 * (count + others)) if capacity is None else max(int(capacity), 1)
+        offsets = np.zeros(count + 1, dtype=np.uint64)
+        indices, values = np.empty(room, dtype=np.uint32), np.empty(room, dtype=value_dtype)
+        total = call(offsets, indices, values, room)
+        if total > room:
+            indices, values = np.empty(total, dtype=np.uint32), np.empty(total, dtype=value_dtype)
+            call(offsets, indices, values, total)
+        return result(offsets, indices[:total], values[:total])
+
     def within(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None, *, bound: int,
                capacity: Optional[int] = None, out=None) -> "RangeMatches":
         """Every candidate within ``bound`` edits of every query (``swh_levenshtein_within_*``): a :class:`RangeMatches`, rows in
@@ -830,33 +915,7 @@ class LevenshteinDistances(_Engine):
                            int(room), C.byref(err)), err)
             return int(offsets[count])
 
-        if out is not None:
-            offsets, indices, distances = out
-            room = 0 if indices is None else int(indices.numel() if hasattr(indices, "numel") else indices.size)
-            for array, width, entries in ((offsets, 8, count + 1), (indices, 4, room), (distances, 4, room)):
-                if array is None:
-                    continue
-                size = int(array.numel() if hasattr(array, "numel") else array.size)
-                itemsize = array.element_size() if hasattr(array, "element_size") else array.dtype.itemsize
-                contiguous = array.is_contiguous() if hasattr(array, "is_contiguous") else array.flags.c_contiguous
-                if itemsize != width or size != entries or not contiguous:
-                    raise ValueError("out needs len(queries) + 1 64-bit offsets and two contiguous 32-bit arrays of one size")
-            if (indices is None) != (distances is None):
-                raise ValueError("out needs both arrays, or None for both (the counting call)")
-            total = call(offsets, indices, distances, room)
-            if indices is None:
-                return RangeMatches(offsets, None, None)
-            if total > room:
-                raise ValueError("out holds %d hits, the search found %d (the offsets are written)" % (room, total))
-            return RangeMatches(offsets, indices[:total], distances[:total])
-        room = max(1024, 4 * (count + len(candidates if candidates is not None else queries))) if capacity is None else max(int(capacity), 1)
-        offsets = np.zeros(count + 1, dtype=np.uint64)
-        indices, distances = np.empty(room, dtype=np.uint32), np.empty(room, dtype=np.uint32)
-        total = call(offsets, indices, distances, room)
-        if total > room:
-            indices, distances = np.empty(total, dtype=np.uint32), np.empty(total, dtype=np.uint32)
-            call(offsets, indices, distances, total)
-        return RangeMatches(offsets, indices[:total], distances[:total])
+        return self._csr_search(call, count, len(candidates if candidates is not None else queries), out, capacity, np.uint32, RangeMatches)
 
     def align(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None, bound: Optional[int] = None) -> "Alignments":
         """The edit operations of every pair ``(a[i], b[i])`` on unit costs (``swh_levenshtein_align_*``): an :class:`Alignments` with
@@ -1100,6 +1159,41 @@ class LevenshteinDistances(_Engine):
         N.check(self._two_tapes(queries, candidates, scope, "extract")(N.SCORERS[scorer], int(k), bits[0], bits[1], C.c_void_p(_pointer(indices)),
                                                                        C.c_void_p(_pointer(scores)), C.byref(err)), err)
         return indices, scores
+
+    def extract_within(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None, *, scorer: str,
+                       cutoff: float, prefix_weight: float = 0.1, capacity: Optional[int] = None, out=None) -> "ScoreMatches":
+        """Every candidate of every query whose score under ``scorer`` passes ``cutoff`` (``swh_levenshtein_extract_within_*``): a
+        :class:`ScoreMatches`, rows in candidate order. Scorers, scores and admission are those of ``extract`` -- ``"osa"`` and
+        ``"indel"`` admit ``d <= cutoff`` (a finite cutoff: ``inf`` would be the dense cross-product), ``"lcs"``, ``"ratio"``,
+        ``"jaro"`` and ``"jaro_winkler"`` admit ``s >= cutoff``, a score at the cutoff is admitted, and a score has the bits
+        ``extract`` returns for that pair. ``candidates=None`` searches the queries themselves (diagonal and both orientations
+        included; ``pairs(upper=True)`` of the result is the deduplication form). Capacity and ``out=`` work as in ``within``: the
+        first call is made with room for ``capacity`` hits (default ``max(1024, 4 * (len(queries) + len(candidates)))``) and, only if
+        they did not fit, a second with the exact size the first one counted; ``out=(offsets, indices, scores)`` fills given arrays
+        or device tensors instead (``len(queries) + 1`` 64-bit offsets; 32-bit indices and 64-bit scores of equal size); if they are
+        too small the offsets are still written and ``ValueError`` is raised; ``out=(offsets, None, None)`` is the counting call.
+        A filled call scores the pairs twice (once to count, once to fill), a counting call once.
+        rapidfuzz: ``process.extract(q, candidates, scorer=fuzz.ratio, score_cutoff=cutoff, limit=None)`` per query."""
+        if scope is None:
+            raise ValueError("a DeviceScope is required")
+        if scorer not in N.SCORERS:
+            raise ValueError("scorer must be one of %s" % ", ".join(N.SCORERS))
+        if cutoff is None:
+            raise ValueError("a range search needs a cutoff; without one it is the dense cross-product")
+        queries = _as_tape(queries)
+        if candidates is not None:
+            candidates = _as_tape(candidates)
+        count = len(queries)
+        search = self._two_tapes(queries, candidates, scope, "extract_within")
+        bits = [C.c_uint64(int(np.float64(value).view(np.uint64))) for value in (cutoff, prefix_weight)]   # what memcpy of the double gives
+
+        def call(offsets, indices, scores, room):
+            err = C.c_char_p()
+            N.check(search(N.SCORERS[scorer], bits[0], bits[1], C.c_void_p(_pointer(offsets)), C.c_void_p(_pointer(indices)),
+                           C.c_void_p(_pointer(scores)), int(room), C.byref(err)), err)
+            return int(offsets[count])
+
+        return self._csr_search(call, count, len(candidates if candidates is not None else queries), out, capacity, np.float64, ScoreMatches)
 
     def pairs_sharded(self, batch: "ShardedPairs", scope: DeviceScope, bound: Optional[int] = None, out=None):
         """One batch over every GPU of a multi-device scope; the distances come back gathered, in pair order."""

@@ -157,6 +157,9 @@ extern "C" {
     fn swh_levenshtein_extract_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, scorer: c_int, k: usize, cutoff_bits: u64, prefix_weight_bits: u64, indices: *mut u32, scores: *mut c_void, error: Err) -> c_int;
     fn swh_levenshtein_utf8_extract_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, scorer: c_int, k: usize, cutoff_bits: u64, prefix_weight_bits: u64, indices: *mut u32, scores: *mut c_void, error: Err) -> c_int;
     fn swh_levenshtein_extract_prepared(engine: Handle, scope: Handle, queries: *const PreparedView, candidates: *const PreparedView, scorer: c_int, k: usize, cutoff_bits: u64, prefix_weight_bits: u64, indices: *mut u32, scores: *mut c_void, error: Err) -> c_int;
+    fn swh_levenshtein_extract_within_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, scorer: c_int, cutoff_bits: u64, prefix_weight_bits: u64, row_offsets: *mut usize, indices: *mut u32, scores: *mut c_void, capacity: usize, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_extract_within_u64tape(engine: Handle, scope: Handle, queries: *const TapeU64, candidates: *const TapeU64, scorer: c_int, cutoff_bits: u64, prefix_weight_bits: u64, row_offsets: *mut usize, indices: *mut u32, scores: *mut c_void, capacity: usize, error: Err) -> c_int;
+    fn swh_levenshtein_extract_within_prepared(engine: Handle, scope: Handle, queries: *const PreparedView, candidates: *const PreparedView, scorer: c_int, cutoff_bits: u64, prefix_weight_bits: u64, row_offsets: *mut usize, indices: *mut u32, scores: *mut c_void, capacity: usize, error: Err) -> c_int;
     fn swh_sharded_prepare_u32tape(scope: Handle, a: *const TapeU32, b: *const TapeU32, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_prepare_u64tape(scope: Handle, a: *const TapeU64, b: *const TapeU64, utf8: c_int, sharded: *mut Handle, error: Err) -> c_int;
     fn swh_sharded_free(sharded: Handle) -> c_int;
@@ -493,6 +496,38 @@ impl LevenshteinDistances {
                                                         cutoff.unwrap_or(scorer.no_cutoff()).to_bits(), prefix_weight.to_bits(), indices.as_mut_ptr(),
                                                         scores.as_mut_ptr() as *mut c_void, &mut message) }, message)
     }
+    /// Score range search: every candidate of every query whose score under `scorer` passes `cutoff` (`process.extract(scorer = ...,
+    /// score_cutoff = cutoff, limit = None)` per query), as CSR: row i is `indices` / `scores` `[row_offsets[i] .. row_offsets[i + 1])`,
+    /// ascending by candidate, the scores with the bits `extract_into` gives; `None` = q x q. A distance scorer needs a finite cutoff.
+    /// `row_offsets` (`queries.len() + 1` entries) is always filled; the two arrays only if the total fits them. Returns the total:
+    /// a caller who gets more than `indices.len()` back calls again with larger arrays (two empty slices make the counting call).
+    /// A filled call scores the pairs twice: once to count, once to fill.
+    pub fn extract_within_into(&self, scope: &DeviceScope, queries: &BytesTapeView<u64>, candidates: Option<&BytesTapeView<u64>>, scorer: Scorer,
+                               cutoff: f64, prefix_weight: f64, row_offsets: &mut [usize], indices: &mut [u32], scores: &mut [f64]) -> Result<usize, Error> {
+        assert!(row_offsets.len() > queries.len() && indices.len() == scores.len());
+        let tq = bytes_tape(queries);
+        let tc = candidates.map(bytes_tape);
+        let capacity = indices.len();
+        let (ind, sco) = if capacity == 0 { (ptr::null_mut(), ptr::null_mut()) } else { (indices.as_mut_ptr(), scores.as_mut_ptr() as *mut c_void) };
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_extract_within_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64),
+                                                              scorer as c_int, cutoff.to_bits(), prefix_weight.to_bits(), row_offsets.as_mut_ptr(), ind, sco,
+                                                              capacity, &mut message) }, message)?;
+        Ok(row_offsets[queries.len()])
+    }
+    pub fn extract_within_into_prepared(&self, scope: &DeviceScope, queries: &PreparedTape, candidates: Option<&PreparedTape>, scorer: Scorer,
+                                        cutoff: f64, prefix_weight: f64, row_offsets: &mut [usize], indices: &mut [u32], scores: &mut [f64]) -> Result<usize, Error> {
+        assert!(row_offsets.len() > queries.len() && indices.len() == scores.len());
+        let vq = queries.view();
+        let vc = candidates.map(|c| c.view());
+        let capacity = indices.len();
+        let (ind, sco) = if capacity == 0 { (ptr::null_mut(), ptr::null_mut()) } else { (indices.as_mut_ptr(), scores.as_mut_ptr() as *mut c_void) };
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_extract_within_prepared(self.handle, scope.handle, &vq, vc.as_ref().map_or(ptr::null(), |v| v as *const PreparedView),
+                                                               scorer as c_int, cutoff.to_bits(), prefix_weight.to_bits(), row_offsets.as_mut_ptr(), ind, sco,
+                                                               capacity, &mut message) }, message)?;
+        Ok(row_offsets[queries.len()])
+    }
     /// Range search: every candidate within `bound` edits of every query (`process.extract(score_cutoff = bound, limit = None)` per
     /// query), as CSR: row i is `indices` / `distances` `[row_offsets[i] .. row_offsets[i + 1])`, ascending by candidate; `None` = q x q.
     /// `row_offsets` (`queries.len() + 1` entries) is always filled; the two arrays only if the total fits them. Returns the total:
@@ -733,6 +768,20 @@ impl LevenshteinDistancesUtf8 {
         check(unsafe { swh_levenshtein_utf8_extract_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64), scorer as c_int, k,
                                                             cutoff.unwrap_or(scorer.no_cutoff()).to_bits(), prefix_weight.to_bits(), indices.as_mut_ptr(),
                                                             scores.as_mut_ptr() as *mut c_void, &mut message) }, message)
+    }
+    /// Score range search over code points (see `LevenshteinDistances::extract_within_into`).
+    pub fn extract_within_into(&self, scope: &DeviceScope, queries: &CharsTapeView<u64>, candidates: Option<&CharsTapeView<u64>>, scorer: Scorer,
+                               cutoff: f64, prefix_weight: f64, row_offsets: &mut [usize], indices: &mut [u32], scores: &mut [f64]) -> Result<usize, Error> {
+        assert!(row_offsets.len() > queries.len() && indices.len() == scores.len());
+        let tq = chars_tape(queries);
+        let tc = candidates.map(chars_tape);
+        let capacity = indices.len();
+        let (ind, sco) = if capacity == 0 { (ptr::null_mut(), ptr::null_mut()) } else { (indices.as_mut_ptr(), scores.as_mut_ptr() as *mut c_void) };
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_utf8_extract_within_u64tape(self.handle, scope.handle, &tq, tc.as_ref().map_or(ptr::null(), |t| t as *const TapeU64),
+                                                                   scorer as c_int, cutoff.to_bits(), prefix_weight.to_bits(), row_offsets.as_mut_ptr(), ind,
+                                                                   sco, capacity, &mut message) }, message)?;
+        Ok(row_offsets[queries.len()])
     }
     /// Top-k search over code points (see `LevenshteinDistances::topk_into`).
     pub fn topk_into(&self, scope: &DeviceScope, queries: &CharsTapeView<u64>, candidates: Option<&CharsTapeView<u64>>, k: usize, bound: Option<u32>,

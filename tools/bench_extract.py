@@ -8,6 +8,10 @@ Queries x candidate names of 5 .. 25 bytes, prepared tapes, device outputs, k = 
   - the yardstick, where the dense form fits (`--yardstick-candidates`, 65 536 by default): `jaro_counts_cross` / `lcs_cross` into host
     matrices, the similarity in numpy (engines.py's expressions) and `argpartition` + a sort of the k kept, timed as one; its rows are
     compared with the search's (same scores; same indices wherever the k-th score is not tied).
+`--within CUTOFF` measures the score range search (`engine.extract_within`) on the same batch instead: the counting call and the filled
+call (device arrays of exactly the counted size), their hit total, and from one profiled filled call the kernel time with its split into
+the scoring kernel (`dominant_ms` of `extract_within/<kernel>`: both walks) and the rest. Beside it stands the scoring time of one
+`extract` call on the same shape and scorer: a filled call scores the pairs twice, so twice that figure is what it is compared with.
 Prints one JSON object per (shape, scorer); `--out` appends them to a jsonl file."""
 import argparse
 import json
@@ -85,6 +89,44 @@ def yardstick(engine, scope, pq, pc, scorer, k, lengths):
     return time.perf_counter() - t0, indices, best
 
 
+def emit(row, path):
+    print(json.dumps(row), flush=True)
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "a") as f:
+            f.write(json.dumps(row) + "\n")
+
+
+def within_row(sw, torch, engine, scope, pq, pc, scorer, args, count):
+    """One (shape, scorer) of `--within`: the counting call, the filled call, one profiled filled call, and extract's scoring time."""
+    offsets = torch.empty(args.queries + 1, dtype=torch.int64, device="cuda")
+    counting = lambda: engine.extract_within(pq, pc, scope, scorer=scorer, cutoff=args.within, out=(offsets, None, None))
+    total = int(counting().offsets[-1])
+    hits = (torch.empty(max(total, 1), dtype=torch.int32, device="cuda"), torch.empty(max(total, 1), dtype=torch.float64, device="cuda"))
+    filled = lambda: engine.extract_within(pq, pc, scope, scorer=scorer, cutoff=args.within, out=(offsets, hits[0], hits[1]))
+    filled()
+    row = {"bench": "extract_within", "scorer": scorer, "cutoff": args.within, "queries": args.queries, "candidates": count,
+           "pairs": args.queries * count, "hits": total, "count_ms": median_ms(counting, args.reps), "filled_ms": median_ms(filled, args.reps)}
+    top = (torch.empty((args.queries, args.k), dtype=torch.int32, device="cuda"), torch.empty((args.queries, args.k), dtype=torch.float64, device="cuda"))
+    ranked = lambda: engine.extract(pq, pc, scope, scorer=scorer, k=args.k, out=top)
+    ranked()
+    scope.set_profiling(True)
+    try:
+        split = stamps_of(filled)
+        timing = scope.last_timing()
+        stamps_of(ranked)   # (its stamp lines are not this mode's subject)
+        extract_timing = scope.last_timing()
+    finally:
+        scope.set_profiling(False)
+    row.update(kernel=timing["dominant_name"], kernels=timing["kernels"], cells=timing["cells"], kernels_ms=timing["compute_ms"],
+               scoring_ms=timing["dominant_ms"], compaction_and_rest_ms=timing["compute_ms"] - timing["dominant_ms"],
+               scoring_share=timing["dominant_ms"] / timing["compute_ms"] if timing["compute_ms"] else None, kernel_split_ms=split,
+               extract_kernel=extract_timing["dominant_name"], extract_scoring_ms=extract_timing["dominant_ms"],
+               twice_extract_scoring_ms=2 * extract_timing["dominant_ms"],
+               mpairs_per_s=row["pairs"] / (row["filled_ms"] * 1e-3) / 1e6)
+    return row
+
+
 def main():
     os.environ.setdefault("STRINGWARS_AMD_STAMPS", "1")   # read by the library once, at its first profiled call
     import torch
@@ -96,6 +138,7 @@ def main():
     parser.add_argument("--scorers", nargs="+", default=["jaro_winkler", "ratio"])
     parser.add_argument("--k", type=int, default=10)
     parser.add_argument("--reps", type=int, default=3)
+    parser.add_argument("--within", type=float, default=None, metavar="CUTOFF", help="measure extract_within at this cutoff instead of extract")
     parser.add_argument("--out", default=None)
     args = parser.parse_args()
     scope = sw.DeviceScope(gpu_device=0)
@@ -107,6 +150,9 @@ def main():
         pc = sw.PreparedTape(scope, sw.Strs(candidates))
         lengths = (np.array([len(s) for s in queries], dtype=np.float64), np.array([len(s) for s in candidates], dtype=np.float64))
         for scorer in args.scorers:
+            if args.within is not None:
+                emit(within_row(sw, torch, engine, scope, pq, pc, scorer, args, count), args.out)
+                continue
             out = (torch.empty((args.queries, args.k), dtype=torch.int32, device="cuda"), torch.empty((args.queries, args.k), dtype=torch.float64, device="cuda"))
             call = lambda: engine.extract(pq, pc, scope, scorer=scorer, k=args.k, out=out)
             call()
@@ -128,11 +174,7 @@ def main():
                 row.update(yardstick_ms=seconds * 1e3, search_vs_yardstick=seconds * 1e3 / row["search_ms"],
                            scores_equal=bool((got_s.view(np.uint64) == best.view(np.uint64)).all()),
                            indices_equal_share=float((got_i == indices).mean()))
-            print(json.dumps(row), flush=True)
-            if args.out:
-                os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-                with open(args.out, "a") as f:
-                    f.write(json.dumps(row) + "\n")
+            emit(row, args.out)
 
 
 if __name__ == "__main__":

@@ -35,6 +35,7 @@ KERNELS = {
     "jaro": ("swh::k_jaro<unsigned char,", ("jaro.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
     "jaro_u32": ("swh::k_jaro<unsigned int,", ("jaro.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
     "extract_select": ("swh::k_extract_select<", ("extract.hip", "extract.hpp", "topk_fold.hpp", "cross_words.hpp", "common.hpp")),
+    "extract_within": ("swh::k_extract_within<", ("extract_within.hip", "extract.hpp", "topk_fold.hpp", "cross_words.hpp", "common.hpp")),
 }
 
 
