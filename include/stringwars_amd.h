@@ -22,7 +22,7 @@
  * `swh_scope_init_gpu_stream` and `swh_scope_init_gpus` return swh_no_device_k and leave `*scope` NULL. What a caller then holds is a
  * NULL handle, and every call refuses one, writes none of its outputs and, where it has an `error` parameter, sets a message:
  *  - a NULL scope or engine (or a prepared view whose `tape` is NULL) is swh_invalid_argument_k;
- *  - the infix, OSA, LCS and Jaro calls first ask whether a device is visible and return swh_no_device_k for a NULL scope or engine
+ *  - the infix, OSA, LCS, partial-ratio and Jaro calls first ask whether a device is visible and return swh_no_device_k for a NULL scope or engine
  *    where there is none (swh_invalid_argument_k where there is one);
  *  - the `*_free` calls accept NULL and return swh_success_k; `swh_device_count` returns swh_success_k and a count of 0;
  *  - `swh_version` and `swh_capabilities` need no device.
@@ -154,7 +154,7 @@ swh_status_t swh_copy_to_host(swh_scope_t scope, void *host_dst, const void *dev
  *  - Totals are 64-bit with u64 offsets, and up to 2^32 - 1 with u32 offsets (entries at or above 2^31 are plain unsigned values).
  *  - One string holds fewer than 2^30 bytes (hence fewer than 2^30 symbols). A longer one is refused with
  *    swh_unsupported_length_k: by `swh_tape_prepare_*` (and so by every call that prepares its raw tapes: top-k, within, align,
- *    infix, OSA, LCS, Jaro) on the offsets alone, and by the pairwise and cross-product calls on raw tapes as soon as they have
+ *    infix, OSA, LCS, partial ratio, Jaro) on the offsets alone, and by the pairwise and cross-product calls on raw tapes as soon as they have
  *    measured the batch (lengths are measured as 64-bit differences: an entry of 2^32 bytes or more does not wrap into a short
  *    one) -- no kernel scores a pair with such a string; the call's outputs may have been written and mean nothing. */
 typedef struct swh_tape_u32_t { const uint8_t *data; const uint32_t *offsets; size_t count; } swh_tape_u32_t;
@@ -460,6 +460,79 @@ swh_status_t swh_levenshtein_lcs_cross_prepared(swh_levenshtein_t engine, swh_sc
                                                 const swh_prepared_view_t *b, size_t *indel, size_t *lcs, size_t row_stride_bytes,
                                                 const char **error);
 
+/* ---- Partial ratio: the best Indel ratio of the shorter string against the windows of the longer one (rapidfuzz
+ *      `fuzz.partial_ratio`, `fuzz.partial_ratio_alignment`, `process.cdist(..., scorer=fuzz.partial_ratio)`), unit costs only. ----
+ * Unlike the infix search above -- a Levenshtein distance to the best substring of ANY length -- this is the best `fuzz.ratio` over
+ * windows of the needle's length: lawn in "flaw in law" is infix (1, 1, 4), but partial window (8, 11) with score 85.71.
+ * For a pair (a, b) the needle p (m symbols) is the shorter string and the haystack t (n symbols) the longer one. The windows of t
+ * are t[max(0, o) .. min(n, o + m)) for every offset o in -(m - 1) .. n - 1: every full-length window and the shorter prefixes and
+ * suffixes an overhanging needle leaves, n + m - 1 windows, each of some length l.
+ *  - A window scores 200 L / (m + l), L = LCS(p, window): `fuzz.ratio(p, window)`.
+ *  - Windows are compared exactly, as the rationals L / (m + l) (cross-multiplied in 64-bit integers); among equals the window of
+ *    the smallest offset o is the result (rapidfuzz's scan order with strict improvement).
+ *  - len(a) < len(b): the needle is a, the window lies in b, side 0. len(a) > len(b): the needle is b, the window lies in a, side 1.
+ *    len(a) == len(b): the two directions differ (abbb / abab: 75 with needle a, 85.71 with needle b) and both are evaluated; side 1
+ *    wins only on a strictly larger rational.
+ *  - If no window shares a symbol with the needle: L = 0, window (0, m), the side as above.
+ *  - m == 0: L = 0, window (0, 0), the side as above (two empty strings: side 0); the score is 100 if n == 0, else 0.
+ * Per pair: lcs = L, starts / ends = the window in the haystack (in symbols), sides = 0 or 1. Callers evaluate the float64 score
+ * 100 * (2 L) / (m + (end - start)) from them (and the m == 0 rule).
+ *      a / b                      score     L  start end side
+ *      kitten / the sitting cat   66.66...  4  4     10  0
+ *      abc / xxabcxx              100       3  2     5   0
+ *      lawn / flaw in law         85.714... 3  8     11  0
+ *      yankees / new york yankees 100       7  9     16  0
+ *      ab / ba                    66.66...  1  0     1   0    (a three-way tie: the smallest offset)
+ *      abcx / xabc                85.714... 3  1     4   0
+ *      aab / baa                  80        2  1     3   0
+ *      abbb / abab                85.714... 3  0     3   1    (the window lies in a)
+ *      aaa / bbb                  0         0  0     3   0
+ *      "" / ""                    100       0  0     0   0
+ *      "" / abc                   0         0  0     0   0
+ * rapidfuzz filters windows by character set before it scores them and may therefore report a later window of the same score:
+ * the scores correspond, the windows only up to ties.
+ * Pairs (swh_levenshtein_partial_pairs_*):
+ *  - a->count == b->count, else swh_invalid_argument_k;
+ *  - any of the four outputs may be NULL (that output is not wanted), not all: swh_invalid_argument_k;
+ *  - `out_stride_bytes` is the distance between consecutive results of every output (>= 4; 0 means 4); each output may be in host
+ *    or device memory, independently of the others.
+ * Cross (swh_levenshtein_partial_cross_*):
+ *  - four row-major `size_t` matrices, [i][j] of (a_i, b_j), rows `row_stride_bytes` apart in all of them (0 means b->count * 8);
+ *    any may be NULL, not all;
+ *  - b == NULL means a x a: the diagonal holds L = len(a_i), window (0, len(a_i)), side 0;
+ *  - the matrices are filled in slices of whole rows; the call's scratch memory follows the slice's windows, not the matrix.
+ * Both:
+ *  - symbols are bytes, or code points in the UTF-8 variant (invalid UTF-8 -> swh_invalid_utf8_k); the prepared variant takes
+ *    what the tapes were prepared as (both of the same kind, any mix of 32- and 64-bit offsets);
+ *  - a pair whose SHORTER string has more than SWH_PARTIAL_MAX_NEEDLE symbols makes the call return swh_unsupported_length_k before
+ *    any output is written; the message names the first such pair. The haystack has no limit beyond the tapes' own;
+ *  - an engine whose costs are not (match 0, mismatch 1, open 1, extend 1) returns swh_not_implemented_k;
+ *  - there is no score cutoff;
+ *  - count == 0 (an empty matrix) succeeds and writes nothing.
+ * The call is synchronous on every scope: on an asynchronous or pipelined scope it first joins the outstanding work (as
+ * swh_scope_synchronize) and returns with the results visible. The same inputs give the same bytes on every run. With profiling on,
+ * swh_scope_last_timing describes the whole call: `cells` = sum m n (the nominal accounting: the windows cost about m times that);
+ * `dominant_name` is its longest kernel ("partial" for bytes, "partial_u32" for code points). */
+#define SWH_PARTIAL_MAX_NEEDLE 2048u  /* symbols of a pair's shorter string: one wave's 64 blocks of 32 rows */
+swh_status_t swh_levenshtein_partial_pairs_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                   const swh_tape_u64_t *b, uint32_t *lcs, uint32_t *starts, uint32_t *ends,
+                                                   uint32_t *sides, size_t out_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_utf8_partial_pairs_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                        const swh_tape_u64_t *b, uint32_t *lcs, uint32_t *starts, uint32_t *ends,
+                                                        uint32_t *sides, size_t out_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_partial_pairs_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *a,
+                                                    const swh_prepared_view_t *b, uint32_t *lcs, uint32_t *starts, uint32_t *ends,
+                                                    uint32_t *sides, size_t out_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_partial_cross_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                   const swh_tape_u64_t *b, size_t *lcs, size_t *starts, size_t *ends, size_t *sides,
+                                                   size_t row_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_utf8_partial_cross_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                        const swh_tape_u64_t *b, size_t *lcs, size_t *starts, size_t *ends,
+                                                        size_t *sides, size_t row_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_partial_cross_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *a,
+                                                    const swh_prepared_view_t *b, size_t *lcs, size_t *starts, size_t *ends,
+                                                    size_t *sides, size_t row_stride_bytes, const char **error);
+
 /* ---- Jaro and Jaro-Winkler similarities (rapidfuzz `distance.Jaro` / `distance.JaroWinkler`, jellyfish `jaro_similarity` /
  *      `jaro_winkler_similarity`), unit-cost engines only. The calls return the integer counts; callers evaluate the two
  *      similarity expressions below. ---------------------------------------------------------------------------------------------
@@ -742,7 +815,7 @@ const char *swh_version(void);
 /* Comma-separated capability string, e.g. "gfx950,hip,wavefront,bitparallel,banded,utf8,...";
  * "topk" when the swh_levenshtein_topk_* calls are present, "within" when the swh_levenshtein_within_* calls are, "align" when the swh_levenshtein_align_* calls are,
  * "infix" when the swh_levenshtein_infix_* calls are, "osa" when the swh_levenshtein_osa_* calls are,
- * "lcs" when the swh_levenshtein_lcs_* calls are, "jaro" when the swh_levenshtein_jaro_* calls are, "extract" when the
+ * "lcs" when the swh_levenshtein_lcs_* calls are, "partial" when the swh_levenshtein_partial_* calls are, "jaro" when the swh_levenshtein_jaro_* calls are, "extract" when the
  * swh_levenshtein_extract_* calls are, "extract_within" when the swh_levenshtein_extract_within_* calls are. */
 const char *swh_capabilities(void);
 

@@ -320,6 +320,43 @@ public:
         swh_status_t status__ = swh_levenshtein_lcs_cross_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, indel, lcs, row_stride_bytes, &err);
         check(status__, err);
     }
+    /// Partial ratios (swh_levenshtein_partial_pairs_*; rapidfuzz fuzz.partial_ratio / fuzz.partial_ratio_alignment): the shorter string
+    /// of a pair is the needle (m symbols, at most SWH_PARTIAL_MAX_NEEDLE); lcs[i] is its LCS length with the best window
+    /// [starts[i], ends[i]) of the other string, sides[i] is 0 where that window lies in b_i and 1 where it lies in a_i. The score is
+    /// 100 * (2 lcs) / (m + end - start) (an empty needle: 100 against an empty string, else 0). The four outputs go in one
+    /// PartialCounts (four pointers of one type are easily passed in the wrong order): any may be nullptr, not all; host or device memory.
+    template <typename T> struct PartialCounts { T *lcs = nullptr, *starts = nullptr, *ends = nullptr, *sides = nullptr; };
+    void partial(const DeviceScope &scope, const PartialCounts<uint32_t> &out, const BytesTapeView &a, const BytesTapeView &b) const {
+        const char *err = nullptr;
+        swh_tape_u64_t ta = a.c(), tb = b.c();
+        auto fn = utf8_ ? swh_levenshtein_utf8_partial_pairs_u64tape : swh_levenshtein_partial_pairs_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &ta, &tb, out.lcs, out.starts, out.ends, out.sides, 4, &err);
+        check(status__, err);
+    }
+    void partial(const DeviceScope &scope, const PartialCounts<uint32_t> &out, const PreparedTape &a, const PreparedTape &b) const {
+        const char *err = nullptr;
+        swh_prepared_view_t va = a.c(), vb = b.c();
+        swh_status_t status__ = swh_levenshtein_partial_pairs_prepared(handle_, scope.handle(), &va, &vb, out.lcs, out.starts, out.ends, out.sides, 4, &err);
+        check(status__, err);
+    }
+    /// The four dense matrices of partial-ratio counts (swh_levenshtein_partial_cross_*), row-major `size_t`, any may be nullptr;
+    /// `candidates == nullptr` is the self-product.
+    void partial_cross(const DeviceScope &scope, const PartialCounts<size_t> &out, const BytesTapeView &queries, const BytesTapeView *candidates,
+                       size_t row_stride_bytes = 0) const {
+        const char *err = nullptr;
+        swh_tape_u64_t q = queries.c(), c = candidates ? candidates->c() : q;
+        auto fn = utf8_ ? swh_levenshtein_utf8_partial_cross_u64tape : swh_levenshtein_partial_cross_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &q, candidates ? &c : nullptr, out.lcs, out.starts, out.ends, out.sides, row_stride_bytes, &err);
+        check(status__, err);
+    }
+    void partial_cross(const DeviceScope &scope, const PartialCounts<size_t> &out, const PreparedTape &queries, const PreparedTape *candidates,
+                       size_t row_stride_bytes = 0) const {
+        const char *err = nullptr;
+        swh_prepared_view_t q = queries.c(), c = candidates ? candidates->c() : q;
+        swh_status_t status__ = swh_levenshtein_partial_cross_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, out.lcs, out.starts, out.ends,
+                                                                       out.sides, row_stride_bytes, &err);
+        check(status__, err);
+    }
     /// Jaro / Jaro-Winkler counts (swh_levenshtein_jaro_pairs_*; rapidfuzz distance.Jaro / distance.JaroWinkler): matches[i] = M,
     /// transpositions[i] = t, prefix[i] = the common prefix of at most four symbols of (a_i, b_i) -- a_i drives the matching, b_i is
     /// flagged; any output may be nullptr, not all. jaro = (M / m + M / n + (M - t) / M) / 3 (1 for two empty strings, 0 where M = 0),

@@ -56,6 +56,7 @@ INFIX_MAX_PATTERN = 2048   # SWH_INFIX_MAX_PATTERN: symbols per pattern an infix
 INFIX_NONE = 0xFFFFFFFF    # SWH_INFIX_NONE: start / end of a pair whose best occurrence is over the bound
 OSA_MAX_SHORTER = 2048     # SWH_OSA_MAX_SHORTER: symbols of a pair's shorter string an OSA call accepts
 LCS_MAX_SHORTER = 2048     # SWH_LCS_MAX_SHORTER: symbols of a pair's shorter string an LCS / Indel call accepts
+PARTIAL_MAX_NEEDLE = 2048  # SWH_PARTIAL_MAX_NEEDLE: symbols of a pair's shorter string a partial-ratio call accepts
 JARO_MAX_LENGTH = 2048     # SWH_JARO_MAX_LENGTH: symbols of either string of a pair a Jaro call accepts
 # SWH_SCORER_*: the scores a score search (swh_levenshtein_extract_*) ranks by, by name
 SCORERS = {"osa": 0, "indel": 1, "lcs": 2, "ratio": 3, "jaro": 4, "jaro_winkler": 5}
@@ -204,6 +205,12 @@ SIGNATURES = {
     "swh_levenshtein_lcs_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, C.c_size_t, _ERR]),
     "swh_levenshtein_utf8_lcs_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, C.c_size_t, _ERR]),
     "swh_levenshtein_lcs_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_partial_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_utf8_partial_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_partial_pairs_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, _P, _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_partial_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_utf8_partial_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, _P, C.c_size_t, _ERR]),
+    "swh_levenshtein_partial_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, _P, _P, _P, C.c_size_t, _ERR]),
     "swh_levenshtein_jaro_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, C.c_size_t, _ERR]),
     "swh_levenshtein_utf8_jaro_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, C.c_size_t, _ERR]),
     "swh_levenshtein_jaro_pairs_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, _P, _P, C.c_size_t, _ERR]),

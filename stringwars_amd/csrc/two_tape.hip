@@ -1,5 +1,5 @@
 // two_tape.hip -- the synchronous two-tape calls of include/stringwars_amd.h: top-k, range, score and score range searches,
-// alignments, infix search and the scored families (OSA, LCS / Indel, Jaro). Host code only: the kernels are the families' own files,
+// alignments, infix search and the scored families (OSA, LCS / Indel, partial ratio, Jaro). Host code only: the kernels are the families' own files,
 // the engine-call path the searches score their slices on is api.hip (api.hpp: what the two files share).
 #include <algorithm>
 #include <cmath>
@@ -14,6 +14,7 @@
 #include "infix.hpp"
 #include "osa.hpp"
 #include "lcs.hpp"
+#include "partial.hpp"
 #include "jaro.hpp"
 #include "extract.hpp"
 
@@ -845,8 +846,8 @@ swh_status_t swh_levenshtein_infix_prepared(swh_levenshtein_t e, swh_scope_t s, 
     return infix_run(call.scope, call.pair, bound, InfixOutputs{distances, starts, ends}, error);
 }
 
-// ---- OSA distances, LCS lengths / Indel distances, Jaro counts (osa.hip, lcs.hip, jaro.hip): one planner --------------------------------
-// The three families score pairs on the same phases. A sizes kernel measures the pairs (cells, symbols, the first pair over the
+// ---- OSA distances, LCS lengths / Indel distances, partial ratios, Jaro counts (osa.hip, lcs.hip, partial.hip, jaro.hip): one planner ------
+// The four families score pairs on the same phases. A sizes kernel measures the pairs (cells, symbols, the first pair over the
 // family's length limit) and cuts them into work items; one read-back of the measurements decides the errors before any output is
 // written; the family's kernel scores the items and writes whichever of its outputs the caller asked for. A pairwise call is one such
 // round. A cross-product maps pair p to (p / nb, p % nb) and runs in slices of whole rows of about kScoredChunkPairs pairs -- the item
@@ -859,14 +860,18 @@ swh_status_t swh_levenshtein_infix_prepared(swh_levenshtein_t e, swh_scope_t s, 
 //  - LCS / Indel: OSA's sizes kernel and limit as they stand (SWH_LCS_MAX_SHORTER); two outputs, indel and lcs.
 //  - Jaro: k_jaro_sizes cuts the items by the blocks of b, and neither string holds more than SWH_JARO_MAX_LENGTH symbols; three
 //    outputs, matches, transpositions and prefix, and the only family that holds strides to multiples of the element.
+//  - Partial ratio: k_partial_sizes gives a pair an item per run of its windows, so a slice's items are counted, the item part of the
+//    scratch sized by the count, and the items placed by a second measurement (`item_bytes`); they are scored once per slice (`score`)
+//    and the launch merges each pair's records into its four outputs, lcs, starts, ends and sides. SWH_PARTIAL_MAX_NEEDLE on the shorter string.
 constexpr uint64_t kScoredChunkPairs = (uint64_t)1 << 21;
-constexpr int kScoredOutputs = 3;
+constexpr int kScoredOutputs = 4;
 
 struct ScoredFamily {
     int outputs;   // of kScoredOutputs
-    void (*sizes)(Scope *scope, const OsaTapes &t, OsaSizes *sizes, LaneItem *items);
+    // measures the pairs and, with `items`, cuts them (`counted`: the items an earlier measurement found, where item_bytes asks for one)
+    void (*sizes)(Scope *scope, const OsaTapes &t, OsaSizes *sizes, void *items, uint64_t counted);
     // scores the items into where[0 .. outputs), null where an output is not written by this launch, all at `stride`
-    void (*launch)(Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride,
+    void (*launch)(Scope *scope, const OsaTapes &t, const void *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride,
                    uint32_t bound, bool wide);
     const char *chunk_hook;      // the test hook that lowers the slice
     const char *oversize;        // how the refusal of a pair over the length limit ends
@@ -874,14 +879,21 @@ struct ScoredFamily {
     const char *null_outputs;    // the refusal of a call that wants no output ...
     bool null_outputs_on_empty;  // ... which a call without pairs meets too
     bool element_strides;        // strides are multiples of the element (4 bytes pairwise, 8 cross), not merely large enough
+    // Null: a pair is at most one LaneItem, and the first measurement of a slice cuts it. Otherwise the family's items follow from the
+    // pairs' lengths: every slice is measured once to count them, the item scratch is sized by item_bytes(pairs, items), and a second
+    // measurement cuts.
+    size_t (*item_bytes)(uint64_t pairs, uint64_t items) = nullptr;
+    // Null: `launch` does the scoring. Otherwise the items are scored once per slice here, and `launch` only writes outputs from
+    // what this left in the item scratch (a slice with outputs in host and in device memory launches twice).
+    void (*score)(Scope *scope, const OsaTapes &t, void *items, uint64_t item_count, bool wide) = nullptr;
 };
 
 static const ScoredFamily kOsaFamily = {
-    1, launch_osa_sizes,
-    [](Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
+    1, [](Scope *scope, const OsaTapes &t, OsaSizes *sizes, void *items, uint64_t) { launch_osa_sizes(scope, t, sizes, (LaneItem *)items); },
+    [](Scope *scope, const OsaTapes &t, const void *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
        bool wide) {
         OsaRun run{};
-        run.items = items; run.item_count = item_count;
+        run.items = (const LaneItem *)items; run.item_count = item_count;
         run.out = where[0];
         run.stride = stride; run.bound = bound; run.wide = wide;
         launch_osa(scope, t, run);
@@ -889,11 +901,11 @@ static const ScoredFamily kOsaFamily = {
     "STRINGWARS_AMD_OSA_CHUNK_PAIRS", "the shorter string exceeds SWH_OSA_MAX_SHORTER (2048)",
     "OSA distances need unit costs (match 0, mismatch 1, open 1, extend 1)", "null output pointer", false, false};
 static const ScoredFamily kLcsFamily = {
-    2, launch_osa_sizes,
-    [](Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
+    2, [](Scope *scope, const OsaTapes &t, OsaSizes *sizes, void *items, uint64_t) { launch_osa_sizes(scope, t, sizes, (LaneItem *)items); },
+    [](Scope *scope, const OsaTapes &t, const void *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t bound,
        bool wide) {
         LcsRun run{};
-        run.items = items; run.item_count = item_count;
+        run.items = (const LaneItem *)items; run.item_count = item_count;
         run.indel = where[0]; run.lcs = where[1];
         run.stride = stride; run.bound = bound; run.wide = wide;
         launch_lcs(scope, t, run);
@@ -902,11 +914,11 @@ static const ScoredFamily kLcsFamily = {
     "LCS lengths and Indel distances are called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)",
     "null output pointers: one of indel and lcs is needed", true, false};
 static const ScoredFamily kJaroFamily = {
-    3, launch_jaro_sizes,
-    [](Scope *scope, const OsaTapes &t, const LaneItem *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t,
+    3, [](Scope *scope, const OsaTapes &t, OsaSizes *sizes, void *items, uint64_t) { launch_jaro_sizes(scope, t, sizes, (LaneItem *)items); },
+    [](Scope *scope, const OsaTapes &t, const void *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t,
        bool wide) {
         JaroRun run{};
-        run.items = items; run.item_count = item_count;
+        run.items = (const LaneItem *)items; run.item_count = item_count;
         run.matches = where[0]; run.transpositions = where[1]; run.prefix = where[2];
         run.stride = stride; run.wide = wide;
         launch_jaro(scope, t, run);
@@ -914,6 +926,17 @@ static const ScoredFamily kJaroFamily = {
     "STRINGWARS_AMD_JARO_CHUNK_PAIRS", "a string exceeds SWH_JARO_MAX_LENGTH (2048)",
     "Jaro and Jaro-Winkler counts are called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)",
     "null output pointers: one of matches, transpositions and prefix is needed", true, true};
+// Partial ratio: k_partial_sizes gives a pair an item per run of its n + m - 1 windows (per direction), so the items are counted before
+// they are placed; k_partial scores them into records once per slice, and the launch merges each pair's records into its outputs.
+static const ScoredFamily kPartialFamily = {
+    4, [](Scope *scope, const OsaTapes &t, OsaSizes *sizes, void *items, uint64_t counted) { launch_partial_sizes(scope, t, sizes, items, counted); },
+    [](Scope *scope, const OsaTapes &t, const void *items, uint64_t item_count, char *const where[kScoredOutputs], uint64_t stride, uint32_t, bool) {
+        launch_partial_merge(scope, t, PartialMerge{items, where[0], where[1], where[2], where[3], stride}, item_count);
+    },
+    "STRINGWARS_AMD_PARTIAL_CHUNK_PAIRS", "the shorter string exceeds SWH_PARTIAL_MAX_NEEDLE (2048)",
+    "partial ratios are called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)",
+    "null output pointers: one of lcs, starts, ends and sides is needed", true, false,
+    partial_scratch_bytes, launch_partial_items};
 
 static uint64_t scored_chunk_pairs(const char *chunk_hook) {
     const char *hook = test_hook(chunk_hook);
@@ -941,9 +964,10 @@ static OsaTapes scored_view(const TapePair &p, size_t a_first, size_t na, size_t
     return t;
 }
 // makes `pairs` pairs from row `row0` on the view's launch, measures them and, with `items`, cuts them into items
-static OsaSizes scored_measure(Scope *scope, const ScoredFamily &f, OsaTapes &t, uint64_t row0, uint64_t pairs, OsaSizes *sizes, LaneItem *items) {
+static OsaSizes scored_measure(Scope *scope, const ScoredFamily &f, OsaTapes &t, uint64_t row0, uint64_t pairs, OsaSizes *sizes, void *items,
+                               uint64_t counted = 0) {
     t.row0 = row0; t.count = pairs;
-    return measure(scope, sizes, [&] { f.sizes(scope, t, sizes, items); });
+    return measure(scope, sizes, [&] { f.sizes(scope, t, sizes, items, counted); });
 }
 // both byte tapes hold at least 16 bytes: the kernels read the columns' string with 128-bit loads
 static bool scored_wide(const OsaTapes &t, const OsaSizes &got) { return !t.cp && got.a_total >= 16 && got.b_total >= 16; }
@@ -965,7 +989,8 @@ static swh_status_t scored_run(Scope *scope, const ScoredFamily &f, const TapePa
         SWH_HIP_CHECK(hipSetDevice(scope->device));
         hipStream_t stream = scope->stream;
         // (an output the caller does not want is null, as are those past the family's count: not staged, not written)
-        Staged<char> outs[kScoredOutputs] = {Staged<char>((char *)r.outs[0]), Staged<char>((char *)r.outs[1]), Staged<char>((char *)r.outs[2])};
+        Staged<char> outs[kScoredOutputs] = {Staged<char>((char *)r.outs[0]), Staged<char>((char *)r.outs[1]), Staged<char>((char *)r.outs[2]),
+                                             Staged<char>((char *)r.outs[3])};
         size_t staged_count = 0, wanted = 0;
         for (int k = 0; k < f.outputs; ++k) { staged_count += outs[k].on_device ? 0 : 1; wanted += r.outs[k] ? 1 : 0; }
         OsaTapes t = scored_view(p, 0, na, 0, nb, r.cross);
@@ -977,15 +1002,21 @@ static swh_status_t scored_run(Scope *scope, const ScoredFamily &f, const TapePa
         const size_t width = r.cross ? 8 : 4;
 
         AlignScratch *sc_entry = call_scratch(scope);
-        // sizes | items | the slice's results (one array per output that lives on the host)
-        const size_t need = pad(sizeof(OsaSizes)) + pad(slice_pairs * sizeof(LaneItem)) + staged_count * pad(slice_pairs * width);
-        Carver sc = carve(sc_entry->buf, sc_entry->bytes, need);
-        OsaSizes *sizes = sc.take<OsaSizes>(1);
-        LaneItem *items = sc.take<LaneItem>(slice_pairs);
-        for (int k = 0; k < f.outputs; ++k) outs[k].place(sc, slice_pairs * width);
+        // sizes | the slice's results (one array per output that lives on the host) | items. A family that counts its items sizes
+        // the last part slice by slice: the scratch is laid out again -- nothing in it outlives a slice -- once the count is known.
+        OsaSizes *sizes;
+        char *items;
+        auto lay_out = [&](size_t item_bytes) {
+            const size_t need = pad(sizeof(OsaSizes)) + staged_count * pad(slice_pairs * width) + pad(item_bytes);
+            Carver sc = carve(sc_entry->buf, sc_entry->bytes, need);
+            sizes = sc.take<OsaSizes>(1);
+            for (int k = 0; k < f.outputs; ++k) outs[k].place(sc, slice_pairs * width);
+            items = sc.take<char>(item_bytes);
+        };
+        lay_out(f.item_bytes ? 0 : slice_pairs * sizeof(LaneItem));
 
         // with more than one slice the whole matrix is measured first (no items): a refusal comes before the first row is written
-        const OsaSizes whole = scored_measure(scope, f, t, 0, total, sizes, slices == 1 ? items : nullptr);
+        const OsaSizes whole = scored_measure(scope, f, t, 0, total, sizes, slices == 1 && !f.item_bytes ? items : nullptr);
         if (whole.first_oversize != ~0ull) {
             scope->stamps_used = 0;
             const size_t first = (size_t)whole.first_oversize;
@@ -998,7 +1029,15 @@ static swh_status_t scored_run(Scope *scope, const ScoredFamily &f, const TapePa
         for (uint64_t q = 0; q < slices; ++q) {
             const uint64_t row0 = q * rows_per_slice, rows = std::min<uint64_t>(rows_per_slice, na - row0);
             const uint64_t pairs = r.cross ? rows * nb : na;
-            const uint64_t item_count = slices == 1 ? whole.items : scored_measure(scope, f, t, row0, pairs, sizes, items).items;
+            uint64_t item_count;
+            if (f.item_bytes) {
+                item_count = slices == 1 ? whole.items : scored_measure(scope, f, t, row0, pairs, sizes, nullptr).items;
+                lay_out(f.item_bytes(pairs, item_count));
+                scored_measure(scope, f, t, row0, pairs, sizes, items, item_count);
+            } else {
+                item_count = slices == 1 ? whole.items : scored_measure(scope, f, t, row0, pairs, sizes, items).items;
+            }
+            if (f.score) f.score(scope, t, items, item_count, wide);
             for (int packed = 0; packed < 2; ++packed) {
                 char *where[kScoredOutputs] = {};
                 bool any = false;
@@ -1060,7 +1099,7 @@ static swh_status_t scored_tapes(const ScoredFamily &f, swh_levenshtein_t e, swh
     if ((status = call.begin(s, error)) != swh_success_k) return status;
     const bool pairs = a->count && b_count;
     if ((status = call.prepare(a, b, utf8, pairs, pairs, error)) != swh_success_k) return status;
-    return scored_run(call.scope, f, call.pair, ScoredRequest{cross, bound, {outs[0], outs[1], outs[2]}, stride}, error);
+    return scored_run(call.scope, f, call.pair, ScoredRequest{cross, bound, {outs[0], outs[1], outs[2], outs[3]}, stride}, error);
 }
 static swh_status_t scored_prepared(const ScoredFamily &f, swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a,
                                     const swh_prepared_view_t *b, bool cross, uint32_t bound, void *const (&outs)[kScoredOutputs], size_t stride,
@@ -1071,7 +1110,7 @@ static swh_status_t scored_prepared(const ScoredFamily &f, swh_levenshtein_t e, 
     if ((status = call.views(a, b, cross, error)) != swh_success_k) return status;
     if ((status = scored_checks(f, e, call.pair.a_count, call.pair.b_count, cross, outs, stride, error)) != swh_success_k) return status;
     if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
-    return scored_run(call.scope, f, call.pair, ScoredRequest{cross, bound, {outs[0], outs[1], outs[2]}, stride}, error);
+    return scored_run(call.scope, f, call.pair, ScoredRequest{cross, bound, {outs[0], outs[1], outs[2], outs[3]}, stride}, error);
 }
 
 swh_status_t swh_levenshtein_osa_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, uint32_t bound,
@@ -1122,6 +1161,36 @@ swh_status_t swh_levenshtein_utf8_lcs_cross_u64tape(swh_levenshtein_t e, swh_sco
 swh_status_t swh_levenshtein_lcs_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
                                                 size_t *indel, size_t *lcs, size_t row_stride, const char **error) {
     return scored_prepared(kLcsFamily, e, s, a, b, true, SWH_UNBOUNDED, {indel, lcs}, row_stride, error);
+}
+
+// (no bound: there is no score cutoff)
+swh_status_t swh_levenshtein_partial_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                   uint32_t *lcs, uint32_t *starts, uint32_t *ends, uint32_t *sides, size_t stride, const char **error) {
+    return scored_tapes(kPartialFamily, e, s, a, b, false, false, SWH_UNBOUNDED, {lcs, starts, ends, sides}, stride, error);
+}
+swh_status_t swh_levenshtein_utf8_partial_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                        uint32_t *lcs, uint32_t *starts, uint32_t *ends, uint32_t *sides, size_t stride,
+                                                        const char **error) {
+    return scored_tapes(kPartialFamily, e, s, a, b, true, false, SWH_UNBOUNDED, {lcs, starts, ends, sides}, stride, error);
+}
+swh_status_t swh_levenshtein_partial_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                    uint32_t *lcs, uint32_t *starts, uint32_t *ends, uint32_t *sides, size_t stride,
+                                                    const char **error) {
+    return scored_prepared(kPartialFamily, e, s, a, b, false, SWH_UNBOUNDED, {lcs, starts, ends, sides}, stride, error);
+}
+swh_status_t swh_levenshtein_partial_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                   size_t *lcs, size_t *starts, size_t *ends, size_t *sides, size_t row_stride, const char **error) {
+    return scored_tapes(kPartialFamily, e, s, a, b, false, true, SWH_UNBOUNDED, {lcs, starts, ends, sides}, row_stride, error);
+}
+swh_status_t swh_levenshtein_utf8_partial_cross_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                        size_t *lcs, size_t *starts, size_t *ends, size_t *sides, size_t row_stride,
+                                                        const char **error) {
+    return scored_tapes(kPartialFamily, e, s, a, b, true, true, SWH_UNBOUNDED, {lcs, starts, ends, sides}, row_stride, error);
+}
+swh_status_t swh_levenshtein_partial_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                    size_t *lcs, size_t *starts, size_t *ends, size_t *sides, size_t row_stride,
+                                                    const char **error) {
+    return scored_prepared(kPartialFamily, e, s, a, b, true, SWH_UNBOUNDED, {lcs, starts, ends, sides}, row_stride, error);
 }
 
 // (the Jaro kernel takes no bound)

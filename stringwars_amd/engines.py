@@ -26,7 +26,7 @@ from . import _native as N
 __all__ = [
     "DeviceScope", "Strs", "DeviceTape", "PreparedTape", "ShardedPairs", "shard_cuts", "LevenshteinDistances", "LevenshteinDistancesUTF8",
     "NeedlemanWunschScores", "SmithWatermanScores", "edit_distance", "StringWarsError", "UNBOUNDED", "TOPK_MAX",
-    "ALIGN_MAX_CELLS", "Alignments", "RangeMatches", "ScoreMatches", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "OSA_MAX_SHORTER", "LCS_MAX_SHORTER",
+    "ALIGN_MAX_CELLS", "Alignments", "RangeMatches", "ScoreMatches", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "OSA_MAX_SHORTER", "LCS_MAX_SHORTER", "PARTIAL_MAX_NEEDLE", "PartialAlignments",
     "JARO_MAX_LENGTH", "SCORERS",
 ]
 
@@ -38,6 +38,7 @@ INFIX_MAX_PATTERN = N.INFIX_MAX_PATTERN
 INFIX_NONE = N.INFIX_NONE
 OSA_MAX_SHORTER = N.OSA_MAX_SHORTER
 LCS_MAX_SHORTER = N.LCS_MAX_SHORTER
+PARTIAL_MAX_NEEDLE = N.PARTIAL_MAX_NEEDLE
 JARO_MAX_LENGTH = N.JARO_MAX_LENGTH
 SCORERS = tuple(N.SCORERS)   # the scorers of ``engine.extract``, by name
 
@@ -605,6 +606,29 @@ class InfixMatches:
         return int(self.distances[i]), int(self.starts[i]), int(self.ends[i])
 
 
+class PartialAlignments:
+    """The result of ``LevenshteinDistances.partial_ratio_alignment``, after rapidfuzz's ``ScoreAlignment``: ``score[i]`` is
+    ``fuzz.partial_ratio(a[i], b[i])`` as float64, reached between ``a[i][src_start[i]:src_end[i]]`` and
+    ``b[i][dest_start[i]:dest_end[i]]``. The shorter string (the needle) spans its whole length, the other side is the best window --
+    among windows of equal score the one of the smallest offset. Positions count symbols: bytes, or code points for the UTF-8 engine."""
+
+    def __init__(self, score, src_start, src_end, dest_start, dest_end):
+        self.score = np.asarray(score, dtype=np.float64)
+        self.src_start, self.src_end, self.dest_start, self.dest_end = (np.asarray(x, dtype=np.uint32) for x in (src_start, src_end, dest_start, dest_end))
+        if not len(self.score) == len(self.src_start) == len(self.src_end) == len(self.dest_start) == len(self.dest_end):
+            raise ValueError("one entry per pair in every array")
+
+    def __len__(self) -> int:
+        return len(self.score)
+
+    def __getitem__(self, i: int):
+        """``(score, src_start, src_end, dest_start, dest_end)`` of pair ``i``."""
+        if not -len(self) <= i < len(self):
+            raise IndexError("pair index out of range")
+        i %= len(self)
+        return (float(self.score[i]), int(self.src_start[i]), int(self.src_end[i]), int(self.dest_start[i]), int(self.dest_end[i]))
+
+
 def _as_tape(obj: TapeLike):
     if isinstance(obj, (Strs, DeviceTape, PreparedTape)):
         return obj
@@ -1063,6 +1087,56 @@ class LevenshteinDistances(_Engine):
     def ratio_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None):
         """The dense float64 matrix of ``fuzz.ratio``: rapidfuzz's ``process.cdist(queries, candidates, scorer=fuzz.ratio)``, unrounded."""
         return self._ratio(*self._lcs_call(queries, candidates, scope, True, None, True, True))
+
+    def partial_counts(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None, out=None):
+        """The counts behind the partial ratio of every pair ``(a[i], b[i])`` as four uint32 arrays (``swh_levenshtein_partial_pairs_*``):
+        ``lcs``, ``starts``, ``ends`` and ``sides``. The shorter string is the needle (at most ``PARTIAL_MAX_NEEDLE`` symbols); ``lcs`` is
+        its LCS length with the best window ``[starts, ends)`` of the other string -- the largest ``lcs / (m + end - start)``, compared
+        exactly, the smallest offset among equals; ``sides`` is 0 where the window lies in ``b[i]``, 1 where it lies in ``a[i]``.
+        ``out``: four arrays to fill, None where an output is not wanted (not all)."""
+        return tuple(self._scored_call("partial", a, b, scope, False, (True,) * 4 if out is None else tuple(out))[0])
+
+    def partial_counts_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None, out=None):
+        """The four dense uint64 matrices of counts, ``[i][j]`` of ``(queries[i], candidates[j])`` (``swh_levenshtein_partial_cross_*``);
+        ``candidates=None`` is the self-product."""
+        return tuple(self._scored_call("partial", queries, candidates, scope, True, (True,) * 4 if out is None else tuple(out))[0])
+
+    @staticmethod
+    def _partial_score(lcs, starts, ends, m, n):
+        """``100 (2 L) / (m + (end - start))`` as float64, evaluated as ``_ratio`` does, ``m`` the needle's and ``n`` the haystack's
+        symbols; an empty needle scores 100 against an empty haystack and 0 against any other."""
+        twice = 2.0 * lcs.astype(np.float64)
+        total = np.asarray(m, dtype=np.float64) + (ends.astype(np.float64) - starts.astype(np.float64))
+        return np.where(total > 0, 100.0 * twice / np.where(total > 0, total, 1.0), np.where(np.asarray(n) == 0, 100.0, 0.0))
+
+    def _partial(self, a, b, scope, cross):
+        (lcs, starts, ends, sides), a, b = self._scored_call("partial", a, b, scope, cross, (True,) * 4)
+        la, lb = _symbol_lengths(a, self._utf8, scope), _symbol_lengths(b, self._utf8, scope)
+        if cross:
+            la, lb = la[:, None], lb[None, :]
+        la, lb = np.broadcast_to(la, lcs.shape), np.broadcast_to(lb, lcs.shape)
+        score = self._partial_score(lcs, starts, ends, np.minimum(la, lb), np.maximum(la, lb))
+        return score, starts, ends, sides, la, lb
+
+    def partial_ratio(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None):
+        """rapidfuzz's ``fuzz.partial_ratio(a[i], b[i])``, unrounded, as float64: the best ``fuzz.ratio`` of the shorter string against
+        the windows of its own length of the longer one, the shorter windows at both ends included (``lawn`` in ``flaw in law``:
+        85.71...); with equal lengths both directions are tried. From one call's counts (``partial_counts``)."""
+        return self._partial(a, b, scope, False)[0]
+
+    def partial_ratio_alignment(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None) -> "PartialAlignments":
+        """rapidfuzz's ``fuzz.partial_ratio_alignment(a[i], b[i])`` for every pair, as a :class:`PartialAlignments`: the score and the
+        two substrings it was reached between. rapidfuzz filters windows by character set first and may report a later window of the
+        same score; the scores correspond."""
+        score, starts, ends, sides, la, lb = self._partial(a, b, scope, False)
+        in_b = sides == 0
+        zero = np.zeros_like(starts)
+        return PartialAlignments(score, np.where(in_b, zero, starts), np.where(in_b, la, ends), np.where(in_b, starts, zero), np.where(in_b, ends, lb))
+
+    def partial_ratio_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None):
+        """The dense float64 matrix of ``fuzz.partial_ratio``: rapidfuzz's ``process.cdist(queries, candidates,
+        scorer=fuzz.partial_ratio)``, unrounded; ``candidates=None`` is the self-product."""
+        return self._partial(queries, candidates, scope, True)[0]
 
     @staticmethod
     def _jaro(matches, transpositions, m, n):

@@ -64,6 +64,8 @@ pub const INFIX_NONE: u32 = u32::MAX;
 pub const OSA_MAX_SHORTER: u32 = 2048;
 /// `SWH_LCS_MAX_SHORTER`: symbols of a pair's shorter string an LCS / Indel call accepts.
 pub const LCS_MAX_SHORTER: u32 = 2048;
+/// `SWH_PARTIAL_MAX_NEEDLE`: symbols of a pair's shorter string a partial-ratio call accepts.
+pub const PARTIAL_MAX_NEEDLE: u32 = 2048;
 /// `SWH_JARO_MAX_LENGTH`: symbols of either string of a pair a Jaro call accepts.
 pub const JARO_MAX_LENGTH: u32 = 2048;
 /// `SWH_OP_*`: the op bytes of an alignment.
@@ -148,6 +150,12 @@ extern "C" {
     fn swh_levenshtein_lcs_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, indel: *mut usize, lcs: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_utf8_lcs_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, indel: *mut usize, lcs: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_lcs_cross_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, indel: *mut usize, lcs: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_partial_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, lcs: *mut u32, starts: *mut u32, ends: *mut u32, sides: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_partial_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, lcs: *mut u32, starts: *mut u32, ends: *mut u32, sides: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_partial_pairs_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, lcs: *mut u32, starts: *mut u32, ends: *mut u32, sides: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_partial_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, lcs: *mut usize, starts: *mut usize, ends: *mut usize, sides: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_partial_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, lcs: *mut usize, starts: *mut usize, ends: *mut usize, sides: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_partial_cross_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, lcs: *mut usize, starts: *mut usize, ends: *mut usize, sides: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_jaro_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, matches: *mut u32, transpositions: *mut u32, prefix: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_utf8_jaro_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, matches: *mut u32, transpositions: *mut u32, prefix: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_jaro_pairs_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, matches: *mut u32, transpositions: *mut u32, prefix: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;

@@ -32,6 +32,8 @@ KERNELS = {
     "infix": ("swh::k_infix<", ("infix.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
     "osa": ("swh::k_osa<", ("osa.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
     "lcs": ("swh::k_lcs<", ("lcs.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
+    "partial": ("swh::k_partial<unsigned char,", ("partial.hip", "partial.hpp", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
+    "partial_u32": ("swh::k_partial<unsigned int,", ("partial.hip", "partial.hpp", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
     "jaro": ("swh::k_jaro<unsigned char,", ("jaro.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
     "jaro_u32": ("swh::k_jaro<unsigned int,", ("jaro.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
     "extract_select": ("swh::k_extract_select<", ("extract.hip", "extract.hpp", "topk_fold.hpp", "cross_words.hpp", "common.hpp")),
