@@ -139,12 +139,6 @@ SIGNATURES = {
     "swh_levenshtein_init": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P), _ERR]),
     "swh_levenshtein_free": (C.c_int, [_P]),
     "swh_levenshtein_set_algorithm": (C.c_int, [_P, C.c_int]),
-    "swh_levenshtein_pairs_u32tape": (C.c_int, [_P, _P, C.POINTER(TapeU32), C.POINTER(TapeU32), C.c_uint32, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_pairs_u32tape": (C.c_int, [_P, _P, C.POINTER(TapeU32), C.POINTER(TapeU32), C.c_uint32, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, C.c_size_t, _ERR]),
     "swh_sharded_prepare_u32tape": (C.c_int, [_P, C.POINTER(TapeU32), C.POINTER(TapeU32), C.c_int, C.POINTER(_P), _ERR]),
     "swh_sharded_prepare_u64tape": (C.c_int, [_P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_int, C.POINTER(_P), _ERR]),
     "swh_sharded_free": (C.c_int, [_P]),
@@ -162,67 +156,13 @@ SIGNATURES = {
     "swh_nw_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P), _ERR]),
     "swh_nw_init_classes": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(_P), _ERR]),
     "swh_nw_free": (C.c_int, [_P]),
-    "swh_nw_pairs_u32tape": (C.c_int, [_P, _P, C.POINTER(TapeU32), C.POINTER(TapeU32), _P, C.c_size_t, _ERR]),
-    "swh_nw_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, C.c_size_t, _ERR]),
-    "swh_nw_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, C.c_size_t, _ERR]),
     "swh_sw_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P), _ERR]),
     "swh_sw_init_classes": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(_P), _ERR]),
     "swh_sw_free": (C.c_int, [_P]),
-    "swh_sw_pairs_u32tape": (C.c_int, [_P, _P, C.POINTER(TapeU32), C.POINTER(TapeU32), _P, C.c_size_t, _ERR]),
-    "swh_sw_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, C.c_size_t, _ERR]),
-    "swh_sw_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, C.c_size_t, _ERR]),
     "swh_tape_prepare_u32": (C.c_int, [_P, C.POINTER(TapeU32), C.c_int, C.POINTER(_P), _ERR]),
     "swh_tape_prepare_u64": (C.c_int, [_P, C.POINTER(TapeU64), C.c_int, C.POINTER(_P), _ERR]),
     "swh_prepared_info": (C.c_int, [_P, C.POINTER(PreparedInfo)]),
     "swh_prepared_free": (C.c_int, [_P]),
-    "swh_levenshtein_pairs_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_uint32, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, C.c_size_t, _ERR]),
-    "swh_nw_pairs_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, C.c_size_t, _ERR]),
-    "swh_nw_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, C.c_size_t, _ERR]),
-    "swh_sw_pairs_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, C.c_size_t, _ERR]),
-    "swh_sw_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_topk_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_size_t, C.c_uint32, _P, _P, _ERR]),
-    "swh_levenshtein_utf8_topk_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_size_t, C.c_uint32, _P, _P, _ERR]),
-    "swh_levenshtein_topk_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_size_t, C.c_uint32, _P, _P, _ERR]),
-    "swh_levenshtein_within_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_within_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_within_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_uint32, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_align_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_align_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_align_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_uint32, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_infix_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, _P, _ERR]),
-    "swh_levenshtein_utf8_infix_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, _P, _ERR]),
-    "swh_levenshtein_infix_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_uint32, _P, _P, _P, _ERR]),
-    "swh_levenshtein_osa_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_osa_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_osa_pairs_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_uint32, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_osa_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_osa_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_osa_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_lcs_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_lcs_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_uint32, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_lcs_pairs_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_uint32, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_lcs_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_lcs_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_lcs_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_partial_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_partial_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_partial_pairs_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_partial_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_partial_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_partial_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_jaro_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_jaro_pairs_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_jaro_pairs_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_jaro_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_jaro_cross_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_jaro_cross_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_extract_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, _P, _P, _ERR]),
-    "swh_levenshtein_utf8_extract_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, _P, _P, _ERR]),
-    "swh_levenshtein_extract_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, _P, _P, _ERR]),
-    "swh_levenshtein_extract_within_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_utf8_extract_within_u64tape": (C.c_int, [_P, _P, C.POINTER(TapeU64), C.POINTER(TapeU64), C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P, C.c_size_t, _ERR]),
-    "swh_levenshtein_extract_within_prepared": (C.c_int, [_P, _P, C.POINTER(PreparedView), C.POINTER(PreparedView), C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P, C.c_size_t, _ERR]),
     "swh_version": (C.c_char_p, []),
     "swh_capabilities": (C.c_char_p, []),
     # harness header
@@ -237,6 +177,48 @@ SIGNATURES = {
     "swh_format_si_rate": (C.c_size_t, [C.c_double, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]),
     "swh_format_seconds": (C.c_size_t, [C.c_double, C.c_char_p, C.c_size_t]),
 }
+
+_U32, _U64, _SIZE = C.c_uint32, C.c_uint64, C.c_size_t
+# The two-tape calls: (prefix, stem, tail, forms). Every export of one takes (engine, scope, tape a, tape b, *tail, err). A stem has
+# `<prefix>_<stem>_u64tape` on raw tapes and `<prefix>_<stem>_prepared` on prepared views; `forms` names what exists beside them:
+# "utf8", the `<prefix>_utf8_<stem>_*tape` twins of the raw forms, and "u32", the `*_u32tape` twins on 32-bit offsets. A new call is one row.
+TWO_TAPE = [
+    ("swh_levenshtein", "pairs", [_U32, _P, _SIZE], ("utf8", "u32")),
+    ("swh_levenshtein", "cross", [_P, _SIZE], ("utf8",)),
+    ("swh_levenshtein", "topk", [_SIZE, _U32, _P, _P], ("utf8",)),
+    ("swh_levenshtein", "within", [_U32, _P, _P, _P, _SIZE], ("utf8",)),
+    ("swh_levenshtein", "align", [_U32, _P, _P, _P, _SIZE], ("utf8",)),
+    ("swh_levenshtein", "infix", [_U32, _P, _P, _P], ("utf8",)),
+    ("swh_levenshtein", "osa_pairs", [_U32, _P, _SIZE], ("utf8",)),
+    ("swh_levenshtein", "osa_cross", [_P, _SIZE], ("utf8",)),
+    ("swh_levenshtein", "lcs_pairs", [_U32, _P, _P, _SIZE], ("utf8",)),
+    ("swh_levenshtein", "lcs_cross", [_P, _P, _SIZE], ("utf8",)),
+    ("swh_levenshtein", "partial_pairs", [_P, _P, _P, _P, _SIZE], ("utf8",)),
+    ("swh_levenshtein", "partial_cross", [_P, _P, _P, _P, _SIZE], ("utf8",)),
+    ("swh_levenshtein", "jaro_pairs", [_P, _P, _P, _SIZE], ("utf8",)),
+    ("swh_levenshtein", "jaro_cross", [_P, _P, _P, _SIZE], ("utf8",)),
+    ("swh_levenshtein", "extract", [C.c_int, _SIZE, _U64, _U64, _P, _P], ("utf8",)),
+    ("swh_levenshtein", "extract_within", [C.c_int, _U64, _U64, _P, _P, _P, _SIZE], ("utf8",)),
+    ("swh_nw", "pairs", [_P, _SIZE], ("u32",)),
+    ("swh_nw", "cross", [_P, _SIZE], ()),
+    ("swh_sw", "pairs", [_P, _SIZE], ("u32",)),
+    ("swh_sw", "cross", [_P, _SIZE], ()),
+]
+U32_STEMS = frozenset(stem for _, stem, _, forms in TWO_TAPE if "u32" in forms)   # the stems whose raw tapes may keep 32-bit offsets
+
+
+def _two_tape_rows(prefix, stem, tail, forms):
+    """The SIGNATURES rows of one TWO_TAPE row."""
+    raw = [("u64tape", TapeU64)] + ([("u32tape", TapeU32)] if "u32" in forms else [])
+    sides = [("%s_%s" % (stem, suffix), tape) for suffix, tape in raw]
+    if "utf8" in forms:
+        sides += [("utf8_" + form, tape) for form, tape in sides]
+    sides.append((stem + "_prepared", PreparedView))
+    return {"%s_%s" % (prefix, form): (C.c_int, [_P, _P, C.POINTER(tape), C.POINTER(tape), *tail, _ERR]) for form, tape in sides}
+
+
+for _row in TWO_TAPE:
+    SIGNATURES.update(_two_tape_rows(*_row))
 
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here == the library does not export a declared symbol

@@ -730,6 +730,32 @@ def test_topk_offset_widths(sw, orc, scope):
 
 
 @pytest.mark.gpu
+def test_topk_refuses_device_tensors_of_the_wrong_size(sw, scope):
+    """3 queries, 4 candidates, k = 2: six entries. A device tensor of 5 or 7 int32, of 6 int64, or a ``[::2]`` view of 12 int32, as the
+    indices or as the distances, is a ValueError before the library -- which cannot know a tensor's size -- sees its address: both
+    tensors keep their sentinel. A right pair then gives the rows of the numpy call."""
+    import torch
+    engine = sw.LevenshteinDistances(capabilities=scope)
+    queries, candidates = sw.Strs(["kitten", "lawn", ""]), sw.Strs(["sitting", "flaw", "law", "kitchen"])
+    want = engine.topk(queries, candidates, scope, k=2)
+    assert want[1].tolist() == [[2, 3], [1, 2], [3, 4]] and want[0].tolist() == [[3, 0], [2, 1], [2, 1]]
+    wrong = {"five": lambda: torch.full((5,), -7, dtype=torch.int32, device="cuda"), "seven": lambda: torch.full((7,), -7, dtype=torch.int32, device="cuda"),
+             "int64": lambda: torch.full((6,), -7, dtype=torch.int64, device="cuda"),
+             "strided": lambda: torch.full((12,), -7, dtype=torch.int32, device="cuda")[::2]}
+    for name, make in wrong.items():
+        for slot in (0, 1):
+            out = [torch.full((3, 2), -7, dtype=torch.int32, device="cuda"), torch.full((3, 2), -7, dtype=torch.int32, device="cuda")]
+            out[slot] = make()
+            with pytest.raises(ValueError):
+                engine.topk(queries, candidates, scope, k=2, out=tuple(out))
+            torch.cuda.synchronize()
+            assert all(bool((t == -7).all()) for t in out), (name, slot)
+    out = torch.full((6,), -7, dtype=torch.int32, device="cuda"), torch.full((3, 2), -7, dtype=torch.int32, device="cuda")
+    got = engine.topk(queries, candidates, scope, k=2, out=out)
+    assert got[0] is out[0] and (_host(out[0]).reshape(3, 2) == want[0]).all() and (_host(out[1]) == want[1]).all()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("width", [np.uint32, np.uint64])
 def test_topk_prepared_tape_changed_after_it_was_measured(sw, orc, scope, width):
     """A prepared DEVICE tape is measured once and its memory stays the caller's. When a candidate has grown beyond 32 bytes since, the
