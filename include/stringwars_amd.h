@@ -533,6 +533,76 @@ swh_status_t swh_levenshtein_partial_cross_prepared(swh_levenshtein_t engine, sw
                                                     const swh_prepared_view_t *b, size_t *lcs, size_t *starts, size_t *ends,
                                                     size_t *sides, size_t row_stride_bytes, const char **error);
 
+/* ---- Token-sorted tapes, token_sort_ratio and token_set_ratio (rapidfuzz `fuzz.token_sort_ratio`, `fuzz.token_set_ratio`). --------
+ * Tokens are the maximal runs of non-whitespace symbols of a string: what Python's split() without an argument returns.
+ *  - On a tape prepared with utf8 = 0 whitespace is the six bytes of bytes.split(): 09 0A 0B 0C 0D 20.
+ *  - On a tape prepared with utf8 = 1 it is the 29 code points of str.isspace(): U+0009-000D, U+001C-001F, U+0020, U+0085, U+00A0,
+ *    U+1680, U+2000-200A, U+2028, U+2029, U+202F, U+205F, U+3000 -- in UTF-8 the single bytes 09-0D and 1C-20, C2 85, C2 A0,
+ *    E1 9A 80, E2 80 80..8A, E2 80 A8, E2 80 A9, E2 80 AF, E2 81 9F and E3 80 80. U+200B, U+180E, U+FEFF, U+0084 and U+00A1 are no
+ *    whitespace; neither are 1C-1F and the raw bytes 85 and A0 on a byte tape.
+ * Tokens are ordered by symbol value, a proper prefix first: Python's sorted() on bytes or str (on valid UTF-8 byte order is
+ * code-point order). The two normal forms of a string s:
+ *  - SWH_TOKENS_SORTED: b" ".join(sorted(s.split())), duplicates kept;
+ *  - SWH_TOKENS_UNIQUE: b" ".join(sorted(set(s.split()))).
+ * The separator is one 0x20, none leads or trails, a string without a token becomes the empty string, and a normal form is never
+ * longer than its string.
+ *
+ * swh_tape_token_sort derives the tape of normal forms of a prepared view's strings on the device. The result is a new prepared tape
+ * like any other: in the view's mode, with offsets[0] = 0 and offsets of the view's tape's width, measured (swh_prepared_info),
+ * accepted by every call that takes a prepared view, and the owner of its buffers -- freeing the source does not touch it. So
+ *      token_sort_ratio(a, b)         = ratio (swh_levenshtein_lcs_pairs_prepared) of the two SWH_TOKENS_SORTED tapes,
+ *      cdist(scorer=token_sort_ratio) = swh_levenshtein_lcs_cross_prepared of them,
+ *      process.extract(scorer=token_sort_ratio) = swh_levenshtein_extract_prepared(SWH_SCORER_RATIO) of them,
+ *      partial_token_sort_ratio       = swh_levenshtein_partial_pairs_prepared of them.
+ *  - a string of more than SWH_TOKEN_MAX_BYTES bytes makes the call return swh_unsupported_length_k, the message naming the first such
+ *    string of the view; *out is NULL then;
+ *  - a view of no strings gives a valid empty tape; a `form` that is neither of the two is swh_invalid_argument_k;
+ *  - the call is synchronous on every scope, and the same input gives the same bytes on every run.
+ * swh_prepared_read copies a prepared tape's count + 1 byte offsets, rebased so that offsets[0] = 0, and -- unless `data` is NULL --
+ * its offsets[count] bytes to the host: call it with NULL first to size `data`. It reads any prepared tape, derived or not.
+ *
+ * token_set_ratio. Let A and B be the token sets of a and b, S the SWH_TOKENS_UNIQUE join of A & B, X that of A - B and Y that of
+ * B - A, s, x and y their lengths in symbols (bytes, or code points on a UTF-8 tape) and L = LCS(X, Y). The calls return the four
+ * integers per pair -- sect = s, ab = x, ba = y, lcs = L -- and callers evaluate the float64 score, with
+ * q(d, t) = t > 0 ? 100.0 * (double)(t - d) / (double)t : 100.0:
+ *      if s == 0 and (x == 0 or y == 0): 0.0        (a side without tokens; two empty strings score 0, not 100)
+ *      elif x == 0 or y == 0:            100.0      (one token set contains the other)
+ *      else: e = s > 0 ? 1 : 0; sab = s + e + x; sba = s + e + y;
+ *            r = q(x + y - 2 L, sab + sba);
+ *            score = s == 0 ? r : max(r, q(e + x, s + sab), q(e + y, s + sba))
+ *      a / b                                                                     token_sort   s  x  y  L   token_set
+ *      fuzzy was a bear / fuzzy fuzzy was a bear                                 84.2105...   16 0  0  0   100
+ *      mariners vs angels / los angeles angels of anaheim at seattle mariners    50.7462...   15 2  33 1   90.9090...
+ *      york new / new jersey                                                     33.3333...   3  4  6  1   55.5555...
+ *      a a b / b c                                                               25           1  1  1  0   66.6666...
+ *      "  b  a " / "a\tb\n"                                                      100          3  0  0  0   100
+ *      "" / ""                                                                   100          0  0  0  0   0
+ *      "   " / a                                                                 0            0  0  1  0   0
+ * Pairs (swh_levenshtein_token_set_pairs_*):
+ *  - the tapes may be any tapes: the call derives the SWH_TOKENS_UNIQUE forms itself, and uses a prepared tape that
+ *    swh_tape_token_sort made in that form as it stands; every string holds at most SWH_TOKEN_MAX_BYTES bytes;
+ *  - a->count == b->count, else swh_invalid_argument_k;
+ *  - any of the four outputs may be NULL, not all: swh_invalid_argument_k; `out_stride_bytes` is the distance between consecutive
+ *    results of every output (>= 4; 0 means 4); each output may be in host or device memory;
+ *  - a pair of which the SHORTER normal form has more than SWH_LCS_MAX_SHORTER symbols makes the call return
+ *    swh_unsupported_length_k before any output is written; the message names the first such pair and both lengths;
+ *  - an engine whose costs are not (match 0, mismatch 1, open 1, extend 1) returns swh_not_implemented_k; invalid UTF-8 is
+ *    swh_invalid_utf8_k; count == 0 succeeds and writes nothing; the call is synchronous on every scope. */
+#define SWH_TOKEN_MAX_BYTES 4096u     /* bytes of a string whose tokens are sorted: one wave holds it and its token table in LDS */
+#define SWH_TOKENS_SORTED 0
+#define SWH_TOKENS_UNIQUE 1
+swh_status_t swh_tape_token_sort(swh_scope_t scope, const swh_prepared_view_t *view, int form, swh_prepared_t *out, const char **error);
+swh_status_t swh_prepared_read(swh_scope_t scope, swh_prepared_t prepared, void *data, size_t *offsets, const char **error);
+swh_status_t swh_levenshtein_token_set_pairs_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                     const swh_tape_u64_t *b, uint32_t *sect, uint32_t *ab, uint32_t *ba, uint32_t *lcs,
+                                                     size_t out_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_utf8_token_set_pairs_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *a,
+                                                          const swh_tape_u64_t *b, uint32_t *sect, uint32_t *ab, uint32_t *ba,
+                                                          uint32_t *lcs, size_t out_stride_bytes, const char **error);
+swh_status_t swh_levenshtein_token_set_pairs_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *a,
+                                                      const swh_prepared_view_t *b, uint32_t *sect, uint32_t *ab, uint32_t *ba,
+                                                      uint32_t *lcs, size_t out_stride_bytes, const char **error);
+
 /* ---- Jaro and Jaro-Winkler similarities (rapidfuzz `distance.Jaro` / `distance.JaroWinkler`, jellyfish `jaro_similarity` /
  *      `jaro_winkler_similarity`), unit-cost engines only. The calls return the integer counts; callers evaluate the two
  *      similarity expressions below. ---------------------------------------------------------------------------------------------

@@ -130,7 +130,42 @@ public:
     size_t size() const { return count_; }
     swh_prepared_info_t info() const { swh_prepared_info_t i{}; swh_prepared_info(handle_, &i); return i; }
     swh_prepared_view_t c() const { return swh_prepared_view_t{handle_, first_, count_}; }
+    /// The token-sorted normal form of every string of this view (`swh_tape_token_sort`; `form`: SWH_TOKENS_SORTED or
+    /// SWH_TOKENS_UNIQUE), derived on the device: a tape of its own, in this tape's mode. lcs_pairs / lcs_cross / extract / partial of
+    /// two SWH_TOKENS_SORTED tapes are rapidfuzz's fuzz.token_sort_ratio, its cdist, its process.extract and partial_token_sort_ratio.
+    PreparedTape token_sorted(const DeviceScope &scope, int form = SWH_TOKENS_SORTED) const {
+        const char *err = nullptr;
+        swh_prepared_view_t view = c();
+        swh_prepared_t derived = nullptr;
+        swh_status_t status__ = swh_tape_token_sort(scope.handle(), &view, form, &derived, &err);
+        check(status__, err);
+        PreparedTape tape(derived, 0, count_);
+        tape.owner_ = true;
+        return tape;
+    }
+    /// The whole tape on the host (`swh_prepared_read`): its bytes, and its size() + 1 offsets from 0 into `offsets`.
+    std::vector<uint8_t> read(const DeviceScope &scope, std::vector<size_t> &offsets) const {
+        const char *err = nullptr;
+        offsets.assign(info().count + 1, 0);
+        swh_status_t status__ = swh_prepared_read(scope.handle(), handle_, nullptr, offsets.data(), &err);
+        check(status__, err);
+        std::vector<uint8_t> data(offsets.back());
+        status__ = swh_prepared_read(scope.handle(), handle_, data.data(), offsets.data(), &err);
+        check(status__, err);
+        return data;
+    }
 };
+
+/// rapidfuzz's fuzz.token_set_ratio, unrounded, from the four counts of LevenshteinDistances::token_set (include/stringwars_amd.h has
+/// the definition): 0 where a side has no token, 100 where one token set holds the other.
+inline double token_set_score(uint32_t sect, uint32_t ab, uint32_t ba, uint32_t lcs) {
+    const auto q = [](uint64_t d, uint64_t t) { return t > 0 ? 100.0 * (double)(t - d) / (double)t : 100.0; };
+    const uint64_t s = sect, x = ab, y = ba;
+    if (x == 0 || y == 0) return s == 0 ? 0.0 : 100.0;
+    const uint64_t e = s > 0 ? 1 : 0, sab = s + e + x, sba = s + e + y;
+    const double r = q(x + y - 2 * (uint64_t)lcs, sab + sba);
+    return s == 0 ? r : std::max(r, std::max(q(e + x, s + sab), q(e + y, s + sba)));
+}
 
 /// One pairwise batch resident on every GPU of a multi-device scope (`swh_sharded_prepare_u64tape`), cells-balanced shards.
 class ShardedPairs {
@@ -355,6 +390,24 @@ public:
         swh_prepared_view_t q = queries.c(), c = candidates ? candidates->c() : q;
         swh_status_t status__ = swh_levenshtein_partial_cross_prepared(handle_, scope.handle(), &q, candidates ? &c : nullptr, out.lcs, out.starts, out.ends,
                                                                        out.sides, row_stride_bytes, &err);
+        check(status__, err);
+    }
+    /// Token set counts (swh_levenshtein_token_set_pairs_*; rapidfuzz fuzz.token_set_ratio): with A and B the sets of the two strings'
+    /// tokens, sect[i], ab[i] and ba[i] are the symbols of the sorted, space-joined A & B, A - B and B - A, and lcs[i] the LCS length
+    /// of the last two; token_set_score evaluates them. Any tapes: the call derives the SWH_TOKENS_UNIQUE forms itself and takes a
+    /// prepared tape that token_sorted made in that form as it stands. Any output may be nullptr, not all; host or device memory.
+    template <typename T> struct TokenSetCounts { T *sect = nullptr, *ab = nullptr, *ba = nullptr, *lcs = nullptr; };
+    void token_set(const DeviceScope &scope, const TokenSetCounts<uint32_t> &out, const BytesTapeView &a, const BytesTapeView &b) const {
+        const char *err = nullptr;
+        swh_tape_u64_t ta = a.c(), tb = b.c();
+        auto fn = utf8_ ? swh_levenshtein_utf8_token_set_pairs_u64tape : swh_levenshtein_token_set_pairs_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &ta, &tb, out.sect, out.ab, out.ba, out.lcs, 4, &err);
+        check(status__, err);
+    }
+    void token_set(const DeviceScope &scope, const TokenSetCounts<uint32_t> &out, const PreparedTape &a, const PreparedTape &b) const {
+        const char *err = nullptr;
+        swh_prepared_view_t va = a.c(), vb = b.c();
+        swh_status_t status__ = swh_levenshtein_token_set_pairs_prepared(handle_, scope.handle(), &va, &vb, out.sect, out.ab, out.ba, out.lcs, 4, &err);
         check(status__, err);
     }
     /// Jaro / Jaro-Winkler counts (swh_levenshtein_jaro_pairs_*; rapidfuzz distance.Jaro / distance.JaroWinkler): matches[i] = M,

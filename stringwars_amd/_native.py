@@ -58,6 +58,8 @@ OSA_MAX_SHORTER = 2048     # SWH_OSA_MAX_SHORTER: symbols of a pair's shorter st
 LCS_MAX_SHORTER = 2048     # SWH_LCS_MAX_SHORTER: symbols of a pair's shorter string an LCS / Indel call accepts
 PARTIAL_MAX_NEEDLE = 2048  # SWH_PARTIAL_MAX_NEEDLE: symbols of a pair's shorter string a partial-ratio call accepts
 JARO_MAX_LENGTH = 2048     # SWH_JARO_MAX_LENGTH: symbols of either string of a pair a Jaro call accepts
+TOKEN_MAX_BYTES = 4096     # SWH_TOKEN_MAX_BYTES: bytes of a string whose tokens swh_tape_token_sort sorts
+TOKENS_SORTED, TOKENS_UNIQUE = 0, 1   # SWH_TOKENS_*: the normal forms of swh_tape_token_sort
 # SWH_SCORER_*: the scores a score search (swh_levenshtein_extract_*) ranks by, by name
 SCORERS = {"osa": 0, "indel": 1, "lcs": 2, "ratio": 3, "jaro": 4, "jaro_winkler": 5}
 OP_MATCH, OP_SUBST, OP_DEL, OP_INS = ord("="), ord("X"), ord("D"), ord("I")   # SWH_OP_*: the bytes of an alignment's ops
@@ -163,6 +165,8 @@ SIGNATURES = {
     "swh_tape_prepare_u64": (C.c_int, [_P, C.POINTER(TapeU64), C.c_int, C.POINTER(_P), _ERR]),
     "swh_prepared_info": (C.c_int, [_P, C.POINTER(PreparedInfo)]),
     "swh_prepared_free": (C.c_int, [_P]),
+    "swh_tape_token_sort": (C.c_int, [_P, C.POINTER(PreparedView), C.c_int, C.POINTER(_P), _ERR]),
+    "swh_prepared_read": (C.c_int, [_P, _P, _P, _P, _ERR]),
     "swh_version": (C.c_char_p, []),
     "swh_capabilities": (C.c_char_p, []),
     # harness header
@@ -195,6 +199,7 @@ TWO_TAPE = [
     ("swh_levenshtein", "lcs_cross", [_P, _P, _SIZE], ("utf8",)),
     ("swh_levenshtein", "partial_pairs", [_P, _P, _P, _P, _SIZE], ("utf8",)),
     ("swh_levenshtein", "partial_cross", [_P, _P, _P, _P, _SIZE], ("utf8",)),
+    ("swh_levenshtein", "token_set_pairs", [_P, _P, _P, _P, _SIZE], ("utf8",)),
     ("swh_levenshtein", "jaro_pairs", [_P, _P, _P, _SIZE], ("utf8",)),
     ("swh_levenshtein", "jaro_cross", [_P, _P, _P, _SIZE], ("utf8",)),
     ("swh_levenshtein", "extract", [C.c_int, _SIZE, _U64, _U64, _P, _P], ("utf8",)),

@@ -52,6 +52,7 @@ struct Prepared {
     // tiled kernel's planning needs of the strings, laid out so that it finds it by string number (tiled.hip: kSide). Only built where
     // that kernel can be chosen: prepare_tape has the conditions.
     const uint4 *side = nullptr;
+    int token_form = -1;         // SWH_TOKENS_*: the normal form swh_tape_token_sort derived this tape in; -1 for every other tape
     std::vector<void *> owned;   // device buffers that go with the handle
 };
 // (declared here, not in common.hpp, which every kernel family's profile stamp hashes)

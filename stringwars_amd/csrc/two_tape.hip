@@ -1,5 +1,6 @@
 // two_tape.hip -- the synchronous two-tape calls of include/stringwars_amd.h: top-k, range, score and score range searches,
-// alignments, infix search and the scored families (OSA, LCS / Indel, partial ratio, Jaro). Host code only: the kernels are the families' own files,
+// alignments, infix search, the scored families (OSA, LCS / Indel, partial ratio, Jaro) and the token-sorted tapes with token_set_ratio.
+// Host code only: the kernels are the families' own files,
 // the engine-call path the searches score their slices on is api.hip (api.hpp: what the two files share).
 #include <algorithm>
 #include <cmath>
@@ -15,6 +16,7 @@
 #include "osa.hpp"
 #include "lcs.hpp"
 #include "partial.hpp"
+#include "tokens.hpp"
 #include "jaro.hpp"
 #include "extract.hpp"
 
@@ -1217,6 +1219,288 @@ swh_status_t swh_levenshtein_utf8_jaro_cross_u64tape(swh_levenshtein_t e, swh_sc
 swh_status_t swh_levenshtein_jaro_cross_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
                                                  size_t *matches, size_t *transpositions, size_t *prefix, size_t row_stride, const char **error) {
     return scored_prepared(kJaroFamily, e, s, a, b, true, SWH_UNBOUNDED, {matches, transpositions, prefix}, row_stride, error);
+}
+
+// ---- token-sorted tapes and token_set_ratio (tokens.hip) ---------------------------------------------------------------------------------
+// A normal form is never longer than its string, and neither are the two differences of a pair's token sets. So the kernels write
+// into staging laid out like their source and leave the lengths beside it; the lengths become offsets through the range search's scan
+// (launch_within_offsets), k_token_compact moves the results into buffers of their own, and prepare_tape measures those in place like
+// any device tape (and decodes them, in UTF-8 mode): the handle that comes out owns them and is a prepared tape like every other.
+// token_set_ratio derives the SWH_TOKENS_UNIQUE forms of both sides (or takes a tape that already is one), asks the LCS family's sizes
+// kernel for the first pair it would refuse -- x <= len(a'), y <= len(b'), so the rule of ratio on the normal forms covers the
+// differences -- splits every pair (k_token_set_split: s, x, y and the bytes of X and Y) and runs the LCS pairs route on the two
+// difference tapes for L.
+struct DeviceBuffer {
+    void *p = nullptr;
+    ~DeviceBuffer() { if (p) (void)hipFree(p); }
+    void *alloc(size_t bytes) { SWH_HIP_CHECK(hipMalloc(&p, bytes ? bytes : 16)); return p; }
+    void *release() { void *q = p; p = nullptr; return q; }
+};
+
+// strings [first, first + count) of a prepared tape as the token kernels read them (up to two reads and waits)
+static TokenSide token_side(const Prepared *p, size_t first, size_t count, hipStream_t stream) {
+    TokenSide s{};
+    s.view = prepared_view(p, false, first, count);
+    s.off64 = p->off64;
+    s.total = p->total_bytes;
+    s.base = first == 0 ? p->first_byte : std::min(read_offset(s.view.offsets, (int)p->off64, 0, true, stream), s.total);
+    const uint64_t end = first + count == p->bytes.count ? s.total : std::min(read_offset(s.view.offsets, (int)p->off64, count, true, stream), s.total);
+    s.span = end > s.base ? end - s.base : 0;
+    return s;
+}
+
+// What a scan of `count` lengths needs beside them, and the tape it leads to.
+struct TokenScan {
+    uint64_t *block_sums, *starts, *offsets;
+    static size_t need(uint64_t count) {
+        return pad((count + kWithinScanTile - 1) / kWithinScanTile * 8) + pad(count * 8) + pad((count + 1) * 8);
+    }
+    void place(Carver &sc, uint64_t count) {
+        block_sums = sc.take<uint64_t>((count + kWithinScanTile - 1) / kWithinScanTile);
+        starts = sc.take<uint64_t>(count);
+        offsets = sc.take<uint64_t>(count + 1);
+    }
+};
+struct TokenTape {
+    DeviceBuffer data, offsets;
+    uint32_t off64 = 0;
+};
+// the results of `like`'s strings, `lengths` bytes each in `staging`, as a tape of its own with `off64`-wide offsets (one read and wait)
+static void token_pack(Scope *scope, const TokenSide &like, const uint8_t *staging, const uint32_t *lengths, const TokenScan &scan, uint32_t off64,
+                       TokenTape &tape) {
+    const uint64_t count = like.view.count;
+    launch_within_offsets(scope, lengths, count, 1, scan.block_sums, scan.starts, scan.offsets);
+    const uint64_t total = read_offset(scan.offsets, 1, count, true, scope->stream);
+    TokenCompact c{};
+    c.like = like; c.staging = staging; c.lengths = lengths; c.starts = scan.offsets;
+    c.out = (uint8_t *)tape.data.alloc(total + 16);
+    c.out_offsets = tape.offsets.alloc((count + 1) * (off64 ? 8 : 4) + 16);
+    c.out_off64 = tape.off64 = off64;
+    launch_token_compact(scope, c);
+}
+// measures a packed tape in place and hands its buffers to the handle
+static swh_status_t token_adopt(Scope *scope, TokenTape &tape, uint64_t count, bool utf8, int form, Prepared **out, const char **error) {
+    swh_prepared_t handle = nullptr;
+    const HostTape host{(const uint8_t *)tape.data.p, tape.offsets.p, (size_t)count, (int)tape.off64};
+    const swh_status_t status = prepare_tape(scope, host, utf8, &handle, error);
+    if (status != swh_success_k) return status;
+    Prepared *p = (Prepared *)handle;
+    p->owned.push_back(tape.data.release());
+    p->owned.push_back(tape.offsets.release());
+    p->token_form = form;
+    *out = p;
+    return swh_success_k;
+}
+
+// The tape of normal forms of strings [first, first + count) of `src`, on a scope held synchronous. HIP failures are thrown.
+static swh_status_t token_derive(Scope *scope, const Prepared *src, size_t first, size_t count, int form, Prepared **out, const char **error) {
+    *out = nullptr;
+    SWH_HIP_CHECK(hipSetDevice(scope->device));
+    hipStream_t stream = scope->stream;
+    TokenTape tape;
+    if (count == 0) {   // a valid empty tape: offsets[0] = 0
+        tape.off64 = src->off64;
+        tape.data.alloc(16);
+        SWH_HIP_CHECK(hipMemsetAsync(tape.offsets.alloc(16), 0, 16, stream));
+        return token_adopt(scope, tape, 0, src->utf8, form, out, error);
+    }
+    const TokenSide side = token_side(src, first, count, stream);
+    DeviceBuffer work;
+    Carver sc{(char *)work.alloc(pad(8) + pad(side.span) + pad(count * 4) + TokenScan::need(count)), 0, 0};
+    TokenDerive d{};
+    d.src = side; d.utf8 = src->utf8 ? 1 : 0; d.form = (uint32_t)form;
+    d.first_oversize = sc.take<unsigned long long>(1);
+    d.staging = sc.take<uint8_t>(side.span);
+    d.lengths = sc.take<uint32_t>(count);
+    TokenScan scan;
+    scan.place(sc, count);
+    // the launch for short strings where the tape's longest is one; it runs again for long ones if the tape's memory has changed since
+    bool small = src->longest_bytes <= kTokenSmallBytes;
+    unsigned long long oversize = ~0ull;
+    for (;;) {
+        SWH_HIP_CHECK(hipMemsetAsync(d.first_oversize, 0xFF, 8, stream));
+        launch_token_derive(scope, d, small);
+        SWH_HIP_CHECK(hipMemcpyAsync(&oversize, d.first_oversize, 8, hipMemcpyDeviceToHost, stream));
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        if (oversize == ~0ull || !small) break;
+        small = false;
+    }
+    if (oversize != ~0ull) {
+        const uint64_t bytes = string_symbols(side.view, side.off64, (size_t)oversize, stream);
+        scope->stamps_used = 0;
+        return fail(error, swh_unsupported_length_k, "string %llu: %llu bytes exceed SWH_TOKEN_MAX_BYTES (4096)", oversize, (unsigned long long)bytes);
+    }
+    token_pack(scope, side, d.staging, d.lengths, scan, src->off64, tape);
+    SWH_HIP_CHECK(hipStreamSynchronize(stream));   // (before the staging goes)
+    return token_adopt(scope, tape, count, src->utf8, form, out, error);
+}
+
+swh_status_t swh_tape_token_sort(swh_scope_t s, const swh_prepared_view_t *view, int form, swh_prepared_t *out, const char **error) {
+    if (out) *out = nullptr;
+    if (!s) return probe_null_handles(nullptr, nullptr, error);   // (no device, where none is visible)
+    if (!out) return fail(error, swh_invalid_argument_k, "null output");
+    if (!view || !view->tape) return fail(error, swh_invalid_argument_k, "null prepared view");
+    if (form != SWH_TOKENS_SORTED && form != SWH_TOKENS_UNIQUE)
+        return fail(error, swh_invalid_argument_k, "form must be SWH_TOKENS_SORTED or SWH_TOKENS_UNIQUE");
+    if (!view_fits(view)) return fail(error, swh_invalid_argument_k, "view exceeds the prepared tape");
+    const Prepared *src = (const Prepared *)view->tape;
+    if (src->device != ((Scope *)s)->device) return fail(error, swh_invalid_argument_k, "a prepared tape lives on another device than the scope");
+    TwoTapeCall call;
+    const swh_status_t status = call.begin(s, error);
+    if (status != swh_success_k) return status;
+    return synchronous_run(call.scope, error, [&]() -> swh_status_t {
+        Prepared *derived = nullptr;
+        const swh_status_t made = token_derive(call.scope, src, view->first, view->count, form, &derived, error);
+        if (made != swh_success_k) return made;
+        *out = (swh_prepared_t)derived;
+        close_call(call.scope, 0, src->total_bytes + derived->total_bytes);
+        return swh_success_k;
+    });
+}
+
+swh_status_t swh_prepared_read(swh_scope_t s, swh_prepared_t prepared, void *data, size_t *offsets, const char **error) {
+    static_assert(sizeof(size_t) == sizeof(uint64_t), "the offsets are read as 64-bit words");
+    if (!s) return probe_null_handles(nullptr, nullptr, error);   // (no device, where none is visible)
+    if (!prepared || !offsets) return fail(error, swh_invalid_argument_k, "null tape or offsets");
+    const Prepared *p = (const Prepared *)prepared;
+    if (p->device != ((Scope *)s)->device) return fail(error, swh_invalid_argument_k, "a prepared tape lives on another device than the scope");
+    TwoTapeCall call;
+    const swh_status_t status = call.begin(s, error);
+    if (status != swh_success_k) return status;
+    return synchronous_run(call.scope, error, [&]() -> swh_status_t {
+        SWH_HIP_CHECK(hipSetDevice(call.scope->device));
+        hipStream_t stream = call.scope->stream;
+        const size_t count = (size_t)p->bytes.count;
+        if (p->off64) {
+            SWH_HIP_CHECK(hipMemcpyAsync(offsets, p->bytes.offsets, (count + 1) * 8, hipMemcpyDeviceToHost, stream));
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        } else {
+            std::vector<uint32_t> narrow(count + 1);
+            SWH_HIP_CHECK(hipMemcpyAsync(narrow.data(), p->bytes.offsets, (count + 1) * 4, hipMemcpyDeviceToHost, stream));
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+            for (size_t i = 0; i <= count; ++i) offsets[i] = narrow[i];
+        }
+        const uint64_t base = std::min<uint64_t>(offsets[0], p->total_bytes);
+        for (size_t i = 0; i <= count; ++i) offsets[i] = std::min<uint64_t>(std::max<uint64_t>(offsets[i], base), p->total_bytes) - base;
+        if (data && offsets[count]) {
+            SWH_HIP_CHECK(hipMemcpyAsync(data, (const uint8_t *)p->bytes.data + base, offsets[count], hipMemcpyDeviceToHost, stream));
+            SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        }
+        return swh_success_k;
+    });
+}
+
+struct TokenSetOutputs {
+    uint32_t *sect, *ab, *ba, *lcs;
+    size_t stride;
+};
+// `n` packed device words to an output of the caller's, in host or device memory, at its stride
+static void token_set_copy(uint32_t *out, size_t stride, const uint32_t *dev, uint64_t n, hipStream_t stream) {
+    if (!out) return;
+    const hipMemcpyKind kind = is_device_pointer(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (stride == 4) SWH_HIP_CHECK(hipMemcpyAsync(out, dev, n * 4, kind, stream));
+    else SWH_HIP_CHECK(hipMemcpy2DAsync(out, stride, dev, 4, 4, n, kind, stream));
+}
+
+static swh_status_t token_set_run(Scope *scope, const TapePair &p, const TokenSetOutputs &r, const char **error) {
+    const uint64_t n = p.a_count;
+    if (n == 0) return swh_success_k;
+    PreparedOwner unique_a, unique_b, x, y;
+    const swh_status_t status = synchronous_run(scope, error, [&]() -> swh_status_t {
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        TapePair u = p;
+        swh_status_t made = swh_success_k;
+        if (p.pa->token_form != SWH_TOKENS_UNIQUE) {
+            if ((made = token_derive(scope, p.pa, p.a_first, n, SWH_TOKENS_UNIQUE, &unique_a.p, error)) != swh_success_k) return made;
+            u.pa = unique_a.p; u.a_first = 0;
+        }
+        if (p.pb->token_form != SWH_TOKENS_UNIQUE) {
+            if ((made = token_derive(scope, p.pb, p.b_first, n, SWH_TOKENS_UNIQUE, &unique_b.p, error)) != swh_success_k) return made;
+            u.pb = unique_b.p; u.b_first = 0;
+        }
+        // the first pair the LCS route would refuse on the normal forms, before anything is written
+        AlignScratch *sc_entry = call_scratch(scope);
+        Carver measuring = carve(sc_entry->buf, sc_entry->bytes, pad(sizeof(OsaSizes)));
+        OsaTapes t = scored_view(u, 0, n, 0, n, false);
+        const OsaSizes whole = scored_measure(scope, kLcsFamily, t, 0, n, measuring.take<OsaSizes>(1), nullptr);
+        if (whole.first_oversize != ~0ull) {
+            scope->stamps_used = 0;
+            const size_t first = (size_t)whole.first_oversize;
+            return scored_oversize(kLcsFamily, t, first, first, false, stream, error);
+        }
+
+        TokenSplit split{};
+        split.a = token_side(u.pa, u.a_first, n, stream);
+        split.b = token_side(u.pb, u.b_first, n, stream);
+        split.utf8 = u.pa->utf8 ? 1 : 0;
+        DeviceBuffer work;
+        Carver sc{(char *)work.alloc(pad(split.a.span) + pad(split.b.span) + 5 * pad(n * 4) + TokenScan::need(n)), 0, 0};
+        split.x_staging = sc.take<uint8_t>(split.a.span); split.y_staging = sc.take<uint8_t>(split.b.span);
+        split.x_lengths = sc.take<uint32_t>(n); split.y_lengths = sc.take<uint32_t>(n);
+        split.sect = sc.take<uint32_t>(n); split.ab = sc.take<uint32_t>(n); split.ba = sc.take<uint32_t>(n);
+        TokenScan scan;
+        scan.place(sc, n);
+        launch_token_set_split(scope, split, u.pa->longest_bytes <= kTokenSmallBytes && u.pb->longest_bytes <= kTokenSmallBytes);
+        token_set_copy(r.sect, r.stride, split.sect, n, stream);
+        token_set_copy(r.ab, r.stride, split.ab, n, stream);
+        token_set_copy(r.ba, r.stride, split.ba, n, stream);
+        TokenTape tape_x, tape_y;
+        if (r.lcs) {
+            token_pack(scope, split.a, split.x_staging, split.x_lengths, scan, u.pa->off64, tape_x);
+            token_pack(scope, split.b, split.y_staging, split.y_lengths, scan, u.pb->off64, tape_y);
+        }
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));   // (before the staging goes)
+        if (r.lcs) {
+            if ((made = token_adopt(scope, tape_x, n, u.pa->utf8, -1, &x.p, error)) != swh_success_k) return made;
+            if ((made = token_adopt(scope, tape_y, n, u.pb->utf8, -1, &y.p, error)) != swh_success_k) return made;
+        }
+        close_call(scope, 0, u.pa->total_bytes + u.pb->total_bytes + 3 * n * 4);
+        return swh_success_k;
+    });
+    if (status != swh_success_k || !r.lcs) return status;
+    TapePair differences;
+    differences.pa = x.p; differences.pb = y.p; differences.a_count = differences.b_count = (size_t)n;
+    return scored_run(scope, kLcsFamily, differences, ScoredRequest{false, SWH_UNBOUNDED, {nullptr, r.lcs, nullptr, nullptr}, r.stride}, error);
+}
+
+// the argument rules are the scored families' (scored_checks): this row holds the words of this call
+static const ScoredFamily kTokenSetRules = {
+    4, nullptr, nullptr, nullptr, "", "token set counts are called on a unit-cost engine (match 0, mismatch 1, open 1, extend 1)",
+    "null output pointers: one of sect, ab, ba and lcs is needed", true, false};
+
+static swh_status_t token_set_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b, bool utf8,
+                                    void *const (&outs)[kScoredOutputs], size_t stride, const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    if (!a || !b) return fail(error, swh_invalid_argument_k, "null tape");
+    if ((status = scored_checks(kTokenSetRules, e, a->count, b->count, false, outs, stride, error)) != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    const bool pairs = a->count != 0;
+    if ((status = call.prepare(a, b, utf8, pairs, pairs, error)) != swh_success_k) return status;
+    return token_set_run(call.scope, call.pair, TokenSetOutputs{(uint32_t *)outs[0], (uint32_t *)outs[1], (uint32_t *)outs[2], (uint32_t *)outs[3], stride}, error);
+}
+swh_status_t swh_levenshtein_token_set_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                     uint32_t *sect, uint32_t *ab, uint32_t *ba, uint32_t *lcs, size_t stride, const char **error) {
+    return token_set_tapes(e, s, a, b, false, {sect, ab, ba, lcs}, stride, error);
+}
+swh_status_t swh_levenshtein_utf8_token_set_pairs_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *a, const swh_tape_u64_t *b,
+                                                          uint32_t *sect, uint32_t *ab, uint32_t *ba, uint32_t *lcs, size_t stride,
+                                                          const char **error) {
+    return token_set_tapes(e, s, a, b, true, {sect, ab, ba, lcs}, stride, error);
+}
+swh_status_t swh_levenshtein_token_set_pairs_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *a, const swh_prepared_view_t *b,
+                                                      uint32_t *sect, uint32_t *ab, uint32_t *ba, uint32_t *lcs, size_t stride,
+                                                      const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    void *const outs[kScoredOutputs] = {sect, ab, ba, lcs};
+    TwoTapeCall call;
+    if ((status = call.views(a, b, false, error)) != swh_success_k) return status;
+    if ((status = scored_checks(kTokenSetRules, e, call.pair.a_count, call.pair.b_count, false, outs, stride, error)) != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return token_set_run(call.scope, call.pair, TokenSetOutputs{sect, ab, ba, lcs, stride}, error);
 }
 
 // ---- score search (extract.hip): the k best candidates by an OSA, Indel, LCS, ratio, Jaro or Jaro-Winkler score ------------------------

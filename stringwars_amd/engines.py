@@ -32,7 +32,7 @@ __all__ = [
     "DeviceScope", "Strs", "DeviceTape", "PreparedTape", "ShardedPairs", "shard_cuts", "LevenshteinDistances", "LevenshteinDistancesUTF8",
     "NeedlemanWunschScores", "SmithWatermanScores", "edit_distance", "StringWarsError", "UNBOUNDED", "TOPK_MAX",
     "ALIGN_MAX_CELLS", "Alignments", "RangeMatches", "ScoreMatches", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "OSA_MAX_SHORTER", "LCS_MAX_SHORTER", "PARTIAL_MAX_NEEDLE", "PartialAlignments",
-    "JARO_MAX_LENGTH", "SCORERS",
+    "JARO_MAX_LENGTH", "TOKEN_MAX_BYTES", "SCORERS",
 ]
 
 StringWarsError = N.StringWarsError
@@ -45,6 +45,7 @@ OSA_MAX_SHORTER = N.OSA_MAX_SHORTER
 LCS_MAX_SHORTER = N.LCS_MAX_SHORTER
 PARTIAL_MAX_NEEDLE = N.PARTIAL_MAX_NEEDLE
 JARO_MAX_LENGTH = N.JARO_MAX_LENGTH
+TOKEN_MAX_BYTES = N.TOKEN_MAX_BYTES
 SCORERS = tuple(N.SCORERS)   # the scorers of ``engine.extract``, by name
 
 
@@ -495,6 +496,78 @@ class LevenshteinDistances(_Engine):
         """The dense float64 matrix of ``fuzz.partial_ratio``: rapidfuzz's ``process.cdist(queries, candidates,
         scorer=fuzz.partial_ratio)``, unrounded; ``candidates=None`` is the self-product."""
         return self._partial(queries, candidates, scope, True)[0]
+
+    def _token_sorted(self, tape, scope, unique=False):
+        """The token-sorted form of one side of a call, and whether the call owns it: a ``PreparedTape`` is derived from as it stands;
+        anything else is prepared in the engine's mode, derived from and freed again."""
+        _need_scope(scope)
+        tape = _as_tape(tape)
+        if isinstance(tape, PreparedTape):
+            self._need_mode(tape)
+            return tape.token_sorted(unique)
+        prepared = PreparedTape(scope, tape, utf8=self._utf8)
+        try:
+            return prepared.token_sorted(unique)
+        finally:
+            prepared.free()
+
+    def _on_token_sorted(self, call, a, b, scope):
+        """``call(sorted a, sorted b, scope)`` on the ``SWH_TOKENS_SORTED`` forms of the two sides (``b`` None stays None); the derived
+        tapes are freed when it returns."""
+        derived = [self._token_sorted(a, scope)]
+        try:
+            derived.append(None if b is None else self._token_sorted(b, scope))
+            return call(derived[0], derived[1], scope)
+        finally:
+            for tape in derived:
+                if tape is not None:
+                    tape.free()
+
+    def token_sort_ratio(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None):
+        """rapidfuzz's ``fuzz.token_sort_ratio(a[i], b[i])``, unrounded, as float64: ``ratio`` of the two strings with their tokens
+        (``split()``) sorted and joined by one space -- ``new york mets`` / ``mets york new``: 100. The forms are derived on the device
+        (``PreparedTape.token_sorted``); a string holds at most ``TOKEN_MAX_BYTES`` bytes. The two sides are tapes, lists, device
+        tapes or ``PreparedTape``s; to score one collection many times, derive its tape once and call ``ratio``."""
+        if b is None:
+            raise ValueError("pairwise scoring needs two collections")
+        return self._on_token_sorted(self.ratio, a, b, scope)
+
+    def token_sort_ratio_cross(self, queries: TapeLike, candidates: Optional[TapeLike] = None, scope: Optional[DeviceScope] = None):
+        """The dense float64 matrix of ``fuzz.token_sort_ratio``: rapidfuzz's ``process.cdist(queries, candidates,
+        scorer=fuzz.token_sort_ratio)``, unrounded; ``candidates=None`` is the self-product."""
+        return self._on_token_sorted(self.ratio_cross, queries, candidates, scope)
+
+    def token_set_counts(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None, out=None):
+        """The counts behind the token set ratio of every pair ``(a[i], b[i])`` as four uint32 arrays
+        (``swh_levenshtein_token_set_pairs_*``): with A and B the sets of the two strings' tokens, the symbols ``s`` of the sorted,
+        space-joined A & B, ``x`` of A - B and ``y`` of B - A, and the LCS length of the last two. The call derives the unique
+        token-sorted forms itself; a ``PreparedTape`` from ``token_sorted(unique=True)`` is used as it stands. ``out``: four arrays
+        to fill, None where an output is not wanted (not all)."""
+        return tuple(self._scored_call("token_set", a, b, scope, False, (True,) * 4 if out is None else tuple(out))[0])
+
+    @staticmethod
+    def _token_set_score(s, x, y, lcs):
+        """rapidfuzz's ``fuzz.token_set_ratio`` from the four counts, as float64. With ``q(d, t) = 100.0 * (t - d) / t`` (100 where
+        ``t`` is 0), the expression ``_ratio`` evaluates for ``t = m + n``: 0 where a side has no token, 100 where one token set holds
+        the other, else ``max(q(x + y - 2 L, sab + sba), q(e + x, s + sab), q(e + y, s + sba))`` with ``e = 1`` for the separator behind
+        a non-empty intersection, ``sab = s + e + x`` and ``sba = s + e + y`` -- the first term alone where nothing is shared."""
+        s, x, y, lcs = (np.asarray(v).astype(np.float64) for v in (s, x, y, lcs))   # (counts: every sum below is exact)
+        e = (s > 0).astype(np.float64)
+        sab, sba = s + e + x, s + e + y
+        with np.errstate(divide="ignore", invalid="ignore"):   # (a zero total only where the result is decided without it)
+            t = sab + sba
+            r = 100.0 * (t - (x + y - 2.0 * lcs)) / t
+            t = s + sab
+            q_ab = 100.0 * (t - (e + x)) / t
+            t = s + sba
+            q_ba = 100.0 * (t - (e + y)) / t
+        score = np.where(s == 0, r, np.maximum(r, np.maximum(q_ab, q_ba)))
+        return np.where((x == 0) | (y == 0), np.where(s == 0, 0.0, 100.0), score)
+
+    def token_set_ratio(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None):
+        """rapidfuzz's ``fuzz.token_set_ratio(a[i], b[i])``, unrounded, as float64 -- ``mariners vs angels`` /
+        ``los angeles angels of anaheim at seattle mariners``: 90.909... -- from one call's counts (``token_set_counts``)."""
+        return self._token_set_score(*self.token_set_counts(a, b, scope))
 
     @staticmethod
     def _jaro(matches, transpositions, m, n):

@@ -66,6 +66,11 @@ pub const OSA_MAX_SHORTER: u32 = 2048;
 pub const LCS_MAX_SHORTER: u32 = 2048;
 /// `SWH_PARTIAL_MAX_NEEDLE`: symbols of a pair's shorter string a partial-ratio call accepts.
 pub const PARTIAL_MAX_NEEDLE: u32 = 2048;
+/// `SWH_TOKEN_MAX_BYTES`: bytes of a string whose tokens `PreparedTape::token_sorted` sorts.
+pub const TOKEN_MAX_BYTES: u32 = 4096;
+/// `SWH_TOKENS_SORTED` / `SWH_TOKENS_UNIQUE`: the normal forms of `PreparedTape::token_sorted`.
+pub const TOKENS_SORTED: c_int = 0;
+pub const TOKENS_UNIQUE: c_int = 1;
 /// `SWH_JARO_MAX_LENGTH`: symbols of either string of a pair a Jaro call accepts.
 pub const JARO_MAX_LENGTH: u32 = 2048;
 /// `SWH_OP_*`: the op bytes of an alignment.
@@ -114,6 +119,8 @@ extern "C" {
     fn swh_tape_prepare_u64(scope: Handle, tape: *const TapeU64, utf8: c_int, prepared: *mut Handle, error: Err) -> c_int;
     fn swh_prepared_info(prepared: Handle, info: *mut PreparedInfo) -> c_int;
     fn swh_prepared_free(prepared: Handle) -> c_int;
+    fn swh_tape_token_sort(scope: Handle, view: *const PreparedView, form: c_int, out: *mut Handle, error: Err) -> c_int;
+    fn swh_prepared_read(scope: Handle, prepared: Handle, data: *mut c_void, offsets: *mut usize, error: Err) -> c_int;
     // Levenshtein
     fn swh_levenshtein_init(scope: Handle, r#match: c_int, mismatch: c_int, open: c_int, extend: c_int, engine: *mut Handle, error: Err) -> c_int;
     fn swh_levenshtein_free(engine: Handle) -> c_int;
@@ -156,6 +163,9 @@ extern "C" {
     fn swh_levenshtein_partial_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, lcs: *mut usize, starts: *mut usize, ends: *mut usize, sides: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_utf8_partial_cross_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, lcs: *mut usize, starts: *mut usize, ends: *mut usize, sides: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_partial_cross_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, lcs: *mut usize, starts: *mut usize, ends: *mut usize, sides: *mut usize, row_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_token_set_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, sect: *mut u32, ab: *mut u32, ba: *mut u32, lcs: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_token_set_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, sect: *mut u32, ab: *mut u32, ba: *mut u32, lcs: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
+    fn swh_levenshtein_token_set_pairs_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, sect: *mut u32, ab: *mut u32, ba: *mut u32, lcs: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_jaro_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, matches: *mut u32, transpositions: *mut u32, prefix: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_utf8_jaro_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, matches: *mut u32, transpositions: *mut u32, prefix: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_jaro_pairs_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, matches: *mut u32, transpositions: *mut u32, prefix: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
@@ -357,6 +367,24 @@ impl<'tape> PreparedTape<'tape> {
     pub fn is_empty(&self) -> bool { self.count == 0 }
     pub fn info(&self) -> PreparedInfo { let mut info = PreparedInfo::default(); unsafe { swh_prepared_info(self.handle, &mut info) }; info }
     fn view(&self) -> PreparedView { PreparedView { tape: self.handle, first: self.first, count: self.count } }
+    /// The token-sorted normal form of every string of this view (`swh_tape_token_sort`; `form`: `TOKENS_SORTED` or `TOKENS_UNIQUE`),
+    /// derived on the device: a tape of its own, which borrows nothing. `ratio` of two `TOKENS_SORTED` tapes is rapidfuzz's
+    /// `fuzz::token_sort_ratio`.
+    pub fn token_sorted(&self, scope: &DeviceScope, form: c_int) -> Result<PreparedTape<'static>, Error> {
+        let view = self.view();
+        let (mut handle, mut message) = (ptr::null_mut(), ptr::null());
+        check(unsafe { swh_tape_token_sort(scope.handle, &view, form, &mut handle, &mut message) }, message)?;
+        Ok(PreparedTape { handle, first: 0, count: self.count, owner: true, _borrow: PhantomData })
+    }
+    /// The whole tape's bytes and its `count + 1` offsets, from 0, on the host (`swh_prepared_read`).
+    pub fn read(&self, scope: &DeviceScope) -> Result<(Vec<u8>, Vec<usize>), Error> {
+        let mut offsets = vec![0usize; self.info().count + 1];
+        let mut message = ptr::null();
+        check(unsafe { swh_prepared_read(scope.handle, self.handle, ptr::null_mut(), offsets.as_mut_ptr(), &mut message) }, message)?;
+        let mut data = vec![0u8; offsets[offsets.len() - 1]];
+        check(unsafe { swh_prepared_read(scope.handle, self.handle, data.as_mut_ptr() as *mut c_void, offsets.as_mut_ptr(), &mut message) }, message)?;
+        Ok((data, offsets))
+    }
 }
 impl Drop for PreparedTape<'_> { fn drop(&mut self) { if self.owner { unsafe { swh_prepared_free(self.handle) }; } } }
 
@@ -401,6 +429,17 @@ impl ShardedCross {
 }
 impl Drop for ShardedCross { fn drop(&mut self) { unsafe { swh_sharded_cross_free(self.handle) }; } }
 
+/// rapidfuzz's `fuzz::token_set_ratio`, unrounded, from the counts of `token_set_into_prepared`.
+pub fn token_set_score(s: u32, x: u32, y: u32, lcs: u32) -> f64 {
+    let q = |d: u64, t: u64| if t > 0 { 100.0 * (t - d) as f64 / t as f64 } else { 100.0 };
+    let (s, x, y, lcs) = (s as u64, x as u64, y as u64, lcs as u64);
+    if x == 0 || y == 0 { return if s == 0 { 0.0 } else { 100.0 }; }
+    let e = if s > 0 { 1 } else { 0 };
+    let (sab, sba) = (s + e + x, s + e + y);
+    let r = q(x + y - 2 * lcs, sab + sba);
+    if s == 0 { r } else { r.max(q(e + x, s + sab)).max(q(e + y, s + sba)) }
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // Engines
 // ------------------------------------------------------------------------------------------------------------
@@ -439,6 +478,17 @@ impl LevenshteinDistances {
         let (va, vb) = (a.view(), b.view());
         let mut message = ptr::null();
         check(unsafe { swh_levenshtein_pairs_prepared(self.handle, scope.handle, &va, &vb, bound.unwrap_or(UNBOUNDED), out.as_mut_ptr(), 4, &mut message) }, message)
+    }
+    /// The counts behind `fuzz::token_set_ratio` of every pair (`swh_levenshtein_token_set_pairs_prepared`): the symbols of the joined
+    /// intersection and of the two differences of the pairs' token sets, and the LCS length of the differences; `token_set_score`
+    /// evaluates them. Any tapes: the unique token-sorted forms are derived by the call.
+    pub fn token_set_into_prepared(&self, scope: &DeviceScope, a: &PreparedTape, b: &PreparedTape, sect: &mut [u32], ab: &mut [u32], ba: &mut [u32],
+                                   lcs: &mut [u32]) -> Result<(), Error> {
+        assert!(sect.len() >= a.len() && ab.len() >= a.len() && ba.len() >= a.len() && lcs.len() >= a.len(), "one result per pair");
+        let (va, vb) = (a.view(), b.view());
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_token_set_pairs_prepared(self.handle, scope.handle, &va, &vb, sect.as_mut_ptr(), ab.as_mut_ptr(), ba.as_mut_ptr(),
+                                                                lcs.as_mut_ptr(), 4, &mut message) }, message)
     }
     /// A resident sharded batch over every GPU of a multi-device scope, distances gathered with RCCL (`<Ngpu>` rows).
     pub fn pairs_into_sharded_resident(&self, scope: &DeviceScope, batch: &ShardedPairs, bound: Option<u32>, out: &mut [u32]) -> Result<(), Error> {

@@ -266,7 +266,42 @@ class PreparedTape(_Owner):
         self._handle, self._root, self.utf8 = handle, self, bool(utf8)
         self._keepalive = keep if isinstance(keep, DeviceTape) else None   # device tapes are used in place
         self._source, self._lengths = tape, None   # what symbol_lengths measures, once
+        self._scope = scope
         self.first, self.count = 0, len(tape)
+
+    @classmethod
+    def _adopt(cls, scope: DeviceScope, handle: C.c_void_p, utf8: bool, count: int) -> "PreparedTape":
+        """A tape the library made on the device (``token_sorted``): the handle is this object's, there is no host source."""
+        self = cls.__new__(cls)
+        self._handle, self._root, self.utf8 = handle, self, bool(utf8)
+        self._keepalive, self._source, self._lengths, self._scope = None, None, None, scope
+        self.first, self.count = 0, int(count)
+        return self
+
+    def token_sorted(self, unique: bool = False) -> "PreparedTape":
+        """The token-sorted normal form of every string of this view as a new ``PreparedTape`` (``swh_tape_token_sort``), derived on
+        the device: ``" ".join(sorted(s.split()))``, or with ``unique`` ``" ".join(sorted(set(s.split())))`` -- whitespace as
+        ``bytes.split()`` sees it, or ``str.split()`` on a ``utf8=True`` tape. The result owns its memory (the source may be freed),
+        is in this tape's mode and is taken wherever a prepared tape is: ``ratio`` of two of them is rapidfuzz's
+        ``fuzz.token_sort_ratio``, ``partial_ratio`` its ``partial_token_sort_ratio``. A string holds at most ``TOKEN_MAX_BYTES`` bytes."""
+        scope = self._root._scope
+        handle, err, view = C.c_void_p(), C.c_char_p(), self.view()
+        form = N.TOKENS_UNIQUE if unique else N.TOKENS_SORTED
+        N.check(N.lib.swh_tape_token_sort(scope.handle, C.byref(view), form, C.byref(handle), C.byref(err)), err)
+        return PreparedTape._adopt(scope, handle, self.utf8, self.count)
+
+    def to_strs(self) -> "Strs":
+        """The strings of this view on the host, as a ``Strs`` with uint64 offsets from 0 (``swh_prepared_read``)."""
+        root, err = self._root, C.c_char_p()
+        offsets = np.zeros(root.count + 1, dtype=np.uint64)
+        N.check(N.lib.swh_prepared_read(root._scope.handle, root._handle, None, C.c_void_p(offsets.ctypes.data), C.byref(err)), err)
+        data = np.zeros(int(offsets[-1]), dtype=np.uint8)
+        if data.nbytes:
+            N.check(N.lib.swh_prepared_read(root._scope.handle, root._handle, C.c_void_p(data.ctypes.data), C.c_void_p(offsets.ctypes.data),
+                                            C.byref(err)), err)
+        window = offsets[self.first:self.first + self.count + 1]
+        lo, hi = int(window[0]), int(window[-1])
+        return Strs(data=data[lo:hi].copy(), offsets=window - window[0])
 
     def __len__(self) -> int:
         return self.count
@@ -297,8 +332,8 @@ class PreparedTape(_Owner):
     def symbol_lengths(self, scope: DeviceScope) -> np.ndarray:
         """Symbols (bytes, or code points of a ``utf8=True`` tape) of every string of this view, as int64, on the host."""
         root = self._root
-        if root._lengths is None:
-            root._lengths = _symbol_lengths(root._source, root.utf8, scope)
+        if root._lengths is None:   # (a tape derived on the device has no host source: it is read back)
+            root._lengths = _symbol_lengths(root.to_strs() if root._source is None else root._source, root.utf8, scope)
         return root._lengths[self.first:self.first + self.count]
 
     def free(self) -> None:
