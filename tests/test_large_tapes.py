@@ -19,7 +19,16 @@ Regimes -- the engine chooses its kernels by the batch's lengths, so each regime
   * `lines`   200 .. 1200 bytes, 60 pairs   bitparallel.hip / tiled.hip (7 .. 38 blocks), banded.hip (k = 0, 7, 32: one word; 100: two words
                                             and the doubling schedule), align.hip's stored Pv / Mv walk, infix.hip, the searches' general path
   * `long`    2100 .. 6000 bytes, 8 pairs   bitparallel.hip's multi-pass kernel (more than 64 blocks), nwprofile.hip and wavefront.hip
-    (`long_shorter`: the shorter side cut to 2048 for OSA and LCS; `long_both`: both sides, for Jaro: their 64-block items)
+    (`long_shorter`: the shorter side cut to 2048 for OSA and LCS; `long_both`: both sides, for Jaro and partial_ratio: their 64-block
+    items; `long_near`: the longer side cut to 2048 + 16, partial_ratio's needle of 64 blocks under more than one whole window)
+  * `spaced_words`, `spaced_tokens`, `spaced_lines`: the same batches with every `t` a space, so a string is 1 .. 300 tokens of `acg`
+                                            between single and repeated spaces: tokens.hip (PreparedTape.token_sorted, token_sort_ratio,
+                                            token_set_counts) -- a line holds at most 1200 bytes, under the calls' cap of 4096
+The score searches (extract.hip, extract_within.hip over the slices of two_tape.hip's ExtractSweep) run windows of 12 x 20 words and 4 x 6
+lines; partial.hip the words, the tokens, `infix` (the tokens' a side cut to 64 symbols in the lines: hundreds of windows a pair),
+`long_both` (equal lengths: both directions) and the pair of `long_near` at the threshold. Its reference scores every whole window of
+the haystack against the needle, 2048 big-integer steps each: 0.07 s a pair at equal lengths, 0.2 s with 17 windows, seconds with
+the hundreds of `long_shorter` -- which is why partial_ratio has regimes of its own for needles of 64 blocks.
 The code-point engine runs the same regimes with the letters mapped to four of `a é Ж 中 😀` (lengths in symbols, layout in bytes) on
 the first 2^30 + 2^21 + 16 bytes of the same buffers, at the control and the 2^30 base: bp_item.hpp's SymWindow32 and prepass.hip's
 staging; staged string by string the symbols lie where the bytes did, at indices at or above 2^30 of a symbol buffer of over 4 GiB.
@@ -30,14 +39,21 @@ above-2^32 region, called through sub-views; (far a, far b), (far a, small b in 
 host everywhere and on the device once per family (alignments and infix matches come back on the host by their interface).
 Not every family takes every form, by the interface and not by choice: cross-products, top-k and within have raw exports for u64
 offsets only, so their u32 tapes run prepared (`raw32=False`); align, infix, OSA, LCS and Jaro prepare the device tapes they are given
-in the Python wrapper before they call, so for them a raw form would be the prepared one again and only those run (`raw=False`); the
-code-point engine runs at two bases, and raw with one far tape only (device memory, below).
+in the Python wrapper before they call, so for them a raw form would be the prepared one again and only those run (`raw=False`) -- as
+do partial_ratio and the token calls, which derive their tapes from prepared ones; extract and extract_within have raw exports for u64
+offsets only, like top-k; the code-point engine runs at two bases, and raw with one far tape only (device memory, below).
 
 Device memory, by arithmetic from api.hip and, for the searches, two_tape.hip (no test may need more than 24 GiB):
   * the two buffers: 2 x (2^32 + 2^21 + 16) B = 8.004 GiB, allocated once per module and freed at its teardown;
   * byte calls add the regions' small copies, offsets, results and the searches' matrices (24 x 400 x 4 B): under 0.1 GiB -> 8.1 GiB;
+  * the score searches carve ExtractSweep::need() -- 16 B of first over-long strings, one OsaSizes, 16 B of LaneItem and up to 3 counts
+    of 8 B per pair of a slice, 12 x 20 pairs here -- and k x 16 B of lists per query: some 10 KiB; token_sorted stages the view's span
+    (at most 60 lines of 1200 B: 72 KiB) and owns a derived tape no larger; partial_ratio's scratch (partial_scratch_bytes) is 8 B per
+    pair and 16 + 12 B per item of at most 4096 column steps: under 1 MiB for the 60 `infix` pairs. None of it is seen next to 8 GiB;
   * a prepared UTF-8 tape owns (total + 4) x 4 B of symbols = 4.008 GiB at total = 2^30 + S/2, 8 B per string of offsets, and while it
-    is prepared utf8_scratch_words(total) x 4 B = 36 words per 8 KiB tile = 0.018 GiB: two far prepared tapes 8.02 GiB -> 16.1 GiB;
+    is prepared utf8_scratch_words(total) x 4 B = 36 words per 8 KiB tile = 0.018 GiB: two far prepared tapes 8.02 GiB -> 16.1 GiB
+    (partial_ratio and the token calls of the code-point engine run on these prepared tapes alone, freed form by form; the searches
+    also raw, as the next line has it);
   * a raw UTF-8 call stages in the scope's scratch: per tape (bytes + 4) x 4 B twice (the flat and the string-by-string staging are both
     provided for) + the scratch words; `ensure` allocates need x 1.25 + 1 MiB. One far tape against a small one: 8.03 GiB x 1.25 =
     10.04 GiB -> 18.1 GiB with the buffers, on a scope of the test's own that is closed afterwards, after the prepared tapes are freed.
@@ -48,9 +64,15 @@ import functools
 import numpy as np
 import pytest
 
+import test_partial_ratio as partial_tests
+import test_token_ratios as token_tests
 from test_align import script_errors
+from test_extract import LARGER_IS_BETTER, SCORERS, assert_rows, expected_rows, reference_scores
+from test_extract_within import assert_csr, batch_cutoffs, expected_within
 from test_gpu_parity import ALGORITHMS
+from test_lcs import reference_lcs
 from test_osa import mutated
+from test_search_edges import counts_of, extract_rows, within_csr
 from test_tape_edges import expanded, expected, remember, run_cross, run_pairs, same
 from test_topk import check_rows, expected_topk
 from test_within import check_csr, expected_csr
@@ -69,7 +91,9 @@ U32_BASES = ("control", "2^30", "2^31")
 UTF8_BASES = ("control", "2^30")
 ARRANGEMENTS = ("inside", "boundary")
 REGIMES = {"words": (400, 0, 16), "tokens": (300, 20, 96), "lines": (60, 200, 1200), "long": (8, 2100, 6000)}   # pairs, shortest, longest
-DERIVED = ("long_shorter", "long_both", "infix")
+SPACED = ("spaced_words", "spaced_tokens", "spaced_lines")   # the token calls' batches: every `t` of the strings is a space
+NEAR = 16   # symbols the haystack of `long_near` holds more than its needle
+DERIVED = ("long_shorter", "long_both", "long_near", "infix") + SPACED
 MANY_WORDS = (1 << 16) + 64   # pairs of the `many_words` batch: k_short_tiled takes word batches of 2^16 pairs and more
 BOUNDS = (0, 7, 32, 100)
 COSTS = (0, 1, 2, 1)
@@ -92,8 +116,13 @@ def batch(regime, base):
     if regime == "long_both":      # Jaro: neither holds more
         a, b = batch("long", base)
         return [x[:CUT] for x in a], [y[:CUT] for y in b]
+    if regime == "long_near":      # partial_ratio: a needle of 2048 symbols, 17 whole windows of the haystack between the 2047 cut ones at either end
+        a, b = batch("long_shorter", base)
+        return [x[:CUT + NEAR] for x in a], [y[:CUT + NEAR] for y in b]
     if regime == "infix":          # patterns: tokens' a side cut to 64 symbols; texts: the lines' b side
         return [x[:64] for x in batch("tokens", base)[0][:REGIMES["lines"][0]]], batch("lines", base)[1]
+    if regime in SPACED:           # tokens of `acg` between single and repeated spaces; the fill `z` is no space
+        return tuple([x.replace("t", " ") for x in side] for side in batch(regime[len("spaced_"):], base))
     if regime == "many_words":
         return many_words(base)
     count, shortest, longest = REGIMES[regime]
@@ -132,8 +161,9 @@ def many_words(base):
 
 def glyph_map(regime, base):
     """Four of the five glyphs (one to four bytes each), another four for every batch."""
-    drop = seed_of(regime.split("_")[0], base) % 5   # (the infix batch draws on two regimes: it runs on bytes alone)
-    return str.maketrans(LETTERS, GLYPHS[:drop] + GLYPHS[drop + 1:])
+    source = regime[len("spaced_"):] if regime in SPACED else regime.split("_")[0]   # (the infix batch draws on two regimes: it runs on bytes alone)
+    drop = seed_of(source, base) % 5
+    return str.maketrans(LETTERS, GLYPHS[:drop] + GLYPHS[drop + 1:])   # (a spaced batch has no `t` left: its spaces stay spaces)
 
 
 def items(regime, base, utf8):
@@ -259,14 +289,27 @@ def string_extents(region):
     return [(int(s), int(e)) for s, e in zip(region.offsets, region.offsets[1:])]
 
 
+def ratio_row(query, candidates):
+    """The reference extract result of one query under `ratio`, k = 3: (indices, score patterns)."""
+    lcs = reference_lcs([query] * len(candidates), candidates).reshape(1, len(candidates))
+    unused = np.zeros_like(lcs)
+    lengths = np.array([len(query)], dtype=np.int64), np.array([len(c) for c in candidates], dtype=np.int64)
+    return expected_rows(reference_scores("ratio", (unused, lcs, unused, unused, unused) + lengths), True, 3)
+
+
 def test_layout_can_catch_misaddressing(sw, orc):
     """The generators alone, on a sparse model of the buffers: every threshold falls where its arrangement says, every batch is
     distinct, the u32 forms stay below 2^32, no live region overlaps another -- and for every misaddressing model, reading a batch
-    through it changes the oracle's Levenshtein distance of some pair, wherever the model changes any address at all."""
-    payloads, caught = [], set()
+    through it changes the oracle's Levenshtein distance of some pair, wherever the model changes any address at all; on the words
+    also a row of the reference `extract` result under `ratio` (one query against the six candidates around it) and a row of the
+    partial-ratio reference, and on the spaced words a token normal form."""
+    from stringwars_amd import _native as N
+    # the searches have raw exports for u64 offsets only: their u32 tapes run prepared (`raw32=False`)
+    assert all("u32" not in kinds for _, stem, _, kinds in N.TWO_TAPE if stem in ("extract", "extract_within", "topk", "within"))
+    payloads, caught, caught_search, caught_partial, caught_tokens = [], set(), set(), set(), set()
     for utf8 in (False, True):
         size = FAR_BYTES_UTF8 if utf8 else FAR_BYTES
-        for regime in tuple(REGIMES) + (() if utf8 else DERIVED + ("many_words",)):
+        for regime in tuple(REGIMES) + (("spaced_words",) if utf8 else DERIVED + ("many_words",)):
             for arrangement in ARRANGEMENTS:
                 lay = layout(regime, arrangement, utf8, UTF8_BASES if utf8 else BASES)
                 tapes = [SparseTape(size, [lay[base][side] for base in lay]) for side in (0, 1)]
@@ -289,24 +332,40 @@ def test_layout_can_catch_misaddressing(sw, orc):
                         else:
                             assert first == T and r.lengths[r.at - 1] and r.lengths[r.at], (regime, base, side)
                     assert regime not in ("lines", "long") or (regions[0].deep and regions[1].deep)
-                if utf8 or regime not in REGIMES:
+                if utf8 or regime not in tuple(REGIMES) + ("spaced_words",):
                     continue
                 for base, regions in lay.items():
                     a, b = items(regime, base, False)
-                    want = levenshtein_of(sw, orc, a, b)
+                    want = levenshtein_of(sw, orc, a, b) if regime in REGIMES else None
                     true = [string_extents(r) for r in regions]
                     for model in MODELS:
                         moved = [[misaddressed(model, s, e, int(r.offsets[-1])) for s, e in x] for r, x in zip(regions, true)]
                         changed = [k for k in range(len(a)) if moved[0][k] != true[0][k] or moved[1][k] != true[1][k]]
                         # (the pairs whose misread strings are shortest first: the oracle is quadratic, and one changed distance is enough)
                         changed.sort(key=lambda k: sum(m[k][1] - m[k][0] for m in moved))
-                        if changed:
-                            assert any(orc.levenshtein(tapes[0].read(*moved[0][k]), tapes[1].read(*moved[1][k]), algo="hyyro") != want[k] for k in changed), \
-                                (regime, base, arrangement, model)
+                        if not changed:
+                            continue
+                        misread = [lambda k, side=side: tapes[side].read(*moved[side][k]) for side in (0, 1)]
+                        where = (regime, base, arrangement, model)
+                        if regime in REGIMES:
+                            assert any(orc.levenshtein(misread[0](k), misread[1](k), algo="hyyro") != want[k] for k in changed), where
                             caught.add((model, base))
+                        if regime == "words":   # what sections i and j compare: one changed row each is enough, the cheapest pairs first
+                            around = lambda k: range(max(0, k - 2), min(len(b), k + 4))
+                            assert any(not all((x == y).all() for x, y in zip(ratio_row(misread[0](k), [misread[1](j) for j in around(k)]),
+                                                                               ratio_row(a[k], [b[j] for j in around(k)]))) for k in changed), where
+                            caught_search.add((model, base))
+                            assert any((partial_tests.expected([misread[0](k)], [misread[1](k)]) != partial_tests.expected([a[k]], [b[k]])).any()
+                                       for k in changed), where
+                            caught_partial.add((model, base))
+                        if regime == "spaced_words":   # section k
+                            assert any(token_tests.normal_form(misread[side](k), unique) != token_tests.normal_form((a, b)[side][k], unique)
+                                       for k in changed for side in (0, 1) for unique in (False, True)), where
+                            caught_tokens.add((model, base))
     # every model moves something at every base it can: the first four from the threshold they are named for on, the fifth everywhere
     for model, first in zip(MODELS, ("2^32", "2^31", "2^31", "2^30", "control")):
-        assert {base for m, base in caught if m == model} == set(BASES[BASES.index(first):]), (model, caught)
+        for kind in (caught, caught_search, caught_partial, caught_tokens):
+            assert {base for m, base in kind if m == model} == set(BASES[BASES.index(first):]), (model, kind)
     for regime in tuple(REGIMES) + ("many_words",):   # the u32 tape that ends at 2^32 - 1, placed alone (it lies where the 2^32 base's strings do)
         for r in layout(regime, "inside", False, ("u32max",))["u32max"]:
             assert r.offsets[-1] == (1 << 32) - 1 and r.offsets[0] > (1 << 31) and r.start + r.bytes <= FAR_BYTES
@@ -755,6 +814,155 @@ def test_scored_families(sw, scope, far, lev, call, regimes):
             queries, candidates = sides(lay, what[1], where)
             same(call, run_cross(call, lev, tq, tc, scope), expected(call, *expanded(queries, candidates), False), ("cross", arrangement, what))
     assert on_device
+
+
+# ---- i. the score searches ----------------------------------------------------------------------------------------------------------
+def search_counts(queries, candidates, utf8=False):
+    return known(("search counts", utf8, tuple(queries), tuple(candidates)), lambda: counts_of(queries, candidates, utf8))
+
+
+def check_searches(engine, scope, tq, tc, counts, what):
+    """extract (k = 3) and extract_within (at the median score) of one form under all six scorers."""
+    for scorer in SCORERS:
+        scores, larger = reference_scores(scorer, counts), LARGER_IS_BETTER[scorer]
+        assert_rows(extract_rows(engine, scope, tq, tc, scorer=scorer, k=3), expected_rows(scores, larger, 3), (what, scorer))
+        cutoff = batch_cutoffs(scores, larger)[0]
+        assert_csr(within_csr(engine, scope, tq, tc, scorer=scorer, cutoff=cutoff), expected_within(scores, larger, cutoff), (what, scorer, cutoff))
+
+
+@gpu
+@pytest.mark.parametrize("regime", ["words", "lines"])
+def test_score_searches(sw, scope, far, lev, regime):
+    """extract and extract_within: 12 queries x 20 candidates of the words around the threshold, 4 x 6 of the lines. The scoring kernels
+    read a slice view while k_extract_select and the range search's kernel read the lengths from the whole tapes' offsets. Once with
+    the outputs left on the device."""
+    import torch
+    shape = iter(((12, 20) if regime == "words" else (4, 6)) * 1000)
+    on_device = False
+    for arrangement, lay in placements(far, regime):
+        for what, tq, tc, *where in forms(far, scope, lay, select=lambda r: r.window(next(shape)), raw32=False):
+            queries, candidates = sides(lay, what[1], where)
+            counts = search_counts(queries, candidates)
+            check_searches(lev, scope, tq, tc, counts, (regime, arrangement, what))
+            if what == ("raw u64", "2^32") and arrangement == "inside":
+                scores = reference_scores("ratio", counts)
+                rows = (torch.full((len(queries), 3), -7, dtype=torch.int32, device="cuda"), torch.full((len(queries), 3), 7.0, dtype=torch.float64, device="cuda"))
+                lev.extract(tq, tc, scope, scorer="ratio", k=3, out=rows)
+                assert_rows((device_result(scope, rows[0], np.uint32), device_result(scope, rows[1], np.uint64)), expected_rows(scores, True, 3), (regime, "device out"))
+                cutoff = batch_cutoffs(scores, True)[0]
+                want = expected_within(scores, True, cutoff)
+                room = int(want[0][-1])
+                out = (torch.full((len(queries) + 1,), -7, dtype=torch.int64, device="cuda"), torch.full((room,), -7, dtype=torch.int32, device="cuda"),
+                       torch.full((room,), 7.0, dtype=torch.float64, device="cuda"))
+                lev.extract_within(tq, tc, scope, scorer="ratio", cutoff=cutoff, out=out)
+                assert_csr((device_result(scope, out[0], np.uint64), device_result(scope, out[1], np.uint32), device_result(scope, out[2], np.uint64)), want,
+                           (regime, "within, device out"))
+                on_device = True
+    assert on_device
+
+
+# ---- j. partial_ratio -----------------------------------------------------------------------------------------------------------------
+def partial_counts_of(a, b, utf8=False):
+    return known(("partial", utf8, tuple(a), tuple(b)), lambda: partial_tests.expected(a, b, utf8))
+
+
+@gpu
+@pytest.mark.parametrize("regime", ["words", "tokens", "infix", "long_both", "long_near"])
+def test_partial_ratio(sw, scope, far, lev, regime):
+    """partial_counts pairwise: partial.hip cuts the haystack's windows into items by offsets of its own. Needles of one block (words),
+    of 1 .. 3 (tokens), of at most 2 with hundreds of windows a pair (infix: the tokens' a side, cut, in the lines) and of 64 blocks, one
+    window an item: at equal lengths, where both directions run (long_both), and 16 symbols under the haystack (long_near: the pair whose
+    a side holds or begins at the threshold -- the reference takes 0.2 s for such a pair). 6 x 8 words as a cross-product."""
+    for arrangement, lay in placements(far, regime):
+        first = {id(r): regions[0].at for regions in lay.values() for r in regions}   # (both sides of a pairwise call take the same strings)
+        select = (lambda r: (first[id(r)], 1)) if regime == "long_near" else (lambda r: (0, len(r.strings)))
+        for what, ta, tb, *where in forms(far, scope, lay, select=select, raw=False):
+            a, b = sides(lay, what[1], where)
+            partial_tests.assert_counts(lev.partial_counts(ta, tb, scope), partial_counts_of(a, b), lambda k: (regime, arrangement, what, int(k)))
+    if regime != "words":
+        return
+    shape = iter((6, 8) * 1000)
+    for arrangement, lay in placements(far, "words"):
+        for what, tq, tc, *where in forms(far, scope, lay, select=lambda r: r.window(next(shape)), raw=False):
+            queries, candidates = sides(lay, what[1], where)
+            want = partial_counts_of(*expanded(queries, candidates))
+            partial_tests.assert_counts(lev.partial_counts_cross(tq, tc, scope), want, lambda k: ("cross", arrangement, what, int(k)))
+
+
+# ---- k. token-sorted tapes ------------------------------------------------------------------------------------------------------------
+def check_token_calls(engine, scope, ta, tb, a, b, utf8, what):
+    """Both normal forms of both sides, derived on the device and read back; then token_sort_ratio, token_set_counts and token_set_ratio."""
+    for tape, strings in ((ta, a), (tb, b)):
+        for unique in (False, True):
+            derived = tape.token_sorted(unique=unique)
+            try:
+                token_tests.assert_tape(derived.to_strs(), [token_tests.normal_form(x, unique) for x in strings])
+            except AssertionError as wrong:
+                raise AssertionError((what, unique)) from wrong
+            derived.free()
+    want = known(("tokens", utf8, tuple(a), tuple(b)), lambda: token_tests.reference(a, b, utf8))
+    token_tests.check_scores(engine, scope, ta, tb, utf8, want=want)
+
+
+@gpu
+@pytest.mark.parametrize("regime", SPACED)
+def test_token_sorted_tapes(sw, scope, far, lev, regime):
+    """tokens.hip addresses a string through base + rel against the view's span and total, and stages "laid out like the source": the
+    words, the tokens and the lines with every `t` a space, on every prepared form and the sub-views of the spanning tape. The
+    spanning tape as a whole is refused: its filler string holds more than 4096 bytes."""
+    refused = False
+    for arrangement, lay in placements(far, regime):
+        for what, ta, tb, *where in forms(far, scope, lay, raw=False):
+            a, b = sides(lay, what[1], where)
+            check_token_calls(lev, scope, ta, tb, a, b, False, (regime, arrangement, what))
+        if "2^32" in lay and "above" in lay and not refused:
+            whole, _ = far.spanning(lay, 0, scope)
+            with pytest.raises(sw.StringWarsError) as refusal:
+                whole.token_sorted()
+            assert refusal.value.status == "unsupported_length", str(refusal.value)
+            refused = True
+    assert refused
+
+
+# ---- l. the code-point engine on i, j and k ---------------------------------------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("regime", ["words", "spaced_words"])
+def test_searches_partial_and_tokens_utf8(sw, far, regime):
+    """The code-point engine at its two bases, on prepared tapes (decoded once; freed form by form: the module's docstring): the
+    searches on windows of 12 x 20 words and partial_ratio on the words, pairwise and 6 x 8; the token calls on the spaced words. The
+    searches then run raw, one far tape against a small one (18.1 GiB: the docstring); partial_ratio and the token calls prepare the
+    device tapes they are given, so for them a raw form would be the prepared one again."""
+    scope = sw.DeviceScope(gpu_device=0)
+    engine = sw.LevenshteinDistancesUTF8(capabilities=scope)
+    try:
+        for arrangement, lay in placements(far, regime, utf8=True):
+            for what, ta, tb, *where in forms(far, scope, lay, raw=False, utf8=True, u32=UTF8_BASES):
+                a, b = sides(lay, what[1], where, utf8=True)
+                if regime == "spaced_words":
+                    check_token_calls(engine, scope, ta, tb, a, b, True, (arrangement, what))
+                else:
+                    partial_tests.assert_counts(engine.partial_counts(ta, tb, scope), partial_counts_of(a, b, True), lambda k: (arrangement, what, int(k)))
+                    for rows, columns, check in ((12, 20, "searches"), (6, 8, "partial")):
+                        (fq, nq), (fc, nc) = lay[what[1]][0].window(rows), lay[what[1]][1].window(columns)
+                        queries, candidates = a[fq:fq + nq], b[fc:fc + nc]
+                        if check == "searches":
+                            check_searches(engine, scope, ta[fq:fq + nq], tb[fc:fc + nc], search_counts(queries, candidates, True), (arrangement, what))
+                        else:
+                            partial_tests.assert_counts(engine.partial_counts_cross(ta[fq:fq + nq], tb[fc:fc + nc], scope),
+                                                             partial_counts_of(*expanded(queries, candidates), True), lambda k: ("cross", arrangement, what, int(k)))
+                ta.free(); tb.free()
+            if regime != "words":
+                continue
+            # the searches' raw exports (utf8_u64tape), staged in the call: one far tape against a small one, as test_levenshtein_utf8 runs its raw form
+            for base in lay:
+                (fq, nq), (fc, nc) = lay[base][0].window(12), lay[base][1].window(20)
+                counts = search_counts(*sides(lay, base, (fq, nq, fc, nc), utf8=True), True)
+                for small_side in (1, 0):
+                    tq, tc = far.tape(lay, base, 0, 64, fq, nq, small=small_side == 0), far.tape(lay, base, 1, 64, fc, nc, small=small_side == 1)
+                    check_searches(engine, scope, tq, tc, counts, (arrangement, "raw, small side %d" % small_side, base))
+    finally:
+        del engine
+        scope.close()
 
 
 # ---- h. strings the windows cannot index are refused --------------------------------------------------------------------------------
