@@ -365,6 +365,53 @@ swh_status_t swh_levenshtein_infix_prepared(swh_levenshtein_t engine, swh_scope_
                                             const swh_prepared_view_t *texts, uint32_t bound, uint32_t *distances, uint32_t *starts,
                                             uint32_t *ends, const char **error);
 
+/* ---- Infix search for EVERY occurrence within a bound, as CSR rows (edlib `mode="HW"` `locations`, Myers' "every column whose
+ *      score is within k", an approximate grep's line positions), unit costs only. --------------------------------------------
+ * Pairs, symbols, tapes and the pattern limit are those of the infix search above; what differs is the result. For pattern p of
+ * m symbols and text t of n symbols let D(e) = min over 0 <= s <= e of d(p, t[s..e)) for e = 0 .. n -- the last row of the
+ * semi-global Wagner-Fischer matrix, D(0) = m -- and d* = min over e of D(e). A hit is an end e with D(e) <= bound that passes
+ * `select`:
+ *  - SWH_INFIX_SELECT_ALL: every such e;
+ *  - SWH_INFIX_SELECT_BEST: those with D(e) = d* (edlib's `locations`, whose ends are inclusive); the row is empty if d* > bound;
+ *  - SWH_INFIX_SELECT_MINIMA: one hit per dip of the score curve -- with D(-1) = D(n + 1) = +infinity, e is reported iff
+ *    D(e) <= bound, D(e - 1) > D(e), and the first f > e with D(f) != D(e) has D(f) > D(e): the first column of every plateau that
+ *    is a weak local minimum;
+ *  - any other `select` is swh_invalid_argument_k.
+ * Row i holds pair i's hits in ASCENDING e at entries [row_offsets[i], row_offsets[i + 1]): ends[h] = e (exclusive),
+ * distances[h] = D(e), the true value, never clamped, and -- if `starts` is given -- starts[h] = the largest s <= e with
+ * d(p, t[s..e)) = D(e), the infix search's rule applied to this end. bound == SWH_UNBOUNDED is accepted and means no cutoff.
+ * abc in xxabcxx, bound 1: ALL (2,4,1) (2,5,0) (2,6,1) as (start, end, d), BEST and MINIMA (2,5,0); lawn in "flaw in law", bound 1:
+ * ALL (1,4,1) (1,5,1) (8,11,1), MINIMA (1,4,1) (8,11,1); aaa in bbb: nothing at bound 2, ALL (0,0,3) (1,1,3) (2,2,3) (3,3,3) and
+ * MINIMA (0,0,3) at bound 3; an empty pattern in abc: ALL (0,0,0) (1,1,0) (2,2,0) (3,3,0), MINIMA (0,0,0). Whenever the infix
+ * search's d_i <= bound, its (d_i, starts[i], ends[i]) is the first hit of the BEST row.
+ * The counting protocol is that of swh_levenshtein_within_*: `row_offsets` (count + 1 entries, row_offsets[0] = 0) is ALWAYS
+ * written in full, with the true counts. `ends` and `distances` (and `starts`; `capacity` entries each) are written only if
+ * row_offsets[count] <= capacity; otherwise they are left untouched and the call still returns swh_success_k. starts == ends ==
+ * distances == NULL with capacity == 0 is the counting call (one walk). `starts` alone may be NULL: the start pass is skipped.
+ * `ends` and `distances` come together; any other NULL mix, or a NULL `row_offsets`, is swh_invalid_argument_k and nothing is
+ * written. Each output may be host or device memory, independently; the output is bit-for-bit deterministic.
+ * Refusals are the infix search's: a count mismatch, a pattern over SWH_INFIX_MAX_PATTERN symbols (before any output is written;
+ * the message names the first such pair), costs other than (0, 1, 1, 1), invalid UTF-8, no device. count == 0 writes
+ * row_offsets[0] = 0 only. The call is synchronous on every scope. A filled call walks the texts twice -- counted, then stored --
+ * and nothing is kept between the walks but a count per pair (and d* for SELECT_BEST). With profiling on, `cells` = sum m n,
+ * counted once; the kernels are stamped "infix_hits" / "infix_hits_u32" (the walks) and "infix_hit_starts" /
+ * "infix_hit_starts_u32" (the start pass). */
+#define SWH_INFIX_SELECT_ALL 0u
+#define SWH_INFIX_SELECT_BEST 1u
+#define SWH_INFIX_SELECT_MINIMA 2u
+swh_status_t swh_levenshtein_infix_all_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *patterns,
+                                               const swh_tape_u64_t *texts, uint32_t bound, uint32_t select, size_t *row_offsets,
+                                               uint32_t *starts, uint32_t *ends, uint32_t *distances, size_t capacity,
+                                               const char **error);
+swh_status_t swh_levenshtein_utf8_infix_all_u64tape(swh_levenshtein_t engine, swh_scope_t scope, const swh_tape_u64_t *patterns,
+                                                    const swh_tape_u64_t *texts, uint32_t bound, uint32_t select, size_t *row_offsets,
+                                                    uint32_t *starts, uint32_t *ends, uint32_t *distances, size_t capacity,
+                                                    const char **error);
+swh_status_t swh_levenshtein_infix_all_prepared(swh_levenshtein_t engine, swh_scope_t scope, const swh_prepared_view_t *patterns,
+                                                const swh_prepared_view_t *texts, uint32_t bound, uint32_t select, size_t *row_offsets,
+                                                uint32_t *starts, uint32_t *ends, uint32_t *distances, size_t capacity,
+                                                const char **error);
+
 /* ---- Damerau-Levenshtein (OSA) distances: a swap of two neighbouring symbols costs one edit (rapidfuzz `distance.OSA`,
  *      `process.cdist(..., scorer=OSA.distance)`), unit costs only. -----------------------------------------------------------
  * The optimal-string-alignment distance, also called restricted Damerau-Levenshtein: for a of m symbols and b of n symbols, D is

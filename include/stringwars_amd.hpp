@@ -286,6 +286,33 @@ public:
         swh_status_t status__ = swh_levenshtein_infix_prepared(handle_, scope.handle(), &vp, &vt, bound, distances, starts, ends, &err);
         check(status__, err);
     }
+    /// Infix search for every occurrence within `bound` (swh_levenshtein_infix_all_*): row i = [row_offsets[i], row_offsets[i + 1]) holds, in
+    /// ascending end, every end e of texts[i] whose best distance D(e) to patterns[i] is within `bound` and passes `select`
+    /// (SWH_INFIX_SELECT_ALL / _BEST / _MINIMA): ends[h] = e, distances[h] = D(e) unclamped, starts[h] the start of the shortest such
+    /// occurrence. The counting protocol is `within`'s: row_offsets (count + 1 entries) is always written; the arrays (`capacity` entries
+    /// each) only if row_offsets[count] <= capacity. All arrays null with capacity 0 counts; `starts` alone null skips the start pass.
+    /// Each array in host or device memory.
+    struct InfixOccurrencesOut {
+        size_t *row_offsets = nullptr;
+        uint32_t *starts = nullptr, *ends = nullptr, *distances = nullptr;
+        size_t capacity = 0;
+    };
+    void infix_all(const DeviceScope &scope, InfixOccurrencesOut out, const BytesTapeView &patterns, const BytesTapeView &texts,
+                   uint32_t bound = SWH_UNBOUNDED, uint32_t select = SWH_INFIX_SELECT_ALL) const {
+        const char *err = nullptr;
+        swh_tape_u64_t tp = patterns.c(), tt = texts.c();
+        auto fn = utf8_ ? swh_levenshtein_utf8_infix_all_u64tape : swh_levenshtein_infix_all_u64tape;
+        swh_status_t status__ = fn(handle_, scope.handle(), &tp, &tt, bound, select, out.row_offsets, out.starts, out.ends, out.distances, out.capacity, &err);
+        check(status__, err);
+    }
+    void infix_all(const DeviceScope &scope, InfixOccurrencesOut out, const PreparedTape &patterns, const PreparedTape &texts,
+                   uint32_t bound = SWH_UNBOUNDED, uint32_t select = SWH_INFIX_SELECT_ALL) const {
+        const char *err = nullptr;
+        swh_prepared_view_t vp = patterns.c(), vt = texts.c();
+        swh_status_t status__ = swh_levenshtein_infix_all_prepared(handle_, scope.handle(), &vp, &vt, bound, select, out.row_offsets, out.starts, out.ends,
+                                                                   out.distances, out.capacity, &err);
+        check(status__, err);
+    }
     /// Damerau-Levenshtein distances in the optimal-string-alignment form (swh_levenshtein_osa_pairs_*): out[i] = min(osa(a_i, b_i), bound + 1);
     /// a swap of two neighbouring symbols costs one edit, no substring is edited twice (ca / abc: 3). The shorter string of a pair holds
     /// at most SWH_OSA_MAX_SHORTER symbols; `out` in host or device memory.

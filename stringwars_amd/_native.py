@@ -54,6 +54,7 @@ TOPK_MAX = 64   # SWH_TOPK_MAX: the largest k of a top-k search
 ALIGN_MAX_CELLS = 1 << 30   # SWH_ALIGN_MAX_CELLS: len(a_i) * len(b_i) an alignment accepts per pair
 INFIX_MAX_PATTERN = 2048   # SWH_INFIX_MAX_PATTERN: symbols per pattern an infix search accepts
 INFIX_NONE = 0xFFFFFFFF    # SWH_INFIX_NONE: start / end of a pair whose best occurrence is over the bound
+INFIX_SELECT_ALL, INFIX_SELECT_BEST, INFIX_SELECT_MINIMA = 0, 1, 2   # SWH_INFIX_SELECT_*: which ends within the bound infix_all reports
 OSA_MAX_SHORTER = 2048     # SWH_OSA_MAX_SHORTER: symbols of a pair's shorter string an OSA call accepts
 LCS_MAX_SHORTER = 2048     # SWH_LCS_MAX_SHORTER: symbols of a pair's shorter string an LCS / Indel call accepts
 PARTIAL_MAX_NEEDLE = 2048  # SWH_PARTIAL_MAX_NEEDLE: symbols of a pair's shorter string a partial-ratio call accepts
@@ -193,6 +194,7 @@ TWO_TAPE = [
     ("swh_levenshtein", "within", [_U32, _P, _P, _P, _SIZE], ("utf8",)),
     ("swh_levenshtein", "align", [_U32, _P, _P, _P, _SIZE], ("utf8",)),
     ("swh_levenshtein", "infix", [_U32, _P, _P, _P], ("utf8",)),
+    ("swh_levenshtein", "infix_all", [_U32, _U32, _P, _P, _P, _P, _SIZE], ("utf8",)),
     ("swh_levenshtein", "osa_pairs", [_U32, _P, _SIZE], ("utf8",)),
     ("swh_levenshtein", "osa_cross", [_P, _SIZE], ("utf8",)),
     ("swh_levenshtein", "lcs_pairs", [_U32, _P, _P, _SIZE], ("utf8",)),

@@ -37,4 +37,35 @@ struct InfixRun {
 void launch_infix_forward(Scope *scope, const InfixTapes &t, const InfixRun &r);
 void launch_infix_starts(Scope *scope, const InfixTapes &t, const InfixRun &r);
 
+// ---- every occurrence within a bound (swh_levenshtein_infix_all_*) ----
+// A hit of pair p is an end e, 0 <= e <= n, whose bottom-row score D(e) is within `bound` and passes `select` (SWH_INFIX_SELECT_*).
+// The forward walk runs twice over the pairs' items: the count walk leaves counts[p] (and, for SELECT_BEST, best[p] = the pair's
+// smallest score, or ~0 if that is over the bound); the fill walk stores (end, distance) of pair p's hits at cursors[p] onwards, in
+// column order, and never at or beyond `total`.
+struct InfixHitsRun {
+    const LaneItem *items;
+    uint64_t item_count;
+    uint32_t bound, select;
+    uint32_t *counts, *best;    // [pair]
+    const uint64_t *cursors;    // [pair]: exclusive scan of counts (fill walk)
+    uint64_t total;             // hits of the call = entries of ends / distances that may be written (fill walk)
+    uint32_t *ends, *distances;
+    bool wide_text;             // the text tape holds at least 16 bytes: it is read with 128-bit loads
+};
+void launch_infix_hits(Scope *scope, const InfixTapes &t, const InfixHitsRun &r, bool fill);
+
+// The start pass over hits: hit h belongs to pair rows[h]; starts[h] = the largest s <= ends[h] with d(p, t[s..ends[h])) = distances[h].
+// launch_infix_hit_items finds every hit's pair in the row offsets (`count` + 1 entries), writes it to `rows` and cuts the hits into
+// items of consecutive hits (`items`: room for `total`; sizes->items counts them; `sizes` zeroed by the caller).
+struct InfixHitStartsRun {
+    const LaneItem *items;
+    uint64_t item_count;
+    const uint64_t *rows;
+    const uint32_t *ends, *distances;
+    uint32_t *starts;
+};
+void launch_infix_hit_items(Scope *scope, const InfixTapes &t, const uint64_t *row_offsets, uint64_t total, InfixSizes *sizes, uint64_t *rows,
+                            LaneItem *items);
+void launch_infix_hit_starts(Scope *scope, const InfixTapes &t, const InfixHitStartsRun &r);
+
 }  // namespace swh

@@ -848,6 +848,146 @@ swh_status_t swh_levenshtein_infix_prepared(swh_levenshtein_t e, swh_scope_t s, 
     return infix_run(call.scope, call.pair, bound, InfixOutputs{distances, starts, ends}, error);
 }
 
+// ---- infix search for every occurrence within a bound (infix.hip's k_infix_hits / k_infix_hit_starts) -------------------------------------
+// infix_run's measurement and items with within_run's protocol: the count walk leaves a count per pair, the scan turns the counts into
+// cursors and the row offsets, the host reads the total (8 bytes), and only if the caller's arrays hold it the fill walk stores the
+// hits; then, if starts are wanted, the hits are cut into items of their own and the start pass runs over them. The per-pair scratch
+// (items, counts, best scores, cursors, the scan's block sums, staged offsets) is the scope's alignment scratch; the per-hit scratch
+// (staged outputs, a row and at most an item per hit) is scope->within_out, sized once the total is known.
+struct InfixAllOutputs {
+    size_t *row_offsets;
+    uint32_t *starts, *ends, *distances;
+    size_t capacity;
+};
+
+static swh_status_t infix_all_run(Scope *scope, const TapePair &p, uint32_t bound, uint32_t select, const InfixAllOutputs &r, const char **error) {
+    static_assert(sizeof(size_t) == sizeof(uint64_t), "row offsets are scanned as 64-bit words");
+    return synchronous_run(scope, error, [&]() -> swh_status_t {
+        const uint64_t count = p.a_count;
+        SWH_HIP_CHECK(hipSetDevice(scope->device));
+        hipStream_t stream = scope->stream;
+        Staged<uint64_t> offs((uint64_t *)r.row_offsets);
+        Staged<uint32_t> starts(r.starts), ends(r.ends), distances(r.distances);   // (null in a counting call: nothing staged or filled)
+        if (count == 0) {
+            offs.fill_zero(stream, 1);
+            return swh_success_k;
+        }
+        const bool cp = p.pa->utf8;
+        InfixTapes t{};
+        t.patterns = tape_side(p.pa, cp, p.a_first, count, t.p_off64);
+        t.texts = tape_side(p.pb, cp, p.b_first, count, t.t_off64);
+        t.cp = cp ? 1 : 0;
+        t.count = count;
+
+        AlignScratch *sc_entry = call_scratch(scope);
+        const uint64_t tiles = (count + kWithinScanTile - 1) / kWithinScanTile;
+        // sizes | items | a count, a best score and a cursor per pair | the scan's block sums | row offsets bound for the host
+        const size_t need = pad(sizeof(InfixSizes)) + pad(count * sizeof(LaneItem)) + 2 * pad(count * 4) + pad(count * 8) + pad(tiles * 8) +
+                            offs.need(count + 1);
+        Carver sc = carve(sc_entry->buf, sc_entry->bytes, need);
+        InfixSizes *sizes = sc.take<InfixSizes>(1);
+        LaneItem *items = sc.take<LaneItem>(count);
+        uint32_t *counts = sc.take<uint32_t>(count), *best = sc.take<uint32_t>(count);
+        uint64_t *cursors = sc.take<uint64_t>(count), *block_sums = sc.take<uint64_t>(tiles);
+        offs.place(sc, count + 1);
+
+        const InfixSizes got = measure(scope, sizes, [&] { launch_infix_sizes(scope, t, sizes, items); });
+        if (got.first_oversize != ~0ull) {
+            const size_t i = (size_t)got.first_oversize;
+            const uint64_t m = string_symbols(t.patterns, t.p_off64, i, stream);
+            scope->stamps_used = 0;
+            return fail(error, swh_unsupported_length_k, "pair %zu: a pattern of %llu symbols exceeds SWH_INFIX_MAX_PATTERN (2048)", i,
+                        (unsigned long long)m);
+        }
+
+        InfixHitsRun run{};
+        run.items = items; run.item_count = got.items;
+        run.bound = bound; run.select = select;
+        run.counts = counts; run.best = best; run.cursors = cursors;
+        run.wide_text = !cp && got.text_symbols >= 16;
+        launch_infix_hits(scope, t, run, false);
+        launch_within_offsets(scope, counts, count, 1, block_sums, cursors, offs.dev);
+        // the offsets are complete on the device: their last word, the total (one read and wait), decides the fill
+        const uint64_t total = read_offset(offs.dev, 1, count, true, stream);
+        offs.copy_back(stream, count + 1);
+        const bool filled = total && total <= r.capacity;
+        if (filled) {
+            // where the fill walk and the start pass write: the caller's device arrays, or staging for its host arrays
+            const size_t per_hit = r.starts ? pad(sizeof(InfixSizes)) + pad(total * 8) + pad(total * sizeof(LaneItem)) : 0;
+            Carver oc = carve(scope->within_out, scope->within_out_bytes, ends.need(total) + distances.need(total) + starts.need(total) + per_hit);
+            run.ends = ends.place(oc, total); run.distances = distances.place(oc, total); run.total = total;
+            launch_infix_hits(scope, t, run, true);
+            if (r.starts) {
+                starts.place(oc, total);
+                InfixSizes *hit_sizes = oc.take<InfixSizes>(1);
+                uint64_t *rows = oc.take<uint64_t>(total);
+                LaneItem *hit_items = oc.take<LaneItem>(total);
+                const InfixSizes cut = measure(scope, hit_sizes, [&] { launch_infix_hit_items(scope, t, offs.dev, total, hit_sizes, rows, hit_items); });
+                InfixHitStartsRun pass{};
+                pass.items = hit_items; pass.item_count = cut.items;
+                pass.rows = rows; pass.ends = run.ends; pass.distances = run.distances; pass.starts = starts.dev;
+                launch_infix_hit_starts(scope, t, pass);
+                starts.copy_back(stream, total);
+            }
+            ends.copy_back(stream, total); distances.copy_back(stream, total);
+        }
+        SWH_HIP_CHECK(hipStreamSynchronize(stream));
+        // the tapes (twice if filled), the offsets of both, the row offsets and 8 or 12 bytes per stored hit
+        close_call(scope, got.cells, (filled ? 2 : 1) * (cp ? 4 : 1) * got.symbols + 2 * (count + 1) * 8 + (count + 1) * 8 +
+                                         (filled ? total * (r.starts ? 12 : 8) : 0));
+        return swh_success_k;
+    });
+}
+
+static swh_status_t infix_all_checks(swh_levenshtein_t e, size_t p_count, size_t t_count, uint32_t select, const InfixAllOutputs &r,
+                                     const char **error) {
+    const Engine *engine = (const Engine *)e;
+    if (engine->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
+    if (!engine->unit_costs) return fail(error, swh_not_implemented_k, "infix search needs unit costs (match 0, mismatch 1, open 1, extend 1)");
+    if (p_count != t_count) return fail(error, swh_invalid_argument_k, "patterns and texts must hold the same number of strings");
+    if (select > SWH_INFIX_SELECT_MINIMA) return fail(error, swh_invalid_argument_k, "select must be one of SWH_INFIX_SELECT_ALL, _BEST, _MINIMA");
+    if (!r.row_offsets) return fail(error, swh_invalid_argument_k, "null row_offsets");
+    if (!r.ends != !r.distances) return fail(error, swh_invalid_argument_k, "ends and distances must both be given, or neither");
+    if (!r.ends && r.starts) return fail(error, swh_invalid_argument_k, "starts without ends and distances");
+    if (!r.ends && r.capacity) return fail(error, swh_invalid_argument_k, "a capacity without arrays: the counting call passes NULL, NULL, NULL, 0");
+    return swh_success_k;
+}
+
+static swh_status_t infix_all_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts, bool utf8,
+                                    uint32_t bound, uint32_t select, const InfixAllOutputs &outs, const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    if (!patterns || !texts) return fail(error, swh_invalid_argument_k, "null tape");
+    if ((status = infix_all_checks(e, patterns->count, texts->count, select, outs, error)) != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.begin(s, error)) != swh_success_k) return status;
+    const bool pairs = patterns->count != 0;
+    if ((status = call.prepare(patterns, texts, utf8, pairs, pairs, error)) != swh_success_k) return status;
+    return infix_all_run(call.scope, call.pair, bound, select, outs, error);
+}
+swh_status_t swh_levenshtein_infix_all_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts,
+                                               uint32_t bound, uint32_t select, size_t *row_offsets, uint32_t *starts, uint32_t *ends,
+                                               uint32_t *distances, size_t capacity, const char **error) {
+    return infix_all_tapes(e, s, patterns, texts, false, bound, select, InfixAllOutputs{row_offsets, starts, ends, distances, capacity}, error);
+}
+swh_status_t swh_levenshtein_utf8_infix_all_u64tape(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns,
+                                                    const swh_tape_u64_t *texts, uint32_t bound, uint32_t select, size_t *row_offsets,
+                                                    uint32_t *starts, uint32_t *ends, uint32_t *distances, size_t capacity, const char **error) {
+    return infix_all_tapes(e, s, patterns, texts, true, bound, select, InfixAllOutputs{row_offsets, starts, ends, distances, capacity}, error);
+}
+swh_status_t swh_levenshtein_infix_all_prepared(swh_levenshtein_t e, swh_scope_t s, const swh_prepared_view_t *patterns,
+                                                const swh_prepared_view_t *texts, uint32_t bound, uint32_t select, size_t *row_offsets,
+                                                uint32_t *starts, uint32_t *ends, uint32_t *distances, size_t capacity, const char **error) {
+    swh_status_t status = probe_null_handles(e, s, error);
+    if (status != swh_success_k) return status;
+    TwoTapeCall call;
+    if ((status = call.views(patterns, texts, false, error)) != swh_success_k) return status;
+    const InfixAllOutputs outs{row_offsets, starts, ends, distances, capacity};
+    if ((status = infix_all_checks(e, call.pair.a_count, call.pair.b_count, select, outs, error)) != swh_success_k) return status;
+    if ((status = call.begin_on_views(s, error)) != swh_success_k) return status;
+    return infix_all_run(call.scope, call.pair, bound, select, outs, error);
+}
+
 // ---- OSA distances, LCS lengths / Indel distances, partial ratios, Jaro counts (osa.hip, lcs.hip, partial.hip, jaro.hip): one planner ------
 // The four families score pairs on the same phases. A sizes kernel measures the pairs (cells, symbols, the first pair over the
 // family's length limit) and cuts them into work items; one read-back of the measurements decides the errors before any output is

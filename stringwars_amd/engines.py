@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .results import Alignments, InfixMatches, PartialAlignments, RangeMatches, ScoreMatches  # noqa: F401
+from .results import Alignments, InfixMatches, InfixOccurrences, PartialAlignments, RangeMatches, ScoreMatches  # noqa: F401
 from .tapes import (  # noqa: F401  (every name that was reachable as ``engines.X`` still is)
     DeviceScope, DeviceTape, PreparedTape, ShardedCross, ShardedPairs, Strs, TapeLike, shard_cuts,
     _as_tape, _c_tape, _c_tapes, _Owner, _pointer, _symbol_lengths,
@@ -31,7 +31,7 @@ from .tapes import (  # noqa: F401  (every name that was reachable as ``engines.
 __all__ = [
     "DeviceScope", "Strs", "DeviceTape", "PreparedTape", "ShardedPairs", "shard_cuts", "LevenshteinDistances", "LevenshteinDistancesUTF8",
     "NeedlemanWunschScores", "SmithWatermanScores", "edit_distance", "StringWarsError", "UNBOUNDED", "TOPK_MAX",
-    "ALIGN_MAX_CELLS", "Alignments", "RangeMatches", "ScoreMatches", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "OSA_MAX_SHORTER", "LCS_MAX_SHORTER", "PARTIAL_MAX_NEEDLE", "PartialAlignments",
+    "ALIGN_MAX_CELLS", "Alignments", "RangeMatches", "ScoreMatches", "INFIX_MAX_PATTERN", "INFIX_NONE", "InfixMatches", "InfixOccurrences", "OSA_MAX_SHORTER", "LCS_MAX_SHORTER", "PARTIAL_MAX_NEEDLE", "PartialAlignments",
     "JARO_MAX_LENGTH", "TOKEN_MAX_BYTES", "SCORERS",
 ]
 
@@ -357,6 +357,52 @@ class LevenshteinDistances(_Engine):
         err = C.c_char_p()
         N.check(call(_bound(bound), *(C.c_void_p(array.ctypes.data) for array in (distances, starts, ends)), C.byref(err)), err)
         return InfixMatches(distances, starts, ends)
+
+    _INFIX_SELECT = {"all": N.INFIX_SELECT_ALL, "best": N.INFIX_SELECT_BEST, "minima": N.INFIX_SELECT_MINIMA}
+
+    def infix_all(self, patterns: TapeLike, texts: TapeLike, scope: Optional[DeviceScope] = None, *, bound: Optional[int] = None,
+                  select: str = "all", starts: bool = True, capacity: Optional[int] = None, out=None) -> "InfixOccurrences":
+        """EVERY end at which ``patterns[i]`` occurs in ``texts[i]`` within ``bound`` edits (``swh_levenshtein_infix_all_*``): an
+        :class:`InfixOccurrences`, rows ascending by end with the true distances. ``select`` keeps every such end (``"all"``), those
+        that reach the pair's best distance (``"best"``: edlib's ``locations``, ends inclusive there) or one per dip of the score
+        curve (``"minima"``: the first column of every plateau that is a weak local minimum). ``bound=None`` is no cutoff.
+        ``starts=False`` skips the start pass and leaves ``.starts`` None. The hit total is not known in advance: as in ``within``
+        the first call has room for ``capacity`` hits (default ``max(1024, 8 * len(patterns))``) and a second is made with the exact
+        size only if they did not fit. ``out=(offsets, starts, ends, distances)`` fills given arrays or device tensors instead
+        (``starts`` None where ``starts=False``); ``out=(offsets, None, None, None)`` is the counting call (one walk). The two
+        sides are tapes, or both ``PreparedTape``s."""
+        _need_scope(scope)
+        if select not in self._INFIX_SELECT:
+            raise ValueError("select must be one of %s" % ", ".join(map(repr, self._INFIX_SELECT)))
+        patterns, texts = self._promoted(patterns, texts, scope, at=DeviceTape)
+        if len(patterns) != len(texts):
+            raise ValueError("patterns and texts must hold the same number of strings")
+        count = len(patterns)
+        search = self._two_tapes(patterns, texts, scope, "infix_all")
+        if isinstance(patterns, PreparedTape):
+            self._need_mode(texts)
+        held = [None]   # the starts that go with the (ends, distances) of the latest call
+
+        if out is not None:
+            offsets, held[0], ends, distances = out
+            if bool(starts) != (held[0] is not None) and ends is not None:
+                raise ValueError("out holds starts exactly where starts=True")
+            if held[0] is not None:
+                _check_out(held[0], 4, 0 if ends is None else int(ends.numel() if hasattr(ends, "numel") else ends.size))
+            out = (offsets, ends, distances)
+
+        def call(offsets, ends, distances, room):
+            if out is None and starts:
+                held[0] = np.empty(room, dtype=np.uint32)
+            err = C.c_char_p()
+            N.check(search(_bound(bound), C.c_uint32(self._INFIX_SELECT[select]), C.c_void_p(_pointer(offsets)), C.c_void_p(_pointer(held[0])),
+                           C.c_void_p(_pointer(ends)), C.c_void_p(_pointer(distances)), int(room), C.byref(err)), err)
+            return int(offsets[count])
+
+        def result(offsets, ends, distances):
+            return InfixOccurrences(offsets, None if held[0] is None or ends is None else held[0][:len(ends)], ends, distances)
+
+        return self._csr_search(call, count, count, out, capacity, np.uint32, result)
 
     def osa(self, a: TapeLike, b: TapeLike, scope: Optional[DeviceScope] = None, bound: Optional[int] = None, out=None):
         """Damerau-Levenshtein distances in the optimal-string-alignment (OSA, restricted) form of every pair ``(a[i], b[i])``

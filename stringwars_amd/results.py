@@ -172,6 +172,49 @@ class InfixMatches:
         return int(self.distances[i]), int(self.starts[i]), int(self.ends[i])
 
 
+class InfixOccurrences:
+    """The result of ``LevenshteinDistances.infix_all``: for every pair the ends at which the pattern occurs within the bound, as CSR.
+    Row ``i`` is ``[offsets[i], offsets[i + 1])`` of ``starts``, ``ends`` and ``distances``, ascending by end: the pattern occurs as
+    ``text[starts[h]:ends[h]]`` with the true distance ``distances[h]``, the shortest occurrence that ends there. ``starts`` is None
+    where the call skipped the start pass (``starts=False``); a counting call has ``offsets`` and ``counts`` only. Arrays that live
+    on the device (``out=`` tensors) are brought to the host when a row is asked for. Positions count symbols."""
+
+    def __init__(self, offsets, starts, ends, distances):
+        self.offsets, self.starts, self.ends, self.distances = offsets, starts, ends, distances
+        if len(offsets) < 1 or (ends is None) != (distances is None) or (ends is None and starts is not None):
+            raise ValueError("offsets needs at least one entry; ends and distances come together, starts only with them")
+        if ends is not None and (len(ends) != len(distances) or (starts is not None and len(starts) != len(ends))):
+            raise ValueError("starts, ends and distances must have the same length")
+
+    _host = staticmethod(_CsrMatches._host)
+
+    def __len__(self) -> int:
+        """The number of pairs (rows)."""
+        return len(self.offsets) - 1
+
+    @property
+    def counts(self) -> np.ndarray:
+        """Hits per pair."""
+        return np.diff(self._host(self.offsets, np.uint64)).astype(np.uint64)
+
+    def row(self, i: int):
+        """``(starts, ends, distances)`` of pair ``i``; ``starts`` is None where the call skipped the start pass."""
+        if not -len(self) <= i < len(self):
+            raise IndexError("pair index out of range")
+        i %= len(self)
+        if self.ends is None:
+            raise ValueError("a counting call holds no rows")
+        offsets = self._host(self.offsets, np.uint64)
+        first, last = int(offsets[i]), int(offsets[i + 1])
+        starts = None if self.starts is None else self._host(self.starts, np.uint32)[first:last]
+        return starts, self._host(self.ends, np.uint32)[first:last], self._host(self.distances, np.uint32)[first:last]
+
+    def __getitem__(self, i: int):
+        """The hits of pair ``i`` as a list of ``(distance, start, end)``, ascending by end (``start`` None without the start pass)."""
+        starts, ends, distances = self.row(i)
+        return [(int(distances[h]), None if starts is None else int(starts[h]), int(ends[h])) for h in range(len(ends))]
+
+
 class PartialAlignments:
     """The result of ``LevenshteinDistances.partial_ratio_alignment``, after rapidfuzz's ``ScoreAlignment``: ``score[i]`` is
     ``fuzz.partial_ratio(a[i], b[i])`` as float64, reached between ``a[i][src_start[i]:src_end[i]]`` and

@@ -60,6 +60,17 @@ pub const ALIGN_MAX_CELLS: u64 = 1 << 30;
 pub const INFIX_MAX_PATTERN: u32 = 2048;
 /// `SWH_INFIX_NONE`: start / end of a pair whose best occurrence is over the bound.
 pub const INFIX_NONE: u32 = u32::MAX;
+/// `SWH_INFIX_SELECT_*`: which ends within the bound `infix_all_into` reports.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(u32)]
+pub enum InfixSelect {
+    /// every end whose score is within the bound
+    All = 0,
+    /// those that reach the pair's best score (edlib's `locations`, whose ends are inclusive)
+    Best = 1,
+    /// the first column of every plateau of the score curve that is a weak local minimum
+    Minima = 2,
+}
 /// `SWH_OSA_MAX_SHORTER`: symbols of a pair's shorter string an OSA call accepts.
 pub const OSA_MAX_SHORTER: u32 = 2048;
 /// `SWH_LCS_MAX_SHORTER`: symbols of a pair's shorter string an LCS / Indel call accepts.
@@ -145,6 +156,9 @@ extern "C" {
     fn swh_levenshtein_infix_u64tape(engine: Handle, scope: Handle, patterns: *const TapeU64, texts: *const TapeU64, bound: u32, distances: *mut u32, starts: *mut u32, ends: *mut u32, error: Err) -> c_int;
     fn swh_levenshtein_utf8_infix_u64tape(engine: Handle, scope: Handle, patterns: *const TapeU64, texts: *const TapeU64, bound: u32, distances: *mut u32, starts: *mut u32, ends: *mut u32, error: Err) -> c_int;
     fn swh_levenshtein_infix_prepared(engine: Handle, scope: Handle, patterns: *const PreparedView, texts: *const PreparedView, bound: u32, distances: *mut u32, starts: *mut u32, ends: *mut u32, error: Err) -> c_int;
+    fn swh_levenshtein_infix_all_u64tape(engine: Handle, scope: Handle, patterns: *const TapeU64, texts: *const TapeU64, bound: u32, select: u32, row_offsets: *mut usize, starts: *mut u32, ends: *mut u32, distances: *mut u32, capacity: usize, error: Err) -> c_int;
+    fn swh_levenshtein_utf8_infix_all_u64tape(engine: Handle, scope: Handle, patterns: *const TapeU64, texts: *const TapeU64, bound: u32, select: u32, row_offsets: *mut usize, starts: *mut u32, ends: *mut u32, distances: *mut u32, capacity: usize, error: Err) -> c_int;
+    fn swh_levenshtein_infix_all_prepared(engine: Handle, scope: Handle, patterns: *const PreparedView, texts: *const PreparedView, bound: u32, select: u32, row_offsets: *mut usize, starts: *mut u32, ends: *mut u32, distances: *mut u32, capacity: usize, error: Err) -> c_int;
     fn swh_levenshtein_osa_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, bound: u32, out: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_utf8_osa_pairs_u64tape(engine: Handle, scope: Handle, a: *const TapeU64, b: *const TapeU64, bound: u32, out: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
     fn swh_levenshtein_osa_pairs_prepared(engine: Handle, scope: Handle, a: *const PreparedView, b: *const PreparedView, bound: u32, out: *mut u32, out_stride_bytes: usize, error: Err) -> c_int;
@@ -640,6 +654,35 @@ impl LevenshteinDistances {
         check(unsafe { swh_levenshtein_infix_prepared(self.handle, scope.handle, &vp, &vt, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
                                                       starts.as_mut_ptr(), ends.as_mut_ptr(), &mut message) }, message)
     }
+    /// Infix search for every occurrence within `bound` (`swh_levenshtein_infix_all_*`), as CSR: row i is `[row_offsets[i] .. row_offsets[i + 1])`
+    /// of `starts` / `ends` / `distances`, ascending by end -- every end of `texts[i]` whose best distance to `patterns[i]` is within `bound`
+    /// and passes `select`, the true distance, and the start of the shortest occurrence that ends there (`None` skips the start pass).
+    /// `row_offsets` (`patterns.len() + 1` entries) is always filled; the arrays only if the total fits them. Returns the total: a caller
+    /// who gets more than `ends.len()` back calls again with larger arrays (empty slices make the counting call).
+    pub fn infix_all_into(&self, scope: &DeviceScope, patterns: &BytesTapeView<u64>, texts: &BytesTapeView<u64>, bound: Option<u32>, select: InfixSelect,
+                          row_offsets: &mut [usize], starts: Option<&mut [u32]>, ends: &mut [u32], distances: &mut [u32]) -> Result<usize, Error> {
+        assert!(row_offsets.len() > patterns.len() && ends.len() == distances.len() && starts.as_ref().map_or(true, |s| s.len() == ends.len()));
+        let (vp, vt) = (bytes_tape(patterns), bytes_tape(texts));
+        let capacity = ends.len();
+        let (s, e, d) = if capacity == 0 { (ptr::null_mut(), ptr::null_mut(), ptr::null_mut()) }
+                        else { (starts.map_or(ptr::null_mut(), |s| s.as_mut_ptr()), ends.as_mut_ptr(), distances.as_mut_ptr()) };
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_infix_all_u64tape(self.handle, scope.handle, &vp, &vt, bound.unwrap_or(UNBOUNDED), select as u32, row_offsets.as_mut_ptr(), s, e, d,
+                          capacity, &mut message) }, message)?;
+        Ok(row_offsets[patterns.len()])
+    }
+    pub fn infix_all_into_prepared(&self, scope: &DeviceScope, patterns: &PreparedTape, texts: &PreparedTape, bound: Option<u32>, select: InfixSelect,
+                          row_offsets: &mut [usize], starts: Option<&mut [u32]>, ends: &mut [u32], distances: &mut [u32]) -> Result<usize, Error> {
+        assert!(row_offsets.len() > patterns.len() && ends.len() == distances.len() && starts.as_ref().map_or(true, |s| s.len() == ends.len()));
+        let (vp, vt) = (patterns.view(), texts.view());
+        let capacity = ends.len();
+        let (s, e, d) = if capacity == 0 { (ptr::null_mut(), ptr::null_mut(), ptr::null_mut()) }
+                        else { (starts.map_or(ptr::null_mut(), |s| s.as_mut_ptr()), ends.as_mut_ptr(), distances.as_mut_ptr()) };
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_infix_all_prepared(self.handle, scope.handle, &vp, &vt, bound.unwrap_or(UNBOUNDED), select as u32, row_offsets.as_mut_ptr(), s, e, d,
+                          capacity, &mut message) }, message)?;
+        Ok(row_offsets[patterns.len()])
+    }
     /// Damerau-Levenshtein distances in the optimal-string-alignment form (`swh_levenshtein_osa_*`, rapidfuzz `distance::osa`): `out[i] = min(osa(a[i], b[i]), bound + 1)`;
     /// a swap of two neighbouring symbols costs one edit, no substring is edited twice (`ca` / `abc`: 3). The shorter string of a pair holds at most `OSA_MAX_SHORTER` symbols.
     pub fn osa_into(&self, scope: &DeviceScope, a: &BytesTapeView<u64>, b: &BytesTapeView<u64>, bound: Option<u32>, out: &mut [u32]) -> Result<(), Error> {
@@ -767,6 +810,31 @@ impl LevenshteinDistancesUtf8 {
         let mut message = ptr::null();
         check(unsafe { swh_levenshtein_infix_prepared(self.handle, scope.handle, &vp, &vt, bound.unwrap_or(UNBOUNDED), distances.as_mut_ptr(),
                                                       starts.as_mut_ptr(), ends.as_mut_ptr(), &mut message) }, message)
+    }
+    /// Every occurrence within a bound over code points (see `LevenshteinDistances::infix_all_into`).
+    pub fn infix_all_into(&self, scope: &DeviceScope, patterns: &CharsTapeView<u64>, texts: &CharsTapeView<u64>, bound: Option<u32>, select: InfixSelect,
+                          row_offsets: &mut [usize], starts: Option<&mut [u32]>, ends: &mut [u32], distances: &mut [u32]) -> Result<usize, Error> {
+        assert!(row_offsets.len() > patterns.len() && ends.len() == distances.len() && starts.as_ref().map_or(true, |s| s.len() == ends.len()));
+        let (vp, vt) = (chars_tape(patterns), chars_tape(texts));
+        let capacity = ends.len();
+        let (s, e, d) = if capacity == 0 { (ptr::null_mut(), ptr::null_mut(), ptr::null_mut()) }
+                        else { (starts.map_or(ptr::null_mut(), |s| s.as_mut_ptr()), ends.as_mut_ptr(), distances.as_mut_ptr()) };
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_utf8_infix_all_u64tape(self.handle, scope.handle, &vp, &vt, bound.unwrap_or(UNBOUNDED), select as u32, row_offsets.as_mut_ptr(), s, e, d,
+                          capacity, &mut message) }, message)?;
+        Ok(row_offsets[patterns.len()])
+    }
+    pub fn infix_all_into_prepared(&self, scope: &DeviceScope, patterns: &PreparedTape, texts: &PreparedTape, bound: Option<u32>, select: InfixSelect,
+                          row_offsets: &mut [usize], starts: Option<&mut [u32]>, ends: &mut [u32], distances: &mut [u32]) -> Result<usize, Error> {
+        assert!(row_offsets.len() > patterns.len() && ends.len() == distances.len() && starts.as_ref().map_or(true, |s| s.len() == ends.len()));
+        let (vp, vt) = (patterns.view(), texts.view());
+        let capacity = ends.len();
+        let (s, e, d) = if capacity == 0 { (ptr::null_mut(), ptr::null_mut(), ptr::null_mut()) }
+                        else { (starts.map_or(ptr::null_mut(), |s| s.as_mut_ptr()), ends.as_mut_ptr(), distances.as_mut_ptr()) };
+        let mut message = ptr::null();
+        check(unsafe { swh_levenshtein_infix_all_prepared(self.handle, scope.handle, &vp, &vt, bound.unwrap_or(UNBOUNDED), select as u32, row_offsets.as_mut_ptr(), s, e, d,
+                          capacity, &mut message) }, message)?;
+        Ok(row_offsets[patterns.len()])
     }
     /// OSA distances over code points (see `LevenshteinDistances::osa_into`).
     pub fn osa_into(&self, scope: &DeviceScope, a: &CharsTapeView<u64>, b: &CharsTapeView<u64>, bound: Option<u32>, out: &mut [u32]) -> Result<(), Error> {

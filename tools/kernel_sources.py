@@ -30,6 +30,8 @@ KERNELS = {
     "align_wide": ("swh::k_align_cross_wide<", ("alignshort.hip", "bp_window.hpp", "common.hpp")),
     "align_long": ("swh::k_align_cross_long<", ("alignshort.hip", "bp_window.hpp", "common.hpp")),
     "infix": ("swh::k_infix<", ("infix.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
+    "infix_hits": ("swh::k_infix_hits<", ("infix.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
+    "infix_hit_starts": ("swh::k_infix_hit_starts<", ("infix.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
     "osa": ("swh::k_osa<", ("osa.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
     "lcs": ("swh::k_lcs<", ("lcs.hip", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
     "partial": ("swh::k_partial<unsigned char,", ("partial.hip", "partial.hpp", "bp_lanes.hpp", "bp_item.hpp", "bp_window.hpp", "common.hpp")),
