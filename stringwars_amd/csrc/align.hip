@@ -11,7 +11,7 @@
 // '=' on equal symbols, else 'X' if the diagonal gives D, else 'D' if the cell above does, else 'I' -- in (a, b) terms,
 // reading D(i, j) of a transposed pair as D^T(j, i) (the matrix is symmetric under swapping the strings).
 // The ops come out back to front and are written from the end of the pair's slot, so they sit there in forward order;
-// k_align_emit moves them to their compact place once the counts are scanned.
+// k_align_emit moves them to their compact place once the counts are scanned (scan.hip).
 #include "align.hpp"
 #include "bp_lanes.hpp"   // the offset reader
 
@@ -69,91 +69,6 @@ __global__ void __launch_bounds__(256) k_align_sizes(AlignTapes t, uint64_t *sto
         atomicAdd(&sizes->cells, cells);
         atomicMax(&sizes->max_store, biggest);
     }
-}
-
-// ---- exclusive scan: tiles of 2048 values (256 threads x 8), the tile sums scanned by one workgroup, then added back ----------
-constexpr uint32_t kScanThreads = 256, kScanPer = 8, kScanTile = kScanThreads * kScanPer;
-
-__device__ __forceinline__ uint64_t scan_block_exclusive(uint64_t v, uint64_t *lds, uint64_t &total) {
-    // Hillis-Steele over the workgroup's 256 thread sums
-    const uint32_t t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (uint32_t s = 1; s < kScanThreads; s <<= 1) {
-        const uint64_t add = t >= s ? lds[t - s] : 0;
-        __syncthreads();
-        lds[t] += add;
-        __syncthreads();
-    }
-    total = lds[kScanThreads - 1];
-    const uint64_t inclusive = lds[t];
-    __syncthreads();
-    return inclusive - v;
-}
-
-template <typename In>
-__global__ void __launch_bounds__(kScanThreads) k_align_scan_tiles(const In *in, uint64_t *out, uint64_t n, uint64_t *partials) {
-    __shared__ uint64_t lds[kScanThreads];
-    const uint64_t first = (uint64_t)blockIdx.x * kScanTile + (uint64_t)threadIdx.x * kScanPer;
-    uint64_t v[kScanPer], sum = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kScanPer; ++q) {
-        v[q] = first + q < n ? (uint64_t)in[first + q] : 0;
-        sum += v[q];
-    }
-    uint64_t total;
-    uint64_t run = scan_block_exclusive(sum, lds, total);
-#pragma unroll
-    for (uint32_t q = 0; q < kScanPer; ++q) {
-        if (first + q < n) out[first + q] = run;
-        run += v[q];
-    }
-    if (threadIdx.x == 0) partials[blockIdx.x] = total;
-}
-
-// one workgroup: partials[0 .. tiles) -> exclusive prefix sums; the grand total goes to out[n]
-__global__ void __launch_bounds__(kScanThreads) k_align_scan_partials(uint64_t *partials, uint64_t tiles, uint64_t *out, uint64_t n) {
-    __shared__ uint64_t lds[kScanThreads];
-    const uint64_t per = (tiles + kScanThreads - 1) / kScanThreads;
-    const uint64_t first = threadIdx.x * per, last = first + per < tiles ? first + per : tiles;
-    uint64_t sum = 0;
-    for (uint64_t q = first; q < last; ++q) sum += partials[q];
-    uint64_t total;
-    uint64_t run = scan_block_exclusive(sum, lds, total);
-    for (uint64_t q = first; q < last; ++q) {
-        const uint64_t v = partials[q];
-        partials[q] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) out[n] = total;
-}
-
-__global__ void __launch_bounds__(kScanThreads) k_align_scan_add(uint64_t *out, uint64_t n, const uint64_t *partials) {
-    const uint64_t i = (uint64_t)blockIdx.x * kScanThreads + threadIdx.x;
-    if (i < n) out[i] += partials[i / kScanTile];
-}
-
-size_t align_scan_partials(uint64_t n) { return (size_t)((n + kScanTile - 1) / kScanTile + 1); }
-
-template <typename In>
-static void align_scan(Scope *scope, const In *in, uint64_t *out, uint64_t n, uint64_t *partials) {
-    const uint64_t tiles = (n + kScanTile - 1) / kScanTile;
-    StampGuard guard(scope, "align_scan");
-    if (n) {
-        hipLaunchKernelGGL(k_align_scan_tiles<In>, dim3((uint32_t)tiles), dim3(kScanThreads), 0, scope->stream, in, out, n, partials);
-        SWH_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_align_scan_partials, dim3(1), dim3(kScanThreads), 0, scope->stream, partials, tiles, out, n);
-    SWH_HIP_CHECK(hipGetLastError());
-    if (n) {
-        hipLaunchKernelGGL(k_align_scan_add, dim3((uint32_t)((n + kScanThreads - 1) / kScanThreads)), dim3(kScanThreads), 0, scope->stream,
-                           out, n, (const uint64_t *)partials);
-        SWH_HIP_CHECK(hipGetLastError());
-    }
-}
-void launch_align_scan(Scope *scope, uint64_t *values, uint64_t n, uint64_t *partials) { align_scan(scope, (const uint64_t *)values, values, n, partials); }
-void launch_align_scan_counts(Scope *scope, const uint32_t *counts, uint64_t *offsets, uint64_t n, uint64_t *partials) {
-    align_scan(scope, counts, offsets, n, partials);
 }
 
 // ---- the forward pass and the walk ------------------------------------------------------------------------------------------------

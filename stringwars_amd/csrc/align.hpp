@@ -22,14 +22,9 @@ struct AlignSizes {
     unsigned long long first_oversize;   // the first pair with len(a) * len(b) > SWH_ALIGN_MAX_CELLS, or ~0
 };
 
-// Per pair: stored bytes -> store_base[i], len(a) + len(b) -> slot_base[i] (both then scanned in place), and `sizes`
+// Per pair: stored bytes -> store_base[i], len(a) + len(b) -> slot_base[i] (both then scanned in place: scan.hpp), and `sizes`
 // (zeroed by the caller, first_oversize set to ~0).
 void launch_align_sizes(Scope *scope, const AlignTapes &t, uint64_t *store_base, uint64_t *slot_base, AlignSizes *sizes);
-// In place: values[0 .. n) -> their exclusive prefix sums, values[n] = the total. `partials` holds align_scan_partials(n) words.
-size_t align_scan_partials(uint64_t n);
-void launch_align_scan(Scope *scope, uint64_t *values, uint64_t n, uint64_t *partials);
-// u32 `counts` -> exclusive prefix sums in `offsets` (n + 1 entries)
-void launch_align_scan_counts(Scope *scope, const uint32_t *counts, uint64_t *offsets, uint64_t n, uint64_t *partials);
 
 // The forward pass and the walk of pairs [pair_first, pair_end); `store` holds their part of the batch's storage space, which
 // starts at store_first = store_base[pair_first]. The walk writes pair i's ops, in forward order, to the END of its slot

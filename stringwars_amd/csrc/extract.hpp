@@ -75,7 +75,7 @@ void launch_extract_select(Scope *scope, const ExtractLaunch &x);
 // index and the score's 64 bits, in ascending candidate order, never at or beyond `total` -- and advances the cursor.
 struct ExtractWithinLaunch : ExtractSlice {
     uint32_t *hits;               // count pass: [query]
-    uint64_t *cursors;            // fill pass: [query], where the row's next hit goes
+    uint64_t *cursors;            // fill pass: [query], where the row's next hit goes (from the offsets scan of hits: scan.hpp)
     uint64_t total;               // fill pass: entries that `indices` and `scores` hold
     uint32_t *indices;
     uint64_t *scores;             // float64 patterns

@@ -7,8 +7,8 @@
 // pattern, complemented where the larger score is the better one, so any cutoff admits the same pairs in both calls and a score at
 // the cutoff is admitted.
 //
-// The pairs are walked twice. The count pass adds popcount(ballot) to the row's count; within.hip's scan turns the counts into
-// cursors and row offsets; the fill pass repeats the walk and stores a hit at the row's cursor plus the hits in the lanes below it.
+// The pairs are walked twice. The count pass adds popcount(ballot) to the row's count; the offsets scan (scan.hip) turns the counts
+// into cursors and row offsets; the fill pass repeats the walk and stores a hit at the row's cursor plus the hits in the lanes below it.
 // One wave per query row and slices in stream order: a row meets its candidates in ascending order, no atomics touch the output,
 // nothing is sorted, and every run writes the same bytes.
 #include "extract.hpp"

@@ -26,7 +26,7 @@
 // (Ukkonen's, in its semi-global form) is a later optimisation too.
 //
 // The search for EVERY occurrence within a bound (swh_levenshtein_infix_all_*) stands below k_infix: the same items and the same
-// walk, run around within.hip's scan, with kernels of its own (k_infix_hits, k_infix_hit_items, k_infix_hit_starts).
+// walk, run around the offsets scan (scan.hip), with kernels of its own (k_infix_hits, k_infix_hit_items, k_infix_hit_starts).
 #include "infix.hpp"
 #include "bp_lanes.hpp"
 

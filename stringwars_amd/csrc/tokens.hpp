@@ -4,8 +4,8 @@
 //
 // Neither kernel knows where its results go before it has run: a normal form, X and Y are each never longer than the string they come
 // from, so the kernels write them into a staging buffer laid out as the source view is -- string i's result starts where string i
-// starts, relative to the view's first byte -- with the lengths beside them. The lengths are scanned into offsets by the range
-// search's scan (launch_within_offsets) and k_token_compact moves every result to its place in the tape that is kept.
+// starts, relative to the view's first byte -- with the lengths beside them. The lengths are scanned into offsets by the offsets
+// scan (scan.hpp: launch_offsets_scan) and k_token_compact moves every result to its place in the tape that is kept.
 #pragma once
 #include "common.hpp"
 

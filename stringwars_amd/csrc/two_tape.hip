@@ -11,6 +11,7 @@
 
 #include "api.hpp"
 #include "within.hpp"
+#include "scan.hpp"
 #include "align.hpp"
 #include "infix.hpp"
 #include "osa.hpp"
@@ -143,6 +144,57 @@ template <typename Sizes, typename Launch> static Sizes measure(Scope *scope, Si
     SWH_HIP_CHECK(hipMemcpyAsync(&got, device_sizes, sizeof got, hipMemcpyDeviceToHost, scope->stream));
     SWH_HIP_CHECK(hipStreamSynchronize(scope->stream));
     return got;
+}
+
+// Count, scan, fill: the rows of a CSR call (within, extract_within, infix_all), whose lengths nobody knows before the pairs are
+// walked. The site's count pass leaves a count per (row, slice); scan_counts() turns them into a cursor each and the row offsets
+// (the offsets scan, scan.hpp) and reads their last word, the total (8 bytes: one read and wait); publish() sends the offsets on to a
+// host caller and says whether the site's fill pass runs: only if there are hits and the caller's arrays hold them. Two steps, since a
+// site looks at its call's summary or closes the scan's stamps between them.
+struct CsrRows {
+    Staged<uint64_t> offs;         // the caller's row offsets: rows + 1
+    uint64_t rows, capacity, total = 0;
+    uint32_t *counts = nullptr;    // [row][slice]
+    uint64_t *cursors = nullptr;   // [row][slice]: where the hits of that count begin
+    ScanScratch scan;
+
+    CsrRows(size_t *row_offsets, uint64_t rows_, size_t capacity_) : offs((uint64_t *)row_offsets), rows(rows_), capacity(capacity_) {
+        static_assert(sizeof(size_t) == sizeof(uint64_t), "row offsets are scanned as 64-bit words");
+    }
+    void fill_empty(hipStream_t stream) const { offs.fill_zero(stream, rows + 1); }   // no row, or every row empty
+    size_t need(uint64_t slices = 1) const {   // of the scratch
+        return pad(rows * slices * 4) + pad(rows * slices * 8) + ScanScratch::need(rows * slices) + offs.need(rows + 1);
+    }
+    void place(Carver &sc, uint64_t slices = 1) {
+        counts = sc.take<uint32_t>(rows * slices); cursors = sc.take<uint64_t>(rows * slices);
+        scan.place(sc, rows * slices);
+        offs.place(sc, rows + 1);
+    }
+    void scan_counts(Scope *scope, uint32_t slices = 1) {
+        launch_offsets_scan(scope, counts, rows, slices, scan, cursors, offs.dev);
+        total = read_offset(offs.dev, 1, rows, true, scope->stream);
+    }
+    bool publish(hipStream_t stream) const {
+        offs.copy_back(stream, rows + 1);
+        return total && total <= capacity;
+    }
+};
+// Where a fill pass writes `total` hits: the caller's device arrays, or staging for its host arrays in scope->within_out, sized now
+// that the total is known, with `extra` bytes for the site to carve after them.
+template <typename... T> static Carver carve_hits(Scope *scope, uint64_t total, size_t extra, Staged<T> &...outs) {
+    Carver oc = carve(scope->within_out, scope->within_out_bytes, (outs.need(total) + ... + extra));
+    (outs.place(oc, total), ...);
+    return oc;
+}
+// The output rules the CSR calls share, in the order they are tested: the row offsets always, the per-hit arrays `a` and `b` (`names`:
+// "a and b") both or neither, and no capacity without them (`three_arrays`: the call has a third per-hit array, so one more NULL).
+static swh_status_t csr_output_checks(const void *row_offsets, const void *a, const void *b, const char *names, bool three_arrays, size_t capacity,
+                                      const char **error) {
+    if (!row_offsets) return fail(error, swh_invalid_argument_k, "null row_offsets");
+    if (!a != !b) return fail(error, swh_invalid_argument_k, "%s must both be given, or neither", names);
+    if (!a && capacity)
+        return fail(error, swh_invalid_argument_k, "a capacity without arrays: the counting call passes %sNULL, NULL, 0", three_arrays ? "NULL, " : "");
+    return swh_success_k;
 }
 
 // One side of a launch on prepared tapes as the lane-per-block and alignment kernels read it: strings [first, first + count) as code
@@ -405,51 +457,38 @@ struct WithinOutputs {
 };
 
 static swh_status_t within_run(Scope *scope, const Engine *engine, const TapePair &p, uint32_t bound, const WithinOutputs &r, const char **error) {
-    static_assert(sizeof(size_t) == sizeof(uint64_t), "row offsets are scanned as 64-bit words");
     return synchronous_run(scope, error, [&]() -> swh_status_t {
         const uint64_t nq = p.a_count, nc = p.b_count;
         SWH_HIP_CHECK(hipSetDevice(scope->device));
         hipStream_t stream = scope->stream;
-        Staged<uint64_t> offs((uint64_t *)r.row_offsets);
+        CsrRows csr(r.row_offsets, nq, r.capacity);
         Staged<uint32_t> ind(r.indices), dist(r.distances);   // (both null in a counting call: nothing is staged, nothing filled)
-        if (nq == 0 || nc == 0) {   // no row, or every row empty
-            offs.fill_zero(stream, nq + 1);
+        if (nq == 0 || nc == 0) {
+            csr.fill_empty(stream);
             return swh_success_k;
         }
         const size_t ow = p.pa->off64 ? 8 : 4;
-        // Once the offsets are complete on the device their last word, the total (one read and wait), decides the fill, and the rest
-        // goes to a host caller. Where the fill pass writes: the caller's device arrays, or staging for its host arrays.
-        auto stage_outputs = [&](uint64_t total) {
-            Carver oc = carve(scope->within_out, scope->within_out_bytes, ind.need(total) + dist.need(total));
-            ind.place(oc, total); dist.place(oc, total);
-        };
 
         if (search_is_fused(scope, engine, p, bound, within_force_select(), ind.on_device)) {
             // ---- fused: a count (4 bytes) and a start (8) per (row, slice) ----------------------------------------------------------------
             const SearchSlices cut = search_slices(nq, nc, scope->compute_units, 12, within_slices_hook());
             const uint64_t slices = cut.slices;
-            const uint64_t n_counts = nq * slices, tiles = (n_counts + kWithinScanTile - 1) / kWithinScanTile;
-            const size_t need = pad(n_counts * 4) + pad(n_counts * 8) + pad(tiles * 8) + offs.need(nq + 1);
-            Carver sc = carve(scope->topk_scratch, scope->topk_scratch_bytes, need);
+            Carver sc = carve(scope->topk_scratch, scope->topk_scratch_bytes, csr.need(slices));
+            csr.place(sc, slices);
             WithinLaunch w{};
             w.a = prepared_view(p.pa, false, p.a_first, nq); w.b = prepared_view(p.pb, false, p.b_first, nc);
             w.off64 = p.pa->off64; w.slices = (uint32_t)slices; w.bound = bound; w.prune = within_prune(); w.slice_chunks = cut.slice_chunks;
-            w.counts = sc.take<uint32_t>(n_counts);
-            uint64_t *starts = sc.take<uint64_t>(n_counts), *block_sums = sc.take<uint64_t>(tiles);
-            offs.place(sc, nq + 1);
-            w.starts = starts;
+            w.counts = csr.counts; w.starts = csr.cursors;
             scope->summary_slot = 0;
             launch_cross_within(scope, w, false);
-            launch_within_offsets(scope, w.counts, nq, (uint32_t)slices, block_sums, starts, offs.dev);
-            const uint64_t total = read_offset(offs.dev, 1, nq, true, stream);
+            csr.scan_counts(scope, (uint32_t)slices);
             const CallSummary sm = scope->summary_host[0];
             if (!sm.violation) {
-                offs.copy_back(stream, nq + 1);
-                if (total && total <= r.capacity) {
-                    stage_outputs(total);
-                    w.total = total; w.indices = ind.dev; w.distances = dist.dev;
+                if (csr.publish(stream)) {
+                    carve_hits(scope, csr.total, 0, ind, dist);
+                    w.total = csr.total; w.indices = ind.dev; w.distances = dist.dev;
                     launch_cross_within(scope, w, true);
-                    ind.copy_back(stream, total); dist.copy_back(stream, total);
+                    ind.copy_back(stream, csr.total); dist.copy_back(stream, csr.total);
                 }
                 SWH_HIP_CHECK(hipStreamSynchronize(stream));
                 if (scope->profiling && scope->stamps_used) {
@@ -467,8 +506,8 @@ static swh_status_t within_run(Scope *scope, const Engine *engine, const TapePai
                 }
                 scope->last_timing.cells = sm.cells;
                 // the tapes, a count and a start per (row, slice), the row offsets and the hits
-                scope->last_timing.bytes = p.pa->total_bytes + p.pb->total_bytes + (nq + nc) * ow + n_counts * 12 + (nq + 1) * 8 +
-                                           (total <= r.capacity ? total * 8 : 0);
+                scope->last_timing.bytes = p.pa->total_bytes + p.pb->total_bytes + (nq + nc) * ow + nq * slices * 12 + (nq + 1) * 8 +
+                                           (csr.total <= r.capacity ? csr.total * 8 : 0);
                 return swh_success_k;
             }
             // a string longer than the kernel takes (the memory of a prepared tape changed since it was measured): the general path
@@ -478,32 +517,26 @@ static swh_status_t within_run(Scope *scope, const Engine *engine, const TapePai
 
         // ---- general path: every block scored twice, once to count and once to fill -------------------------------------------------------
         SearchSweep sweep(scope, engine, p, bound);
-        const uint64_t tiles = (nq + kWithinScanTile - 1) / kWithinScanTile;
-        const size_t need = pad(sweep.q_step * sweep.c_step * 4) + pad(nq * 4) + pad(nq * 8) + pad(tiles * 8) + offs.need(nq + 1);
-        Carver sc = carve(scope->topk_scratch, scope->topk_scratch_bytes, need);
+        Carver sc = carve(scope->topk_scratch, scope->topk_scratch_bytes, pad(sweep.q_step * sweep.c_step * 4) + csr.need());
         uint32_t *matrix = sc.take<uint32_t>(sweep.q_step * sweep.c_step);
-        uint32_t *counts = sc.take<uint32_t>(nq);
-        uint64_t *cursors = sc.take<uint64_t>(nq), *block_sums = sc.take<uint64_t>(tiles);
-        offs.place(sc, nq + 1);
-        SWH_HIP_CHECK(hipMemsetAsync(counts, 0, nq * 4, stream));
+        csr.place(sc);
+        SWH_HIP_CHECK(hipMemsetAsync(csr.counts, 0, nq * 4, stream));
         auto no_rows_begin = [](uint64_t, uint64_t) {};   // (counts and cursors span all queries: nothing to open per block)
         swh_status_t status = sweep.walk(matrix, true, error, no_rows_begin, [&](uint64_t q0, uint64_t rows, uint64_t, uint64_t columns, bool) {
-            launch_within_count(scope, matrix, rows, columns, bound, counts + q0);
+            launch_within_count(scope, matrix, rows, columns, bound, csr.counts + q0);
             sweep.time_own_kernels(1);
         });
         if (status != swh_success_k) return status;
-        launch_within_offsets(scope, counts, nq, 1, block_sums, cursors, offs.dev);
+        csr.scan_counts(scope);
         sweep.time_own_kernels(2);
-        const uint64_t total = read_offset(offs.dev, 1, nq, true, stream);
-        offs.copy_back(stream, nq + 1);
-        if (total && total <= r.capacity) {
-            stage_outputs(total);
+        if (csr.publish(stream)) {
+            carve_hits(scope, csr.total, 0, ind, dist);
             status = sweep.walk(matrix, false, error, no_rows_begin, [&](uint64_t q0, uint64_t rows, uint64_t c0, uint64_t columns, bool) {
-                launch_within_fill(scope, matrix, rows, columns, c0, bound, cursors + q0, total, ind.dev, dist.dev);
+                launch_within_fill(scope, matrix, rows, columns, c0, bound, csr.cursors + q0, csr.total, ind.dev, dist.dev);
                 sweep.time_own_kernels(1);
             });
             if (status != swh_success_k) return status;
-            ind.copy_back(stream, total); dist.copy_back(stream, total);
+            ind.copy_back(stream, csr.total); dist.copy_back(stream, csr.total);
         }
         SWH_HIP_CHECK(hipStreamSynchronize(stream));
         sweep.close("within");
@@ -517,10 +550,7 @@ static swh_status_t within_checks(swh_levenshtein_t e, swh_scope_t s, size_t can
     if (((Engine *)e)->kind != 0) return fail(error, swh_invalid_argument_k, "not a Levenshtein engine");
     if (bound == SWH_UNBOUNDED) return fail(error, swh_invalid_argument_k, "a range search needs a bound: without one it is the dense cross-product");
     if (candidates >= 0xFFFFFFFFull) return fail(error, swh_unsupported_length_k, "2^32 - 1 candidates or more");
-    if (!row_offsets) return fail(error, swh_invalid_argument_k, "null row_offsets");
-    if (!indices != !distances) return fail(error, swh_invalid_argument_k, "indices and distances must both be given, or neither");
-    if (!indices && capacity) return fail(error, swh_invalid_argument_k, "a capacity without arrays: the counting call passes NULL, NULL, 0");
-    return swh_success_k;
+    return csr_output_checks(row_offsets, indices, distances, "indices and distances", false, capacity, error);
 }
 
 static swh_status_t within_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *q, const swh_tape_u64_t *c, bool utf8, uint32_t bound,
@@ -610,29 +640,30 @@ static swh_status_t align_run(Scope *scope, const TapePair &p, uint32_t bound, c
         t.count = count;
 
         AlignScratch *sc_entry = call_scratch(scope);
-        // fixed part: sizes | store_base | slot_base | counts | offsets | distances | scan partials
-        const size_t partial_words = align_scan_partials(count);
+        // fixed part: sizes | store_base | slot_base | counts | offsets | distances | the scans' scratch
         const size_t fixed = pad(sizeof(AlignSizes)) + 2 * pad((count + 1) * 8) + pad(count * 4) + offsets.need(count + 1) + distances.need(count) +
-                             pad(partial_words * 8);
+                             ScanScratch::need(count);
         ensure(sc_entry->buf, sc_entry->bytes, fixed);
         Carver sc{};
         AlignSizes *sizes;
-        uint64_t *store_base, *slot_base, *partials;
+        uint64_t *store_base, *slot_base;
         uint32_t *counts;
+        ScanScratch scan;
         auto carve_fixed = [&] {   // (again after the scratch has been regrown)
             sc = Carver{sc_entry->buf, 0, sc_entry->bytes};
             sizes = sc.take<AlignSizes>(1);
             store_base = sc.take<uint64_t>(count + 1); slot_base = sc.take<uint64_t>(count + 1);
             counts = sc.take<uint32_t>(count);
             offsets.place(sc, count + 1); distances.place(sc, count);
-            partials = sc.take<uint64_t>(partial_words);
+            scan.place(sc, count);
         };
         carve_fixed();
 
         const AlignSizes got = measure(scope, sizes, [&] {
             launch_align_sizes(scope, t, store_base, slot_base, sizes);
-            launch_align_scan(scope, store_base, count, partials);
-            launch_align_scan(scope, slot_base, count, partials);
+            // in place: count + 1 words each, the total in the last
+            launch_offsets_scan(scope, store_base, count, 1, scan, nullptr, store_base);
+            launch_offsets_scan(scope, slot_base, count, 1, scan, nullptr, slot_base);
         });
         if (got.first_oversize != ~0ull) {
             const size_t i = (size_t)got.first_oversize;
@@ -686,7 +717,7 @@ static swh_status_t align_run(Scope *scope, const TapePair &p, uint32_t bound, c
             c.store_first = starts[q];
             launch_align_chunk(scope, t, c);
         }
-        launch_align_scan_counts(scope, counts, offsets.dev, count, partials);
+        launch_offsets_scan(scope, counts, count, 1, scan, nullptr, offsets.dev);
         launch_align_emit(scope, count, slot_base, counts, offsets.dev, slots, ops.dev);
         distances.copy_back(stream, count); offsets.copy_back(stream, count + 1);
         if (!ops.on_device) {   // only the ops there are, not the capacity: their number is read first
@@ -861,15 +892,14 @@ struct InfixAllOutputs {
 };
 
 static swh_status_t infix_all_run(Scope *scope, const TapePair &p, uint32_t bound, uint32_t select, const InfixAllOutputs &r, const char **error) {
-    static_assert(sizeof(size_t) == sizeof(uint64_t), "row offsets are scanned as 64-bit words");
     return synchronous_run(scope, error, [&]() -> swh_status_t {
         const uint64_t count = p.a_count;
         SWH_HIP_CHECK(hipSetDevice(scope->device));
         hipStream_t stream = scope->stream;
-        Staged<uint64_t> offs((uint64_t *)r.row_offsets);
+        CsrRows csr(r.row_offsets, count, r.capacity);
         Staged<uint32_t> starts(r.starts), ends(r.ends), distances(r.distances);   // (null in a counting call: nothing staged or filled)
         if (count == 0) {
-            offs.fill_zero(stream, 1);
+            csr.fill_empty(stream);
             return swh_success_k;
         }
         const bool cp = p.pa->utf8;
@@ -880,16 +910,12 @@ static swh_status_t infix_all_run(Scope *scope, const TapePair &p, uint32_t boun
         t.count = count;
 
         AlignScratch *sc_entry = call_scratch(scope);
-        const uint64_t tiles = (count + kWithinScanTile - 1) / kWithinScanTile;
-        // sizes | items | a count, a best score and a cursor per pair | the scan's block sums | row offsets bound for the host
-        const size_t need = pad(sizeof(InfixSizes)) + pad(count * sizeof(LaneItem)) + 2 * pad(count * 4) + pad(count * 8) + pad(tiles * 8) +
-                            offs.need(count + 1);
-        Carver sc = carve(sc_entry->buf, sc_entry->bytes, need);
+        // sizes | items | a best score per pair | the rows' counts, cursors, scan scratch and offsets bound for the host
+        Carver sc = carve(sc_entry->buf, sc_entry->bytes, pad(sizeof(InfixSizes)) + pad(count * sizeof(LaneItem)) + pad(count * 4) + csr.need());
         InfixSizes *sizes = sc.take<InfixSizes>(1);
         LaneItem *items = sc.take<LaneItem>(count);
-        uint32_t *counts = sc.take<uint32_t>(count), *best = sc.take<uint32_t>(count);
-        uint64_t *cursors = sc.take<uint64_t>(count), *block_sums = sc.take<uint64_t>(tiles);
-        offs.place(sc, count + 1);
+        uint32_t *best = sc.take<uint32_t>(count);
+        csr.place(sc);
 
         const InfixSizes got = measure(scope, sizes, [&] { launch_infix_sizes(scope, t, sizes, items); });
         if (got.first_oversize != ~0ull) {
@@ -903,38 +929,34 @@ static swh_status_t infix_all_run(Scope *scope, const TapePair &p, uint32_t boun
         InfixHitsRun run{};
         run.items = items; run.item_count = got.items;
         run.bound = bound; run.select = select;
-        run.counts = counts; run.best = best; run.cursors = cursors;
+        run.counts = csr.counts; run.best = best; run.cursors = csr.cursors;
         run.wide_text = !cp && got.text_symbols >= 16;
         launch_infix_hits(scope, t, run, false);
-        launch_within_offsets(scope, counts, count, 1, block_sums, cursors, offs.dev);
-        // the offsets are complete on the device: their last word, the total (one read and wait), decides the fill
-        const uint64_t total = read_offset(offs.dev, 1, count, true, stream);
-        offs.copy_back(stream, count + 1);
-        const bool filled = total && total <= r.capacity;
+        csr.scan_counts(scope);
+        const bool filled = csr.publish(stream);
         if (filled) {
-            // where the fill walk and the start pass write: the caller's device arrays, or staging for its host arrays
-            const size_t per_hit = r.starts ? pad(sizeof(InfixSizes)) + pad(total * 8) + pad(total * sizeof(LaneItem)) : 0;
-            Carver oc = carve(scope->within_out, scope->within_out_bytes, ends.need(total) + distances.need(total) + starts.need(total) + per_hit);
-            run.ends = ends.place(oc, total); run.distances = distances.place(oc, total); run.total = total;
+            // after the outputs, what the start pass needs: its measurement, and a row and at most an item per hit
+            const size_t per_hit = r.starts ? pad(sizeof(InfixSizes)) + pad(csr.total * 8) + pad(csr.total * sizeof(LaneItem)) : 0;
+            Carver oc = carve_hits(scope, csr.total, per_hit, ends, distances, starts);
+            run.ends = ends.dev; run.distances = distances.dev; run.total = csr.total;
             launch_infix_hits(scope, t, run, true);
             if (r.starts) {
-                starts.place(oc, total);
                 InfixSizes *hit_sizes = oc.take<InfixSizes>(1);
-                uint64_t *rows = oc.take<uint64_t>(total);
-                LaneItem *hit_items = oc.take<LaneItem>(total);
-                const InfixSizes cut = measure(scope, hit_sizes, [&] { launch_infix_hit_items(scope, t, offs.dev, total, hit_sizes, rows, hit_items); });
+                uint64_t *rows = oc.take<uint64_t>(csr.total);
+                LaneItem *hit_items = oc.take<LaneItem>(csr.total);
+                const InfixSizes cut = measure(scope, hit_sizes, [&] { launch_infix_hit_items(scope, t, csr.offs.dev, csr.total, hit_sizes, rows, hit_items); });
                 InfixHitStartsRun pass{};
                 pass.items = hit_items; pass.item_count = cut.items;
                 pass.rows = rows; pass.ends = run.ends; pass.distances = run.distances; pass.starts = starts.dev;
                 launch_infix_hit_starts(scope, t, pass);
-                starts.copy_back(stream, total);
+                starts.copy_back(stream, csr.total);
             }
-            ends.copy_back(stream, total); distances.copy_back(stream, total);
+            ends.copy_back(stream, csr.total); distances.copy_back(stream, csr.total);
         }
         SWH_HIP_CHECK(hipStreamSynchronize(stream));
         // the tapes (twice if filled), the offsets of both, the row offsets and 8 or 12 bytes per stored hit
         close_call(scope, got.cells, (filled ? 2 : 1) * (cp ? 4 : 1) * got.symbols + 2 * (count + 1) * 8 + (count + 1) * 8 +
-                                         (filled ? total * (r.starts ? 12 : 8) : 0));
+                                         (filled ? csr.total * (r.starts ? 12 : 8) : 0));
         return swh_success_k;
     });
 }
@@ -946,11 +968,9 @@ static swh_status_t infix_all_checks(swh_levenshtein_t e, size_t p_count, size_t
     if (!engine->unit_costs) return fail(error, swh_not_implemented_k, "infix search needs unit costs (match 0, mismatch 1, open 1, extend 1)");
     if (p_count != t_count) return fail(error, swh_invalid_argument_k, "patterns and texts must hold the same number of strings");
     if (select > SWH_INFIX_SELECT_MINIMA) return fail(error, swh_invalid_argument_k, "select must be one of SWH_INFIX_SELECT_ALL, _BEST, _MINIMA");
-    if (!r.row_offsets) return fail(error, swh_invalid_argument_k, "null row_offsets");
-    if (!r.ends != !r.distances) return fail(error, swh_invalid_argument_k, "ends and distances must both be given, or neither");
-    if (!r.ends && r.starts) return fail(error, swh_invalid_argument_k, "starts without ends and distances");
-    if (!r.ends && r.capacity) return fail(error, swh_invalid_argument_k, "a capacity without arrays: the counting call passes NULL, NULL, NULL, 0");
-    return swh_success_k;
+    // (infix_all's own rule, where it has always stood: after the row offsets and "both or neither", before the capacity)
+    if (r.row_offsets && !r.ends && !r.distances && r.starts) return fail(error, swh_invalid_argument_k, "starts without ends and distances");
+    return csr_output_checks(r.row_offsets, r.ends, r.distances, "ends and distances", true, r.capacity, error);
 }
 
 static swh_status_t infix_all_tapes(swh_levenshtein_t e, swh_scope_t s, const swh_tape_u64_t *patterns, const swh_tape_u64_t *texts, bool utf8,
@@ -1363,8 +1383,8 @@ swh_status_t swh_levenshtein_jaro_cross_prepared(swh_levenshtein_t e, swh_scope_
 
 // ---- token-sorted tapes and token_set_ratio (tokens.hip) ---------------------------------------------------------------------------------
 // A normal form is never longer than its string, and neither are the two differences of a pair's token sets. So the kernels write
-// into staging laid out like their source and leave the lengths beside it; the lengths become offsets through the range search's scan
-// (launch_within_offsets), k_token_compact moves the results into buffers of their own, and prepare_tape measures those in place like
+// into staging laid out like their source and leave the lengths beside it; the lengths become offsets through the offsets scan
+// (scan.hpp), k_token_compact moves the results into buffers of their own, and prepare_tape measures those in place like
 // any device tape (and decodes them, in UTF-8 mode): the handle that comes out owns them and is a prepared tape like every other.
 // token_set_ratio derives the SWH_TOKENS_UNIQUE forms of both sides (or takes a tape that already is one), asks the LCS family's sizes
 // kernel for the first pair it would refuse -- x <= len(a'), y <= len(b'), so the rule of ratio on the normal forms covers the
@@ -1391,13 +1411,11 @@ static TokenSide token_side(const Prepared *p, size_t first, size_t count, hipSt
 
 // What a scan of `count` lengths needs beside them, and the tape it leads to.
 struct TokenScan {
-    uint64_t *block_sums, *starts, *offsets;
-    static size_t need(uint64_t count) {
-        return pad((count + kWithinScanTile - 1) / kWithinScanTile * 8) + pad(count * 8) + pad((count + 1) * 8);
-    }
+    ScanScratch scratch;
+    uint64_t *offsets;
+    static size_t need(uint64_t count) { return ScanScratch::need(count) + pad((count + 1) * 8); }
     void place(Carver &sc, uint64_t count) {
-        block_sums = sc.take<uint64_t>((count + kWithinScanTile - 1) / kWithinScanTile);
-        starts = sc.take<uint64_t>(count);
+        scratch.place(sc, count);
         offsets = sc.take<uint64_t>(count + 1);
     }
 };
@@ -1409,7 +1427,7 @@ struct TokenTape {
 static void token_pack(Scope *scope, const TokenSide &like, const uint8_t *staging, const uint32_t *lengths, const TokenScan &scan, uint32_t off64,
                        TokenTape &tape) {
     const uint64_t count = like.view.count;
-    launch_within_offsets(scope, lengths, count, 1, scan.block_sums, scan.starts, scan.offsets);
+    launch_offsets_scan(scope, lengths, count, 1, scan.scratch, nullptr, scan.offsets);
     const uint64_t total = read_offset(scan.offsets, 1, count, true, scope->stream);
     TokenCompact c{};
     c.like = like; c.staging = staging; c.lengths = lengths; c.starts = scan.offsets;
@@ -1906,31 +1924,26 @@ struct ExtractWithinRequest {
 };
 
 static swh_status_t extract_within_run(Scope *scope, const TapePair &p, const ExtractWithinRequest &r, const char **error) {
-    static_assert(sizeof(size_t) == sizeof(uint64_t), "row offsets are scanned as 64-bit words");
     return synchronous_run(scope, error, [&]() -> swh_status_t {
         const uint64_t nq = p.a_count, nc = p.b_count;
         SWH_HIP_CHECK(hipSetDevice(scope->device));
         hipStream_t stream = scope->stream;
-        Staged<uint64_t> offs((uint64_t *)r.row_offsets);
+        CsrRows csr(r.row_offsets, nq, r.capacity);
         Staged<uint32_t> ind(r.indices); Staged<uint64_t> sco((uint64_t *)r.scores);   // (both null in a counting call: nothing is staged, nothing filled)
-        if (nq == 0 || nc == 0) {   // no row, or every row empty
-            offs.fill_zero(stream, nq + 1);
+        if (nq == 0 || nc == 0) {
+            csr.fill_empty(stream);
             return swh_success_k;
         }
         ExtractSweep sweep(scope, p, r.scorer, r.cutoff, r.prefix_weight);
-        const uint64_t tiles = (nq + kWithinScanTile - 1) / kWithinScanTile;
-        // the sweep's part | a count and a cursor per query | the scan's block sums | row offsets bound for the host
-        const size_t need = sweep.need() + pad(nq * 4) + pad(nq * 8) + pad(tiles * 8) + offs.need(nq + 1);
-        Carver sc = carve(scope->topk_scratch, scope->topk_scratch_bytes, need);
+        // the sweep's part | the rows' counts, cursors, scan scratch and offsets bound for the host
+        Carver sc = carve(scope->topk_scratch, scope->topk_scratch_bytes, sweep.need() + csr.need());
         sweep.take(sc);
-        uint32_t *hits = sc.take<uint32_t>(nq);
-        uint64_t *cursors = sc.take<uint64_t>(nq), *block_sums = sc.take<uint64_t>(tiles);
-        offs.place(sc, nq + 1);
+        csr.place(sc);
 
         swh_status_t status = sweep.lengths(error);
         if (status != swh_success_k) return status;
         ExtractWithinLaunch x{};
-        x.hits = hits; x.cursors = cursors;
+        x.hits = csr.counts; x.cursors = csr.cursors;
         auto no_rows_begin = [](uint64_t) {};   // (counts and cursors span all queries: nothing to open per block)
         auto launch = [&](bool fill) {
             return [&x, scope, fill](const ExtractSlice &slice, bool) {
@@ -1938,23 +1951,19 @@ static swh_status_t extract_within_run(Scope *scope, const TapePair &p, const Ex
                 launch_extract_within(scope, x, fill);
             };
         };
-        SWH_HIP_CHECK(hipMemsetAsync(hits, 0, nq * 4, stream));
+        SWH_HIP_CHECK(hipMemsetAsync(csr.counts, 0, nq * 4, stream));
         if ((status = sweep.walk(true, error, no_rows_begin, launch(false))) != swh_success_k) return status;
-        launch_within_offsets(scope, hits, nq, 1, block_sums, cursors, offs.dev);
+        csr.scan_counts(scope);
         sweep.absorb(false);
-        // the offsets are complete on the device: their last word, the total (one read and wait), decides the fill
-        const uint64_t total = read_offset(offs.dev, 1, nq, true, stream);
-        offs.copy_back(stream, nq + 1);
-        const bool filled = total && total <= r.capacity;
+        const bool filled = csr.publish(stream);
         if (filled) {
-            // where the fill walk writes: the caller's device arrays, or staging for its host arrays
-            Carver oc = carve(scope->within_out, scope->within_out_bytes, ind.need(total) + sco.need(total));
-            x.indices = ind.place(oc, total); x.scores = sco.place(oc, total); x.total = total;
+            carve_hits(scope, csr.total, 0, ind, sco);
+            x.indices = ind.dev; x.scores = sco.dev; x.total = csr.total;
             if ((status = sweep.walk(false, error, no_rows_begin, launch(true))) != swh_success_k) return status;
-            ind.copy_back(stream, total); sco.copy_back(stream, total);
+            ind.copy_back(stream, csr.total); sco.copy_back(stream, csr.total);
         }
         SWH_HIP_CHECK(hipStreamSynchronize(stream));
-        sweep.close("extract_within", (nq + 1) * 8 + (filled ? total * 12 : 0));
+        sweep.close("extract_within", (nq + 1) * 8 + (filled ? csr.total * 12 : 0));
         return swh_success_k;
     });
 }
@@ -1968,9 +1977,7 @@ static swh_status_t extract_within_checks(swh_levenshtein_t e, swh_scope_t s, in
     if ((status = extract_value_checks(e, scorer, cutoff_bits, prefix_weight_bits, candidates, cutoff, prefix_weight, error)) != swh_success_k) return status;
     if (scorer < SWH_SCORER_LCS && std::isinf(cutoff))
         return fail(error, swh_invalid_argument_k, "a range search by a distance needs a finite cutoff: without one it is the dense cross-product");
-    if (!row_offsets) return fail(error, swh_invalid_argument_k, "null row_offsets");
-    if (!indices != !scores) return fail(error, swh_invalid_argument_k, "indices and scores must both be given, or neither");
-    if (!indices && capacity) return fail(error, swh_invalid_argument_k, "a capacity without arrays: the counting call passes NULL, NULL, 0");
+    if ((status = csr_output_checks(row_offsets, indices, scores, "indices and scores", false, capacity, error)) != swh_success_k) return status;
     request = ExtractWithinRequest{scorer, cutoff, prefix_weight, row_offsets, indices, scores, capacity};
     return swh_success_k;
 }

@@ -2,16 +2,14 @@
 // (swh_levenshtein_within_*, include/stringwars_amd.h). Top-k (topk.hip) folds a walk's distances into a list of k; a range search
 // compacts them: rows in candidate order, no sort, no atomics on the output, the same bits on every run.
 //
-// Every path walks the pairs twice. The count pass leaves hit counts, an exclusive scan turns them into starts and row offsets, the
-// host reads the total (8 bytes) and -- only if the caller's arrays hold it -- the fill pass repeats the walk and stores each hit at
-// its row's cursor: a wave's 64 distances give one ballot, a hit's place is the cursor plus the hits in the lanes below it.
+// Every path walks the pairs twice. The count pass leaves hit counts, the offsets scan (scan.hip) turns them into starts and row
+// offsets, the host reads the total (8 bytes) and -- only if the caller's arrays hold it -- the fill pass repeats the walk and stores
+// each hit at its row's cursor: a wave's 64 distances give one ballot, a hit's place is the cursor plus the hits in the lanes below it.
 //
 // Kernels:
 //   k_cross_within<Off, Fill>  word-sized byte strings (<= 32 bytes, unit costs: the calls top-k serves with k_cross_topk), on the same item
 //                              (cross_words.hpp). A chunk with no lane at |m - n| <= bound is skipped in both passes (d >= |m - n|).
 //                              Lane q keeps query q's count (Fill = false) or cursor (true).
-//   k_within_sums,             the scan of counts[row][slice], row-major: per-tile sums, then every tile adds up the sums before it
-//   k_within_offsets           and scans itself. Two plain launches: no workgroup waits for another.
 //   k_within_count,            the general path: one wave per row of a slice of a dense u32 matrix (scored by the ordinary
 //   k_within_fill              cross-product routes into scratch). Slices run in stream order, so a row's cursor meets its candidates
 //                              in ascending order.
@@ -72,71 +70,6 @@ __global__ __launch_bounds__(kWithinWaves * 64, 4) void k_cross_within(WithinArg
         });
 }
 
-// ---- the scan of the counts --------------------------------------------------------------------------------------------------------
-constexpr int kWithinScanThreads = 256;
-constexpr int kWithinScanPerThread = (int)(kWithinScanTile / kWithinScanThreads);   // 16 consecutive counts per thread
-
-__device__ __forceinline__ uint64_t within_block_sum(unsigned long long v, uint64_t *wave_sums) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return wave_sums[0] + wave_sums[1] + wave_sums[2] + wave_sums[3];
-}
-
-__global__ __launch_bounds__(kWithinScanThreads) void k_within_sums(const uint32_t *counts, uint64_t n, uint64_t *block_sums) {
-    __shared__ uint64_t wave_sums[4];
-    const uint64_t first = (uint64_t)blockIdx.x * kWithinScanTile + (uint64_t)threadIdx.x * kWithinScanPerThread;
-    uint64_t mine = 0;
-#pragma unroll
-    for (int j = 0; j < kWithinScanPerThread; ++j) mine += first + j < n ? counts[first + j] : 0u;
-    const uint64_t sum = within_block_sum(mine, wave_sums);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = sum;
-}
-
-// Tile t: the sums of the tiles before it, then its own exclusive scan. starts[i] for every count; row_offsets[r] = starts[r * slices]
-// and row_offsets[rows] = the total, written by whoever holds count n - 1.
-__global__ __launch_bounds__(kWithinScanThreads) void k_within_offsets(const uint32_t *counts, uint64_t n, uint32_t slices, const uint64_t *block_sums,
-                                                                         uint64_t *starts, uint64_t *row_offsets) {
-    __shared__ uint64_t wave_sums[4];
-    __shared__ uint64_t wave_scan[4];
-    uint64_t before = 0;
-    for (uint32_t b = threadIdx.x; b < blockIdx.x; b += kWithinScanThreads) before += block_sums[b];
-    const uint64_t base = within_block_sum(before, wave_sums);
-    const uint64_t first = (uint64_t)blockIdx.x * kWithinScanTile + (uint64_t)threadIdx.x * kWithinScanPerThread;
-    uint32_t c[kWithinScanPerThread];
-    uint64_t mine = 0;
-#pragma unroll
-    for (int j = 0; j < kWithinScanPerThread; ++j) {
-        c[j] = first + j < n ? counts[first + j] : 0u;
-        mine += c[j];
-    }
-    // exclusive scan of the threads' sums: within the wave by shuffles, across the four waves through LDS
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long other = __shfl_up(incl, off);
-        if (lane >= (uint32_t)off) incl += other;
-    }
-    if (lane == 63) wave_scan[wave] = incl;
-    __syncthreads();
-    uint64_t at = base + incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) at += wave_scan[w];
-#pragma unroll
-    for (int j = 0; j < kWithinScanPerThread; ++j) {
-        const uint64_t i = first + j;
-        if (i < n) {
-            starts[i] = at;
-            if (slices == 1) row_offsets[i] = at;
-            else if (i % slices == 0) row_offsets[i / slices] = at;
-            if (i == n - 1) row_offsets[n / slices] = at + c[j];
-        }
-        at += c[j];
-    }
-}
-
 // ---- the general path's sweeps -----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kWithinWaves * 64) void k_within_count(const uint32_t *scores, uint64_t rows, uint64_t columns, uint32_t bound,
                                                                      uint32_t *counts) {
@@ -190,21 +123,6 @@ void launch_cross_within(Scope *scope, const WithinLaunch &w, bool fill) {
         if (fill) hipLaunchKernelGGL((k_cross_within<uint32_t, true>), grid, block, 0, scope->stream, args);
         else hipLaunchKernelGGL((k_cross_within<uint32_t, false>), grid, block, 0, scope->stream, args);
     }
-    SWH_HIP_CHECK(hipGetLastError());
-}
-
-void launch_within_offsets(Scope *scope, const uint32_t *counts, uint64_t rows, uint32_t slices, uint64_t *block_sums, uint64_t *starts,
-                           uint64_t *row_offsets) {
-    const uint64_t n = rows * slices;
-    const uint32_t blocks = (uint32_t)((n + kWithinScanTile - 1) / kWithinScanTile);
-    {
-        StampGuard guard(scope, "within_sums");
-        hipLaunchKernelGGL(k_within_sums, dim3(blocks), dim3(kWithinScanThreads), 0, scope->stream, counts, n, block_sums);
-        SWH_HIP_CHECK(hipGetLastError());
-    }
-    StampGuard guard(scope, "within_offsets");
-    hipLaunchKernelGGL(k_within_offsets, dim3(blocks), dim3(kWithinScanThreads), 0, scope->stream, counts, n, slices, (const uint64_t *)block_sums,
-                       starts, row_offsets);
     SWH_HIP_CHECK(hipGetLastError());
 }
 

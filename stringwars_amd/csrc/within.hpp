@@ -4,8 +4,6 @@
 
 namespace swh {
 
-constexpr uint64_t kWithinScanTile = 4096;   // counts per workgroup of the offsets scan
-
 // The fused word-sized search: one walk of k_cross_within. `fill` false: the count pass -- counts[row][slice] and the call's summary;
 // `fill` true: the same walk stores every hit at starts[row][slice] onwards (positions at or beyond `total` are never written).
 struct WithinLaunch {
@@ -13,15 +11,11 @@ struct WithinLaunch {
     uint32_t off64, slices, bound, prune;
     uint64_t slice_chunks;            // chunks of 64 candidates per slice
     uint32_t *counts;                 // [query][slice]
-    const uint64_t *starts;           // [query][slice]: exclusive scan of counts
+    const uint64_t *starts;           // [query][slice]: the offsets scan (scan.hpp) of counts
     uint64_t total;                   // hits of the call = entries of indices / distances that may be written
     uint32_t *indices, *distances;
 };
 void launch_cross_within(Scope *scope, const WithinLaunch &w, bool fill);
-// Exclusive scan of counts[0, rows * slices) into starts; row_offsets[r] = starts[r * slices], row_offsets[rows] = the total.
-// `block_sums`: (rows * slices + kWithinScanTile - 1) / kWithinScanTile words of scratch.
-void launch_within_offsets(Scope *scope, const uint32_t *counts, uint64_t rows, uint32_t slices, uint64_t *block_sums, uint64_t *starts,
-                           uint64_t *row_offsets);
 // The general path's two sweeps over a slice of a dense u32 matrix (`columns` wide, row r = query row_first + r, column c = candidate
 // col_first + c): hits (score <= bound) added to counts[row_first + r], or stored at cursors[row_first + r] onwards, which advances.
 void launch_within_count(Scope *scope, const uint32_t *scores, uint64_t rows, uint64_t columns, uint32_t bound, uint32_t *counts);

@@ -534,10 +534,12 @@ def check_offsets_from_ops(a, b, got):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("count", [2047, 2048, 2049, 4096, 256 * 2048 + 1])
+@pytest.mark.parametrize("count", [2047, 2048, 2049, 4095, 4096, 4097, 8192, 256 * 2048 + 1, 256 * 4096 + 1])
 def test_scan_and_emit_edges(sw, scope, lev, count):
-    """Pair counts at the edges of the scans: one tile of 2048 values less one, exactly, plus one, two tiles, and one pair more than 256
-    tiles (the tile sums are then scanned two per thread)."""
+    """Pair counts at the edges of the offsets scan, which works in tiles of 4096 values: one tile less one, exactly, plus one, two
+    tiles, and one pair more than 256 tiles (the scan's 256 threads then add up more than one preceding tile sum apiece). With them the
+    counts at the edges of 2048, the tile of the scan the alignments had of their own, and one pair more than 256 of those. The large
+    counts are checked whole by the vectorised checks and against the reference script at the tile edges and 500 sampled pairs."""
     a, b = sw.generate_pairs("short_words", count, seed=count)
     assert len(a) == len(b) == count
     got = lev.align(a, b, scope)
@@ -546,8 +548,9 @@ def test_scan_and_emit_edges(sw, scope, lev, count):
     within = check_offsets_from_ops(a, b, got)
     assert within.sum() >= count - (a.lengths + b.lengths == 0).sum()
     rng = np.random.default_rng(count)
-    edges = [i for t in range(0, count + 1, 2048) for i in (t - 2, t - 1, t, t + 1) if 0 <= i < count] if count < 10_000 else \
-            [i for t in (0, 2048, 4096, 255 * 2048, 256 * 2048) for i in (t - 2, t - 1, t, t + 1) if 0 <= i < count]
+    last = (count - 1) // 4096 * 4096   # where the last tile begins
+    tiles = range(0, count + 1, 2048) if count < 10_000 else (0, 2048, 4096, 8192, 255 * 2048, 256 * 2048, last - 4096, last)
+    edges = [i for t in tiles for i in (t - 2, t - 1, t, t + 1) if 0 <= i < count]
     sample = sorted(set(edges + [0, count - 1] + rng.choice(count, 500, replace=False).tolist()))
     check_exact(sw, got, {i: a[i] for i in sample}, {i: b[i] for i in sample}, indices=sample)
 

@@ -361,6 +361,23 @@ def test_chunk_edges(sw, scope, lev, lev8, offsets):
 
 
 @gpu
+@pytest.mark.parametrize("count", [4095, 4096, 4097, 8193])
+def test_scan_tile_edges(sw, scope, count):
+    """Tapes of as many strings as the offsets scan's tile of 4096 values holds, one less, one more, and one more than two tiles: the
+    lengths of the normal forms are its only u32 input scanned without a second copy of the starts. One to three short tokens a string,
+    some repeated, every seventh string empty or blank; both forms in full against Python."""
+    rng = np.random.default_rng(count)
+    words = ["a", "b", "ab", "ba", "abc", "zz", "é", "中"]
+    items = []
+    for i in range(count):
+        tokens = [words[int(k)] for k in rng.integers(0, len(words), int(rng.integers(1, 4)))]
+        items.append(("", " ", "\t ")[i % 3] if i % 7 == 3 else (" ", "  ", "\n")[i % 3].join(tokens) + ("", " ")[i % 2])
+    assert {len(s.split()) for s in items} == {0, 1, 2, 3}
+    for utf8 in (False, True):
+        check_derived(sw, scope, as_items(items, utf8), utf8)
+
+
+@gpu
 def test_length_cap_and_refusals(sw, scope, lev, lev8):
     from stringwars_amd import _native as N
     fits, over = b"ab " * 1365 + b"a", b"ab " * 1365 + b"ab"
